@@ -258,3 +258,34 @@ def test_clock_sampler_reads_the_hwmon_files(tmp_path):
     none.start()
     none.stop()
     assert none.summary() is None
+
+
+def test_bench_dump_outputs_are_float32_seeded_and_bounded(tmp_path):
+    """bench.py --dump-outputs: every output lands as DIR/<name>.npy in float32; a concatenation longer than
+    DUMP_SAMPLE is cut to DUMP_SAMPLE elements at seeded positions (the same on every run), and the files together stay
+    within DUMP_LIMIT_BYTES."""
+    import numpy as np
+    import torch
+    import bench
+    model = torch.nn.Sequential(torch.nn.Linear(6, 5), torch.nn.BatchNorm1d(5), torch.nn.Linear(5, 3))
+    x = torch.randn(4, 6, generator=torch.Generator().manual_seed(0))
+    logits = model(x)
+    loss = torch.nn.functional.cross_entropy(logits, torch.tensor([0, 1, 2, 0]))
+    loss.backward()
+    outs = bench.train_outputs(model, loss, logits.detach())
+    assert sorted(outs) == ["buffers", "grads", "logits", "loss", "params"]
+    n_params = sum(p.numel() for p in model.parameters())
+    assert outs["params"].numel() == outs["grads"].numel() == n_params
+    assert outs["buffers"].numel() == 2 * 5                     # running mean / var; num_batches_tracked is no float
+    bench.dump_outputs(str(tmp_path / "d"), outs)
+    got = {f[:-4]: np.load(str(tmp_path / "d" / f)) for f in os.listdir(str(tmp_path / "d"))}
+    assert sorted(got) == sorted(outs) and all(a.dtype == np.float32 for a in got.values())
+    assert got["loss"].shape == (1,) and got["logits"].shape == (4, 3)
+    np.testing.assert_array_equal(got["grads"], torch.cat([p.grad.reshape(-1) for p in model.parameters()]).numpy())
+    # a long output: a fixed sample of DUMP_SAMPLE of its elements, the same positions every time
+    v = torch.arange(bench.DUMP_SAMPLE + 1000, dtype=torch.float32)
+    a, b = bench._dump_sample(v, 2), bench._dump_sample(v, 2)
+    assert a.numel() == bench.DUMP_SAMPLE and torch.equal(a, b) and bool((a[1:] > a[:-1]).all())
+    assert 5 * bench.DUMP_SAMPLE * 4 > bench.DUMP_LIMIT_BYTES >= 3 * bench.DUMP_SAMPLE * 4 + (1 << 20)
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})

@@ -98,6 +98,9 @@ TREE = {
                                    lr=cfg.SOLVER.BASE_LR, momentum=cfg.SOLVER.MOMENTUM)
         def get_epoch_lr(cur_epoch, cfg):
             return lr_policy.get_lr_at_epoch(cfg, cur_epoch)
+        def set_lr(optimizer, new_lr):
+            for group in optimizer.param_groups:
+                group.update(lr=new_lr)
         """,
     "slowfast/models/losses.py": """
         import torch.nn as nn
@@ -273,20 +276,22 @@ def test_standalone_package_has_no_chain(tmp_path):
     subprocess.run([sys.executable, "-c", code], check=True, env=env, cwd=str(tmp_path), timeout=300)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/SlowFast/slowfast"), reason="reference tree not present")
-def test_against_the_real_reference_tree(tmp_path):
-    """The exact imports VERDICT r05 found broken, against the real tree (this container only; read-only, no
-    bytecode written).  The reference's utils/misc.py needs fvcore/psutil/cv2, absent here, so that chain is
-    allowed to warn; lr_policy / optimizer / losses / distributed need nothing that is missing."""
+def test_reference_layout_tree_chains_the_imports_run_net_needs(tmp_path):
+    """The exact imports VERDICT r05 found broken, run against the stand-in of the reference's tree (read-only, no
+    bytecode written): lr_policy / optimizer / losses come from the other tree, the models from this package, and
+    this package's distributed module chains to the other tree's namesake."""
+    tree = tmp_path / "tree"  # (not the cwd: -c puts the cwd first on sys.path)
+    _write_tree(tree)
     code = textwrap.dedent("""
-        import warnings; warnings.simplefilter("ignore", RuntimeWarning)
+        import os, warnings; warnings.simplefilter("ignore", RuntimeWarning)
         import slowfast.utils.lr_policy as lp, slowfast.models.optimizer as optim, slowfast.models.losses as losses
         import slowfast.utils.distributed as du, slowfast.models as M
         from slowfast.config.defaults import get_cfg
-        assert lp.__file__.startswith("/root/reference") and optim.__file__.startswith("/root/reference")
-        assert not M.__file__.startswith("/root/reference") and du.__chained_from__.startswith("/root/reference")
+        other = lambda f: os.path.realpath(f).startswith(%r)
+        assert other(lp.__file__) and other(optim.__file__) and other(losses.__file__)
+        assert not other(M.__file__) and other(du.__chained_from__)
         cfg = get_cfg()
-        cfg.merge_from_file("%s")
+        cfg.merge_from_file(%r)
         cfg.merge_from_list(["NUM_GPUS", 0, "DATA.NUM_FRAMES", 16, "SLOWFAST.ALPHA", 4,
                              "SOLVER.LR_POLICY", "cosine", "SOLVER.MAX_EPOCH", 10])
         model = M.build_model(cfg)
@@ -294,12 +299,13 @@ def test_against_the_real_reference_tree(tmp_path):
         n_bn = sum(1 for n, _ in model.named_parameters() if "bn" in n)
         assert len(opt.param_groups[0]["params"]) == n_bn > 0
         lr = optim.get_epoch_lr(1, cfg); optim.set_lr(opt, lr); assert 0 < lr < cfg.SOLVER.BASE_LR
+        assert all(g["lr"] == lr for g in opt.param_groups)
         assert "CrossEntropyLoss" in repr(losses.get_loss_func("cross_entropy"))
         assert du.is_master_proc() and du.all_gather_unaligned is not None
         print("OK")
-        """) % os.path.join(ROOT, "configs", YAMLS["SlowFastDualAttention"])
+        """) % (os.path.realpath(str(tree)), os.path.join(ROOT, "configs", YAMLS["SlowFastDualAttention"]))
     env = {k: v for k, v in os.environ.items() if k != "PYTHONPATH"}
-    env.update({"PYTHONPATH": PKG + os.pathsep + "/root/reference/SlowFast", "PYTHONDONTWRITEBYTECODE": "1"})
+    env.update({"PYTHONPATH": PKG + os.pathsep + str(tree), "PYTHONDONTWRITEBYTECODE": "1"})
     p = subprocess.run([sys.executable, "-c", code], env=env, cwd=str(tmp_path), stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, universal_newlines=True, timeout=600)
     assert p.returncode == 0 and "OK" in p.stdout, p.stderr[-3000:]

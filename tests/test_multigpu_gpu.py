@@ -99,8 +99,8 @@ def test_spawned_rank_runs_the_chunked_allreduce_on_rccl():
     lines = []
     for extra in ([], ["--no-overlap-allreduce"]):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "2",
-                            "--no-cpu-baseline", "--no-extras", "--batch", "2"] + extra, env=env, capture_output=True,
-                           text=True, timeout=600)
+                            "--full", "--no-cpu-baseline", "--no-extras", "--batch", "2"] + extra, env=env,
+                           capture_output=True, text=True, timeout=600)
         if r.returncode != 0:  # keep the whole log where a gpurun call can bring it back
             try:
                 os.makedirs(os.path.join(root, "gpurun_out"), exist_ok=True)
@@ -137,7 +137,8 @@ def test_two_ranks_through_bench_py_on_one_gpu():
         lines = []
         for extra in ([], ["--no-overlap-allreduce"]):
             r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup",
-                                "1", "--workload", "dual", "--batch", "1", "--no-cpu-baseline", "--no-extras"] + extra,
+                                "1", "--workload", "dual", "--batch", "1", "--full", "--no-cpu-baseline", "--no-extras"]
+                               + extra,
                                env=env, capture_output=True, text=True, timeout=900)
             if r.returncode != 0:
                 try:

@@ -2,7 +2,7 @@
 # box), then the GPU suite, then smoke -> gpurun_out/final_r6b
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/final_r6b; mkdir -p $O
 cd $R
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_cmd.jsonl 2> $O/driver_cmd.err; echo "bench rc=$?"
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/driver_cmd.jsonl 2> $O/driver_cmd.err; echo "bench rc=$?"
 timeout 900 python -m pytest tests -m gpu -x -q > $O/gputest_full.log 2>&1; echo "pytest rc=$?"; tail -2 $O/gputest_full.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log
 python3 -c "

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/final_r5; mkdir -p $O
 cd $R
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_cmd.jsonl 2> $O/driver_cmd.err
 cd /tmp && export TMPDIR=/tmp
-timeout 500 rocprofv3 --kernel-trace --stats -d $O/default --output-format csv -- python3 $R/bench.py --no-cpu-baseline > $O/default.log 2>&1
+timeout 500 rocprofv3 --kernel-trace --stats -d $O/default --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline > $O/default.log 2>&1
 cp $(find $O/default -name "*kernel_stats.csv" | head -1) $O/bench_default_kernel_stats.csv; rm -rf $O/default
 SF_OVERLAP_PATHS=0 timeout 300 rocprofv3 --kernel-trace --stats -d $O/serial --output-format csv -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extras --no-graph > $O/serial.log 2>&1
 cp $(find $O/serial -name "*kernel_stats.csv" | head -1) $O/bench_train_only_serial_kernel_stats.csv; rm -rf $O/serial
@@ -25,10 +25,10 @@ timeout 300 python tools/microbench/wgrad_bx_bench.py > $O/wgrad_bx_ab.txt 2>&1
 (timeout 300 python tools/microbench/attn_pp_check.py; for d in 0 256 128 512 640 2048 4096 32 64; do echo -n "ping-pong, SF_ATTN_BX_DBG=$d: "; SF_ATTN_BX_PP=1 SF_ATTN_BX_DBG=$d ATTN_SHAPES=32 ATTN_ITERS=3 timeout 100 python tools/microbench/attn_bench.py 2>&1 | grep "d=32" | sed "s/.*backward//"; done) 2>&1 | grep -v amdgpu > $O/attn_pingpong_ablations.txt
 timeout 200 python tools/microbench/bn_passes.py 2>&1 | grep -v amdgpu > $O/bn_passes.txt
 timeout 300 python tools/host_lead.py > $O/host_lead.txt 2>&1
-timeout 700 python bench.py > $O/bench_dual.json 2> $O/bench_dual.err
-for w in slowfast ghostnet shufflenetv2; do timeout 900 python bench.py --workload $w >> $O/bench_lines_workloads.jsonl 2>> $O/bench_workloads.err; done
+timeout 700 python bench.py --full > $O/bench_dual.json 2> $O/bench_dual.err
+for w in slowfast ghostnet shufflenetv2; do timeout 900 python bench.py --full --workload $w >> $O/bench_lines_workloads.jsonl 2>> $O/bench_workloads.err; done
 # second half of the round: cfg #5 at 8 clips, the depthwise marches, the 4x4x1 attention backward, grouped convs
-timeout 600 python bench.py --workload ghostnet --batch 8 --no-cpu-baseline > $O/bench_line_ghostnet_b8.jsonl 2> $O/bench_ghostnet_b8.err
+timeout 600 python bench.py --full --workload ghostnet --batch 8 --no-cpu-baseline > $O/bench_line_ghostnet_b8.jsonl 2> $O/bench_ghostnet_b8.err
 (for on in 1 0; do echo "SF_ATTN_SMALL_44=$on"; SF_ATTN_SMALL_44=$on timeout 200 python tools/microbench/attn_small_bench.py; done) 2>&1 | grep -v amdgpu > $O/attn_small_44_ab.txt
 timeout 100 ./tools/microbench/build/mfma4x4_probe > $O/mfma4x4_probe.txt 2>&1
 timeout 200 python tools/microbench/grouped_conv_ab.py 2>&1 | grep -v amdgpu > $O/grouped_conv_ab.txt

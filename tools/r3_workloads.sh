@@ -2,9 +2,9 @@
 # timelines of the cfg #3 train step.  Run on the GPU box: gpurun -- bash tools/r3_workloads.sh
 cd /tmp && export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r3w; mkdir -p $O; cd $R
 for w in slowfast ghostnet shufflenetv2; do
-  timeout 600 python bench.py --workload $w > $O/bench_$w.json 2> $O/bench_$w.err
+  timeout 600 python bench.py --full --workload $w > $O/bench_$w.json 2> $O/bench_$w.err
 done
-timeout 600 python bench.py --workload ghostnet --batch 8 > $O/bench_ghostnet_b8.json 2> $O/bench_ghostnet_b8.err
+timeout 600 python bench.py --full --workload ghostnet --batch 8 > $O/bench_ghostnet_b8.json 2> $O/bench_ghostnet_b8.err
 cd /tmp
 for w in slowfast ghostnet shufflenetv2; do
   SF_OVERLAP_PATHS=0 timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_$w --output-format csv -- python3 $R/bench.py --workload $w --steps 6 --warmup 2 --no-cpu-baseline --no-extras --no-graph > $O/prof_$w.log 2>&1
