@@ -15,7 +15,6 @@
 #include "attn_args.h"
 #include "attn_bx.h"
 #include <stdlib.h>
-#include <type_traits>
 
 namespace {
 
@@ -31,7 +30,6 @@ struct BwdArgs {
   int zs;                                            // fused kernels: the swept (query) range is cut into zs parts
   float* dkp; float* dvp;                            // zs > 1: dK / dV partials [B][zs][N][CP], summed afterwards
   float* dqp;                                        // two-kernel form with zs > 1: dQ partials [B][zs][N][CP]
-  int stagger;                                       // bf16-piece sweeps: s_sleep units the OLDER wavefront of each SIMD waits per tile
 };
 
 constexpr float POS_BIG = 3.0e38f;
@@ -626,31 +624,16 @@ __global__ __launch_bounds__(64 * NW, (CP >= 64) ? 2 : 1) void attn_bwd_fused_ke
 constexpr int BXB_QT = 64;                        // queries per tile
 constexpr int BXB_PL = BXB_QT * BX_KP;            // one piece of one tile in LDS (bf16 elements)
 constexpr int BXB_TP = 36;                        // dS image row pitch (bf16): 72 B
-// DBG (timing ablations, results invalid): 1 = P and dS are not split (leading piece three times), 2 = no dQ product
-// (no image write / transposed read), 4 = one MFMA per product instead of six.
-template <int DBG, class V>
-__device__ __forceinline__ void bxb_split(float a, float b, V (&dst)[3], int idx) {
-  if constexpr (DBG & 1) {
-    dst[0][idx] = dst[1][idx] = dst[2][idx] = cvt_pk_bf16(a, b);
-  } else {
-    split_pair(a, b, dst, idx);
-  }
-}
-template <int DBG>
-__device__ __forceinline__ f32x16 bxb_mfma(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x16 c) {
-  if constexpr (DBG & 4) return mfma_bf(a[0], b[0], c);
-  return mfma_split(a, b, c);
-}
 // A workgroup barrier for LDS hand-overs only (__syncthreads() also drains vmcnt — here that would wait for the dQ plane
 // store's acknowledgement once per tile): every LDS access of this wavefront has landed / been served, then the workgroup barrier; vmcnt is left alone
-#define PP_BARRIER()                                                  \
+#define LDS_BARRIER()                                                 \
   do {                                                                \
     __builtin_amdgcn_sched_barrier(0);                                \
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
     __builtin_amdgcn_sched_barrier(0);                                \
   } while (0)
 constexpr int bxb_lds_bytes(int nw) { return 6 * BXB_PL * 2 + 2 * BXB_QT * 4 + nw * BXB_QT * 32 * 4; }
-template <int DBG, int NW>
+template <int NW>
 __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_bx_kernel(const BwdArgs p, float* __restrict__ ws,
                                                                       const unsigned short* __restrict__ qb,
                                                                       const unsigned short* __restrict__ db, int n64) {
@@ -765,17 +748,9 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_bx_kernel(const BwdA
     store_tile();
   }
   __syncthreads();
-  unsigned long long st_acc[5] = {0, 0, 0, 0, 0}, st0 = 0, st1 = 0, st2 = 0, st3 = 0, st4 = 0;  // DBG & 8: s_memtime per phase
   for (int t = t0; t < ntiles; ++t) {
     const bool more = (t + 1) < ntiles;
-    if constexpr (DBG & 8) { __builtin_amdgcn_sched_barrier(0); st0 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
     if (more) load_tile(t + 1);
-    // Both wavefronts of a SIMD leave the tile's barrier in the same phase (MFMAs of S' / dP first) and then fight for
-    // the matrix pipe and the vector port in lock step; letting the older one (which wins every arbitration) start a
-    // little later puts the pair in anti-phase: one in its MFMA stretch while the other splits / exponentiates.
-    if (NW == 8 && wave < 4 && p.stagger > 0) {
-      for (int i = 0; i < p.stagger; ++i) __builtin_amdgcn_s_sleep(16);  // 16 x 64 cycles each
-    }
     f32x16 dqp[2];
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub) {
@@ -803,8 +778,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_bx_kernel(const BwdA
           qa[pc] = *reinterpret_cast<const u32x4*>(rowp + pc * PL + 16 * c);
           da[pc] = *reinterpret_cast<const u32x4*>(rowp + (3 + pc) * PL + 16 * c);
         }
-        s = bxb_mfma<DBG>(qa, kfb[c], s);
-        dp = bxb_mfma<DBG>(da, vfb[c], dp);
+        s = mfma_split(qa, kfb[c], s);
+        dp = mfma_split(da, vfb[c], dp);
       }
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r]);  // P
@@ -815,7 +790,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_bx_kernel(const BwdA
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
-          for (int e = 0; e < 4; ++e) bxb_split<DBG>(s[8 * m + 2 * e], s[8 * m + 2 * e + 1], pf[m], e);
+          for (int e = 0; e < 4; ++e) split_pair(s[8 * m + 2 * e], s[8 * m + 2 * e + 1], pf[m], e);
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
           u32x4 a[3];
@@ -825,7 +800,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_bx_kernel(const BwdA
             const u32x2 hi = lds_read_tr(colp + (3 + pc) * PL + (16 * m + 8) * KP);
             a[pc] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
           }
-          dv = bxb_mfma<DBG>(a, pf[m], dv);
+          dv = mfma_split(a, pf[m], dv);
         }
       }
       // ---- dS = P dP;  dK^T += Q^T dS
@@ -835,7 +810,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_bx_kernel(const BwdA
 #pragma unroll
       for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) bxb_split<DBG>(s[8 * m + 2 * e], s[8 * m + 2 * e + 1], sf[m], e);
+        for (int e = 0; e < 4; ++e) split_pair(s[8 * m + 2 * e], s[8 * m + 2 * e + 1], sf[m], e);
 #pragma unroll
       for (int m = 0; m < 2; ++m) {
         u32x4 a[3];
@@ -845,9 +820,8 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_bx_kernel(const BwdA
           const u32x2 hi = lds_read_tr(colp + pc * PL + (16 * m + 8) * KP);
           a[pc] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
         }
-        dk = bxb_mfma<DBG>(a, sf[m], dk);
+        dk = mfma_split(a, sf[m], dk);
       }
-      if constexpr (DBG & 2) continue;
       // ---- dS pieces -> [key][query] image (registers 4g..4g+3 = queries 8g + 4h .. +3 of this lane's key)
 #pragma unroll
       for (int pc = 0; pc < 3; ++pc)
@@ -869,20 +843,17 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_bx_kernel(const BwdA
           const u32x2 hi = lds_read_tr(imgp + (pc * 32 + 16 * m + 4) * TP);
           a[pc] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
         }
-        dqp[sub] = bxb_mfma<DBG>(a, kbr[m], dqp[sub]);
+        dqp[sub] = mfma_split(a, kbr[m], dqp[sub]);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();  // the image is rewritten by the next block
     }
     // this wavefront's partial [QT][CP] into its slot (rows kappa(r,lh), channel on the lane)
-    if constexpr (DBG & 8) { __builtin_amdgcn_sched_barrier(0); st1 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
       for (int r = 0; r < 16; ++r) myslot[(sub * 32 + kappa(r, lh)) * CP + li] = dqp[sub][r];
-    if constexpr (DBG & 8) { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_waitcnt(0xc07f); st2 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
-    PP_BARRIER();  // every wavefront is done with the tile and has its partial in place
-    if constexpr (DBG & 8) { __builtin_amdgcn_sched_barrier(0); st3 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
+    LDS_BARRIER();  // every wavefront is done with the tile and has its partial in place
     if (more) store_tile();
     for (int e0 = tid * 4; e0 < SLOT; e0 += NT * 4) {  // fixed-order sum of the NW partials to the plane
       f32x4 v = *reinterpret_cast<const f32x4*>(slots + e0);
@@ -890,469 +861,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_bx_kernel(const BwdA
       for (int w = 1; w < NW; ++w) v += *reinterpret_cast<const f32x4*>(slots + w * SLOT + e0);
       *reinterpret_cast<f32x4*>(ws + ((((long)b * nq + t) * p.nt + kb) * (long)SLOT) + e0) = v;  // rows >= N: never read
     }
-    if constexpr (DBG & 8) { __builtin_amdgcn_sched_barrier(0); st4 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
-    PP_BARRIER();
-    if constexpr (DBG & 8) {
-      __builtin_amdgcn_sched_barrier(0);
-      const unsigned long long st5 = __builtin_amdgcn_s_memtime();
-      st_acc[0] += st1 - st0; st_acc[1] += st2 - st1; st_acc[2] += st3 - st2; st_acc[3] += st4 - st3; st_acc[4] += st5 - st4;
-    }
-  }
-  if constexpr (DBG & 8) {
-    if ((blockIdx.x == 7 || blockIdx.x == 2000) && lane == 0 && (wave == 0 || wave == 5) && ntiles > t0) {
-      const unsigned long long n = ntiles - t0;
-      printf("bwd_bx stamps (workgroup %d wave %d, %llu tiles): per tile  compute %llu  slot writes %llu  barrier-1 wait %llu  "
-             "stage + slot sum %llu  barrier-2 wait %llu  = %llu cycles\n", (int)blockIdx.x, wave, n, st_acc[0] / n,
-             st_acc[1] / n, st_acc[2] / n, st_acc[3] / n, st_acc[4] / n,
-             (st_acc[0] + st_acc[1] + st_acc[2] + st_acc[3] + st_acc[4]) / n);
-    }
-  }
-  if (!jok) return;
-  float* okp;
-  float* ovp;
-  if (p.zs > 1) {  // this query part's share of dK / dV; attn_dq_reduce_kernel adds the parts in order
-    okp = p.dkp + ((long)bz * N + jrow) * CP;
-    ovp = p.dvp + ((long)bz * N + jrow) * CP;
-  } else {
-    okp = p.dk + (brow + jrow) * p.dk_cs;
-    ovp = p.dv + (brow + jrow) * p.dv_cs;
-  }
-#pragma unroll
-  for (int r = 0; r < 16; r += 4) {
-    const int c = 8 * (r >> 2) + 4 * lh;
-    if (p.zs > 1 || c < C) {  // C % 4 == 0 on this path
-      *reinterpret_cast<f32x4*>(okp + c) = (f32x4){dk[r], dk[r + 1], dk[r + 2], dk[r + 3]};
-      *reinterpret_cast<f32x4*>(ovp + c) = (f32x4){dv[r], dv[r + 1], dv[r + 2], dv[r + 3]};
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------- fused, bf16 pieces, ping-pong
-// attn_bwd_bx_kernel<., 8> re-scheduled (round 5).  Its stamps (SF_ATTN_BX_DBG=8) show where a 64-query tile's 12 850
-// cycles go: the two wavefronts of a SIMD need 11 100 for 2 x 120 MFMAs = 7 680 cycles of the matrix pipe — every
-// product waits for its fragment reads right in front of it, every exp2 / split for its product, and the older
-// wavefront wins both pipes whenever it can issue — and 1 750 go to the dQ hand-over (slot stores, two barriers, the
-// sum) with no MFMA in flight.  tools/microbench/mfma_pingpong.hip: a wavefront that alternates a pure MFMA segment
-// with a pure vector segment, its SIMD partner one segment behind and s_setprio 1 inside MFMA segments, keeps the
-// pipe 95-99 % busy.  So here the loop is cut into such segments, software-pipelined by one 32-query SUB-block k:
-//   M(k):  back(k-1)  dV^T += dO^T P, dK^T += Q^T dS, dQ(k-1) = dS K   (36 MFMAs; P / dS pieces from registers, dS^T
-//                     from the wavefront's LDS image), then
-//          front(k)   S' = Q K'^T - LSE, dP = dO V^T - D                (24 MFMAs) — all fragment reads, no vector work;
-//   V(k):  dQ(k-1) partial -> slot, P = exp2(S'), split, dS = P dP, split, dS pieces -> image; wavefronts 0-3 also sum
-//          the eight slots of sub-block k-2 into the dQ plane, wavefronts 4-7 issue the LDS-DMA loads of sub-block k+2's Q / dO pieces.
-// Wavefronts 4-7 (the SIMD partners of 0-3) run one segment behind; EVERY segment ends in one raw s_barrier (LDS
-// counters drained, global loads / stores stay in flight), which is all the synchronisation there is: sub-block
-// buffers are a ring of three (sub-block j is read in intervals 2j .. 2j+3 and refilled in 2j+4), slots alternate by
-// sub-block parity, the image is private to its wavefront.  Same products, same accumulation order, same slot-sum
-// order as attn_bwd_bx_kernel: the results are bit-identical to it (tests/test_attention_bx_gpu.py).
-// Sub-block buffers are unpadded [piece 6][row 32][32 channels] with the 16-byte chunk index XORed by (row >> 2) & 3:
-// conflict-free for the row reads (ds_read_b128), the transposing reads and the staging stores.
-constexpr int PP_SUB = 32;                      // queries per sub-block
-constexpr int PP_PIECE = PP_SUB * 32;           // one piece of one sub-block (bf16 elements; 2 KB)
-constexpr int PP_TILE = 6 * PP_PIECE;           // Q pieces 0..2, dO pieces 3..5
-constexpr int PP_IMG = 3 * 32 * BXB_TP;         // one wavefront's dS image (bf16 elements)
-constexpr int PP_SLOT = PP_SUB * 32;            // one wavefront's dQ partial of a sub-block (floats)
-constexpr int PP_LDS_BYTES = 3 * PP_TILE * 2 + 8 * PP_IMG * 2 + 8 * 2 * PP_SLOT * 4 + 3 * 2 * PP_SUB * 4;
-static_assert(PP_LDS_BYTES <= 160 * 1024, "one workgroup per CU");
-// the barrier behind an M segment also drains vmcnt: the LDS-DMA pieces this wavefront issued at the start of its V
-// segment, an interval ago, have landed before anybody reads their ring slot
-#define PP_BARRIER_VM()                                                          \
-  do {                                                                           \
-    __builtin_amdgcn_sched_barrier(0);                                           \
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   \
-    __builtin_amdgcn_sched_barrier(0);                                           \
-  } while (0)
-typedef __attribute__((address_space(3))) void lds_void;
-template <int DBG>
-__global__ __launch_bounds__(512, 1) void attn_bwd_bxpp_kernel(const BwdArgs p, float* __restrict__ ws,
-                                                               const unsigned short* __restrict__ qb,
-                                                               const unsigned short* __restrict__ db, int n64) {
-  constexpr int CP = 32, TP = BXB_TP;
-  // FOUR LDS objects, not one carved buffer: the ring is filled by LDS-DMA (buffer_load ... lds), whose completion is a
-  // vmcnt event, and hipcc puts s_waitcnt vmcnt(0) in front of every LDS access that MAY touch what an outstanding
-  // LDS-DMA writes — with one buffer that is every image / slot store of the segment that issued the loads (a whole
-  // memory latency in the middle of it); distinct objects cannot alias.
-  __shared__ __attribute__((aligned(16))) unsigned short tiles[3 * PP_TILE];     // ring of 3 sub-block buffers
-  __shared__ __attribute__((aligned(16))) unsigned short imgs[8 * PP_IMG];       // [wave][piece][key 32][TP]
-  __shared__ __attribute__((aligned(16))) float slots[8 * 2 * PP_SLOT];          // [wave][parity][PP_SLOT]
-  __shared__ __attribute__((aligned(16))) float lsd[3 * 2 * PP_SUB];             // [buffer][-LSE 32 | -D 32]
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int grp = wave >> 2;  // 0: wavefronts 0-3, 1: their SIMD partners, one segment behind
-  const int li = lane & 31, lh = lane >> 5;
-  const int bz = blockIdx.x / p.nt;  // workgroup -> (clip b, query part z, key block kb)
-  const int kb = blockIdx.x - bz * p.nt;
-  const int b = bz / p.zs, z = bz - b * p.zs;
-  const int j0 = kb * 256 + wave * 32;
-  const int N = p.N, C = p.C;
-  const long brow = (long)b * N;
-  const float gamma = p.gamma[0];
-  float* const myslot = slots + wave * 2 * PP_SLOT;
-  unsigned short* const img = imgs + wave * PP_IMG;
-
-  // ---- this wavefront's keys: K' = K log2(e) and V as B operands [k = channel][col = key], K as [k = key][col = channel]
-  u32x4 kfb[2][3], vfb[2][3], kbr[2][3];
-  const int jrow = j0 + li;
-  const bool jok = jrow < N;
-  {
-    const float* kp = p.k + (brow + (jok ? jrow : 0)) * p.k_cs + 8 * lh;
-    const float* vp = p.v + (brow + (jok ? jrow : 0)) * p.v_cs + 8 * lh;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      f32x4 k0 = {0.f, 0.f, 0.f, 0.f}, k1 = k0, v0 = k0, v1 = k0;
-      if (jok && 16 * c + 8 * lh < C) {
-        k0 = *reinterpret_cast<const f32x4*>(kp + 16 * c);
-        v0 = *reinterpret_cast<const f32x4*>(vp + 16 * c);
-      }
-      if (jok && 16 * c + 8 * lh + 4 < C) {
-        k1 = *reinterpret_cast<const f32x4*>(kp + 16 * c + 4);
-        v1 = *reinterpret_cast<const f32x4*>(vp + 16 * c + 4);
-      }
-      k0 *= LOG2E;
-      k1 *= LOG2E;
-      split_pair(k0[0], k0[1], kfb[c], 0);
-      split_pair(k0[2], k0[3], kfb[c], 1);
-      split_pair(k1[0], k1[1], kfb[c], 2);
-      split_pair(k1[2], k1[3], kfb[c], 3);
-      split_pair(v0[0], v0[1], vfb[c], 0);
-      split_pair(v0[2], v0[3], vfb[c], 1);
-      split_pair(v1[0], v1[1], vfb[c], 2);
-      split_pair(v1[2], v1[3], vfb[c], 3);
-    }
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      float kv[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int key = j0 + 16 * m + 8 * lh + e;
-        kv[e] = (key < N && li < C) ? p.k[(brow + key) * p.k_cs + li] : 0.f;
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) split_pair(kv[2 * e], kv[2 * e + 1], kbr[m], e);
-    }
-  }
-  f32x16 dk, dv;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { dk[r] = 0.f; dv[r] = 0.f; }
-
-  // ---- the sub-blocks of this workgroup's query part
-  const int nq = (N + 63) / 64;
-  const int tz = (nq + p.zs - 1) / p.zs;  // 64-query tiles per part
-  const int t0 = z * tz;
-  const int ntiles = min(nq, t0 + tz);
-  const int NS = t0 < ntiles ? 2 * (ntiles - t0) : 0;  // sub-blocks; sub-block j is rows (2 t0 + j) * 32 ..
-  const int S0 = 2 * t0;
-
-  // ---- staging: a sub-block is 6 pieces x 2 KB = twelve 1 KB LDS-DMA wave-instructions (buffer_load_dwordx4 ... lds:
-  // no staging registers, no LDS stores), three per wavefront 4-7 at the start of V(k) for sub-block k+2: its ring slot
-  // held sub-block k-1, last read in the interval before; the first reader comes two intervals later, behind the
-  // vmcnt(0) barrier that ends the issuing wavefront's next M segment.  An LDS-DMA image is lane-linear, so the chunk
-  // swizzle sits on the SOURCE address: lane l fills position (row l >> 2, chunk l & 3) of its 16 rows with source
-  // chunk (l & 3) ^ ((row >> 2) & 3).
-  const long plane = (long)n64 * 64 * 32;
-  const __amdgpu_buffer_rsrc_t q_rs =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(qb + (long)b * 3 * plane), 0, (unsigned)(3 * plane * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t d_rs =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(db + (long)b * 3 * plane), 0, (unsigned)(3 * plane * 2), 0x00020000);
-  const unsigned dma_voff[2] = {  // halves: rows 0..15, 16..31
-      (unsigned)((lane >> 2) * 64 + (((lane & 3) ^ ((lane >> 4) & 3)) << 4)),
-      (unsigned)((16 + (lane >> 2)) * 64 + (((lane & 3) ^ ((lane >> 4) & 3)) << 4))};
-  // piece `id` (0..11: Q pieces x halves, then dO pieces x halves) of sub-block j into ring buffer buf
-  auto stage_piece = [&](int j, int buf, int id) {
-    const int which = id >= 6, pc = (id % 6) >> 1, half = id & 1;
-    const unsigned so = (unsigned)(((long)pc * plane + (long)(S0 + j) * (PP_SUB * 32)) * 2);
-    unsigned short* const dst = tiles + buf * PP_TILE + (which * 3 + pc) * PP_PIECE + half * 512;
-    if (which)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(d_rs, (lds_void*)dst, 16, dma_voff[half], so, 0, 0);
-    else
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(q_rs, (lds_void*)dst, 16, dma_voff[half], so, 0, 0);
-  };
-  // -LSE / -D of the sub-block's queries: lanes 0..31 of ONE wavefront — loaded in M (raw: nothing there may wait for
-  // the loads), negated / scaled and stored in V
-  float rl = 0.f, rD = 0.f;
-  auto lsd_load = [&](int j) {
-    const int i = (S0 + j) * PP_SUB + li;
-    const long src = brow + (i < N ? i : 0);
-    rl = p.lse[src];
-    rD = p.dvec[src];
-  };
-  auto lsd_store = [&](int j, int buf) {
-    if (lane < PP_SUB) {
-      const bool ok = (S0 + j) * PP_SUB + li < N;
-      lsd[buf * 64 + lane] = ok ? -rl : -POS_BIG;  // P = 2^(s - BIG) = 0 for padded queries
-      lsd[buf * 64 + 32 + lane] = ok ? -rD * gamma : 0.f;
-    }
-  };
-  // fragment addresses (bf16 elements inside a sub-block buffer)
-  const int row_off0 = li * 32 + (((0 + lh) ^ ((li >> 2) & 3)) << 3);  // row fragment of channel chunk c = 0
-  const int row_off1 = li * 32 + (((2 + lh) ^ ((li >> 2) & 3)) << 3);  //                              c = 1
-  // transposing reads: lane 4q+p of a 16-lane group addresses row q, columns 4p..4p+3 of the block
-  const int tr_row = (lane & 15) >> 2, tr_col = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-  // rows 16 m + 4 lh + tr_row (+ 8): (row >> 2) & 3 = lh (lh + 2)
-  const int col_lo = (4 * lh + tr_row) * 32 + ((((tr_col >> 3) ^ lh) << 3) | (tr_col & 7));
-  const int col_hi = (8 + 4 * lh + tr_row) * 32 + ((((tr_col >> 3) ^ (lh + 2)) << 3) | (tr_col & 7));
-  const unsigned short* const imgp = img + (8 * lh + tr_row) * TP + tr_col;
-
-  unsigned long long st_acc[7] = {0, 0, 0, 0, 0, 0, 0}, sa = 0, sb = 0;  // DBG & 8: cycles in M, barrier, V, barrier; M's parts
-  f32x16 s, dp, dqp;
-  u32x4 pf[2][3], sf[2][3];
-  typedef std::integral_constant<bool, true> yes_t;
-  typedef std::integral_constant<bool, false> no_t;
-
-  // ================================================================ M(k): back(k-1), then front(k); no vector work
-  // Eight chains of 6 (12) MFMAs; the fragment reads of chain i+1 are issued in front of chain i's MFMAs and pinned there
-  // (sched_barrier): the compiler's own order reads each chain's fragments right in front of it and waits for them
-  // (~100-200 cycles of idle matrix pipe per chain — the partner wavefront is in its vector segment and cannot fill it).
-#define PP_PIN() __builtin_amdgcn_sched_barrier(0)
-  auto cols = [&](const unsigned short* base, int m, u32x4 (&a)[3]) {  // transposed reads: A = columns of a sub-block
-    if constexpr (DBG & 128) return;  // timing ablation: no fragment reads
-#pragma unroll
-    for (int pc = 0; pc < 3; ++pc) {
-      const u32x2 lo = lds_read_tr(base + pc * PP_PIECE + 512 * m + col_lo);
-      const u32x2 hi = lds_read_tr(base + pc * PP_PIECE + 512 * m + col_hi);
-      a[pc] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
-    }
-  };
-  auto imgf = [&](int m, u32x4 (&a)[3]) {  // transposed reads of this wavefront's dS image: A = dS, query on the lane
-    if constexpr (DBG & 128) return;
-#pragma unroll
-    for (int pc = 0; pc < 3; ++pc) {
-      const u32x2 lo = lds_read_tr(imgp + (pc * 32 + 16 * m) * TP);
-      const u32x2 hi = lds_read_tr(imgp + (pc * 32 + 16 * m + 4) * TP);
-      a[pc] = (u32x4){lo[0], lo[1], hi[0], hi[1]};
-    }
-  };
-  auto rows = [&](const unsigned short* tf, int c, u32x4 (&qa)[3], u32x4 (&da)[3]) {
-    if constexpr (DBG & 128) return;
-    const int ro = c ? row_off1 : row_off0;
-#pragma unroll
-    for (int pc = 0; pc < 3; ++pc) {
-      qa[pc] = *reinterpret_cast<const u32x4*>(tf + pc * PP_PIECE + ro);
-      da[pc] = *reinterpret_cast<const u32x4*>(tf + (3 + pc) * PP_PIECE + ro);
-    }
-  };
-  // S' and dP start from zero; -LSE and -D are added in V(k), which reads them there (eight 16-byte LDS reads that carry
-  // 256 bytes of distinct data: in M they queued in front of the fragment reads the MFMAs wait for)
-  auto init_acc = [&](int) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-  };
-  auto mm = [&](const u32x4 (&a)[3], const u32x4 (&bb)[3], f32x16 c) -> f32x16 {
-    if constexpr (DBG & 64) {  // timing ablation: no MFMAs (the fragments are still read)
-      c[0] += __builtin_bit_cast(float, a[0][0] ^ a[1][1] ^ a[2][2] ^ a[0][3] ^ bb[0][0]);
-      return c;
-    } else {
-      return mfma_split(a, bb, c);
-    }
-  };
-  // dQ plane rows of sub-block j = fixed-order sum of the eight wavefronts' partials (256 threads, one float4 each)
-  const int stid = tid & 255;
-  f32x4 sum_v;
-  auto sum_read = [&](int par, int w0, int w1) {
-    const float* const sl = slots + par * PP_SLOT + stid * 4;
-#pragma unroll
-    for (int w = 0; w < 8; ++w)
-      if (w >= w0 && w < w1) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(sl + w * 2 * PP_SLOT);
-        sum_v = (w == 0) ? x : sum_v + x;
-      }
-  };
-  auto sum_store = [&](int j) {  // absolute sub-block S0 + j: tile >> 1, rows (& 1) * 32 ..
-    const int a = S0 + j;
-    *reinterpret_cast<f32x4*>(ws + ((((long)b * nq + (a >> 1)) * p.nt + kb) * (long)(2 * PP_SLOT)) + (a & 1) * PP_SLOT +
-                              stid * 4) = sum_v;  // rows >= N: never read
-  };
-  auto seg_m = [&](const int k, auto has_back, auto has_front) {
-    constexpr bool BACK = decltype(has_back)::value, FRONT = decltype(has_front)::value;
-    if constexpr (DBG & 8) { __builtin_amdgcn_sched_barrier(0); sa = __builtin_amdgcn_s_memtime(); }
-    if (wave == 4 && k + 2 < NS && !(DBG & 512) && !(DBG & 4096)) lsd_load(k + 2);  // raw; stored at the start of V(k)
-    if constexpr (DBG & 8) { __builtin_amdgcn_sched_barrier(0); st_acc[4] += __builtin_amdgcn_s_memtime() - sa; }
-    if constexpr (!(DBG & 16)) __builtin_amdgcn_s_setprio(1);
-    const unsigned short* const tb = tiles + ((k + 2) % 3) * PP_TILE;  // sub-block k-1
-    const int bf = k % 3;
-    const unsigned short* const tf = tiles + bf * PP_TILE;             // sub-block k
-    u32x4 a0[3] = {}, a1[3] = {}, a2[3] = {}, qa0[3] = {}, da0[3] = {}, qa1[3] = {}, da1[3] = {};
-    // fragment reads run TWO chains (384 matrix-pipe cycles) ahead of the MFMAs that take them: with the partner's vector
-    // segment and the LDS stores of four other wavefronts in flight a read needs ~300 cycles, and one chain ahead left
-    // every chain waiting (SF_ATTN_BX_DBG=128, no fragment reads: 9.1 -> 6.7 ms)
-    // ... and they are dealt ONE per MFMA gap (sched_group_barrier: MFMA, LDS read, MFMA, LDS read ...): six reads in a
-    // row in front of a chain hold the wavefront's issue past the previous MFMA's 32-cycle shadow
-#define PP_MIX(n)                                              \
-  do {                                                         \
-    _Pragma("unroll") for (int i_ = 0; i_ < (n); ++i_) {       \
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);       \
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);       \
-    }                                                          \
-    __builtin_amdgcn_sched_barrier(0);                         \
-  } while (0)
-    if constexpr (BACK) {
-      cols(tb + 3 * PP_PIECE, 0, a0);                                                     // dO columns, k-step 0
-      cols(tb + 3 * PP_PIECE, 1, a1);                                                     //             k-step 1
-      PP_PIN();
-      cols(tb, 0, a2); dv = mm(a0, pf[0], dv); PP_MIX(6);                                  // dV^T += dO^T P
-      cols(tb, 1, a0); dv = mm(a1, pf[1], dv); PP_MIX(6);
-      imgf(0, a1);     dk = mm(a2, sf[0], dk); PP_MIX(6);                                  // dK^T += Q^T dS
-      imgf(1, a2);     dk = mm(a0, sf[1], dk); PP_MIX(6);
-      if constexpr (!(DBG & 1024)) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dqp[r] = 0.f;
-      }
-      if constexpr (FRONT) rows(tf, 0, qa0, da0);
-      dqp = mm(a1, kbr[0], dqp);                                                          // dQ(k-1) = dS K
-      PP_MIX(6);
-      if constexpr (FRONT) {
-        init_acc(bf);
-        rows(tf, 1, qa1, da1);
-      }
-      dqp = mm(a2, kbr[1], dqp);
-      PP_MIX(6);
-    } else {
-      init_acc(bf);
-      rows(tf, 0, qa0, da0);
-      rows(tf, 1, qa1, da1);
-      PP_PIN();
-    }
-    if constexpr (FRONT) {  // S' = Q K'^T,  dP = dO V^T   (queries in registers, key on the lane)
-      s = mm(qa0, kfb[0], s);
-      dp = mm(da0, vfb[0], dp);
-      PP_PIN();
-      s = mm(qa1, kfb[1], s);
-      dp = mm(da1, vfb[1], dp);
-    }
-    if constexpr (!(DBG & 16)) __builtin_amdgcn_s_setprio(0);
-    if constexpr (DBG & 8) { __builtin_amdgcn_sched_barrier(0); sb = __builtin_amdgcn_s_memtime(); st_acc[0] += sb - sa; }
-  };
-  // ================================================================ V(k): everything that is not an MFMA
-  auto seg_v = [&](const int k, auto has_back, auto has_front) {
-    if constexpr (DBG & 8) { __builtin_amdgcn_sched_barrier(0); sa = __builtin_amdgcn_s_memtime(); st_acc[1] += sa - sb; }
-    if (grp == 1 && k + 2 < NS && !(DBG & 512) && !(DBG & 4096)) {  // sub-block k+2 into the ring (global work first: it has this whole
-      const int buf = (k + 2) % 3;                  // segment and the next to land)
-      if (wave == 4) lsd_store(k + 2, buf);  // BEFORE the pieces: vmcnt counts in order, and its loads are an interval old
-      PP_PIN();
-#pragma unroll
-      for (int u = 0; u < 3; ++u) stage_piece(k + 2, buf, (wave - 4) * 3 + u);
-    }
-    if constexpr (decltype(has_back)::value) {  // dQ(k-1) partial [32 queries][CP] -> this wavefront's slot
-      float* const sl = myslot + ((k - 1) & 1) * PP_SLOT;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sl[kappa(r, lh) * CP + li] = dqp[r];
-    }
-    if constexpr (decltype(has_front)::value && (DBG & 256)) {  // timing ablation: the probe's vector segment instead
-      float f[8];
-      for (int i = 0; i < 8; ++i) f[i] = s[i];
-      const float bb = dp[0];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) asm volatile("v_exp_f32 %0, %0" : "+v"(f[q & 7]));
-#pragma unroll
-      for (int q = 0; q < 48; ++q) asm volatile("v_cvt_pk_bf16_f32 %0, %0, %1" : "+v"(f[q & 7]) : "v"(bb));
-#pragma unroll
-      for (int q = 0; q < 150; ++q) asm volatile("v_fma_f32 %0, %0, %1, %1" : "+v"(f[q & 7]) : "v"(bb));
-      for (int i = 0; i < 8; ++i) pf[0][0][i & 3] ^= __builtin_bit_cast(unsigned, f[i]);
-    }
-    if constexpr (decltype(has_front)::value && !(DBG & 32) && !(DBG & 256)) {
-      {
-        const int bf = k % 3;
-        f32x4 l4[4], d4[4];
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-          l4[g4] = *reinterpret_cast<const f32x4*>(lsd + bf * 64 + 8 * g4 + 4 * lh);
-          d4[g4] = *reinterpret_cast<const f32x4*>(lsd + bf * 64 + 32 + 8 * g4 + 4 * lh);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r] + l4[r >> 2][r & 3]);  // P = 2^(S' - LSE)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dp[r] = (dp[r] + d4[r >> 2][r & 3]) * s[r];  // dS = P (dP - D)
-      }
-      // Both three-way splits STAGE by stage over all 16 pairs (in place: s and dp end as the third residuals): the
-      // partner wavefront is in its MFMA segment and covers nothing, so a pair's own chain (convert -> expand ->
-      // subtract -> convert ...: seven dependent steps) must not be what the vector pipe waits for — the compiler's
-      // order interleaved two pairs and the segment took 1 900 cycles with the matrix pipe idle beside it.
-#pragma unroll
-      for (int st = 0; st < 3; ++st) {
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            pf[m][st][e] = cvt_pk_bf16(s[8 * m + 2 * e], s[8 * m + 2 * e + 1]);
-            sf[m][st][e] = cvt_pk_bf16(dp[8 * m + 2 * e], dp[8 * m + 2 * e + 1]);
-          }
-        PP_PIN();
-        if (st < 2) {
-#pragma unroll
-          for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              s[8 * m + 2 * e] = bx_res_lo(s[8 * m + 2 * e], pf[m][st][e]);
-              s[8 * m + 2 * e + 1] = bx_res_hi(s[8 * m + 2 * e + 1], pf[m][st][e]);
-              dp[8 * m + 2 * e] = bx_res_lo(dp[8 * m + 2 * e], sf[m][st][e]);
-              dp[8 * m + 2 * e + 1] = bx_res_hi(dp[8 * m + 2 * e + 1], sf[m][st][e]);
-            }
-          PP_PIN();
-        }
-      }
-      // dS pieces -> [key][query] image (registers 4g..4g+3 = queries 8g + 4h .. +3 of this lane's key)
-#pragma unroll
-      for (int pc = 0; pc < 3; ++pc)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<u32x2*>(img + (pc * 32 + li) * TP + 8 * g + 4 * lh) =
-              (u32x2){sf[g >> 1][pc][2 * (g & 1)], sf[g >> 1][pc][2 * (g & 1) + 1]};
-    }
-    if (grp == 0 && k >= 2 && !(DBG & 512) && !(DBG & 2048)) {  // sub-block k-2's eight dQ partials (complete since the barrier before this
-      sum_read(k & 1, 0, 8);                   // segment) -> its rows of the dQ plane
-      sum_store(k - 2);
-    }
-    if constexpr (DBG & 8) { __builtin_amdgcn_sched_barrier(0); sb = __builtin_amdgcn_s_memtime(); st_acc[2] += sb - sa; }
-  };
-  auto sync = [&]() {
-    PP_BARRIER();
-    if constexpr (DBG & 8) { sa = __builtin_amdgcn_s_memtime(); st_acc[3] += sa - sb; sb = sa; }
-  };
-
-  if (NS > 0) {  // (every wavefront of the workgroup has the same NS: the barrier counts agree)
-    {  // prologue: sub-blocks 0 and 1 (twelve pieces each, three per wavefront)
-#pragma unroll
-      for (int u = 0; u < 3; ++u) {
-        const int id = wave * 3 + u;  // 0..23
-        stage_piece(id / 12, id / 12, id % 12);
-      }
-      if (wave < 2) {
-        lsd_load(wave);
-        lsd_store(wave, wave);
-      }
-    }
-    PP_BARRIER_VM();
-    if (grp == 1) PP_BARRIER();  // one segment behind
-    seg_m(0, no_t(), yes_t());
-    PP_BARRIER_VM();
-    seg_v(0, no_t(), yes_t());
-    sync();
-    for (int k = 1; k < NS; ++k) {
-      seg_m(k, yes_t(), yes_t());
-      PP_BARRIER_VM();
-      seg_v(k, yes_t(), yes_t());
-      sync();
-    }
-    seg_m(NS, yes_t(), no_t());
-    PP_BARRIER_VM();
-    seg_v(NS, yes_t(), no_t());
-    sync();
-    if (grp == 0) {
-      PP_BARRIER();
-      // the last sub-block's partials (written in V(NS))
-      sum_read((NS - 1) & 1, 0, 8);
-      sum_store(NS - 1);
-    }
-  }
-  if constexpr (DBG & 8) {
-    if ((blockIdx.x == 7 || blockIdx.x == 2000) && lane == 0 && (wave == 0 || wave == 5) && NS > 0) {
-      const unsigned long long n = NS + 1;
-      printf("bwd_bxpp stamps (workgroup %d wave %d, %d sub-blocks): per sub-block  M %llu (staging stores until %llu, bookkeeping until %llu, back "
-             "until %llu)  barrier %llu  V %llu  barrier %llu  = %llu cycles\n", (int)blockIdx.x, wave, NS, st_acc[0] / n,
-             st_acc[6] / n, st_acc[4] / n, st_acc[5] / n, st_acc[1] / n, st_acc[2] / n, st_acc[3] / n,
-             (st_acc[0] + st_acc[1] + st_acc[2] + st_acc[3]) / n);
-    }
+    LDS_BARRIER();
   }
   if (!jok) return;
   float* okp;
@@ -1978,14 +1487,9 @@ int sf_attn_dq_reduce(const float* ws, float* dq, int dq_cs, int B, int N, int C
 static int g_attn_nw = [] { const char* e = getenv("SF_ATTN_BX_NW"); return e ? atoi(e) : 0; }();
 static int g_sweep_parts = [] { const char* e = getenv("SF_SWEEP_PARTS"); return e ? atoi(e) : 0; }();
 
-// SF_ATTN_BX_PP / sf_attn_tune(2, .): the 8-wavefront bf16-piece backward as the ping-pong schedule
-// (attn_bwd_bxpp_kernel) or as the free-running sweep (attn_bwd_bx_kernel<., 8>)
-static int g_attn_pp = [] { const char* e = getenv("SF_ATTN_BX_PP"); return e ? atoi(e) : 0; }();
-
 extern "C" int sf_attn_tune(int knob, int value) {
   if (knob == 0 && (value == 0 || value == 4 || value == 8)) g_attn_nw = value;
   else if (knob == 1 && value >= 0 && value <= SF_SWEEP_PARTS_MAX) g_sweep_parts = value;
-  else if (knob == 2 && (value == 0 || value == 1)) g_attn_pp = value;
   else return SF_EINVAL;
   return SF_OK;
 }
@@ -2045,50 +1549,14 @@ int launch_fused_bx(BwdArgs a, float* ws, float* bx_ws, hipStream_t s) {
   a.dvp = a.dkp + part;
   unsigned short* qb = reinterpret_cast<unsigned short*>(bx_ws);
   unsigned short* db = qb + sf_attn_bx_plane_elems(a.B, a.N);
-  static const int stagger = [] { const char* e = getenv("SF_ATTN_STAGGER"); return e ? atoi(e) : 0; }();
-  a.stagger = stagger;
   int rc = sf_attn_bx_split(a.q, a.q_cs, nullptr, a.B, a.N, a.C, qb, nullptr, s);
   if (rc == SF_OK) rc = sf_attn_bx_split(a.dz, a.dz_cs, a.gamma, a.B, a.N, a.C, db, nullptr, s);
   if (rc != SF_OK) return rc;
-  using Kern = void (*)(const BwdArgs, float*, const unsigned short*, const unsigned short*, int);
-  static const Kern kern = [] {  // SF_ATTN_BX_DBG: timing ablations (see the kernel)
-    const char* e = getenv("SF_ATTN_BX_DBG");
-    const int dbg = e ? atoi(e) : 0;
-    if (NW == 8) return dbg == 2 ? (Kern)attn_bwd_bx_kernel<2, 8> : dbg == 8 ? (Kern)attn_bwd_bx_kernel<8, 8> : (Kern)attn_bwd_bx_kernel<0, 8>;
-    switch (dbg) {
-      case 1: return (Kern)attn_bwd_bx_kernel<1, 4>;
-      case 2: return (Kern)attn_bwd_bx_kernel<2, 4>;
-      case 3: return (Kern)attn_bwd_bx_kernel<3, 4>;
-      case 4: return (Kern)attn_bwd_bx_kernel<4, 4>;
-      case 7: return (Kern)attn_bwd_bx_kernel<7, 4>;
-      default: return (Kern)attn_bwd_bx_kernel<0, 4>;
-    }
-  }();
-  static const int pad = [] { const char* e = getenv("SF_ATTN_BX_PADLDS"); return e ? atoi(e) : 0; }();  // occupancy probe
-  if (NW == 8 && g_attn_pp) {  // the ping-pong schedule of the same sweep
-    static const Kern pp = [] {
-      const char* e = getenv("SF_ATTN_BX_DBG");
-      switch (e ? atoi(e) : 0) {
-        case 8: return (Kern)attn_bwd_bxpp_kernel<8>;
-        case 16: return (Kern)attn_bwd_bxpp_kernel<16>;    // no s_setprio
-        case 32: return (Kern)attn_bwd_bxpp_kernel<32>;    // V segments without exp2 / splits / image (results invalid)
-        case 64: return (Kern)attn_bwd_bxpp_kernel<64>;    // M segments without MFMAs (results invalid)
-        case 256: return (Kern)attn_bwd_bxpp_kernel<256>;    // (no stamps: a stamp's s_memtime drains lgkmcnt)
-        case 512: return (Kern)attn_bwd_bxpp_kernel<512>;
-        case 128: return (Kern)attn_bwd_bxpp_kernel<128>;
-        case 640: return (Kern)attn_bwd_bxpp_kernel<640>;
-        case 2048: return (Kern)attn_bwd_bxpp_kernel<2048>;  // no slot sums (results invalid)
-        case 4096: return (Kern)attn_bwd_bxpp_kernel<4096>;  // no staging (results invalid)  // V segments with the probe's register-only vector work, stamps  // M segments without fragment reads (results invalid), stamps
-        default: return (Kern)attn_bwd_bxpp_kernel<0>;
-      }
-    }();
-    hipLaunchKernelGGL(pp, dim3(a.B * a.zs * a.nt), dim3(512), 0, s, a, ws, qb, db, sf_cdiv(a.N, qt));  // static LDS
-  } else {
-    static SfLdsAttr lds_attr;
-    if (!sf_ensure_dyn_lds(lds_attr, reinterpret_cast<const void*>(kern), bxb_lds_bytes(NW) + pad)) return SF_ELAUNCH;
-    hipLaunchKernelGGL(kern, dim3(a.B * a.zs * a.nt), dim3(64 * NW), bxb_lds_bytes(NW) + pad, s, a, ws, qb, db,
-                       sf_cdiv(a.N, qt));
-  }
+  static SfLdsAttr lds_attr;
+  if (!sf_ensure_dyn_lds(lds_attr, reinterpret_cast<const void*>(attn_bwd_bx_kernel<NW>), bxb_lds_bytes(NW)))
+    return SF_ELAUNCH;
+  hipLaunchKernelGGL((attn_bwd_bx_kernel<NW>), dim3(a.B * a.zs * a.nt), dim3(64 * NW), bxb_lds_bytes(NW), s, a, ws, qb,
+                     db, sf_cdiv(a.N, qt));
   SF_CHECK_LAUNCH();
   if (a.zs > 1) {
     rc = sf_attn_dq_reduce(a.dkp, a.dk, a.dk_cs, a.B, a.N, a.C, CP, a.zs, s);
@@ -2199,7 +1667,7 @@ extern "C" int sf_attn_bwd(const float* q, int q_cs, const float* k, int k_cs, c
   a.dq = dq; a.dk = dk; a.dv = dv;
   a.q_cs = q_cs; a.k_cs = k_cs; a.v_cs = v_cs; a.dz_cs = dz_cs; a.dq_cs = dq_cs; a.dk_cs = dk_cs; a.dv_cs = dv_cs;
   a.B = B; a.C = C; a.N = N; a.nt = sf_cdiv(N, 128);
-  a.zs = 1; a.dkp = a.dvp = a.dqp = nullptr; a.stagger = 0;
+  a.zs = 1; a.dkp = a.dvp = a.dqp = nullptr;
   hipStream_t s = (hipStream_t)stream;
   if (C <= 16)  // 16x16x4 tiles: no padded rows
     return sf_attn_small_bwd_dispatch(q, q_cs, k, k_cs, v, v_cs, dz, dz_cs, lse, dvec, gamma, dq, dq_cs, dk, dk_cs,
@@ -2246,13 +1714,11 @@ static bool sf_attn_bx_wide(int B, int N) {
 // 5 / 6 = f32 MFMA d <= 32 / d <= 64, 7 = two-kernel form (d = 128); 0 = shape not served.
 extern "C" int sf_attn_bwd_variant(int B, int N, int C) {
   if (sf_attn_bwd_fused_ws_floats(B, N, C) == 0) return 0;
-  const bool bx = sf_attn_bx_level() >= 1;
-  if (C > 4 && C <= 8 && C % 4 == 0 && bx) return 20 + (g_attn_nw == 8 ? 8 : 4);
+  if (C > 4 && C <= 8 && C % 4 == 0) return 20 + (g_attn_nw == 8 ? 8 : 4);
   if (C <= 16) return 14;
   if (C > 64) return 74;
-  if (C <= 32) return (C % 4 == 0 && bx) ? 30 + (sf_attn_bx_wide(B, N) ? 8 : 4) : 54;
-  static const bool bx64 = [] { const char* e = getenv("SF_ATTN_BX64"); return !(e && e[0] == '0'); }();
-  return (C % 4 == 0 && bx && bx64) ? 44 : 64;
+  if (C <= 32) return C % 4 == 0 ? 30 + (sf_attn_bx_wide(B, N) ? 8 : 4) : 54;
+  return C % 4 == 0 ? 44 : 64;
 }
 
 extern "C" int sf_attn_bwd_fused(const float* q, int q_cs, const float* k, int k_cs, const float* v, int v_cs,
@@ -2261,14 +1727,14 @@ extern "C" int sf_attn_bwd_fused(const float* q, int q_cs, const float* k, int k
                                  float* ws, void* stream) {
   if (!q || !k || !v || !dz || !lse || !dvec || !gamma || !dq || !dk || !dv || !ws) return SF_EINVAL;
   if (sf_attn_bwd_fused_ws_floats(B, N, C) == 0 || !sf_aligned16(ws)) return SF_EINVAL;
-  if (C > 4 && C <= 8 && C % 4 == 0 && sf_attn_bx_level() >= 1 && (q_cs % 4 == 0) && (k_cs % 4 == 0) &&
+  if (C > 4 && C <= 8 && C % 4 == 0 && (q_cs % 4 == 0) && (k_cs % 4 == 0) &&
       (v_cs % 4 == 0) && (dz_cs % 4 == 0) && (dk_cs % 4 == 0) && (dv_cs % 4 == 0) && sf_aligned16(q) &&
       sf_aligned16(k) && sf_aligned16(v) && sf_aligned16(dz) && sf_aligned16(dk) && sf_aligned16(dv)) {
     BwdArgs a;  // packed planes on the bf16 pipe
     a.q = q; a.k = k; a.v = v; a.dz = dz; a.lse = lse; a.dvec = dvec; a.gamma = gamma;
     a.dq = dq; a.dk = dk; a.dv = dv;
     a.q_cs = q_cs; a.k_cs = k_cs; a.v_cs = v_cs; a.dz_cs = dz_cs; a.dq_cs = dq_cs; a.dk_cs = dk_cs; a.dv_cs = dv_cs;
-    a.B = B; a.C = C; a.N = N; a.dqp = nullptr; a.stagger = 0;
+    a.B = B; a.C = C; a.N = N; a.dqp = nullptr;
     // 128 keys per workgroup: the dQ planes are a quarter of the d = 32 ones, and 8-wavefront barriers cost more than
     // halving them saves (N = 25 088, B = 8: 5.00 ms against 5.26).  SF_ATTN_BX_NW=8 forces the wide form.
     const bool wide = g_attn_nw == 8;
@@ -2285,7 +1751,6 @@ extern "C" int sf_attn_bwd_fused(const float* q, int q_cs, const float* k, int k
   a.q_cs = q_cs; a.k_cs = k_cs; a.v_cs = v_cs; a.dz_cs = dz_cs; a.dq_cs = dq_cs; a.dk_cs = dk_cs; a.dv_cs = dv_cs;
   a.B = B; a.C = C; a.N = N; a.nt = sf_cdiv(N, 128);
   a.dqp = nullptr;
-  a.stagger = 0;
   if (C > 64) {  // d = 128: both kernels of the two-kernel form, their sweeps cut into parts so that B * N/128 < 2 x 256
     hipStream_t st = (hipStream_t)stream;  // workgroups become B * N/128 * z; the parts are summed in part order
     a.zs = sf_sweep_parts((long)B * a.nt, sf_cdiv(N, 32));
@@ -2305,7 +1770,7 @@ extern "C" int sf_attn_bwd_fused(const float* q, int q_cs, const float* k, int k
     const bool vec4 = (C % 4 == 0) && (q_cs % 4 == 0) && (k_cs % 4 == 0) && (v_cs % 4 == 0) && (dz_cs % 4 == 0) &&
                       (dk_cs % 4 == 0) && (dv_cs % 4 == 0) && sf_aligned16(q) && sf_aligned16(k) && sf_aligned16(v) &&
                       sf_aligned16(dz) && sf_aligned16(dk) && sf_aligned16(dv);
-    if (vec4 && sf_attn_bx_level() >= 1) {
+    if (vec4) {
       // 256 keys (8 wavefronts, one workgroup per CU) per workgroup where that still fills the chip: half the dQ
       // planes to write and to sum (N = 25 088, B = 8: 9.20 -> 8.70 ms).  SF_ATTN_BX_NW=4|8 forces either.
       const bool wide = sf_attn_bx_wide(B, N);
@@ -2319,8 +1784,7 @@ extern "C" int sf_attn_bwd_fused(const float* q, int q_cs, const float* k, int k
     const bool vec4 = (C % 4 == 0) && (q_cs % 4 == 0) && (k_cs % 4 == 0) && (v_cs % 4 == 0) && (dz_cs % 4 == 0) &&
                       (dk_cs % 4 == 0) && (dv_cs % 4 == 0) && sf_aligned16(q) && sf_aligned16(k) && sf_aligned16(v) &&
                       sf_aligned16(dz) && sf_aligned16(dk) && sf_aligned16(dv);
-    static const bool bx64 = [] { const char* e = getenv("SF_ATTN_BX64"); return !(e && e[0] == '0'); }();
-    if (vec4 && bx64 && sf_attn_bx_level() >= 1)
+    if (vec4)
       return launch_fused_bx2(a, ws, ws + (sf_attn_bwd_fused_ws_floats(B, N, C) - 2 * sf_attn_bx_plane_elems(B, N)),
                               (hipStream_t)stream);
   }

@@ -25,7 +25,6 @@
 // fp32 throughout (the reference never leaves fp32; gfx950 has no reduced-precision f32 MFMA path).
 #include "attn_args.h"
 #include "attn_bx.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -231,8 +230,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs p) {
       // a v_sub / v_add issued beside them is NOT hidden (tools/microbench/mfma_coexec.hip: +4.5 cycles each, v_exp
       // +7.5) — so the softmax keeps its vector work minimal: the tile is accumulated ON TOP of -m_ref (the first
       // MFMA's C operand is a register block holding -m_ref of this lane's query), with m_ref a STALE running
-      // maximum that is only refreshed when a tile exceeds it by more than 2^soft_t (then S is recomputed from 0 and
-      // O, l are rescaled — the classic online-softmax step, taken a handful of times per sweep): no subtraction,
+      // maximum that is only refreshed when a tile exceeds it by more than 2^ATTN_SOFT_T (then S is recomputed from 0
+      // and O, l are rescaled — the classic online-softmax step, taken a handful of times per sweep): no subtraction,
       // no per-tile rescale factor, and the row sums are kept as packed partial sums.
       krow = Ks + (buf * KT + sub * 32 + li) * KS + lh * 4;
       s = negm;
@@ -254,7 +253,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs p) {
 #pragma unroll
       for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, s[r]), s[r + 1]);
       mx = fmaxf(mx, s[15]);
-      if (__any(mx > p.soft_t)) {  // refresh the reference (always on the first tile: -m_ref = +BIG there)
+      if (__any(mx > ATTN_SOFT_T)) {  // refresh the reference (always on the first tile: -m_ref = +BIG there)
 #pragma unroll
         for (int r = 0; r < 16; ++r) s[r] = 0.f;
 #pragma unroll
@@ -447,27 +446,12 @@ __global__ __launch_bounds__(256) void attn_bx_split_packed_kernel(const float* 
 // everything else in the step) around the softmax of block g, then the second product of block g around the
 // reference check of block g+1.  K is therefore needed one block earlier than V: three K buffers (tile t+2 is staged
 // while t is swept), two V buffers, one barrier per 64-key tile.
-// DBG: 1 = P^T is not split (its leading piece three times), 4 = one product instead of six (timing ablations,
-// results invalid); 32 = the compiler's instruction order instead of the placed one (valid results, 4 % slower).
-template <int DBG, class V>
-__device__ __forceinline__ void split_pair_dbg(float a, float b, V (&dst)[3], int idx) {
-  if constexpr (DBG != 0) {
-    dst[0][idx] = dst[1][idx] = dst[2][idx] = cvt_pk_bf16(a, b);
-  } else {
-    split_pair(a, b, dst, idx);
-  }
-}
-template <int DBG>
-__device__ __forceinline__ f32x16 mfma_split_dbg(const u32x4 (&a)[3], const u32x4 (&b)[3], f32x16 c) {
-  if constexpr (DBG & 4) return mfma_bf(a[0], b[0], c);
-  return mfma_split(a, b, c);
-}
 
 constexpr int BX_VP = BX_KT + 8;         // V^T plane row pitch in LDS (144 B)
 constexpr int BX_KPL = BX_KT * BX_KP, BX_VPL = 32 * BX_VP;
 constexpr int BX_LDS_BYTES = (3 * 3 * BX_KPL + 2 * 3 * BX_VPL) * 2;  // 72 KB: two workgroups per CU
 
-template <int CP, int DBG = 0>
+template <int CP>
 __global__ __launch_bounds__(256, 2) void attn_fwd_bx_kernel(const AttnArgs p, const unsigned short* kb,
                                                              const unsigned short* vb, int n64) {
   static_assert(CP == 32, "plane layout and staging are laid out for d = 32");
@@ -563,17 +547,17 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bx_kernel(const AttnArgs p, c
       for (int pc = 0; pc < 3; ++pc) kf[c][pc] = *reinterpret_cast<const u32x4*>(krow + pc * KPL + 16 * c);
     s_next = negm;
 #pragma unroll
-    for (int c = 0; c < NC; ++c) s_next = mfma_split_dbg<DBG>(kf[c], qf[c], s_next);
+    for (int c = 0; c < NC; ++c) s_next = mfma_split(kf[c], qf[c], s_next);
   };
-  // Slow path, a handful of times per sweep: the block exceeds the stale reference by more than 2^soft_t somewhere
-  // (always on the first block, where -m_ref = +BIG), or it reaches past N (the planes are zero there, the scores must
-  // be -BIG).  Recompute it from 0, mask, move the reference, rescale O and l.
+  // Slow path, a handful of times per sweep: the block exceeds the stale reference by more than 2^ATTN_SOFT_T
+  // somewhere (always on the first block, where -m_ref = +BIG), or it reaches past N (the planes are zero there, the
+  // scores must be -BIG).  Recompute it from 0, mask, move the reference, rescale O and l.
   auto refresh = [&](int jbase) {
     f32x16 s;
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = 0.f;
 #pragma unroll
-    for (int c = 0; c < NC; ++c) s = mfma_split_dbg<DBG>(kf[c], qf[c], s);
+    for (int c = 0; c < NC; ++c) s = mfma_split(kf[c], qf[c], s);
     if (jbase + 32 > N) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
@@ -600,12 +584,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bx_kernel(const AttnArgs p, c
 #pragma unroll
     for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, s_next[r]), s_next[r + 1]);
     mx = fmaxf(mx, s_next[15]);
-    if (__any(mx > p.soft_t) || jbase + 32 > N) refresh(jbase);
+    if (__any(mx > ATTN_SOFT_T) || jbase + 32 > N) refresh(jbase);
   };
-  // one pipeline step: softmax + second product of the block in s_next, first product of the block after it
-  auto step = [&](auto HAS_NEXT, int vbuf, int sub, int kbuf_n, int sub_n) {
+  // the last pipeline step: softmax + second product of the block in s_next (no block after it)
+  auto step = [&](int vbuf, int sub) {
     f32x16 s = s_next;
-    if constexpr (decltype(HAS_NEXT)::value) qk(kbuf_n, sub_n);
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r]);
 #pragma unroll
@@ -617,28 +600,26 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bx_kernel(const AttnArgs p, c
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) split_pair_dbg<(DBG & 1)>(s[8 * m + 2 * e], s[8 * m + 2 * e + 1], pf[m], e);
+      for (int e = 0; e < 4; ++e) split_pair(s[8 * m + 2 * e], s[8 * m + 2 * e + 1], pf[m], e);
     const unsigned short* vrow = Vs + vbuf * 3 * VPL + li * VP + sub * 32 + 8 * lh;
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
       u32x4 vf[3];
 #pragma unroll
       for (int pc = 0; pc < 3; ++pc) vf[pc] = *reinterpret_cast<const u32x4*>(vrow + pc * VPL + 16 * m);
-      o[0] = mfma_split_dbg<DBG>(vf, pf[m], o[0]);
+      o[0] = mfma_split(vf, pf[m], o[0]);
     }
   };
-  // The same step with its vector work PLACED: one MFMA, then the fillers that fit the 24 issue cycles it leaves
-  // (v_exp 8, the others ~4.3 each), pinned by sched_barrier — the compiler's own order front-loads the softmax and
-  // leaves the second product's MFMAs bare.  Worth 4 % (3.61 -> 3.48 ms at N = 25 088, B = 8): with two wavefronts per
-  // SIMD the issue port is shared, and under this load the part holds ~1.6 GHz (20 ns per 32x32x16 MFMA).
+  // Every other step: softmax + second product of the block in s_next, first product of the block after it, with its
+  // vector work PLACED: one MFMA, then the fillers that fit the 24 issue cycles it leaves (v_exp 8, the others ~4.3
+  // each), pinned by sched_barrier — the compiler's own order front-loads the softmax and leaves the second product's
+  // MFMAs bare.  Worth 4 % (3.61 -> 3.48 ms at N = 25 088, B = 8): with two wavefronts per SIMD the issue port is
+  // shared, and under this load the part holds ~1.6 GHz (20 ns per 32x32x16 MFMA).
   float mx_next = 0.f;  // max of s_next over this lane's 16 keys, formed in the step's last MFMA gaps
   auto check_placed = [&](int jbase) {
-    if (__any(mx_next > p.soft_t) || jbase + 32 > N) refresh(jbase);
+    if (__any(mx_next > ATTN_SOFT_T) || jbase + 32 > N) refresh(jbase);
   };
-  unsigned long long st_acc[5] = {0, 0, 0, 0, 0};  // DBG & 64: cycles per phase (s_memtime), printed by one wavefront
   auto step_placed = [&](int vbuf, int sub, int kbuf_n, int sub_n) {
-    unsigned long long tq0 = 0, tq1 = 0, tq2 = 0, tq3 = 0;
-    if constexpr (DBG & 64) { __builtin_amdgcn_sched_barrier(0); tq0 = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
     constexpr int OA[6] = {0, 2, 1, 0, 1, 0}, OB[6] = {2, 0, 1, 1, 0, 0};  // mfma_split's order, small terms first
     f32x16 s = s_next;
     const unsigned short* krow = Ks + kbuf_n * 3 * KPL + (sub_n * 32 + li) * KP + 8 * lh;
@@ -690,7 +671,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bx_kernel(const AttnArgs p, c
     QK(9); SA(0, 3); SF_GAP();
     QK(10); SB(0, 3); SF_GAP();
     QK(11); E(9); E(10); E(11); SF_GAP();
-    if constexpr (DBG & 64) { tq1 = __builtin_amdgcn_s_memtime(); SF_GAP(); }
     PV(0); E(12); E(13); E(14); SF_GAP();
     PV(1); E(15); SA(1, 0); SF_GAP();
     PV(2); SB(1, 0); SF_GAP();
@@ -698,7 +678,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bx_kernel(const AttnArgs p, c
     PV(4); SB(1, 1); SF_GAP();
     PV(5); SA(1, 2); SF_GAP();
     SB(1, 2); SA(1, 3); SB(1, 3); SF_GAP();
-    if constexpr (DBG & 64) { tq2 = __builtin_amdgcn_s_memtime(); SF_GAP(); }
     PV(6); lacc[0] += s[0]; lacc[1] += s[1]; lacc[0] += s[2]; lacc[1] += s[3]; lacc[0] += s[4]; SF_GAP();
     PV(7); lacc[1] += s[5]; lacc[0] += s[6]; lacc[1] += s[7]; lacc[0] += s[8]; lacc[1] += s[9]; SF_GAP();
     PV(8); lacc[0] += s[10]; lacc[1] += s[11]; lacc[0] += s[12]; lacc[1] += s[13]; lacc[0] += s[14]; SF_GAP();
@@ -707,21 +686,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bx_kernel(const AttnArgs p, c
     PV(10); mx_next = fmaxf(fmaxf(mx_next, s_next[7]), s_next[8]); mx_next = fmaxf(fmaxf(mx_next, s_next[9]), s_next[10]);
     mx_next = fmaxf(fmaxf(mx_next, s_next[11]), s_next[12]); SF_GAP();
     PV(11); mx_next = fmaxf(fmaxf(mx_next, s_next[13]), s_next[14]); mx_next = fmaxf(mx_next, s_next[15]); SF_GAP();
-    if constexpr (DBG & 64) {
-      tq3 = __builtin_amdgcn_s_memtime();
-      SF_GAP();
-      st_acc[0] += tq1 - tq0;
-      st_acc[1] += tq2 - tq1;
-      st_acc[2] += tq3 - tq2;
-      st_acc[3] += 1;
-    }
 #undef SF_GAP
   };
-  using T = std::true_type;
-  using F = std::false_type;
 
-  unsigned long long tl0 = 0, st_tile[6] = {0, 0, 0, 0, 0, 0};
-  if constexpr (DBG & 64) tl0 = __builtin_amdgcn_s_memtime();
   if (nt > 0) {
     load_k(t0);
     load_v(t0);
@@ -736,48 +703,23 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bx_kernel(const AttnArgs p, c
     for (int r = 0; r < nt; ++r) {
       const int t = t0 + r;
       const int knext = kcur == 2 ? 0 : kcur + 1, kafter = knext == 2 ? 0 : knext + 1;
-      unsigned long long u0 = 0, u1 = 0, u2 = 0, u3 = 0, u4 = 0, u5 = 0;
-      if constexpr (DBG & 64) u0 = __builtin_amdgcn_s_memtime();
       load_k(min(t + 2, n64 - 1));  // past the part's end: a tile nobody reads
       load_v(min(t + 1, n64 - 1));
-      if constexpr (DBG & 64) { __builtin_amdgcn_sched_barrier(0); u1 = __builtin_amdgcn_s_memtime(); }
-      if constexpr (DBG & 32) step(T{}, r & 1, 0, kcur, 1); else step_placed(r & 1, 0, kcur, 1);
-      if constexpr (DBG & 64) { __builtin_amdgcn_sched_barrier(0); u2 = __builtin_amdgcn_s_memtime(); }
-      if constexpr (DBG & 32) check(t * KT + 32); else check_placed(t * KT + 32);
-      if constexpr (DBG & 64) { __builtin_amdgcn_sched_barrier(0); u3 = __builtin_amdgcn_s_memtime(); }
+      step_placed(r & 1, 0, kcur, 1);
+      check_placed(t * KT + 32);
       if (r + 1 < nt) {
-        if constexpr (DBG & 32) step(T{}, r & 1, 1, knext, 0); else step_placed(r & 1, 1, knext, 0);
-        if constexpr (DBG & 32) check(t * KT + 64); else check_placed(t * KT + 64);
+        step_placed(r & 1, 1, knext, 0);
+        check_placed(t * KT + 64);
       } else {
-        step(F{}, r & 1, 1, 0, 0);
+        step(r & 1, 1);
       }
-      if constexpr (DBG & 64) { __builtin_amdgcn_sched_barrier(0); u4 = __builtin_amdgcn_s_memtime(); }
       store_k(kafter);
       store_v((r + 1) & 1);
       __syncthreads();
-      if constexpr (DBG & 64) {
-        u5 = __builtin_amdgcn_s_memtime();
-        st_tile[0] += u1 - u0;  // loads issue
-        st_tile[1] += u2 - u1;  // step a
-        st_tile[2] += u3 - u2;  // check a
-        st_tile[3] += u4 - u3;  // step b + check b
-        st_tile[4] += u5 - u4;  // stores + barrier
-        st_tile[5] += 1;
-      }
       kcur = knext;
     }
   }
 
-  if constexpr (DBG & 64) {
-    st_acc[4] = __builtin_amdgcn_s_memtime() - tl0;
-    if (blockIdx.x == 7 && tid == 0)
-      printf("fwd_bx stamps (wave 0 of workgroup 7): steps %llu  per step: qk-phase %llu  pv0-phase %llu  pv1-phase %llu  | sweep total %llu = %llu per step\n",
-             st_acc[3], st_acc[0] / st_acc[3], st_acc[1] / st_acc[3], st_acc[2] / st_acc[3], st_acc[4], st_acc[4] / st_acc[3]);
-    if (blockIdx.x == 7 && tid == 0)
-      printf("fwd_bx per tile: loads %llu  step a %llu  check a %llu  step b + check %llu  stores + barrier %llu\n",
-             st_tile[0] / st_tile[5], st_tile[1] / st_tile[5], st_tile[2] / st_tile[5], st_tile[3] / st_tile[5],
-             st_tile[4] / st_tile[5]);
-  }
   const float l_run = lacc[0] + lacc[1];
   attn_fwd_finish<CP, 4>(p, o, m_run, l_run + __shfl_xor(l_run, 32, 64), b, bz, q0 + li, lh);
 }
@@ -897,7 +839,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_bxp_kernel(const AttnArgs p, 
 #pragma unroll
     for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, s_next[r]), s_next[r + 1]);
     mx = fmaxf(mx, s_next[15]);
-    if (__any(mx > p.soft_t) || jbase + 32 > N) refresh(jbase);
+    if (__any(mx > ATTN_SOFT_T) || jbase + 32 > N) refresh(jbase);
   };
   auto step = [&](auto HAS_NEXT, int vbuf, int sub, int kbuf_n, int sub_n) {
     f32x16 s = s_next;
@@ -1113,7 +1055,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_bx2_kernel(const AttnArgs p, 
 #pragma unroll
     for (int r = 3; r < 15; r += 2) mx = fmaxf(fmaxf(mx, s_next[r]), s_next[r + 1]);
     mx = fmaxf(mx, s_next[15]);
-    if (__any(mx > p.soft_t) || jbase + 32 > N) refresh(jbase);
+    if (__any(mx > ATTN_SOFT_T) || jbase + 32 > N) refresh(jbase);
   };
   auto step = [&](auto HAS_NEXT, int vbuf, int sub, int kbuf_n, int sub_n) {
     f32x16 s = s_next;
@@ -1232,14 +1174,11 @@ __global__ __launch_bounds__(256) void attn_fwd_merge_kernel(const AttnArgs p, i
 template <int CP>
 int launch(AttnArgs a, bool vec4, hipStream_t s) {
   const int grid = a.B * a.zs * a.nqt;
-  // SF_ATTN_STALE=0: the per-tile online softmax (running maximum refreshed on every tile); SF_ATTN_SOFT_T: how far
-  // (log2) a tile may exceed the stale reference before it is refreshed
-  static const bool stale_on = [] { const char* e = getenv("SF_ATTN_STALE"); return !(e && e[0] == '0'); }();
-  a.soft_t = sf_attn_soft_t();
-  const bool stale = stale_on && CP <= 64;  // d = 128: the 16 extra registers cost the second wavefront per SIMD
+  // the stale-reference softmax, except at d = 128 (per-tile online softmax there): the 16 extra registers cost the
+  // second wavefront per SIMD
+  constexpr bool STALE = CP <= 64;
   if constexpr (CP == 64) {
-    static const bool bx64 = [] { const char* e = getenv("SF_ATTN_BX64"); return !(e && e[0] == '0'); }();
-    if (vec4 && a.bx_planes && bx64) {
+    if (vec4 && a.bx_planes) {
       const int n64 = sf_cdiv(a.N, BX_KT);
       const long blk_elems = sf_attn_bx_plane_elems(a.B, a.N);
       unsigned short* kb = reinterpret_cast<unsigned short*>(a.bx_planes);
@@ -1265,28 +1204,16 @@ int launch(AttnArgs a, bool vec4, hipStream_t s) {
       if (sf_attn_bx_split(a.k, a.k_cs, nullptr, a.B, a.N, a.C, kb, nullptr, s) != SF_OK ||
           sf_attn_bx_split(a.v, a.v_cs, nullptr, a.B, a.N, a.C, nullptr, vb, s) != SF_OK)
         return SF_ELAUNCH;
-      using Kern = void (*)(const AttnArgs, const unsigned short*, const unsigned short*, int);
-      static const Kern kern = [] {  // SF_ATTN_BX_DBG: timing ablations (see the kernel)
-        const char* e = getenv("SF_ATTN_BX_DBG");
-        const int dbg = e ? atoi(e) : 0;
-        return dbg == 1 ? (Kern)attn_fwd_bx_kernel<32, 1> : dbg == 32 ? (Kern)attn_fwd_bx_kernel<32, 32> : dbg == 64 ? (Kern)attn_fwd_bx_kernel<32, 64> : dbg == 4 ? (Kern)attn_fwd_bx_kernel<32, 4>
-                                                                      : (Kern)attn_fwd_bx_kernel<32, 0>;
-      }();
-      static const int pad = [] { const char* e = getenv("SF_ATTN_BX_PADLDS"); return e ? atoi(e) : 0; }();  // occupancy probe
       static SfLdsAttr lds_attr;  // 72 KB of dynamic LDS
-      if (!sf_ensure_dyn_lds(lds_attr, reinterpret_cast<const void*>(kern), BX_LDS_BYTES + pad)) return SF_ELAUNCH;
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), BX_LDS_BYTES + pad, s, a, kb, vb, n64);
+      if (!sf_ensure_dyn_lds(lds_attr, reinterpret_cast<const void*>(attn_fwd_bx_kernel<32>), BX_LDS_BYTES))
+        return SF_ELAUNCH;
+      hipLaunchKernelGGL(attn_fwd_bx_kernel<32>, dim3(grid), dim3(256), BX_LDS_BYTES, s, a, kb, vb, n64);
       SF_CHECK_LAUNCH();
       return a.zs > 1 ? sf_attn_fwd_merge(a, CP, s) : SF_OK;
     }
   }
-  if (vec4) {
-    if (stale) hipLaunchKernelGGL((attn_fwd_kernel<CP, 4, true>), dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<CP, 4, false>), dim3(grid), dim3(256), 0, s, a);
-  } else {
-    if (stale) hipLaunchKernelGGL((attn_fwd_kernel<CP, 1, true>), dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((attn_fwd_kernel<CP, 1, false>), dim3(grid), dim3(256), 0, s, a);
-  }
+  if (vec4) hipLaunchKernelGGL((attn_fwd_kernel<CP, 4, STALE>), dim3(grid), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((attn_fwd_kernel<CP, 1, STALE>), dim3(grid), dim3(256), 0, s, a);
   SF_CHECK_LAUNCH();
   return a.zs > 1 ? sf_attn_fwd_merge(a, CP, s) : SF_OK;
 }
@@ -1346,20 +1273,10 @@ static int attn_fwd_impl(const float* q, int q_cs, const float* k, int k_cs, con
                     (out_cs % 4 == 0) && (out_coff % 4 == 0) && sf_aligned16(q) && sf_aligned16(k) &&
                     sf_aligned16(v) && sf_aligned16(x) && sf_aligned16(out);
   hipStream_t s = (hipStream_t)stream;
-  // C <= 16: 16-query wavefronts on 16x16x4 tiles (no padded rows in the second product).  The same kernel also
-  // instantiates for 16 < C <= 32 (SF_ATTN_FWD32=small) — a probe of whether the 16x16x4 shape, which sustains a
-  // higher clock than 32x32x2 in a bare MFMA loop on this part, pays at d = 32: it does not in this form (one
-  // ds_read_b32 per MFMA for K^T and V, twice the softmax rows per FLOP): 5.6 -> 6.1 ms at N = 25 088, eval forward
-  // 19.31 -> 19.78 ms.  The 32x32x2 kernel stays the default.
-  static const bool small32 = [] {
-    const char* e = getenv("SF_ATTN_FWD32");
-    return e && e[0] == 's';
-  }();
-  if (C > 4 && C <= 8 && C % 4 == 0 && vec4 && ws && sf_attn_bx_level() >= 1) {  // packed planes on the bf16 pipe
+  if (C > 4 && C <= 8 && C % 4 == 0 && vec4 && ws) {  // packed planes on the bf16 pipe
     a.nqt = sf_cdiv(N, 128);
     a.zs = sf_sweep_parts((long)B * a.nqt, sf_cdiv(N, 64));
     sf_attn_place_parts(a, 8, ws);
-    a.soft_t = sf_attn_soft_t();
     unsigned short* kb = reinterpret_cast<unsigned short*>(ws + (long)B * SF_SWEEP_PARTS_MAX * N * (8 + 2));
     unsigned short* vb = kb + sf_attn_bx_packed_elems(B, (int)N);
     if (sf_attn_bx_split_packed(k, k_cs, nullptr, B, (int)N, C, kb, nullptr, s) != SF_OK ||
@@ -1369,7 +1286,8 @@ static int attn_fwd_impl(const float* q, int q_cs, const float* k, int k_cs, con
     SF_CHECK_LAUNCH();
     return a.zs > 1 ? sf_attn_fwd_merge(a, 8, s) : SF_OK;
   }
-  if (C <= 16 || (C <= 32 && small32))
+  // C <= 16: 16-query wavefronts on 16x16x4 tiles (no padded rows in the second product)
+  if (C <= 16)
     return sf_attn_small_dispatch(q, q_cs, k, k_cs, v, v_cs, x, x_cs, gamma, scale, bias, act, out, out_cs,
                                   out_coff, B, T, H, W, C, alpha, o_save, lse_save, vec4, ws, s);
   const int cp = C <= 32 ? 32 : (C <= 64 ? 64 : 128);
@@ -1377,7 +1295,7 @@ static int attn_fwd_impl(const float* q, int q_cs, const float* k, int k_cs, con
   if (ws) {
     a.zs = sf_sweep_parts((long)B * a.nqt, sf_cdiv(N, cp >= 128 ? 32 : 64));
     sf_attn_place_parts(a, cp, ws);
-    if ((cp == 32 || (cp == 64 && C > 32)) && sf_attn_bx_level() >= 1)  // the split K / V^T planes live behind the part buffers
+    if (cp == 32 || (cp == 64 && C > 32))  // the split K / V^T planes live behind the part buffers
       a.bx_planes = ws + (long)B * SF_SWEEP_PARTS_MAX * N * (cp + 2);
   }
   if (C <= 32) return launch<32>(a, vec4, s);
@@ -1394,9 +1312,7 @@ extern "C" int sf_attn_fwd(const float* q, int q_cs, const float* k, int k_cs, c
 }
 
 extern "C" int sf_attn_products_per_fp32(int C) {
-  if (sf_attn_bx_level() < 1) return 0;
-  static const bool bx64 = [] { const char* e = getenv("SF_ATTN_BX64"); return !(e && e[0] == '0'); }();
-  return ((C > 16 && C <= 32) || (C > 32 && C <= 64 && bx64) || (C > 4 && C <= 8 && C % 4 == 0)) ? 6 : 0;
+  return ((C > 16 && C <= 64) || (C > 4 && C <= 8 && C % 4 == 0)) ? 6 : 0;
 }
 
 // Room for the (O^T, m, l) of up to SF_SWEEP_PARTS_MAX key parts per query row.

@@ -1,5 +1,6 @@
-// attn_lane.hip — flash SpatialAttention for head dims d = 4 and d = 8 with ONE QUERY PER LANE on
-// v_mfma_f32_4x4x1_16B_f32 (16 independent 4x4 outer-product blocks per instruction, K = 1).
+// attn_lane.hip — flash SpatialAttention for head dim d = 4 with ONE QUERY PER LANE on v_mfma_f32_4x4x1_16B_f32
+// (16 independent 4x4 outer-product blocks per instruction, K = 1).  The kernel is written for d = 4 and 8; d = 8
+// stays on attn_small.hip (see sf_attn_lane_try).
 //
 // At d <= 8 the 16x16x4 tiles of attn_small.hip spend the second product (O^T = V^T P^T, M = channels) on 16-row
 // tiles of which d + 1 carry data: 9 of 16 at d = 8 (R50 s1_fuse, N = 25 088), 5 of 16 at d = 4 (GhostNet s1_fuse,
@@ -13,7 +14,6 @@
 // purely per-lane: no shuffles, no LDS exchange.  (wdf_attention_helper.py:41-54 + the CMDA tail
 // custom_video_model_builder.py:143-146, as attn_flash.hip.)
 #include "attn_args.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -245,15 +245,14 @@ int launch(const AttnArgs& a, hipStream_t s) {
 
 }  // namespace
 
-// Takes d = 4 problems whose views are all 16-byte addressable (SF_ATTN_LANE=8: d = 8 too; SF_ATTN_LANE=0: none);
-// returns 1 when it does not take the problem (attn_small.hip then runs).  Measured on MI355X
+// Takes d = 4 problems whose views are all 16-byte addressable and nothing else; returns 1 when it does not take the
+// problem (attn_small.hip then runs).  Measured on MI355X
 // (tools/microbench/attn_small_bench.py, same process pair): d = 4, N = 100 352, B = 2: 8.87 -> 6.3 ms; d = 8,
 // N = 25 088, B = 8: 2.62 -> 2.60 ms — at d = 8 the four-times-smaller MFMA instructions make the loop
 // instruction-issue bound (PMC: MFMA pipe busy 44 %, wavefronts waiting to issue 74 % of their cycles, 2.2 VALU
 // instructions per MFMA), which cancels the padding saved, so d = 8 stays on the 16x16x4 kernel.
 int sf_attn_lane_try(SfAttnArgs a, bool vec4, float* ws, hipStream_t stream) {
-  static const int mode = [] { const char* e = getenv("SF_ATTN_LANE"); return e ? atoi(e) : 4; }();
-  if (mode == 0 || !vec4 || !(a.C == 4 || (a.C == 8 && mode == 8))) return 1;
+  if (!vec4 || a.C != 4) return 1;
   if ((a.scale && !sf_aligned16(a.scale)) || (a.bias && !sf_aligned16(a.bias)) ||
       (a.o_save && !sf_aligned16(a.o_save)))
     return 1;
@@ -263,5 +262,5 @@ int sf_attn_lane_try(SfAttnArgs a, bool vec4, float* ws, hipStream_t stream) {
     a.zs = sf_sweep_parts((long)a.B * a.nqt, sf_cdiv(a.N, 128));
     sf_attn_place_parts(a, a.C, ws);
   }
-  return a.C == 4 ? launch<4>(a, stream) : launch<8>(a, stream);
+  return launch<4>(a, stream);
 }

@@ -22,14 +22,15 @@ constexpr float LOG2E = 1.4426950408889634f;
 
 template <int CP, int VEC>
 __global__ __launch_bounds__(256) void attn_small_kernel(const AttnArgs p) {
+  static_assert(CP <= 16, "d <= 16");
   constexpr int KT = 64;                        // keys per LDS tile = one softmax step
   constexpr int QS = CP / 4;                    // MFMA k-steps of the first product
   constexpr int KP = KT + 16;                   // K^T row pitch: quarter g lands 16 banks further
-  constexpr int VP = (CP == 32) ? 36 : ((CP == 16) ? 20 : 12);  // V row pitch: rows 4 apart land 16 banks apart
+  constexpr int VP = (CP == 16) ? 20 : 12;      // V row pitch: rows 4 apart land 16 banks apart
   constexpr int F4 = CP / 4;
   constexpr int NLD = KT * F4;                  // float4 per tile (K and V each)
-  constexpr int LIT = (NLD + 255) / 256;        // staging passes (2 for CP = 32)
-  constexpr int CTN = (CP + 15) / 16;           // 16-channel output tiles (2 for CP = 32)
+  constexpr int LIT = (NLD + 255) / 256;        // staging passes
+  constexpr int CTN = (CP + 15) / 16;           // 16-channel output tiles
 
   __shared__ __attribute__((aligned(16))) float smem[2 * (CP * KP + KT * VP)];
   float* const Kt = smem;
@@ -147,8 +148,8 @@ __global__ __launch_bounds__(256) void attn_small_kernel(const AttnArgs p) {
     // them costs its full issue time (tools/microbench/mfma_coexec.hip) and this kernel has only 24 MFMAs per 16
     // exponentials: the scores are accumulated ON TOP of -m_ref (C operand of each tile's first MFMA: all 16 scores
     // of a lane belong to ONE query, so a 4-register block serves the four tiles), m_ref being a stale running
-    // maximum that is refreshed only when a tile exceeds it by more than 2^soft_t — then the scores are recomputed
-    // from zero and O (with its ones-row denominator) rescaled, the classic online-softmax step.
+    // maximum that is refreshed only when a tile exceeds it by more than 2^ATTN_SOFT_T — then the scores are
+    // recomputed from zero and O (with its ones-row denominator) rescaled, the classic online-softmax step.
     f32x4 s[4];
     const float* kbase = Kt + (buf * CP + lg) * KP + li;
 #pragma unroll
@@ -185,7 +186,7 @@ __global__ __launch_bounds__(256) void attn_small_kernel(const AttnArgs p) {
     mx = fmaxf(fmaxf(mx, s[2][3]), s[3][0]);
     mx = fmaxf(fmaxf(mx, s[3][1]), s[3][2]);
     mx = fmaxf(mx, s[3][3]);
-    if (__any(mx > p.soft_t)) {  // refresh the reference (always on the first tile: -m_ref = +BIG there)
+    if (__any(mx > ATTN_SOFT_T)) {  // refresh the reference (always on the first tile: -m_ref = +BIG there)
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) {
         s[kt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -332,19 +333,17 @@ int sf_attn_small_dispatch(const float* q, int q_cs, const float* k, int k_cs, c
   a.o_save = o_save; a.lse_save = lse_save;
   a.q_cs = q_cs; a.k_cs = k_cs; a.v_cs = v_cs; a.x_cs = x_cs; a.out_cs = out_cs; a.out_coff = out_coff;
   a.B = B; a.T = T; a.H = H; a.W = W; a.C = C; a.N = T * H * W; a.alpha = alpha; a.act = act;
-  {  // d = 4 / d = 8: one query per lane on 4x4x1 MFMA blocks (attn_lane.hip) — no padded rows in either product
+  {  // d = 4: one query per lane on 4x4x1 MFMA blocks (attn_lane.hip) — no padded rows in either product
     const int rc = sf_attn_lane_try(a, vec4, ws, stream);
     if (rc != 1) return rc;
   }
   a.nqt = sf_cdiv(a.N, 64);
-  a.soft_t = sf_attn_soft_t();
   a.zs = 1; a.part_o = nullptr; a.part_ml = nullptr;
   if (ws) {
     a.zs = sf_sweep_parts((long)B * a.nqt, sf_cdiv(a.N, 64));
-    sf_attn_place_parts(a, C <= 4 ? 4 : (C <= 8 ? 8 : (C <= 16 ? 16 : 32)), ws);
+    sf_attn_place_parts(a, C <= 4 ? 4 : (C <= 8 ? 8 : 16), ws);
   }
   if (C <= 4) return launch<4>(a, vec4, stream);
   if (C <= 8) return launch<8>(a, vec4, stream);
-  if (C <= 16) return launch<16>(a, vec4, stream);
-  return launch<32>(a, vec4, stream);
+  return launch<16>(a, vec4, stream);
 }

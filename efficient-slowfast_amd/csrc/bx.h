@@ -9,7 +9,7 @@
 //     a b = a1 b1 + (a1 b2 + a2 b1) + (a2 b2 + a1 b3 + a3 b1) + O(2^-24 |a b|)
 // six bf16 MFMAs reproduce the fp32 product to fp32 rounding level (the three dropped terms are below 2^-24 |a||b|,
 // the size of one fp32 rounding) at 6/16 of the f32-MFMA cost.  Small terms are accumulated first.
-// tools/microbench/attn_precision.py measures both product paths against fp64.
+// tests/test_attention_bx_gpu.py holds the attention kernels built on this to the f32-MFMA kernels' bounds against fp64.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));

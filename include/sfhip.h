@@ -242,8 +242,8 @@ long sf_attn_fwd_ws_floats(int B, int N, int C);
 /* Which arithmetic serves the attention products of head width C when a workspace is given (sf_attn_fwd_ws,
  * sf_attn_bwd_fused): 0 = v_mfma_f32_*_f32 (fp32 operands); 6 = every fp32 operand as the exact sum of three bf16
  * pieces and every fp32 product as six v_mfma_f32_32x32x16_bf16 (fp32 accumulate; the dropped terms are below
- * 2^-24 |a||b|, one fp32 rounding) — 17 <= C <= 64 (33..64 as two 32-channel blocks; SF_ATTN_BX64=0 keeps those on
- * the f32 MFMA) and C = 8 (packed planes) with 16-byte aligned rows, unless SF_ATTN_BX=0.                        */
+ * 2^-24 |a||b|, one fp32 rounding) — 17 <= C <= 64 (33..64 as two 32-channel blocks) and C = 8 (packed planes)
+ * with 16-byte aligned rows; other views (C % 4 != 0, unaligned strides or pointers) take the f32 MFMA.           */
 int sf_attn_products_per_fp32(int C);
 int sf_attn_fwd_ws(const float* q, int q_cs, const float* k, int k_cs, const float* v, int v_cs,
                    const float* x, int x_cs, const float* gamma, const float* scale, const float* bias,
@@ -273,7 +273,7 @@ int sf_attn_bwd_fused(const float* q, int q_cs, const float* k, int k_cs, const 
  * 0 = shape not served).  The choice depends on the batch (B * ceil(N / 256) >= 256 selects the 8-wavefront form of
  * family 3, i.e. B >= 3 at N = 25 088): parity tests assert which one they exercised.                             */
 int sf_attn_bwd_variant(int B, int N, int C);
-/* Process-wide knobs of the attention launchers for tests / A-B runs: knob 0 = wavefronts per workgroup of the
+/* Process-wide knobs of the attention launchers for tests: knob 0 = wavefronts per workgroup of the
  * bf16-piece backward (0 = by shape, 4, 8); knob 1 = parts every sweep is cut into (0 = by fill, 1..8).          */
 int sf_attn_tune(int knob, int value);
 

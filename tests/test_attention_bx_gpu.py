@@ -1,9 +1,7 @@
 """The d = 32, d = 8 (packed planes) and d <= 64 (two channel blocks) attention kernels on the bf16 matrix pipe (attn_bx.h: fp32 operands as three
 bf16 pieces, six products per fp32 product) against an fp64 softmax attention and its autograd gradients on the same inputs — the bounds are
-those the f32-MFMA kernels meet (tools/microbench/attn_precision.py prints both paths side by side: at unit-scale
-scores O 1.2e-6 / 1.3e-6, gradients 3.7-5.0e-6 / 3.2-3.9e-6 of the tensor's max, split / f32 path)."""
-import os
-
+those the f32-MFMA kernels meet (at unit-scale scores O 1.2e-6 / 1.3e-6, gradients 3.7-5.0e-6 / 3.2-3.9e-6 of the
+tensor's max, split / f32 path)."""
 import pytest
 import torch
 
@@ -27,8 +25,6 @@ def attn_knobs():
 @pytest.mark.parametrize("scale,thw", [(0.3, (3, 27, 31)), (1.0, (3, 27, 31)), (1.0, (2, 16, 16)), (1.0, (1, 5, 7))])
 def test_split_product_attention_matches_fp64(scale, thw, c, nw, parts, attn_knobs):
     import sfhip
-    if os.environ.get("SF_ATTN_BX", "1") == "0":
-        pytest.skip("SF_ATTN_BX=0: the f32-MFMA kernels are selected")
     assert sfhip.lib().sf_attn_products_per_fp32(c) == 6  # d = 33..64: two 32-channel blocks
     if nw and c > 32:
         pytest.skip("the two-block kernels have one workgroup shape")

@@ -24,10 +24,10 @@ CSRC = os.path.join(ROOT, "efficient-slowfast_amd", "csrc")
 HOT = ("conv_rows_kernel", "conv_bx_kernel", "conv_pw_bx_kernel", "conv_bx_wgrad_kernel", "conv_wave_kernel", "conv_wgrad_wave_kernel",
        "attn_bwd_bx_kernel", "attn_bwd_bxp_kernel", "attn_bwd_bx2_kernel", "attn_fwd_bx_kernel", "attn_fwd_bxp_kernel",
        "attn_fwd_bx2_kernel", "conv_stem", "conv_wgrad_stem", "conv_wgrad_rows_kernel", "bn_bwd_", "affine_flat")
-# kernels that are allowed scratch (not launched by default / debug variants)
-EXEMPT = ("attn_bwd_bxpp_kernel",          # parked ping-pong variant: only behind sf_attn_tune(2, 1) / SF_ATTN_BX_PP=1
-          "attn_bwd_fused_kernelILi64",    # f32-input sweep for 32 < d <= 64: only with SF_ATTN_BX=0 (A/B runs)
-          "attn_bwd_dq_kernelILi64", "attn_bwd_dkv_kernelILi64")  # two-kernel f32 form for d = 64: SF_ATTN_BX=0 only
+# kernels that are allowed scratch: the f32-MFMA forms, which run only for views the bf16-piece forms reject
+# (C % 4 != 0, unaligned strides or pointers, sf_attn_fwd without a workspace, the public two-kernel sf_attn_bwd)
+EXEMPT = ("attn_bwd_fused_kernelILi64",    # fused f32 sweep for 32 < d <= 64
+          "attn_bwd_dq_kernelILi64", "attn_bwd_dkv_kernelILi64")  # two-kernel f32 form (sf_attn_bwd) for d = 64
 
 
 def flags_for(name):

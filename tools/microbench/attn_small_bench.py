@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Forward / backward time of the small-head-dim attention at the two production shapes: d = 8, N = 25 088, B = 8 (cfg #3
-s1_fuse) and d = 4, N = 100 352, B = 2 (cfg #5 s1_fuse).  Run with SF_ATTN_LANE=0 / 1 (and SF_ATTN_LANE_BWD) to A/B.
+s1_fuse) and d = 4, N = 100 352, B = 2 (cfg #5 s1_fuse).
 usage: tools/microbench/attn_small_bench.py"""
 import os
 import sys
