@@ -61,7 +61,7 @@ EXPORTS = [
     "sf_bx_planes_elems", "sf_bx_split", "sf_bx_split_batched", "sf_conv_rows_parts", "sf_conv_pw_ws_floats", "sf_conv_pw_stats_floats", "sf_conv_fwd_pw", "sf_conv_bx_ws_floats", "sf_conv_fwd_bx", "sf_conv_wgrad_bx_splits",
     "sf_conv_wgrad_bx_ws_floats", "sf_conv_wgrad_bx",
     "sf_conv_fwd_grouped", "sf_conv_wgrad_grouped_splits", "sf_conv_wgrad_grouped", "sf_channel_shuffle",
-    "sf_dwconv_wgrad_param",
+    "sf_dwconv_wgrad_param", "sf_roi_tpool_fwd", "sf_roi_align_max_fwd", "sf_roi_align_max_bwd", "sf_sigmoid_bwd",
 ]
 _LONG_RET = ("sf_tmax_mean_ws_floats", "sf_channel_stats_ws_floats", "sf_bn_bwd_ws_floats",
              "sf_dwconv_wgrad_ws_floats", "sf_attn_bwd_fused_ws_floats", "sf_conv_fwd_ws_floats",
@@ -179,6 +179,10 @@ def lib():
         L.sf_bn_bwd_reduce_split.argtypes = [vp, ci, ci, vp, ci, ci, vp, ci, ci] + [ci] * 8 + [vp] * 5 + [vp]
         L.sf_bn_bwd_apply_split.argtypes = ([vp, ci, ci, vp, ci, ci, vp, ci, ci] + [ci] * 8 + [vp] * 5 +
                                             [vp, ci, ci, vp, ci, ci, vp])
+        L.sf_roi_tpool_fwd.argtypes = [vp, ci, ci] + [ci] * 5 + [vp, vp]
+        L.sf_roi_align_max_fwd.argtypes = [vp] + [ci] * 4 + [vp, ci, ci, cf, ci, vp, ci, ci, vp, vp]
+        L.sf_roi_align_max_bwd.argtypes = [vp, ci, ci, vp, vp] + [ci] * 7 + [cf, ci, vp, ci, ci, ci, vp]
+        L.sf_sigmoid_bwd.argtypes = [vp, vp, vp, cl, ci, vp]
         for name in EXPORTS:
             fn = getattr(L, name)
             if name != "sf_build_arch" and name not in _LONG_RET:
@@ -1301,3 +1305,68 @@ def gather_add(src, src_cmul, out, accumulate=True):
     _check(lib().sf_gather_add(src.ptr(), src.cs, src.coff, src_cmul, out.ptr(), out.cs, out.coff, out.rows, out.C,
                                1 if accumulate else 0, _stream()), "sf_gather_add")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ RoI head
+def check_boxes(boxes, x):
+    """boxes: [K, 5] float32 on x's device, rows (batch_idx, x1, y1, x2, y2).  Checks metadata only (no sync)."""
+    if not isinstance(boxes, torch.Tensor) or boxes.dim() != 2 or boxes.shape[1] != 5:
+        raise SfhipError("RoI boxes must be a [K, 5] tensor (batch_idx, x1, y1, x2, y2), got %s" % (
+            tuple(boxes.shape) if isinstance(boxes, torch.Tensor) else type(boxes).__name__))
+    if boxes.dtype != torch.float32:
+        raise SfhipError("RoI boxes: expected float32, got %s" % boxes.dtype)
+    if boxes.device != x.buf.device:
+        raise SfhipError("RoI boxes are on %s, the features on %s" % (boxes.device, x.buf.device))
+    return boxes.contiguous()
+
+
+def roi_tpool(x):
+    """AvgPool3d([T,1,1], stride 1) + squeeze: Act [N,T,H,W,C] -> dense Act [N,1,H,W,C]."""
+    _require_gpu(x.buf, "roi_tpool")
+    out = new_act(x, x.N, 1, x.H, x.W, x.C)
+    _check(lib().sf_roi_tpool_fwd(x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C, out.ptr(), _stream()),
+           "sf_roi_tpool_fwd")
+    return out
+
+
+def roi_align_max(x, boxes, resolution, spatial_scale, aligned, out):
+    """RoIAlign(resolution, spatial_scale, sampling_ratio 0, aligned) + MaxPool2d(resolution) in one launch.
+    x: dense Act [N,1,H,W,C]; out: Act [K,1,1,1,C] (a slice of the head's concat buffer).  Returns the winner map
+    (uint8 [K, C]) the backward routes through."""
+    _require_gpu(x.buf, "roi_align_max")
+    assert x.T == 1 and x.coff == 0 and x.cs == x.C, x
+    boxes = check_boxes(boxes, x)
+    K = boxes.shape[0]
+    assert (out.N, out.T, out.H, out.W, out.C) == (K, 1, 1, 1, x.C), (out, K, x)
+    arg = torch.empty((K, x.C), dtype=torch.uint8, device=x.buf.device)
+    if K > 0:
+        _check(lib().sf_roi_align_max_fwd(x.ptr(), x.N, x.H, x.W, x.C, _ptr(boxes), K, int(resolution),
+                                          float(spatial_scale), 1 if aligned else 0, out.ptr(), out.cs, out.coff,
+                                          _ptr(arg), _stream()), "sf_roi_align_max_fwd")
+    return arg
+
+
+def roi_align_max_bwd(dy, arg, boxes, resolution, spatial_scale, aligned, dx, accumulate=True):
+    """dx [N,T,H,W,C] (+)= (1/T) * dL/d(map): the backward of roi_tpool -> roi_align_max (T = 1: of roi_align_max
+    alone).  dy: Act [K,1,1,1,C]; arg: roi_align_max's winner map.  Bitwise reproducible (gather form)."""
+    _require_gpu(dx.buf, "roi_align_max_bwd")
+    boxes = check_boxes(boxes, dx)
+    K = boxes.shape[0]
+    assert arg.dtype == torch.uint8 and tuple(arg.shape) == (K, dx.C) and arg.device == dx.buf.device
+    assert (dy.N, dy.T, dy.H, dy.W, dy.C) == (K, 1, 1, 1, dx.C), (dy, dx)
+    if K == 0 and accumulate:
+        return dx
+    _check(lib().sf_roi_align_max_bwd(dy.ptr() if K else None, dy.cs, dy.coff, _ptr(arg), _ptr(boxes), K, dx.N,
+                                      dx.T, dx.H, dx.W, dx.C, int(resolution), float(spatial_scale),
+                                      1 if aligned else 0, dx.ptr(), dx.cs, dx.coff, 1 if accumulate else 0,
+                                      _stream()), "sf_roi_align_max_bwd")
+    return dx
+
+
+def sigmoid_bwd(y, dy, dx, accumulate=True):
+    """dx (+)= dy * y * (1 - y) over dense tensors of one shape."""
+    _require_gpu(y, "sigmoid_bwd")
+    assert y.shape == dy.shape == dx.shape and y.is_contiguous() and dy.is_contiguous() and dx.is_contiguous()
+    _check(lib().sf_sigmoid_bwd(_ptr(y), _ptr(dy), _ptr(dx), y.numel(), 1 if accumulate else 0, _stream()),
+           "sf_sigmoid_bwd")
+    return dx

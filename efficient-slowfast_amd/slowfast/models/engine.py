@@ -1053,14 +1053,14 @@ class TapedForward(torch.autograd.Function):
     any module).  Activations never become autograd tensors."""
 
     @staticmethod
-    def forward(ctx, model, n_in, *args):
+    def forward(ctx, model, n_in, bboxes, *args):
         inputs, params = list(args[:n_in]), args[n_in:]
         t = Tape()
         t.model = model
         t.input_ids = {id(x): i for i, x in enumerate(inputs)
-                       if isinstance(x, torch.Tensor) and ctx.needs_input_grad[2 + i]}
+                       if isinstance(x, torch.Tensor) and ctx.needs_input_grad[3 + i]}
         with taping(t):
-            out = model._forward_impl(inputs)
+            out = model._forward_impl(inputs) if bboxes is None else model._forward_impl(inputs, bboxes)
         if t.out_act is None:
             raise RuntimeError("the head did not register its logits on the tape")
         ctx.tape = t
@@ -1080,15 +1080,16 @@ class TapedForward(torch.autograd.Function):
         sink = t.sink or {}
         grads = tuple(None if p in sink else t.pgrads.get(p) for p in ctx.params)
         gin = tuple(t.input_grads.get(i) for i in range(ctx.n_in))
-        if any(ctx.needs_input_grad[2 + i] and gin[i] is None for i in range(ctx.n_in)):
+        if any(ctx.needs_input_grad[3 + i] and gin[i] is None for i in range(ctx.n_in)):
             raise NotImplementedError("dL/d(input) was requested for an input this model's stem does not "
                                       "differentiate (PackedClip inputs / non-stem consumers)")
         ctx.tape = None
-        return (None, None) + gin + grads
+        return (None, None, None) + gin + grads
 
 
-def run_model(model, x):
-    """model.forward body shared by all model classes: taped when training with grad enabled."""
+def run_model(model, x, bboxes=None):
+    """model.forward body shared by all model classes: taped when training with grad enabled.  bboxes: the detection
+    head's [K, 5] boxes (models built with DETECTION.ENABLE), handed to _forward_impl; never an autograd input."""
     global _NBT
     outer, _NBT = _NBT, []
     # collective-carrying layers (Sync-BN over > 1 local rank): one stream for this model only.  The decision depends on
@@ -1115,8 +1116,9 @@ def run_model(model, x):
                                    "utils.distributed.FlatGradients on the unwrapped model")
             params = [p for p in model.parameters()]
             repack_all(model)
-            return TapedForward.apply(model, len(x), *x, *params)
-        return model._forward_impl(x)
+            boxes = bboxes.detach() if isinstance(bboxes, torch.Tensor) else bboxes
+            return TapedForward.apply(model, len(x), boxes, *x, *params)
+        return model._forward_impl(x) if bboxes is None else model._forward_impl(x, bboxes)
     finally:
         if x and hasattr(x[0], "device") and x[0].device.type == "cuda":
             join_pending(x[0].device)  # a fusion whose join was deferred and that no later region picked up

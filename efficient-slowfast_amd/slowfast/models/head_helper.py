@@ -1,4 +1,4 @@
-"""Classification heads (reference head_helper.py).  Pooling kernels write into one concat buffer, the
+"""Classification and detection heads (reference head_helper.py).  Pooling kernels write into one concat buffer, the
 projection is the MFMA GEMM, the eval-mode softmax+mean is one small kernel."""
 import torch
 import torch.nn as nn
@@ -95,6 +95,105 @@ class ResNetBasicHead(nn.Module):
             off += x.C
         logits = _project(cat, self.projection, getattr(self, "dropout", None), self.training)
         return _finish(logits, self.training, self._act_name)
+
+
+class ROIAlign(nn.Module):
+    """The settings of detectron2's ROIAlign as ResNetRoIHead builds it (head_helper.py:102-107): no parameters.  The
+    arithmetic runs fused with the following MaxPool2d (sfhip.roi_align_max), so this module is not called alone."""
+
+    def __init__(self, output_size, spatial_scale, sampling_ratio, aligned=True):
+        super(ROIAlign, self).__init__()
+        if sampling_ratio != 0:
+            raise NotImplementedError("ROIAlign: only sampling_ratio 0 (adaptive grid, as ResNetRoIHead uses)")
+        self.output_size = output_size
+        self.spatial_scale = spatial_scale
+        self.sampling_ratio = sampling_ratio
+        self.aligned = aligned
+
+    def forward(self, input, rois):
+        raise NotImplementedError("ROIAlign runs fused with its MaxPool2d inside ResNetRoIHead.forward")
+
+    def __repr__(self):
+        return "ROIAlign(output_size=%s, spatial_scale=%s, sampling_ratio=%s, aligned=%s)" % (
+            self.output_size, self.spatial_scale, self.sampling_ratio, self.aligned)
+
+
+class ResNetRoIHead(nn.Module):
+    """Per pathway AvgPool3d([T,1,1]) -> ROIAlign(R) -> MaxPool2d(R) -> cat -> Dropout -> Linear -> Sigmoid, in train
+    and eval alike (head_helper.py:11-130).  Two launches per pathway write the pooled [K, C] features straight into
+    their slice of the concat buffer (sf_roi_tpool_fwd, sf_roi_align_max_fwd); the backward is one gather launch per
+    pathway that also broadcasts over T (sf_roi_align_max_bwd).  Boxes: [K, 5] (batch_idx, x1, y1, x2, y2) in input
+    pixels, float32 on the features' device."""
+
+    def __init__(self, dim_in, num_classes, pool_size, resolution, scale_factor, dropout_rate=0.0,
+                 act_func="softmax", aligned=True):
+        super(ResNetRoIHead, self).__init__()
+        assert len({len(pool_size), len(dim_in)}) == 1, "pathway dimensions are not consistent."
+        self.num_pathways = len(pool_size)
+        for pathway in range(self.num_pathways):
+            self.add_module("s{}_tpool".format(pathway), nn.AvgPool3d([pool_size[pathway][0], 1, 1], stride=1))
+            self.add_module("s{}_roi".format(pathway), ROIAlign(resolution[pathway],
+                                                                spatial_scale=1.0 / scale_factor[pathway],
+                                                                sampling_ratio=0, aligned=aligned))
+            self.add_module("s{}_spool".format(pathway), nn.MaxPool2d(resolution[pathway], stride=1))
+        if dropout_rate > 0.0:
+            self.dropout = nn.Dropout(dropout_rate)
+        self.projection = nn.Linear(sum(dim_in), num_classes, bias=True)
+        if act_func == "softmax":
+            # the reference builds nn.Softmax(dim=4) here and applies it to the 2-D [K, classes] projection, which
+            # raises IndexError at the first forward: refuse at construction instead
+            raise NotImplementedError("ResNetRoIHead with HEAD_ACT softmax: the reference applies nn.Softmax(dim=4) "
+                                      "to [K, classes] box scores, which cannot run; use HEAD_ACT sigmoid")
+        elif act_func == "sigmoid":
+            self.act = nn.Sigmoid()
+        else:
+            raise NotImplementedError("{} is not supported as an activation function.".format(act_func))
+
+    def forward(self, inputs, bboxes):
+        assert len(inputs) == self.num_pathways, "Input tensor does not contain {} pathway".format(self.num_pathways)
+        xs = engine.enter(inputs)
+        if isinstance(bboxes, torch.Tensor) and bboxes.dtype != torch.float32:
+            bboxes = bboxes.float()
+        boxes = sfhip.check_boxes(bboxes, xs[0])
+        K = boxes.shape[0]
+        t = engine.tape()
+        cat = sfhip.new_act(xs[0], K, 1, 1, 1, sum(x.C for x in xs))
+        off = 0
+        for pathway, x in enumerate(xs):
+            kt = getattr(self, "s{}_tpool".format(pathway)).kernel_size[0]
+            assert x.T - kt + 1 == 1, "temporal pool leaves %d frames (the head needs 1)" % (x.T - kt + 1)
+            roi = getattr(self, "s{}_roi".format(pathway))
+            R = roi.output_size if isinstance(roi.output_size, int) else roi.output_size[0]
+            spool = getattr(self, "s{}_spool".format(pathway)).kernel_size
+            assert all(r == R for r in (roi.output_size if isinstance(roi.output_size, (list, tuple)) else [R])) and \
+                (spool if isinstance(spool, int) else spool[0]) == R, "non-square RoI resolution"
+            pooled = sfhip.roi_tpool(x)
+            piece = cat.slice(off, x.C)
+            arg = sfhip.roi_align_max(pooled, boxes, R, roi.spatial_scale, roi.aligned, out=piece)
+            if t is not None:
+                def bwd(x=x, piece=piece, arg=arg, R=R, roi=roi):
+                    fresh = t.grad_of_uninitialised(x)  # first writer of x's gradient: write, no zero fill / read
+                    dx = fresh if fresh is not None else t.grad_of(x)
+                    sfhip.roi_align_max_bwd(t.grad_of(piece), arg, boxes, R, roi.spatial_scale, roi.aligned, dx,
+                                            accumulate=fresh is None)
+                t.record(bwd)
+            off += x.C
+        classes = self.projection.out_features
+        if K == 0:  # no boxes in this batch: nothing to project
+            probs = torch.empty((0, classes), dtype=torch.float32, device=cat.buf.device)
+            if t is not None:
+                t.out_act = sfhip.Act(probs.view(0, 1, 1, 1, classes))
+            return probs
+        logits = _project(cat, self.projection, getattr(self, "dropout", None), self.training)
+        if LOGITS_TAP is not None:
+            LOGITS_TAP(logits.buf)
+        probs = sfhip.head_act_mean(logits, sfhip.ACT_SIGMOID)  # [K, classes]: sigmoid over one position
+        if t is not None:
+            out_act = sfhip.Act(probs.view(K, 1, 1, 1, classes))
+            t.record(lambda: sfhip.sigmoid_bwd(probs, t.grad_of(out_act).buf.view(K, classes),
+                                               t.grad_of(logits).buf.view(K, classes), accumulate=True))
+            t.out_act = out_act  # the tape's backward starts from dL/d(probabilities)
+        return probs
 
 
 class _ConvBnAct(nn.Module):

@@ -122,8 +122,19 @@ class _TwoPathwayResNet(nn.Module):
                     pool = nn.MaxPool3d(kernel_size=pool_size[pathway], stride=pool_size[pathway], padding=[0, 0, 0])
                     self.add_module("pathway{}_pool".format(pathway), pool)
 
-        if cfg.DETECTION.ENABLE:
-            raise NotImplementedError("DETECTION.ENABLE (ResNetRoIHead / AVA) is out of scope of the HIP path")
+        if cfg.DETECTION.ENABLE:  # video_model_builder.py:349-371 / custom_video_model_builder.py:378-400
+            self.head = head_helper.ResNetRoIHead(
+                dim_in=[width_per_group * 32, width_per_group * 32 // beta_inv],
+                num_classes=cfg.MODEL.NUM_CLASSES,
+                pool_size=[[cfg.DATA.NUM_FRAMES // cfg.SLOWFAST.ALPHA // pool_size[0][0], 1, 1],
+                           [cfg.DATA.NUM_FRAMES // pool_size[1][0], 1, 1]],
+                resolution=[[cfg.DETECTION.ROI_XFORM_RESOLUTION] * 2] * 2,
+                scale_factor=[cfg.DETECTION.SPATIAL_SCALE_FACTOR] * 2,
+                dropout_rate=cfg.MODEL.DROPOUT_RATE,
+                act_func=cfg.MODEL.HEAD_ACT,
+                aligned=cfg.DETECTION.ALIGNED,
+            )
+            return
         self.head = head_helper.ResNetBasicHead(
             dim_in=[width_per_group * 32, width_per_group * 32 // beta_inv],
             num_classes=cfg.MODEL.NUM_CLASSES,
@@ -138,9 +149,9 @@ class _TwoPathwayResNet(nn.Module):
         )
 
     def forward(self, x, bboxes=None):
-        return engine.run_model(self, x)
+        return engine.run_model(self, x, bboxes)
 
-    def _forward_impl(self, x):
+    def _forward_impl(self, x, bboxes=None):
         x = list(x)
         with engine.internal():
             x = self.s1(x, reserve=self.s1_fuse.reserve(None))
@@ -160,7 +171,7 @@ class _TwoPathwayResNet(nn.Module):
             x = self._fuse(self.s4_fuse, x)
             engine.milestone("s5")
             x = self.s5(x)
-            x = self.head(x)
+            x = self.head(x, bboxes) if self.enable_detection else self.head(x)
         return x
 
     def _fuse(self, fuse, x):
@@ -232,8 +243,14 @@ class ResNet(nn.Module):
                 for pathway in range(self.num_pathways):
                     pool = nn.MaxPool3d(kernel_size=pool_size[pathway], stride=pool_size[pathway], padding=[0, 0, 0])
                     self.add_module("pathway{}_pool".format(pathway), pool)
-        if cfg.DETECTION.ENABLE:
-            raise NotImplementedError("DETECTION.ENABLE (ResNetRoIHead / AVA) is out of scope of the HIP path")
+        if cfg.DETECTION.ENABLE:  # video_model_builder.py:570-580
+            self.head = head_helper.ResNetRoIHead(
+                dim_in=[width_per_group * 32], num_classes=cfg.MODEL.NUM_CLASSES,
+                pool_size=[[cfg.DATA.NUM_FRAMES // pool_size[0][0], 1, 1]],
+                resolution=[[cfg.DETECTION.ROI_XFORM_RESOLUTION] * 2],
+                scale_factor=[cfg.DETECTION.SPATIAL_SCALE_FACTOR], dropout_rate=cfg.MODEL.DROPOUT_RATE,
+                act_func=cfg.MODEL.HEAD_ACT, aligned=cfg.DETECTION.ALIGNED)
+            return
         self.head = head_helper.ResNetBasicHead(
             dim_in=[width_per_group * 32], num_classes=cfg.MODEL.NUM_CLASSES,
             pool_size=[None, None] if cfg.MULTIGRID.SHORT_CYCLE else [
@@ -242,9 +259,9 @@ class ResNet(nn.Module):
             dropout_rate=cfg.MODEL.DROPOUT_RATE, act_func=cfg.MODEL.HEAD_ACT)
 
     def forward(self, x, bboxes=None):
-        return engine.run_model(self, x)
+        return engine.run_model(self, x, bboxes)
 
-    def _forward_impl(self, x):
+    def _forward_impl(self, x, bboxes=None):
         x = list(x)
         with engine.internal():
             x = self.s1(x)
@@ -259,5 +276,5 @@ class ResNet(nn.Module):
             x = self.s4(x)
             engine.milestone("s5")
             x = self.s5(x)
-            x = self.head(x)
+            x = self.head(x, bboxes) if self.enable_detection else self.head(x)
         return x

@@ -470,6 +470,28 @@ int sf_row_softmax_fwd(float* x, int cs, int coff, long rows, int C, float scale
 int sf_row_softmax_bwd(const float* p, int p_cs, int p_coff, float* dp, int dp_cs, int dp_coff, long rows, int C,
                        float scale, void* stream);
 
+/* ---- action-detection head (ResNetRoIHead, head_helper.py:11-130; models wire it at video_model_builder.py:349-371,
+ * :570-580 and custom_video_model_builder.py:378-400).  detectron2 ROIAlign semantics (spatial_scale, sampling_ratio 0,
+ * aligned) and the max-pool's first-maximum rule are spelled out in csrc/roi_head.hip.
+ * sf_roi_tpool_fwd: s{p}_tpool = AvgPool3d([T,1,1], stride 1) + squeeze(2) (head_helper.py:96-100, T_out == 1):
+ *   x [N,T,H,W] channel slice (cs, coff) -> out [N,H,W,C] dense.
+ * sf_roi_align_max_fwd: s{p}_roi + s{p}_spool (head_helper.py:102-106): map [N,H,W,C] dense, boxes [K,5] fp32 on the
+ *   device, rows (batch_idx, x1, y1, x2, y2) in input pixels -> out[k, out_coff + c] (the pathway's slice of the
+ *   concat buffer, pitch out_cs) and arg[k, c] = winning bin (row-major, < R*R <= 256).  A box whose batch index does
+ *   not truncate into [0, N) reads nothing and yields 0.  K == 0 launches nothing.
+ * sf_roi_align_max_bwd: dx[n, t, h, w] (+)= (1/T) dL/d(map)[n, h, w]: the RoIAlign / max-pool backward fused with the
+ *   temporal broadcast (T = 1: the map's own gradient).  Gather form: each element walks the boxes of its clip in
+ *   index order, so the result is bitwise reproducible (no atomics).  accumulate == 0 overwrites every element.
+ * sf_sigmoid_bwd: dx (+)= dy * y * (1 - y) over n dense elements (head_helper.py:125, nn.Sigmoid's backward).   */
+int sf_roi_tpool_fwd(const float* x, int cs, int coff, int N, int T, int H, int W, int C, float* out, void* stream);
+int sf_roi_align_max_fwd(const float* x, int N, int H, int W, int C, const float* boxes, int K, int R,
+                         float spatial_scale, int aligned, float* out, int out_cs, int out_coff, unsigned char* arg,
+                         void* stream);
+int sf_roi_align_max_bwd(const float* dy, int dy_cs, int dy_coff, const unsigned char* arg, const float* boxes, int K,
+                         int N, int T, int H, int W, int C, int R, float spatial_scale, int aligned, float* dx,
+                         int dx_cs, int dx_coff, int accumulate, void* stream);
+int sf_sigmoid_bwd(const float* y, const float* dy, float* dx, long n, int accumulate, void* stream);
+
 /* ---- input step (datasets/kinetics.py:230-248 -> datasets/utils.py:298-315 tensor_normalize, :151-203
  * spatial_sampling, :73-112 pack_pathway_output; transform.py:283-337 / 359-393 / 395-423 / 425-468).
  * clip: ONE decoded clip, uint8 [T,H,W,3] on the device.  The short side is scaled bilinearly to (new_h, new_w)
