@@ -559,11 +559,11 @@ static int bn_bwd_reduce_launch(const float* dy, int dy_cs, int dy_coff, const f
   red_geometry(group_rows, C, vec4 ? 4 : 1, &CB, &P);
   // small tensors (the launch-bound models): <= 16 row blocks in the natural geometry — the last arriver's walk is
   // short and the final launch it replaces is a third of the reduction's launches
-  const bool small = ring && sf_tickets_level() >= 1 && S == 1 && P <= 16;
-  const bool few = !small && ring && sf_tickets_level() == 2 && S == 1 && vec4 && C >= 256;
-  const bool fused = (ring && sf_tickets_enabled()) || few || small;
-  const int max_p = few ? 64 : (fused ? 512 : MAX_P);
-  if (fused && !small && CB > 16) {  // <= 64 channels per channel group: the groups' last workgroups finish in parallel
+  const bool small = ring && S == 1 && P <= 16;
+  const bool few = !small && ring && S == 1 && vec4 && C >= 256;
+  const bool fused = few || small;
+  const int max_p = few ? 64 : (small ? 512 : MAX_P);
+  if (few && CB > 16) {  // <= 64 channels per channel group: the groups' last workgroups finish in parallel
     CB = 16;
     long pp = group_rows / ((long)(TPB / CB) * 8);
     P = (int)(pp < 1 ? 1 : (pp > max_p ? max_p : pp));
@@ -630,12 +630,10 @@ static int bn_bwd_apply_launch(const float* dy, int dy_cs, int dy_coff, const fl
                     (!dres || ((dres_cs % 4 == 0) && (dres_coff % 4 == 0) && sf_aligned16(dres)));
   if (relu == 3 && !vec4) return SF_EINVAL;  // the byte mask only exists on the float4 path
   const long total = rows * (vec4 ? C / 4 : C);
-  // four elements per thread where the tensor is large enough to keep every CU busy that way (SF_BN_APPLY_UNROLL=0: off).
+  // four elements per thread where the tensor is large enough to keep every CU busy that way.
   // dz may alias z and dres may alias dy element for element: a thread reads its four elements before it writes any, and
   // no other thread touches them
-  static const int unroll_env = [] { const char* e = getenv("SF_BN_APPLY_UNROLL"); return e ? atoi(e) : 1; }();
-  static const long unroll_min = [] { const char* e = getenv("SF_BN_APPLY_UNROLL_MIN"); return e ? atol(e) : 262144L; }();
-  const int unroll4 = (unroll_env && vec4 && rep == 1 && (relu == 0 || relu == 3) && total >= unroll_min &&
+  const int unroll4 = (vec4 && rep == 1 && (relu == 0 || relu == 3) && total >= 262144L &&
                        total < 0x7fffffffL && rows < 0x7fffffffL && (rows % 4) == 0 &&
                        sf_aligned16(mean) && sf_aligned16(invstd) && sf_aligned16(gamma) && sf_aligned16(dbeta) &&
                        sf_aligned16(dgamma)) ? 1 : 0;

@@ -62,8 +62,6 @@ static inline bool sf_ensure_dyn_lds(SfLdsAttr& m, const void* fn, int bytes) {
   if (dev >= 0 && dev < 64) m.done |= 1ull << dev;
   return true;
 }
-bool sf_tickets_enabled();         // SF_BN_TICKET=1 selects the fused reductions (default: two launches, measured faster)
-int sf_tickets_level();            // SF_BN_TICKET value (2: BN backward reductions of >= 256-channel layers only)
 
 __device__ __forceinline__ void sf_store_sc1(float* p, float v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -58,11 +58,11 @@ __device__ __forceinline__ unsigned mdiv(unsigned n, unsigned mul, unsigned sh) 
 
 typedef __attribute__((address_space(3))) void lds_void;
 
-template <int BN, bool DIRECT, int VAR>
+template <int BN, bool DIRECT, bool AF32>
 __global__ __launch_bounds__(512, 2) void conv_bx_kernel(const BxArgs p) {
-  // VAR & 32 (AF32): the A operand arrives as the fp32 rows themselves (16 KB per step instead of 24 KB of pieces, and
-  // no activation planes) and is split into its three pieces after the fragment read — conv_pw_bx_kernel's A path.
-  constexpr bool AF32 = (VAR & 32) != 0;
+  // AF32: the A operand arrives as the fp32 rows themselves (16 KB per step instead of 24 KB of pieces, and no
+  // activation planes) and is split into its three pieces after the fragment read — conv_pw_bx_kernel's A path.
+  // !AF32: plane-fed (inputs past the 2 GB buffer range).
   constexpr int A_ST = AF32 ? BXC_BM * 64 : BXC_A_STAGE;
   constexpr int B_STAGE = 3 * BN * BXC_ROWB;
   constexpr int STAGE = A_ST + B_STAGE;
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(512, 2) void conv_bx_kernel(const BxArgs p) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();  // ... and every other wave's: the stage is complete, and stage it - 1 is free
-    if (!(VAR & 16) && it + 2 < nsteps) issue((it + 2) % BXC_STAGES);
+    if (it + 2 < nsteps) issue((it + 2) % BXC_STAGES);
     const char* const st = smem + (it % BXC_STAGES) * STAGE;
     u32x4 af[2][3], bf[NT][3];
     if constexpr (AF32) {
@@ -305,31 +305,16 @@ __global__ __launch_bounds__(512, 2) void conv_bx_kernel(const BxArgs p) {
       for (int j = 0; j < NT; ++j)
         bf[j][pc] = *reinterpret_cast<const u32x4*>(st + b_frag + pc * (BN * BXC_ROWB) + j * (32 * BXC_ROWB));
     }
-    if (VAR & 8) {  // ablation: no MFMAs (the fragments stay live through one xor chain)
-      unsigned x = 0;
 #pragma unroll
-      for (int pc = 0; pc < 3; ++pc) {
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int i = 0; i < 2; ++i) x ^= af[i][pc][0] ^ af[i][pc][1] ^ af[i][pc][2] ^ af[i][pc][3];
-#pragma unroll
-        for (int j = 0; j < NT; ++j) x ^= bf[j][pc][0] ^ bf[j][pc][1] ^ bf[j][pc][2] ^ bf[j][pc][3];
-      }
-      acc[0][0][0] += __builtin_bit_cast(float, x & 0x007fffffu);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = mfma_split(af[i], bf[j], acc[i][j]);
-    }
+      for (int j = 0; j < NT; ++j) acc[i][j] = mfma_split(af[i], bf[j], acc[i][j]);
   }
 
   // ---- an accumulator register holds column lane & 31 of rows (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5): 128
   // contiguous bytes per half-wave and row.  DIRECT (one workgroup per tile, dense stores): the conv epilogue here;
   // otherwise the raw partial tile -> ws[split][m][n] for the finish kernel
   const int col = lane & 31, rsub = 4 * (lane >> 5);
-  if ((VAR & 4) && p.M > 0) {  // ablation: no stores (the accumulators stay live: the sum goes out when M <= 0, i.e. never)
-    return;
-  }
   if (DIRECT) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
@@ -382,11 +367,10 @@ __global__ __launch_bounds__(512, 2) void conv_bx_kernel(const BxArgs p) {
 // with LDS-DMA loads the compiler waits for vmcnt(0) at every use, and the prefetch is lost.)  Tile 256 x BN, 8 wavefronts of 64 x BN/2, direct epilogue (scale, bias,
 // residual, activation) and, for training-mode forward convs, the BN batch statistics of what was stored, in
 // conv_wave.hip's record format [part = M tile][C / 4][count, K, S1, S2][4] (K = the tile's first row).
-// ST = 3: three LDS stages, one workgroup per CU (two wavefronts per SIMD).  ST = 2 (BN = 128 only, <= 128 registers):
-// two stages = 56 KB, so TWO workgroups share a CU — four wavefronts per SIMD, and while one workgroup sits in its
-// barrier / load-issue / fragment-read phase the other one's MFMAs keep the matrix pipe busy.
-template <int BN, int ST>
-__global__ __launch_bounds__(512, ST == 2 ? 4 : 2) void conv_pw_bx_kernel(const BxArgs p) {
+// Two LDS stages (<= 128 registers, at most 56 KB), so TWO workgroups share a CU — four wavefronts per SIMD, and while
+// one workgroup sits in its barrier / load-issue / fragment-read phase the other one's MFMAs keep the matrix pipe busy.
+template <int BN>
+__global__ __launch_bounds__(512, 4) void conv_pw_bx_kernel(const BxArgs p) {
   constexpr int A_STAGE = BXC_BM * 64;            // fp32 rows of a step: 256 x 16 channels x 4 B
   constexpr int B_STAGE = 3 * BN * BXC_ROWB;
   constexpr int STAGE = A_STAGE + B_STAGE;
@@ -423,7 +407,7 @@ __global__ __launch_bounds__(512, ST == 2 ? 4 : 2) void conv_pw_bx_kernel(const 
     a_lvoff[u] = m < p.M ? ((unsigned)m * (unsigned)d.in_cs + (unsigned)d.in_coff) * 4u + chunk * 16u : 0x80000000u;
   }
   auto issue = [&](int step) {
-    char* const st = smem + (step % ST) * STAGE;
+    char* const st = smem + (step % 2) * STAGE;
 #pragma unroll
     for (int u = 0; u < 2; ++u)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rs, (lds_void*)(st + wave * 2048 + u * 1024), 16, a_lvoff[u],
@@ -458,17 +442,11 @@ __global__ __launch_bounds__(512, ST == 2 ? 4 : 2) void conv_pw_bx_kernel(const 
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
   if (nsteps > 0) issue(0);
-  if (ST == 3 && nsteps > 1) issue(1);
   for (int it = 0; it < nsteps; ++it) {
-    if (ST == 3 && it + 1 < nsteps) {  // this wave's loads of step `it` have landed once at most those of step it + 1 are outstanding
-      if (b_loader) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    if (it + ST - 1 < nsteps) issue(it + ST - 1);
-    const char* const st = smem + (it % ST) * STAGE;
+    if (it + 1 < nsteps) issue(it + 1);
+    const char* const st = smem + (it % 2) * STAGE;
     u32x4 af[2][3], bf[NT][3];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -838,17 +816,7 @@ void magic(unsigned dv, unsigned* mul, unsigned* sh) {
   *sh = l - 1;
 }
 
-int g_bx_enable = 1;  // sf_conv_tune(7, e)
-int g_bx_dbg = 0;     // sf_conv_tune(8, mask): timing ablations (microbenchmarks): 1 = skip the operand splits (planes of
-                      // the previous call), 2 = skip the finish kernel, 4 = skip the GEMM
-
-bool bx_enabled() {
-  static const int env_on = [] {
-    const char* e = getenv("SF_CONV_BX");
-    return e ? atoi(e) : 1;
-  }();
-  return env_on && g_bx_enable;
-}
+int g_bx_enable = 1;  // sf_conv_tune(7, e): 0 off, 1 where it wins, 2 every shape it covers
 
 struct BxPlan { int bn, S, nk, nk_per, nb_n, tiles, direct; long a_rows; };
 
@@ -858,7 +826,7 @@ struct BxPlan { int bn, S, nk, nk_per, nb_n, tiles, direct; long a_rows; };
 bool bx_af32(const sf_conv_desc* d);
 
 bool bx_plan(const sf_conv_desc* d, BxPlan* pl, bool gate = true) {
-  if (!bx_enabled()) return false;
+  if (!g_bx_enable) return false;
   const long M = (long)d->N * d->To * d->Ho * d->Wo;
   const int ntaps = d->kT * d->kH * d->kW;
   if ((d->Cin % 16) || d->cin_pad != d->Cin || (d->in_cs % 4) || (d->in_coff % 4)) return false;
@@ -894,8 +862,6 @@ bool bx_plan(const sf_conv_desc* d, BxPlan* pl, bool gate = true) {
     else t += out_mb / 4.0;
     if (t < best_t - 1e-9) { best_t = t; best = S; }
   }
-  static const int forced_s = [] { const char* e = getenv("SF_CONV_BX_S"); return e ? atoi(e) : 0; }();
-  if (forced_s > 0 && nk / forced_s >= 1) best = forced_s;
   pl->S = best;
   pl->nk_per = sf_cdiv(nk, best);
   pl->direct = (best == 1 && !scatter) ? 1 : 0;
@@ -920,8 +886,7 @@ int g_pw_enable = 1;  // sf_conv_tune(21, e): 0 off, 1 where the time model says
 struct PwPlan { int bn, nb_n, tiles, nk; };
 
 bool pw_plan(const sf_conv_desc* d, PwPlan* pl, bool gate = true) {
-  static const int env_on = [] { const char* e = getenv("SF_CONV_PW"); return e ? atoi(e) : 1; }();
-  if (!bx_enabled() || !env_on || !g_pw_enable) return false;
+  if (!g_bx_enable || !g_pw_enable) return false;
   if (d->kT != 1 || d->kH != 1 || d->kW != 1 || d->sT != 1 || d->sH != 1 || d->sW != 1 || d->pT || d->pH || d->pW)
     return false;
   if (d->To != d->Ti || d->Ho != d->Hi || d->Wo != d->Wi) return false;
@@ -933,14 +898,10 @@ bool pw_plan(const sf_conv_desc* d, PwPlan* pl, bool gate = true) {
   if (((M - 1) * d->in_cs + d->in_coff + d->Cin) * 4L >= 0x7fffffffL) return false;
   pl->nk = d->Cin / BXC_BK;
   if (3L * (d->Cout + 1) * pl->nk * BXC_ROWB > 0xfffffff0L) return false;
-  // 256 x 128 tiles on two LDS stages, two workgroups per CU (SF_PW_WIDE=1: 256 x 256 on three stages, one per CU)
-  static const int wide = [] { const char* e = getenv("SF_PW_WIDE"); return e ? atoi(e) : 0; }();
-  // 64-wide outputs (res2's 256 -> 64 / 72 -> 64 projections and the data gradients of its 64 -> 256 ones): 256 x 64
-  // tiles — the rows of a tile are read ONCE (one column block), 44 KB of LDS on two stages: SF_PW_64=0 keeps them on the
-  // f32 kernels
-  static const int n64 = [] { const char* e = getenv("SF_PW_64"); return e ? atoi(e) : 1; }();
-  pl->bn = (d->Cout >= 256 && wide) ? 256 : (d->Cout <= 64 ? 64 : 128);
-  if (pl->bn == 64 && !n64) return false;
+  // 256 x 128 tiles on two LDS stages, two workgroups per CU.  64-wide outputs (res2's 256 -> 64 / 72 -> 64 projections
+  // and the data gradients of its 64 -> 256 ones): 256 x 64 tiles — the rows of a tile are read ONCE (one column
+  // block), 44 KB of LDS on two stages
+  pl->bn = d->Cout <= 64 ? 64 : 128;
   pl->nb_n = sf_cdiv(d->Cout, pl->bn);
   pl->tiles = sf_cdiv(M, BXC_BM) * pl->nb_n;
   if (gate && g_pw_enable < 2 && g_bx_enable < 2) {
@@ -970,21 +931,20 @@ bool pw_plan(const sf_conv_desc* d, PwPlan* pl, bool gate = true) {
   return true;
 }
 
-template <int BN, int ST>
+template <int BN>
 int launch_pw(const BxArgs& a, int grid, hipStream_t stream) {
-  constexpr int lds = ST * (BXC_BM * 64 + 3 * BN * BXC_ROWB);
+  constexpr int lds = 2 * (BXC_BM * 64 + 3 * BN * BXC_ROWB);
   static_assert(lds >= (BN + 4 * BN * 2) * 4, "the statistics scratch lives in the stages");
   static SfLdsAttr at;
-  if (!sf_ensure_dyn_lds(at, reinterpret_cast<const void*>(conv_pw_bx_kernel<BN, ST>), lds)) return SF_ELAUNCH;
-  hipLaunchKernelGGL((conv_pw_bx_kernel<BN, ST>), dim3(grid), dim3(512), lds, stream, a);
+  if (!sf_ensure_dyn_lds(at, reinterpret_cast<const void*>(conv_pw_bx_kernel<BN>), lds)) return SF_ELAUNCH;
+  hipLaunchKernelGGL((conv_pw_bx_kernel<BN>), dim3(grid), dim3(512), lds, stream, a);
   SF_CHECK_LAUNCH();
   return SF_OK;
 }
 
-// SF_CONV_BX_AF32 (default 1): forward / data-gradient launches take their activation operand as fp32 rows (no planes)
+// Forward / data-gradient launches take their activation operand as fp32 rows (no planes) while the input fits the
+// 2 GB buffer range; past it they are plane-fed
 bool bx_af32(const sf_conv_desc* d) {
-  static const int on = [] { const char* e = getenv("SF_CONV_BX_AF32"); return e ? atoi(e) : 1; }();
-  if (!on) return false;
   const long rows = (long)d->N * d->Ti * d->Hi * d->Wi;
   return ((rows - 1) * d->in_cs + d->in_coff + d->Cin) * 4L < 0x7fffffffL;
 }
@@ -993,38 +953,26 @@ long align4(long floats) { return (floats + 3) & ~3L; }
 long a_plane_floats(const sf_conv_desc* d, long a_rows) { return align4((3 * (a_rows + 1) * d->Cin + 1) / 2); }
 long b_plane_floats(const sf_conv_desc* d, int nk) { return align4((3L * (d->Cout + 1) * nk * BXC_BK + 1) / 2); }
 
-template <int BN, bool DIRECT, int VAR>
+template <int BN, bool DIRECT, bool AF32>
 int launch_bx_v(const BxArgs& a, int grid, hipStream_t stream) {
-  constexpr int lds = BXC_STAGES * (((VAR & 32) ? BXC_BM * 64 : BXC_A_STAGE) + 3 * BN * BXC_ROWB);
+  constexpr int lds = BXC_STAGES * ((AF32 ? BXC_BM * 64 : BXC_A_STAGE) + 3 * BN * BXC_ROWB);
   static SfLdsAttr at;
-  if (!sf_ensure_dyn_lds(at, reinterpret_cast<const void*>(conv_bx_kernel<BN, DIRECT, VAR>), lds)) return SF_ELAUNCH;
-  hipLaunchKernelGGL((conv_bx_kernel<BN, DIRECT, VAR>), dim3(grid), dim3(512), lds, stream, a);
+  if (!sf_ensure_dyn_lds(at, reinterpret_cast<const void*>(conv_bx_kernel<BN, DIRECT, AF32>), lds)) return SF_ELAUNCH;
+  hipLaunchKernelGGL((conv_bx_kernel<BN, DIRECT, AF32>), dim3(grid), dim3(512), lds, stream, a);
   SF_CHECK_LAUNCH();
   return SF_OK;
 }
 
+// The loop is bound by the arrival of the operand pieces in LDS, not by the matrix pipe (timing ablations)
 template <int BN, bool DIRECT>
 int launch_bx(const BxArgs& a, int grid, hipStream_t stream) {
-  // SF_CONV_BX_VAR: timing ablations (results invalid) — 4 no stores, 8 no MFMAs, 16 no loads inside the loop.
-  // Measured with them on the res4 1x3x3 layer (85 us): fragment reads + barriers alone 25 us, + the LDS-DMA loads
-  // 53 us, MFMAs + fragment reads without the loads 63 us: the loop is bound by the ~48 GB/s per CU at which the
-  // operand pieces arrive in LDS, not by the matrix pipe.  Tried without gain: the loads behind the fragment reads,
-  // s_setprio around the MFMAs, one LDS-DMA piece per MFMA group instead of a burst behind the barrier, tap-major K order.
-  static const int var = [] { const char* e = getenv("SF_CONV_BX_VAR"); return e ? atoi(e) : 0; }();
-  if (a.xf) return launch_bx_v<BN, DIRECT, 32>(a, grid, stream);  // fp32 rows, split after the fragment read
-  switch (var) {
-    case 4: return launch_bx_v<BN, DIRECT, 4>(a, grid, stream);
-    case 12: return launch_bx_v<BN, DIRECT, 12>(a, grid, stream);
-    case 20: return launch_bx_v<BN, DIRECT, 20>(a, grid, stream);
-    case 28: return launch_bx_v<BN, DIRECT, 28>(a, grid, stream);
-    default: return launch_bx_v<BN, DIRECT, 0>(a, grid, stream);
-  }
+  if (a.xf) return launch_bx_v<BN, DIRECT, true>(a, grid, stream);  // fp32 rows, split after the fragment read
+  return launch_bx_v<BN, DIRECT, false>(a, grid, stream);
 }
 
 }  // namespace
 
-int sf_conv_bx_tune(int value) { g_bx_enable = value; return SF_OK; }  // 0 off, 1 on where it wins, 2 every shape it covers
-int sf_conv_bx_dbg(int value) { g_bx_dbg = value; return SF_OK; }
+int sf_conv_bx_tune(int value) { g_bx_enable = value; return SF_OK; }
 
 int sf_conv_bx_takes(const sf_conv_desc* d) {
   BxPlan pl;
@@ -1113,9 +1061,8 @@ int sf_conv_pw_try(const sf_conv_desc* d, const float* in, const float* w_packed
   a.xf_bytes = (unsigned)(((M - 1) * d->in_cs + d->in_coff + d->Cin) * 4L);
   a.stats = stats;
   if (stats) *parts = (int)sf_cdiv(M, BXC_BM);
-  if (pl.bn == 256) return launch_pw<256, 3>(a, pl.tiles, stream);
-  if (pl.bn == 64) return launch_pw<64, 2>(a, pl.tiles, stream);
-  return launch_pw<128, 2>(a, pl.tiles, stream);
+  if (pl.bn == 64) return launch_pw<64>(a, pl.tiles, stream);
+  return launch_pw<128>(a, pl.tiles, stream);
 }
 
 // sf_conv_fwd_ws for the pointwise shapes sf_conv_pw_ws_floats accepts, with the weight planes handed in (or NULL: made
@@ -1156,14 +1103,14 @@ int sf_conv_bx_try(const sf_conv_desc* d, const float* in, const unsigned short*
   if (!in_planes && !af32) {
     unsigned short* const ap = reinterpret_cast<unsigned short*>(cur);
     cur += a_plane_floats(d, pl.a_rows);
-    if (!(g_bx_dbg & 1)) rc = sf_bx_split_rows(in, d->in_cs, d->in_coff, pl.a_rows, d->Cin, ap, stream);
+    rc = sf_bx_split_rows(in, d->in_cs, d->in_coff, pl.a_rows, d->Cin, ap, stream);
     if (rc != SF_OK) return rc;
     in_planes = ap;
   }
   if (!w_planes) {
     unsigned short* const bp = reinterpret_cast<unsigned short*>(cur);
     cur += b_plane_floats(d, pl.nk);
-    if (!(g_bx_dbg & 1)) rc = sf_bx_split_rows(w_packed, pl.nk * BXC_BK, 0, d->Cout, pl.nk * BXC_BK, bp, stream);
+    rc = sf_bx_split_rows(w_packed, pl.nk * BXC_BK, 0, d->Cout, pl.nk * BXC_BK, bp, stream);
     if (rc != SF_OK) return rc;
     w_planes = bp;
   }
@@ -1189,12 +1136,10 @@ int sf_conv_bx_try(const sf_conv_desc* d, const float* in, const unsigned short*
   magic((unsigned)d->Ho, &a.ho_mul, &a.ho_sh);
   magic((unsigned)d->To, &a.to_mul, &a.to_sh);
   const int grid = pl.tiles * pl.S;
-  if (!(g_bx_dbg & 4)) {
-    if (pl.bn == 256) rc = pl.direct ? launch_bx<256, true>(a, grid, stream) : launch_bx<256, false>(a, grid, stream);
-    else rc = pl.direct ? launch_bx<128, true>(a, grid, stream) : launch_bx<128, false>(a, grid, stream);
-    if (rc != SF_OK) return rc;
-  }
-  if (pl.direct || (g_bx_dbg & 2)) return SF_OK;
+  if (pl.bn == 256) rc = pl.direct ? launch_bx<256, true>(a, grid, stream) : launch_bx<256, false>(a, grid, stream);
+  else rc = pl.direct ? launch_bx<128, true>(a, grid, stream) : launch_bx<128, false>(a, grid, stream);
+  if (rc != SF_OK) return rc;
+  if (pl.direct) return SF_OK;
   return sf_conv_splitk_finish(d, cur, pl.S, scale, bias, res, out, stream);
 }
 
@@ -1217,8 +1162,7 @@ struct BxwPlan { int bco, S, nb_col, tiles; long chunk, x_rows; };
 int g_bxw_enable = 1;  // sf_conv_tune(9, e): 0 off, 1 where it wins, 2 every shape it covers
 
 bool bxw_plan(const sf_conv_desc* d, BxwPlan* pl) {
-  static const int env_on = [] { const char* e = getenv("SF_WGRAD_BX"); return e ? atoi(e) : 1; }();
-  if (!env_on || !g_bxw_enable) return false;
+  if (!g_bxw_enable) return false;
   const long M = (long)d->N * d->To * d->Ho * d->Wo;
   const int ntaps = d->kT * d->kH * d->kW;
   if ((d->Cin % 8) || d->cin_pad != d->Cin || (d->in_cs % 4) || (d->in_coff % 4)) return false;
@@ -1245,8 +1189,6 @@ bool bxw_plan(const sf_conv_desc* d, BxwPlan* pl) {
     const double t = 6.0 + (double)rounds * steps * step_us + out_mb * (2.0 * S + 1.0) / 4.0;
     if (t < best_t - 1e-9) { best_t = t; best = S; }
   }
-  static const int forced_s = [] { const char* e = getenv("SF_WGRAD_BX_S"); return e ? atoi(e) : 0; }();
-  if (forced_s > 0) best = forced_s;
   pl->S = best;
   pl->chunk = (sf_cdiv(M, best) + 15) / 16 * 16;
   if (g_bxw_enable < 2) {
@@ -1307,14 +1249,14 @@ extern "C" int sf_conv_wgrad_bx(const sf_conv_desc* d, const float* x, const uns
   if (!x_planes) {
     unsigned short* const xp = reinterpret_cast<unsigned short*>(cur);
     cur += x_plane_floats(d, pl.x_rows);
-    if (!(g_bx_dbg & 1)) rc = sf_bx_split_rows(x, d->in_cs, d->in_coff, pl.x_rows, d->Cin, xp, s);
+    rc = sf_bx_split_rows(x, d->in_cs, d->in_coff, pl.x_rows, d->Cin, xp, s);
     if (rc != SF_OK) return rc;
     x_planes = xp;
   }
   if (!dz_planes) {
     unsigned short* const zp = reinterpret_cast<unsigned short*>(cur);
     cur += z_plane_floats(d, M);
-    if (!(g_bx_dbg & 1)) rc = sf_bx_split_rows(dz, dz_cs, dz_coff, M, d->Cout, zp, s);
+    rc = sf_bx_split_rows(dz, dz_cs, dz_coff, M, d->Cout, zp, s);
     if (rc != SF_OK) return rc;
     dz_planes = zp;
   }
@@ -1333,7 +1275,6 @@ extern "C" int sf_conv_wgrad_bx(const sf_conv_desc* d, const float* x, const uns
   magic((unsigned)d->Ho, &a.ho_mul, &a.ho_sh);
   magic((unsigned)d->To, &a.to_mul, &a.to_sh);
   magic((unsigned)d->Cin, &a.ci_mul, &a.ci_sh);
-  if (g_bx_dbg & 4) return SF_OK;
   const int grid = pl.tiles * pl.S;
   return pl.bco == 256 ? launch_bxw<256>(a, grid, s) : launch_bxw<128>(a, grid, s);
 }

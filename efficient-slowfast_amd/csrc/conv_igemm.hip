@@ -480,7 +480,7 @@ static int splitk_factor(const sf_conv_desc* d, long M) {
 // 111 at M = 65 536).  Tiles of 112 = 7 x 16 rows give 7 * 2^j workgroups instead (448, 896: 0.875; 1792, 3584: whole
 // rounds), so among the MFMA tilings that fit the layer take the one with the best (last-round fill) x (tile
 // efficiency prior); the priors are the measured TFLOP/s of each tiling divided by its fill on the res3 layers
-// (tools/microbench/tile_sweep.py: 3x3 128->128 at M = 50 176: 112x128 93.9, 224x128 86.1, 128x128 85.0, 112x64
+// (measured: 3x3 128->128 at M = 50 176: 112x128 93.9, 224x128 86.1, 128x128 85.0, 112x64
 // 84.3, 64x64 81.3, 128x64 78.3 TFLOP/s).
 enum ConvCfg { CFG_256x16, CFG_256x32, CFG_64x64, CFG_128x64, CFG_128x128, CFG_112x64, CFG_112x128, CFG_224x128,
                CFG_COUNT };
@@ -489,17 +489,12 @@ static const int CFG_BN[] = {16, 32, 64, 64, 128, 64, 128, 128};
 static const double CFG_EFF[] = {0, 0, 0.86, 0.94, 1.00, 0.90, 0.965, 0.97};
 
 static ConvCfg conv_cfg(const sf_conv_desc* d, long M, int ksplit) {
-  static const int forced = [] {
-    const char* e = getenv("SF_CONV_CFG");  // microbenchmark aid: force one tiling for Cout >= 64 layers (-2: no 7x16-row tiles)
-    return e ? atoi(e) : -1;
-  }();
   if (d->Cout <= 16) return CFG_256x16;
   if (d->Cout <= 32) return CFG_256x32;
   if (ksplit > 1) return d->Cout <= 64 ? CFG_128x64 : CFG_128x128;
-  if (forced >= CFG_64x64 && forced < CFG_COUNT) return (ConvCfg)forced;
   // Short reductions into wide outputs (the bottleneck "c" convs, K = Cin <= 256 -> Cout >= 128, with the residual in
   // the epilogue) are prologue / epilogue bound: 64x64 tiles (4x the workgroups) measured 81 vs 67 TFLOP/s on
-  // 256 -> 1024 at M = 12544 and 74 vs 66 on 128 -> 512 at M = 50176 (tools/microbench/tile_sweep.py).
+  // 256 -> 1024 at M = 12544 and 74 vs 66 on 128 -> 512 at M = 50176.
   // (also 256 -> 64 at M = 200704: 78.7 vs 74.5-76.7 for the larger tiles)
   const int nk = d->kT * d->kH * d->kW * (d->cin_pad / BK);
   if (nk <= 16) return CFG_64x64;
@@ -507,7 +502,6 @@ static ConvCfg conv_cfg(const sf_conv_desc* d, long M, int ksplit) {
   double best_score = -1.0;
   for (int c = CFG_64x64; c < CFG_COUNT; ++c) {
     if (CFG_BN[c] == 128 && d->Cout <= 64) continue;
-    if (forced == -2 && CFG_BM[c] % 112 == 0) continue;  // A/B aid: power-of-two tiles only
     const long nbm = sf_cdiv(M, CFG_BM[c]), nbn = sf_cdiv(d->Cout, CFG_BN[c]);
     const long tiles = nbm * nbn;
     const double fill = (double)tiles / (double)(sf_cdiv(tiles, 256) * 256L);

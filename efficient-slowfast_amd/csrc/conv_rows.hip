@@ -50,7 +50,6 @@ struct CRowsArgs {
   int KB;                // channel blocks of XW floats per position stage
   int NB;                // stage buffers of the ring (NB - 1 steps in flight)
   int nhb, nseg, tseg;   // ring over t (3x1x1): 64-position blocks per frame, t segments, frames per segment
-  int dbg;               // SF_CONV_ROWS_DBG timing ablations (results invalid): 1 no loads, 2 no MFMA loop, 4 no stores
   int rows_needed;       // rows of a window that are read (64 + 2 halo); the rest of wrp is padding
   int HW, halo, wrp;     // frame size, halo rows of a 1x3x3 window, rows of one x window in LDS
   int wstride;           // floats per weight row in LDS
@@ -191,7 +190,7 @@ __global__ __launch_bounds__(256) void conv_rows_kernel(const CRowsArgs p) {
   }
   auto issue = [&](const CrCursor& c) {
     const int m0 = mb + c.ps * CR_L;
-    const bool live = c.st < nst && !(p.dbg & 1);
+    const bool live = c.st < nst;
     const unsigned lds0 = stg_base + (unsigned)((c.buf * stage_floats) << 2);
     const int cbx = c.cb * XW;
 #pragma unroll
@@ -340,7 +339,6 @@ __global__ __launch_bounds__(256) void conv_rows_kernel(const CRowsArgs p) {
     };
     CrFrag<NCT> fr[2];
     bool okv[2];
-    if (!(p.dbg & 2)) {
     fetch(0, fr[0], okv[0]);
 #pragma unroll
     for (int it = 0; it < NI; ++it) {
@@ -361,7 +359,6 @@ __global__ __launch_bounds__(256) void conv_rows_kernel(const CRowsArgs p) {
         acc2[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[ct][3], b[3], acc2[ct], 0, 0, 0);
       }
     }
-    }
     if (!last_of_stage) continue;
     // ---- epilogue of position stage ps: lane = position m, channels co0 + 16 ct + 4 g .. + 3
     const int m_first = mb + ps * CR_L + 16 * wave;  // this wavefront's first position of the stage (lane j = 0)
@@ -378,7 +375,7 @@ __global__ __launch_bounds__(256) void conv_rows_kernel(const CRowsArgs p) {
       acc[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
       acc2[ct] = acc[ct];
       if constexpr (RES) v += rv[ct];
-      if (mok && nok && !(p.dbg & 4)) {
+      if (mok && nok) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = sf_act(v[r], d.act);
         *reinterpret_cast<f32x4*>(p.out + (long)m * d.out_cs + d.out_coff + n) = v;
@@ -480,7 +477,7 @@ __global__ __launch_bounds__(256) void conv_rows_tring_kernel(const CRowsArgs p)
     lc[i] = (b < NXB && r_base + row < p.HW && c4 < d.Cin) ? (unsigned)((row * d.in_cs + c4) << 2) : CR_OOB;
   }
   auto issue = [&](int fx, int slot) {
-    const bool fok = (unsigned)fx < (unsigned)T && fx >= t0 - 1 && fx <= t1 && !(p.dbg & 1);
+    const bool fok = (unsigned)fx < (unsigned)T && fx >= t0 - 1 && fx <= t1;
     const unsigned base = fok ? (unsigned)(((((long)n * T + fx) * p.HW + r_base) * d.in_cs + d.in_coff) << 2) : CR_OOB;
     const unsigned lds0 = ring_base + (unsigned)((slot * SLOT) << 2);
 #pragma unroll
@@ -554,37 +551,35 @@ __global__ __launch_bounds__(256) void conv_rows_tring_kernel(const CRowsArgs p)
       acc[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
       acc2[ct] = acc[ct];
     }
-    if (!(p.dbg & 2)) {
-      auto fetch = [&](int it, CrFrag<NCT>& f) {
-        const int tap = it / NQ, q = it - tap * NQ;
-        const int slot = (s_lo + 1 + p.sg * (tap - 1)) & 3;   // frame t + sg (tap - 1)
-        const int c = 4 * q + g;
-        f.b = cr_lds128(ring_base + (unsigned)((slot * SLOT + R * XW + ((c ^ cr_swz<XW>(R)) << 2)) << 2));
-        const unsigned ao = a_lane + (unsigned)((tap * XW + 16 * q) << 2);
+    auto fetch = [&](int it, CrFrag<NCT>& f) {
+      const int tap = it / NQ, q = it - tap * NQ;
+      const int slot = (s_lo + 1 + p.sg * (tap - 1)) & 3;   // frame t + sg (tap - 1)
+      const int c = 4 * q + g;
+      f.b = cr_lds128(ring_base + (unsigned)((slot * SLOT + R * XW + ((c ^ cr_swz<XW>(R)) << 2)) << 2));
+      const unsigned ao = a_lane + (unsigned)((tap * XW + 16 * q) << 2);
 #pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) f.a[ct] = cr_lds128(ao + ct * wrow16);
-      };
-      constexpr int NI = 3 * NQ;
-      CrFrag<NCT> fr[2];
-      fetch(0, fr[0]);
+      for (int ct = 0; ct < NCT; ++ct) f.a[ct] = cr_lds128(ao + ct * wrow16);
+    };
+    constexpr int NI = 3 * NQ;
+    CrFrag<NCT> fr[2];
+    fetch(0, fr[0]);
 #pragma unroll
-      for (int it = 0; it < NI; ++it) {
-        CrFrag<NCT>& f = fr[it & 1];
-        if (it + 1 < NI) {
-          fetch(it + 1, fr[(it + 1) & 1]);
-          cr_wait<1 + NCT, NCT>(f);
-        } else {
-          cr_wait<0, NCT>(f);
-        }
-        f32x4 b = f.b;
-        if (XW < 16 && g >= XW / 4) b = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int it = 0; it < NI; ++it) {
+      CrFrag<NCT>& f = fr[it & 1];
+      if (it + 1 < NI) {
+        fetch(it + 1, fr[(it + 1) & 1]);
+        cr_wait<1 + NCT, NCT>(f);
+      } else {
+        cr_wait<0, NCT>(f);
+      }
+      f32x4 b = f.b;
+      if (XW < 16 && g >= XW / 4) b = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-          acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[ct][0], b[0], acc[ct], 0, 0, 0);
-          acc2[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[ct][1], b[1], acc2[ct], 0, 0, 0);
-          acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[ct][2], b[2], acc[ct], 0, 0, 0);
-          acc2[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[ct][3], b[3], acc2[ct], 0, 0, 0);
-        }
+      for (int ct = 0; ct < NCT; ++ct) {
+        acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[ct][0], b[0], acc[ct], 0, 0, 0);
+        acc2[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[ct][1], b[1], acc2[ct], 0, 0, 0);
+        acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[ct][2], b[2], acc[ct], 0, 0, 0);
+        acc2[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(f.a[ct][3], b[3], acc2[ct], 0, 0, 0);
       }
     }
     // ---- epilogue of frame t: lane = position m, channels co0 + 16 ct + 4 g .. + 3
@@ -600,7 +595,7 @@ __global__ __launch_bounds__(256) void conv_rows_tring_kernel(const CRowsArgs p)
       const bool nok = nn < d.Cout;
       f32x4 v = (acc[ct] + acc2[ct]) * esc[ct] + ebi[ct];
       if constexpr (RES) v += rv[ct];
-      if (rok && nok && !(p.dbg & 4)) {
+      if (rok && nok) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = sf_act(v[r], d.act);
         *reinterpret_cast<f32x4*>(p.out + m * d.out_cs + d.out_coff + nn) = v;
@@ -666,38 +661,20 @@ void cr_magic(unsigned dv, unsigned* mul, unsigned* sh) {
   *sh = l - 1;
 }
 
-// sf_conv_tune(22, e): 0 off, 1 = the environment's level (SF_CONV_ROWS, default 1), 2 every shape the kernels cover.
+// sf_conv_tune(22, e): 0 off, 1 (default) by rule, 2 every shape the kernels cover.
 // Level 1 takes ONLY the 3x1x1 layers with <= 16 output channels over <= 64 input channels, on the ring over t
 // (conv_rows_tring_kernel): the one form that beats what it replaces (profiles/r06_conv_rows_ab.txt: 32 -> 8 65 -> 51 us,
 // 16 -> 8 40 -> 31, 64 -> 16 127 -> 82 / 41.5 -> 34; wider outputs — the data gradients 16 -> 64, 32 -> 128 — lose 10-25 %).
-// The window form (conv_rows_kernel: every other shape) stays OFF — measured on MI355X (profiles/r06_conv_rows_ab.txt, tools/microbench/conv_rows_bench.py, cold operands,
-// launch counts of cfg #3 at 8 clips): 3.72 ms per step against 2.52 ms for the kernels it would replace.  What the
-// ablations say (SF_CONV_ROWS_DBG, true kernel durations by rocprofv3): with loads, MFMAs and stores all switched off a
-// launch keeps 40 .. 50 % of its time, and neither the ring depth (2 .. 8 steps in flight) nor the number of workgroups
-// moves it — it is the step SKELETON: ~100 .. 400 instructions per wavefront and step (piece addressing, the validity
-// bits' three divisions by multiplication, cursor, counted wait, barrier, epilogue) around 4 .. 48 MFMAs, issued by ONE
-// wavefront per SIMD wherever the windows + weights need > 80 KB of LDS, so every instruction's latency is exposed.
-// It is NOT the LDS-DMA path: tools/microbench/lds_delivery.hip measures 7.2 TB/s (HBM) .. 14 TB/s (L2) of contiguous
-// 1 KiB direct-to-LDS pieces, the same as register loads (profiles/r06_lds_delivery.txt).  What would change it: 256
-// positions per stage (four column tiles per wavefront: a quarter of the skeleton per position, and 1.45x instead of
-// 2.8x halo rows for 1x3x3), a ring over t for 3x1x1 (one window per frame instead of three: a third of the LDS, two
-// workgroups per CU), validity bits advanced incrementally.  Kept: correct for every shape it covers
-// (tests/test_conv_rows_gpu.py), selectable for A/B runs.
+// The window form (conv_rows_kernel: every other shape) stays OFF at level 1: 3.72 ms per step against 2.52 ms for the
+// kernels it would replace (profiles/r06_conv_rows_ab.txt; DESIGN.md has the timing ablations that located the cost in
+// the per-step instruction skeleton).  Kept: correct for every shape it covers (tests/test_conv_rows_gpu.py).
 int g_crows_enable = 1;
-
-int crows_level() {
-  static const int env = [] {
-    const char* e = getenv("SF_CONV_ROWS");
-    return e ? atoi(e) : 1;
-  }();
-  return g_crows_enable == 1 ? env : g_crows_enable;
-}
 
 struct CRowsPlan { int ntap, xw, nct, nby; size_t lds; bool ring; };
 
 // Geometry + schedule for a problem this kernel covers; false = leave it to the other dense kernels.
 bool crows_plan(const sf_conv_desc* d, CRowsArgs* a, CRowsPlan* pl) {
-  const int level = crows_level();
+  const int level = g_crows_enable;
   if (level <= 0) return false;
   if (d->sT != 1 || d->sH != 1 || d->sW != 1 || d->dT != 1 || d->dH != 1 || d->dW != 1) return false;
   if (d->To != d->Ti || d->Ho != d->Hi || d->Wo != d->Wi) return false;
@@ -739,14 +716,11 @@ bool crows_plan(const sf_conv_desc* d, CRowsArgs* a, CRowsPlan* pl) {
   a->sg = d->transposed ? -1 : 1;
   // ring depth: as many stage buffers as fit beside the weights in ~72 KB (two workgroups per CU), 3 .. 8
   const size_t wbytes = (size_t)16 * nct * a->wstride * 4, sbytes = (size_t)wps * a->wrp * xw * 4;
-  static const int nb_env = [] { const char* e = getenv("SF_CONV_ROWS_NB"); return e ? atoi(e) : 0; }();
-  int nb = nb_env > 0 ? nb_env : (int)((72 * 1024 - (long)wbytes) / (long)sbytes);
+  int nb = (int)((72 * 1024 - (long)wbytes) / (long)sbytes);
   if (nb < 3) nb = 3;
   if (nb > 8) nb = 8;
   while (nb > 2 && wbytes + nb * sbytes > 150 * 1024) --nb;
   a->NB = nb;
-  static const int dbg_env = [] { const char* e = getenv("SF_CONV_ROWS_DBG"); return e ? atoi(e) : 0; }();
-  a->dbg = dbg_env;
   pl->lds = wbytes + nb * sbytes;
   if (pl->lds > 150 * 1024) return false;
   if (((wps * a->wrp * xw) >> 10) > 24) return false;                   // at most 6 pieces per wavefront and step
@@ -754,8 +728,7 @@ bool crows_plan(const sf_conv_desc* d, CRowsArgs* a, CRowsPlan* pl) {
   pl->ntap = ntap; pl->xw = xw; pl->nct = nct; pl->nby = sf_cdiv(d->Cout, 16 * nct);
   pl->ring = false;
   a->nhb = a->nseg = a->tseg = 0;
-  static const int ring_env = [] { const char* e = getenv("SF_CONV_ROWS_RING"); return e ? atoi(e) : 1; }();
-  if (ntap == 3 && a->KB == 1 && ring_env && d->To >= 2 && a->HW >= 32) {  // 3x1x1 over <= 64 channels: the ring over t
+  if (ntap == 3 && a->KB == 1 && d->To >= 2 && a->HW >= 32) {  // 3x1x1 over <= 64 channels: the ring over t
     const int nhb = sf_cdiv(a->HW, CR_L);
     int nseg = 1;
     while (nseg * 2 <= d->To / 2 && (long)d->N * nhb * nseg * pl->nby < 600 && (long)d->N * nhb * nseg * 2 <= 1024) nseg *= 2;
@@ -777,8 +750,7 @@ bool crows_plan(const sf_conv_desc* d, CRowsArgs* a, CRowsPlan* pl) {
   // workgroups along the positions: ~1024 over the channel blocks, at least two stages each, at most 1024 (the
   // statistics workspace holds >= 4096 records per channel: four per workgroup)
   const long stages = (M + CR_L - 1) / CR_L;
-  static const int wgs = [] { const char* e = getenv("SF_CONV_ROWS_WGS"); return e ? atoi(e) : 768; }();
-  long S = wgs / pl->nby;
+  long S = 768 / pl->nby;
   if (S > 1024) S = 1024;
   if (S > (stages + 1) / 2) S = (stages + 1) / 2;
   if (S < 1) S = 1;

@@ -44,7 +44,6 @@ struct SmallArgs {
   int tiles_per_frame; // spatial
   int c4_shift;        // log2(CK / 4)
   int M;
-  int dbg;             // microbenchmarks: 1 = no staging loads, 2 = no FMA loop, 4 = no stores
   unsigned hw_mul, hw_sh, t_mul, t_sh, w_mul, w_sh;  // n / HW, n / T, n / W as mulhi + shift (mul == 0: divisor 1)
 };
 
@@ -144,7 +143,7 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const SmallArgs p) {
             }
             const int ch = k0 + c4 * 4;
             dst[u] = s * slab_floats + cell * PITCH + c4 * 4;
-            if (src >= 0 && ch < p.Cin && !(p.dbg & 1)) v[u] = *reinterpret_cast<const f32x4*>(p.in + src * p.in_cs + p.in_coff + ch);
+            if (src >= 0 && ch < p.Cin) v[u] = *reinterpret_cast<const f32x4*>(p.in + src * p.in_cs + p.in_coff + ch);
           }
         }
 #pragma unroll
@@ -154,7 +153,7 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const SmallArgs p) {
     }
     __syncthreads();
     // ---- compute: this thread's position x CO_T output channels over the chunk's CK input channels of every tap
-    if (active && !(p.dbg & 2)) {
+    if (active) {
       for (int kt = 0; kt < p.kT; ++kt)
         for (int kh = 0; kh < p.kH; ++kh)
           for (int kw = 0; kw < p.kW; ++kw) {
@@ -191,7 +190,7 @@ __global__ __launch_bounds__(256) void conv_small_kernel(const SmallArgs p) {
       acc[c] = v;
     }
   }
-  if (active && !(p.dbg & 4)) {
+  if (active) {
     float* const o = p.out + (long)m * p.out_cs + p.out_coff + n0;
     const float* const r = p.res ? p.res + (long)m * p.res_cs + p.res_coff + n0 : nullptr;
 #pragma unroll
@@ -250,17 +249,10 @@ static void magic(unsigned dv, unsigned* mul, unsigned* sh) {
   *sh = l - 1;
 }
 
-int g_small_enable = 1;  // sf_conv_tune(6, e): bit 0 = enable, bit 1 = every shape the instantiations cover (as
-int g_small_all = 0;     // SF_CONV_SMALL=2; tests), bits 4.. = ablation mask (microbenchmarks)
-int g_small_dbg = 0;
+int g_small_enable = 1;  // sf_conv_tune(6, e): bit 0 = enable, bit 1 = every shape the instantiations cover (tests)
+int g_small_all = 0;
 
-static int small_level() {
-  static const int env_on = [] {
-    const char* e = getenv("SF_CONV_SMALL");
-    return e ? atoi(e) : 1;
-  }();
-  return g_small_enable ? (g_small_all ? 2 : env_on) : 0;
-}
+static int small_level() { return g_small_enable ? (g_small_all ? 2 : 1) : 0; }
 static bool small_enabled() { return small_level() > 0; }
 
 template <int CO_T, int CK>
@@ -277,9 +269,9 @@ static int launch_small(const SmallArgs& a, int ntile, size_t lds_bytes, hipStre
 }  // namespace
 
 int sf_conv_small_tune(int value) {
+  if (value < 0 || value > 3) return SF_EINVAL;
   g_small_enable = value & 1;
   g_small_all = (value >> 1) & 1;
-  g_small_dbg = value >> 4;
   return SF_OK;
 }
 
@@ -305,7 +297,7 @@ int sf_conv_small_takes(const sf_conv_desc* d, int* parts_out) {
   // latency of its scalar weight loads (a 32 x 3 x 128 table is 49 KB: past the scalar cache, ~700 cycles per wait with
   // one wavefront per SIMD) and by row-per-lane stores of wide outputs: 128 -> 32 3x1x1 25 -> 236 us.  Until those two
   // are fixed (weights through LDS with several positions per thread, LDS-transposed stores) everything else stays
-  // on the matrix-core kernels; SF_CONV_SMALL=2 takes every shape the instantiations cover (A/B runs).
+  // on the matrix-core kernels; sf_conv_tune(6, 3) takes every shape the instantiations cover (tests).
   if (small_level() < 2 && !(cin <= 8 && cout <= 8 && (d->kH > 1 || d->kW > 1))) return 0;
   if ((d->in_cs % 4) || (d->in_coff % 4) || (d->out_cs % 4) || (d->out_coff % 4)) return 0;
   const long M = (long)d->N * d->To * d->Ho * d->Wo;
@@ -344,7 +336,6 @@ int sf_conv_small_try(const sf_conv_desc* d, const float* in, const float* w_pac
   a.flip = d->transposed ? 1 : 0;
   a.act = d->act;
   a.M = (int)((long)d->N * d->To * d->Ho * d->Wo);
-  a.dbg = g_small_dbg;
   a.G = d->Cout > 32 ? d->Cout / 32 : 1;
   const int co_t = d->Cout > 32 ? 32 : d->Cout;
   a.spatial = (d->kH > 1 || d->kW > 1) ? 1 : 0;

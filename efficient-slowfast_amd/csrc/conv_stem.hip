@@ -301,14 +301,10 @@ __global__ __launch_bounds__(256) void conv_stem_pair_kernel(const StemFwdArgs q
 }  // namespace
 
 // Returns SF_OK when the launch was made, 1 when the problem is not this kernel's (the caller takes the implicit-GEMM
-// path), or an error.  SF_CONV_STEM=0 switches it off (A/B).
+// path), or an error.
 int sf_conv_stem_fwd_try(const sf_conv_desc* d, const float* in, const float* w, const float* scale,
                          const float* bias, const float* res, float* out, hipStream_t stream) {
-  static const bool off = [] {
-    const char* e = getenv("SF_CONV_STEM");
-    return e && e[0] == '0';
-  }();
-  if (off || res || d->transposed || d->out_cmul != 1 || d->os_T > 1 || d->os_H > 1 || d->os_W > 1) return 1;
+  if (res || d->transposed || d->out_cmul != 1 || d->os_T > 1 || d->os_H > 1 || d->os_W > 1) return 1;
   if (d->kT != KT || d->kH != KH || d->kW != 1 || d->sT != 1 || d->sW != 1 || d->pH != 0 || d->pW != 0 || d->dT != 1 ||
       d->dH != 1 || d->dW != 1 || d->cin_pad != 32 || d->Cin > 32 || d->Cout > 16 || d->in_coff != 0 ||
       (d->in_cs % 4) != 0 || !sf_aligned16(in) || d->To != d->Ti + 2 * d->pT - KT + 1)
@@ -319,19 +315,12 @@ int sf_conv_stem_fwd_try(const sf_conv_desc* d, const float* in, const float* w,
   q.rowf = d->Wi * d->in_cs;
   q.ps = d->sW * d->in_cs;
   if ((long)(d->Wo - 1) * q.ps + 32 > q.rowf || (long)(d->Ho - 1) * d->sH + KH > d->Hi) return 1;
-  static const bool nopair = [] {
-    const char* e = getenv("SF_STEM_PAIR");
-    return e && e[0] == '0';
-  }();
-  const bool pair = !nopair && d->Cout <= 8 && q.ps == 8 && d->Cin <= 28;
+  const bool pair = d->Cout <= 8 && q.ps == 8 && d->Cin <= 28;
   q.nblk = pair ? ((d->Wo + 1) / 2 + 15) / 16 : (d->Wo + 15) / 16;
   if (q.nblk > MAXBLK || KH * q.rowf > 8 * 256 * 4) return 1;
   const size_t lds6 = (size_t)RING6 * KH * q.rowf * sizeof(float);
-  static const bool dealt = [] {  // SF_STEM_PAIR=1: the pair form with the taps dealt to the wavefronts (A/B)
-    const char* e = getenv("SF_STEM_PAIR");
-    return e && e[0] == '1';
-  }();
-  const bool all_taps = pair && !dealt && lds6 <= 160 * 1024 - 512;
+  // (rows too wide for the six-slab ring: the pair form with the taps dealt to the wavefronts, conv_stem_fwd_kernel<true>)
+  const bool all_taps = pair && lds6 <= 160 * 1024 - 512;
   const size_t lds = all_taps ? lds6 : ((size_t)KT * KH * q.rowf + (size_t)4 * q.nblk * 16 * 16) * sizeof(float);
   if (lds > 160 * 1024 - 512) return 1;
   int best = 1;

@@ -48,7 +48,6 @@ struct WaveArgs {
   unsigned in_bytes, w_bytes;
   unsigned out_bytes, res_bytes;  // extents of the output / residual buffers (buffer load / store bounds)
   int res_buf;                    // output and residual fit 32-bit buffer addressing: the one-pass epilogue's branch-free form
-  int dbg;             // sf_conv_tune(5, mask), microbenchmarks only: 1 = drop the stores, 2 = every A row reads row 0
   int plain;           // 1: 1x1x1 kernel, stride 1, no padding, same extents -> input row == output row
   float* stats;        // != NULL: [part][Cout / 4][count, K, sum(v - K), sum((v - K)^2)][4 channels] of the stored outputs
   // n / d for 0 <= n < 2^31 as (mulhi(n, mul) >> sh); d == 1 has mul == 0 (identity)
@@ -68,9 +67,9 @@ __device__ __forceinline__ unsigned tap_run(int x0, int sg, int n, int kn) {
   return hi > lo ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
 }
 
-template <int TM, int TN, int KS, int KV>
+template <int TM, int TN, int KS>
 __global__ __launch_bounds__(256) void conv_wave_kernel(const WaveArgs p) {
-  constexpr int KB = 16 * KV;                                   // channels per K step: KV 16-byte fragments per lane
+  constexpr int KB = 16;                                        // channels per K step: one 16-byte fragment per lane
   constexpr int BN = TN * 16;
   constexpr int TPW = 4 / KS;                                   // tiles per workgroup
   constexpr int R = (128 / BN) < 1 ? 1 : ((128 / BN) > 4 ? 4 : (128 / BN));  // 16-row slabs per epilogue round
@@ -105,7 +104,7 @@ __global__ __launch_bounds__(256) void conv_wave_kernel(const WaveArgs p) {
       // decode below costs ~300 vector-ALU cycles per row (three magic divisions, 32-bit multiplies) — a quarter of
       // a K = 64 layer's tile on ALUs the fp32 MFMA shares
       a_pm[i] = ok ? (1u | (1u << 10) | (1u << 20)) : 0u;
-      a_base[i] = (mm * (unsigned)d.in_cs + (unsigned)(d.in_coff + fg * 4 * KV)) * 4u;
+      a_base[i] = (mm * (unsigned)d.in_cs + (unsigned)(d.in_coff + fg * 4)) * 4u;
       continue;
     }
     const unsigned q1 = fast_div(mm, p.wo_mul, p.wo_sh);
@@ -130,11 +129,11 @@ __global__ __launch_bounds__(256) void conv_wave_kernel(const WaveArgs p) {
     }
     a_pm[i] = pm;
     const int pos = ((n * d.Ti + t0) * d.Hi + h0) * d.Wi + w0;  // may be negative (window starts in the padding)
-    a_base[i] = (unsigned)(pos * d.in_cs + d.in_coff + fg * 4 * KV) * 4u;
+    a_base[i] = (unsigned)(pos * d.in_cs + d.in_coff + fg * 4) * 4u;
   }
   unsigned b_base[TN];
 #pragma unroll
-  for (int j = 0; j < TN; ++j) b_base[j] = ((unsigned)(n0 + j * 16 + fr) * (unsigned)(p.nk * KB) + (unsigned)(fg * 4 * KV)) * 4u;
+  for (int j = 0; j < TN; ++j) b_base[j] = ((unsigned)(n0 + j * 16 + fr) * (unsigned)(p.nk * KB) + (unsigned)(fg * 4)) * 4u;
 
   const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, (int)p.in_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t b_rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, live ? (int)p.w_bytes : 0, 0x00020000);
@@ -157,24 +156,18 @@ __global__ __launch_bounds__(256) void conv_wave_kernel(const WaveArgs p) {
   };
   set_tap();
 
-  // Loads of the step the iteration state (it, c0, a_cur) currently points at.  A lane's fragment is KV * 16
-  // contiguous bytes: with KV = 2 the four lanes of a row cover one whole 128-byte line per load pair (with KV = 1
-  // every 64-byte half line is fetched into L1 twice, one K step apart — by then evicted).
-  auto load_b = [&](f32x4 (&b)[TN][KV]) {
+  // Loads of the step the iteration state (it, c0, a_cur) currently points at.  A lane's fragment is 16 contiguous
+  // bytes (32-byte fragments — whole 128-byte lines per row and load pair — were measured slower: DESIGN.md).
+  auto load_b = [&](f32x4 (&b)[TN]) {
     const unsigned boff = (unsigned)it * (unsigned)(KB * 4);
 #pragma unroll
     for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int v = 0; v < KV; ++v)
-        b[j][v] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(b_rs, b_base[j] + boff + v * 16, 0, 0));
+      b[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(b_rs, b_base[j] + boff, 0, 0));
   };
-  auto load_a = [&](int i, f32x4 (&a)[KV]) {
+  auto load_a = [&](int i, f32x4& a) {
     const unsigned koff = (unsigned)c0 * 4u;     // OOB + koff stays out of range (koff < 2 GiB)
-#pragma unroll
-    for (int v = 0; v < KV; ++v) {
-      const bool kin = (c0 + (fg * KV + v) * 4) < d.Cin;  // channel tail of a tap whose Cin is not a multiple of KB
-      a[v] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, kin ? a_cur[i] + koff + v * 16 : OOB, 0, 0));
-    }
+    const bool kin = (c0 + fg * 4) < d.Cin;      // channel tail of a tap whose Cin is not a multiple of KB
+    a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, kin ? a_cur[i] + koff : OOB, 0, 0));
   };
   auto advance = [&]() {
     ++it;
@@ -205,7 +198,7 @@ __global__ __launch_bounds__(256) void conv_wave_kernel(const WaveArgs p) {
   // dependent latency).  Loads past the end of the range are harmless (any offset is either valid memory of the
   // buffer or reads zero) and their results are never used.
   {
-    f32x4 fa[TM][KV], fb[TN][KV], fbn[TN][KV];
+    f32x4 fa[TM], fb[TN], fbn[TN];
     const int nsteps = it_end - it_begin;
     load_b(fb);
 #pragma unroll
@@ -216,22 +209,18 @@ __global__ __launch_bounds__(256) void conv_wave_kernel(const WaveArgs p) {
 #pragma unroll
       for (int i2 = 0; i2 < TM; i2 += 2) {
 #pragma unroll
-        for (int v = 0; v < KV; ++v)
+        for (int s = 0; s < 4; ++s)
 #pragma unroll
-          for (int s = 0; s < 4; ++s)
+          for (int i = i2; i < i2 + 2 && i < TM; ++i)
 #pragma unroll
-            for (int i = i2; i < i2 + 2 && i < TM; ++i)
-#pragma unroll
-              for (int j = 0; j < TN; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][v][s], fb[j][v][s], acc[i][j], 0, 0, 0);
+            for (int j = 0; j < TN; ++j)
+              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[i][s], fb[j][s], acc[i][j], 0, 0, 0);
 #pragma unroll
         for (int i = i2; i < i2 + 2 && i < TM; ++i) load_a(i, fa[i]);
         __builtin_amdgcn_sched_barrier(0);  // keep the pair's loads right behind its MFMAs (the scheduler would sink them)
       }
 #pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int v = 0; v < KV; ++v) fb[j][v] = fbn[j][v];
+      for (int j = 0; j < TN; ++j) fb[j] = fbn[j];
       advance();
     }
   }
@@ -477,9 +466,9 @@ __device__ __forceinline__ float row16_sum(float v) {  // sum over the 16 lanes 
 
 // PLAIN (1x1x1, stride 1, no padding — every short-K layer): the source row of an output row is that row for the one
 // tap, so the per-row state is ONE offset (no validity masks, no tap switching): 2*TM registers less.
-template <int TM, int TN, int KV, bool PLAIN>
+template <int TM, int TN, bool PLAIN>
 __global__ __launch_bounds__(256, 2) void conv_wave_p_kernel(const WaveArgs p) {
-  constexpr int KB = 16 * KV;
+  constexpr int KB = 16;
   constexpr int BN = TN * 16;
   const sf_conv_desc& d = p.d;
   const int lane = threadIdx.x & 63;
@@ -507,12 +496,12 @@ __global__ __launch_bounds__(256, 2) void conv_wave_p_kernel(const WaveArgs p) {
       const bool ok = live && rr < p.rows && m < p.M;
       const unsigned mm = ok ? (unsigned)m : 0u;
       if constexpr (PLAIN) {
-        a_cur[i] = ok ? (((p.dbg & 2) ? (unsigned)fr : mm) * (unsigned)d.in_cs + (unsigned)(d.in_coff + fg * 4 * KV)) * 4u : OOB;
+        a_cur[i] = ok ? (mm * (unsigned)d.in_cs + (unsigned)(d.in_coff + fg * 4)) * 4u : OOB;
         continue;
       }
       if (p.plain) {
         a_pm[i % TS] = ok ? (1u | (1u << 10) | (1u << 20)) : 0u;
-        a_base[i % TS] = (mm * (unsigned)d.in_cs + (unsigned)(d.in_coff + fg * 4 * KV)) * 4u;
+        a_base[i % TS] = (mm * (unsigned)d.in_cs + (unsigned)(d.in_coff + fg * 4)) * 4u;
         continue;
       }
       const unsigned q1 = fast_div(mm, p.wo_mul, p.wo_sh);
@@ -537,11 +526,11 @@ __global__ __launch_bounds__(256, 2) void conv_wave_p_kernel(const WaveArgs p) {
       }
       a_pm[i % TS] = pm;
       const int pos = ((n * d.Ti + t0) * d.Hi + h0) * d.Wi + w0;
-      a_base[i % TS] = (unsigned)(pos * d.in_cs + d.in_coff + fg * 4 * KV) * 4u;
+      a_base[i % TS] = (unsigned)(pos * d.in_cs + d.in_coff + fg * 4) * 4u;
     }
 #pragma unroll
     for (int j = 0; j < TN; ++j)
-      b_base[j] = live ? ((unsigned)(n0 + j * 16 + fr) * (unsigned)(p.nk * KB) + (unsigned)(fg * 4 * KV)) * 4u : OOB;
+      b_base[j] = live ? ((unsigned)(n0 + j * 16 + fr) * (unsigned)(p.nk * KB) + (unsigned)(fg * 4)) * 4u : OOB;
   };
 
   const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, (int)p.in_bytes, 0x00020000);
@@ -561,21 +550,16 @@ __global__ __launch_bounds__(256, 2) void conv_wave_p_kernel(const WaveArgs p) {
     }
   };
   auto rewind = [&]() { it = 0; c0 = 0; kw = 0; kh = 0; kt = 0; set_tap(); };
-  auto load_b = [&](f32x4 (&b)[TN][KV]) {
+  auto load_b = [&](f32x4 (&b)[TN]) {
     const unsigned boff = (unsigned)it * (unsigned)(KB * 4);
 #pragma unroll
     for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int v = 0; v < KV; ++v)
-        b[j][v] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(b_rs, b_base[j] + boff + v * 16, 0, 0));
+      b[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(b_rs, b_base[j] + boff, 0, 0));
   };
-  auto load_a = [&](int i, f32x4 (&a)[KV]) {
+  auto load_a = [&](int i, f32x4& a) {
     const unsigned koff = (unsigned)c0 * 4u;
-#pragma unroll
-    for (int v = 0; v < KV; ++v) {
-      const bool kin = (c0 + (fg * KV + v) * 4) < d.Cin;
-      a[v] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, kin ? a_cur[i] + koff + v * 16 : OOB, 0, 0));
-    }
+    const bool kin = (c0 + fg * 4) < d.Cin;
+    a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, kin ? a_cur[i] + koff : OOB, 0, 0));
   };
   auto advance = [&]() {
     ++it;
@@ -608,7 +592,7 @@ __global__ __launch_bounds__(256, 2) void conv_wave_p_kernel(const WaveArgs p) {
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    f32x4 fa[TM][KV], fb[TN][KV], fbn[TN][KV];
+    f32x4 fa[TM], fb[TN], fbn[TN];
     setup(tile);
     rewind();
     load_b(fb);
@@ -627,22 +611,18 @@ __global__ __launch_bounds__(256, 2) void conv_wave_p_kernel(const WaveArgs p) {
 #pragma unroll
         for (int i2 = 0; i2 < TM; i2 += 2) {
 #pragma unroll
-          for (int v = 0; v < KV; ++v)
+          for (int s = 0; s < 4; ++s)
 #pragma unroll
-            for (int s = 0; s < 4; ++s)
+            for (int i = i2; i < i2 + 2 && i < TM; ++i)
 #pragma unroll
-              for (int i = i2; i < i2 + 2 && i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)  // A = weights (rows = channels), B = activations (columns = positions)
-                  acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fb[j][v][s], fa[i][v][s], acc[i][j], 0, 0, 0);
+              for (int j = 0; j < TN; ++j)  // A = weights (rows = channels), B = activations (columns = positions)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fb[j][s], fa[i][s], acc[i][j], 0, 0, 0);
 #pragma unroll
           for (int i = i2; i < i2 + 2 && i < TM; ++i) load_a(i, fa[i]);
           __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int v = 0; v < KV; ++v) fb[j][v] = fbn[j][v];
+        for (int j = 0; j < TN; ++j) fb[j] = fbn[j];
         advance();
       }
       // ---- epilogue of the tile at (m0c, n0c): lane = position (i*16 + fr), registers = channels 4*fg .. 4*fg+3 of
@@ -712,7 +692,7 @@ __global__ __launch_bounds__(256, 2) void conv_wave_p_kernel(const WaveArgs p) {
 #pragma unroll
                   for (int e = 0; e < 4; ++e) v[e] = fminf(fmaxf(v[e], 0.f), hi);
                 }
-                const unsigned off = (ok && !(p.dbg & 1)) ? (orow[i] * (unsigned)d.out_cs + (unsigned)(d.out_coff + n)) * 4u : OOB;
+                const unsigned off = ok ? (orow[i] * (unsigned)d.out_cs + (unsigned)(d.out_coff + n)) * 4u : OOB;
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), o_rs, off, 0, 0);
                 if constexpr (STATS.value) {
                   const f32x4 dv = v - st_k;
@@ -785,20 +765,11 @@ constexpr int NCFG = (int)(sizeof(CFGS) / sizeof(CFGS[0]));
 int g_force_cfg = -1;    // sf_conv_tune(1, c): force configuration c (microbenchmarks); -1 = planner
 int g_force_rows = 0;    // sf_conv_tune(2, r): force rows per M tile
 int g_enable = 1;        // sf_conv_tune(0, e): 0 = never take the wave path
-int g_k32 = 0;           // sf_conv_tune(3, 1): 32-channel K steps where the packed rows allow (measured slower)
-
-int g_dbg = 0;           // sf_conv_tune(5, mask): persistent kernel ablations (microbenchmarks)
-int g_persist = 1;       // sf_conv_tune(4, e): 0 = KS == 1 layers on the one-pass kernel (A/B runs)
+int g_persist = 1;       // sf_conv_tune(4, e): 0 = KS == 1 layers on the one-pass kernel, 1 = level 3, 10 + L = level L
 
 // 0: never; 1: every KS == 1 layer the instantiations cover; 2: plain (1x1x1) layers only; 3 (default): plain layers
 // with at most 4 K steps
-static int persist_level() {
-  static const int env_on = [] {
-    const char* e = getenv("SF_CONV_WAVE_P");
-    return e ? atoi(e) : 3;
-  }();
-  return g_persist >= 10 ? g_persist - 10 : (g_persist ? env_on : 0);
-}
+static int persist_level() { return g_persist >= 10 ? g_persist - 10 : (g_persist ? 3 : 0); }
 
 // launch == false: only report the workgroups of this instantiation a CU holds (registers), asked of the runtime once
 template <int TM, int TN, bool PLAIN>
@@ -806,13 +777,13 @@ static int wave_p(const WaveArgs& a, int nwg, hipStream_t s, bool launch) {
   if (!launch) {
     static const int occ = [] {
       int n = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_wave_p_kernel<TM, TN, 1, PLAIN>, 256, 0) != hipSuccess || n < 1)
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, conv_wave_p_kernel<TM, TN, PLAIN>, 256, 0) != hipSuccess || n < 1)
         n = 1;
       return n > 4 ? 4 : n;
     }();
     return occ;
   }
-  hipLaunchKernelGGL((conv_wave_p_kernel<TM, TN, 1, PLAIN>), dim3(nwg), dim3(256), 0, s, a);
+  hipLaunchKernelGGL((conv_wave_p_kernel<TM, TN, PLAIN>), dim3(nwg), dim3(256), 0, s, a);
   SF_CHECK_LAUNCH();
   return SF_OK;
 }
@@ -833,11 +804,8 @@ static int wave_p_dispatch(int best, const WaveArgs& a, int nwg, hipStream_t s, 
 }
 
 template <int TM, int TN, int KS>
-static int launch_wave(const WaveArgs& a, int kv, hipStream_t s) {
-  if (kv == 2)
-    hipLaunchKernelGGL((conv_wave_kernel<TM, TN, KS, 2>), dim3(a.nwg), dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((conv_wave_kernel<TM, TN, KS, 1>), dim3(a.nwg), dim3(256), 0, s, a);
+static int launch_wave(const WaveArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL((conv_wave_kernel<TM, TN, KS>), dim3(a.nwg), dim3(256), 0, s, a);
   SF_CHECK_LAUNCH();
   return SF_OK;
 }
@@ -849,13 +817,8 @@ static int launch_wave(const WaveArgs& a, int kv, hipStream_t s) {
 // and epilogue are a fixed cost per set of co-resident workgroups; the layer cannot beat its HBM bytes, and the
 // epilogue's stores arrive as one burst when every workgroup finishes together.
 static double plan_score(const sf_conv_desc* d, long M, int nk, bool has_res, const WaveCfg& c, int* rows_out) {
-  // fitted constants (tools/plan/fit_plan.py); SF_PLAN="ld,f0,f1,bw,ep" overrides them for calibration runs
-  static const struct PlanP { double ld, f0, f1, bw, ep; } PP = [] {
-    PlanP q = {60.3, 2229.0, 381.0, 6.64e6, 0.96};  // refit on profiles/r02b_conv_wave_ab.txt (was 60, 10000, 150, 4.5e6, 0.6)
-    if (const char* e = getenv("SF_PLAN")) sscanf(e, "%lf,%lf,%lf,%lf,%lf", &q.ld, &q.f0, &q.f1, &q.bw, &q.ep);
-    return q;
-  }();
-  const double LD = PP.ld, F0 = PP.f0, F1 = PP.f1, BW = PP.bw / 2.1e3 /* bytes per cycle at 2.1 GHz */, EP = PP.ep;
+  // fitted constants (tools/plan/fit_plan.py, on profiles/r02b_conv_wave_ab.txt)
+  const double LD = 60.3, F0 = 2229.0, F1 = 381.0, BW = 6.64e6 / 2.1e3 /* bytes per cycle at 2.1 GHz */, EP = 0.96;
   const int N = d->Cout, ntaps = d->kT * d->kH * d->kW;
   const int nbn = sf_cdiv(N, c.tn * 16);
   const int nbm0 = sf_cdiv(M, c.tm * 16);
@@ -884,7 +847,6 @@ static double plan_score(const sf_conv_desc* d, long M, int nk, bool has_res, co
 int sf_wgrad_wave_tune(int knob, int value);  // conv_wgrad_wave.hip (knobs 10..)
 int sf_conv_small_tune(int value);            // conv_small.hip
 int sf_conv_bx_tune(int value);               // conv_bx.hip
-int sf_conv_bx_dbg(int value);                // conv_bx.hip
 int sf_conv_bxw_tune(int value);              // conv_bx.hip
 int sf_wgrad_rows_tune(int value);            // conv_wgrad_rows.hip
 int sf_conv_pw_tune(int value);               // conv_bx.hip
@@ -906,28 +868,17 @@ extern "C" int sf_conv_tune(int knob, int value) {
   if (knob == 0) g_enable = value;
   else if (knob == 1) g_force_cfg = value;
   else if (knob == 2) g_force_rows = value;
-  else if (knob == 3) g_k32 = value;
   else if (knob == 4) g_persist = value;
-  else if (knob == 5) g_dbg = value;
   else if (knob == 6) return sf_conv_small_tune(value);
   else if (knob == 7) return sf_conv_bx_tune(value);
-  else if (knob == 8) return sf_conv_bx_dbg(value);
   else if (knob == 9) return sf_conv_bxw_tune(value);
   else return SF_EINVAL;
   return SF_OK;
 }
 
-static bool wave_enabled() {
-  static const int env_on = [] {
-    const char* e = getenv("SF_CONV_WAVE");
-    return e ? atoi(e) : 1;
-  }();
-  return env_on && g_enable;
-}
-
 // Shape-only part of the decision (pointer alignment is checked at launch): used to size workspaces.
 int sf_conv_wave_takes(const sf_conv_desc* d) {
-  if (!wave_enabled()) return 0;
+  if (!g_enable) return 0;
   const long M = (long)d->N * d->To * d->Ho * d->Wo;
   if ((d->Cin % 4) || (d->in_cs % 4) || (d->in_coff % 4)) return 0;
   if (d->out_cmul != 1 || (d->Cout % 4) || (d->out_cs % 4) || (d->out_coff % 4)) return 0;
@@ -966,10 +917,7 @@ int sf_conv_wave_try(const sf_conv_desc* d, const float* in, const float* w_pack
   a.in = in; a.w = w_packed; a.scale = scale; a.bias = bias; a.res = res; a.out = out;
   a.M = (int)M;
   a.ntaps = ntaps;
-  // 16-channel K steps; sf_conv_tune(3, 1) selects 32 (whole 128-byte lines per row and load pair) where the packed
-  // rows allow — measured slower on every layer of cfg #3 (one wavefront per SIMD at 256+ registers)
-  const int kv = (d->cin_pad % 32 == 0 && g_k32) ? 2 : 1;
-  a.cpk = d->cin_pad / (16 * kv);
+  a.cpk = d->cin_pad / 16;
   a.nk = ntaps * a.cpk;
   a.in_bytes = (unsigned)in_bytes;
   a.w_bytes = (unsigned)w_bytes;
@@ -979,13 +927,13 @@ int sf_conv_wave_try(const sf_conv_desc* d, const float* in, const float* w_pack
   int best = 0, best_rows = 0;
   if (g_force_cfg >= 0 && g_force_cfg < NCFG) {
     best = g_force_cfg;
-    plan_score(d, M, a.nk * kv, res != nullptr, CFGS[best], &best_rows);
+    plan_score(d, M, a.nk, res != nullptr, CFGS[best], &best_rows);
   } else {
     double bs = 1e30;
     for (int c = 0; c < NCFG; ++c) {
       if (CFGS[c].tn * 16 > ((d->Cout + 15) / 16) * 16 && CFGS[c].tn > 1) continue;  // tile wider than the layer
       int rows = 0;
-      const double s = plan_score(d, M, a.nk * kv, res != nullptr, CFGS[c], &rows);
+      const double s = plan_score(d, M, a.nk, res != nullptr, CFGS[c], &rows);
       if (s < bs) { bs = s; best = c; best_rows = rows; }
     }
   }
@@ -1008,20 +956,18 @@ int sf_conv_wave_try(const sf_conv_desc* d, const float* in, const float* w_pack
   // room for a second row-state set (13x2 stays on the one-pass kernel there)
   const long rows_out = scatter ? (long)d->N * d->ob_T * d->ob_H * d->ob_W : M;
   const long out_b = rows_out * d->out_cs * 4, res_b = res ? rows_out * d->res_cs * 4 : 0;
-  a.dbg = g_dbg;
   a.out_bytes = (unsigned)out_b;
   a.res_bytes = (unsigned)res_b;
   a.res_buf = (out_b > 0 && out_b < 0x7ffffff0L && res_b < 0x7ffffff0L) ? 1 : 0;
-  // Where the persistent form pays (tools/microbench/conv_pw_probe.py, MI355X): plain layers with at most 4 K steps
+  // Where the persistent form pays (measured on MI355X): plain layers with at most 4 K steps
   // (K <= 64: 64 -> 256 at 56^2 79 us on 7x2 tiles against 86-94 us one-pass on any tile; the C <= 32 Fast-pathway
   // projections 10-25 % faster) — a tile there is ~7 k MFMA cycles, as long as the one-pass kernel's fixed part.  From
   // 8 K steps on the two forms are within 3 % of each other and the planner's picks stay on the one-pass kernel.
-  // SF_CONV_WAVE_P=1 sends every KS == 1 layer the instantiations cover to the persistent form (A/B runs).
-  const bool can_p = kv == 1 && persist_level() > 0 && out_b < 0x7ffffff0L && res_b < 0x7ffffff0L;
+  const bool can_p = persist_level() > 0 && out_b < 0x7ffffff0L && res_b < 0x7ffffff0L;
   const bool short_k = a.plain && a.nk <= 5;
   if (can_p && short_k && g_force_cfg < 0 && d->Cout >= 32) {
     best = 5;  // 7x2 tiles: 3 workgroups per CU at 157 registers
-    plan_score(d, M, a.nk * kv, res != nullptr, CFGS[best], &best_rows);
+    plan_score(d, M, a.nk, res != nullptr, CFGS[best], &best_rows);
     a.rows = best_rows;
     a.nb_n = sf_cdiv(d->Cout, CFGS[best].tn * 16);
     a.ntiles = sf_cdiv(M, a.rows) * a.nb_n;
@@ -1043,13 +989,13 @@ int sf_conv_wave_try(const sf_conv_desc* d, const float* in, const float* w_pack
   }
   if (a.stats) *stat_parts = (c.ks == 1 && a.nb_n == 1) ? a.nwg : sf_cdiv(M, a.rows);
   switch (best) {
-    case 0: return launch_wave<13, 2, 4>(a, kv, stream);
-    case 1: return launch_wave<13, 2, 1>(a, kv, stream);
-    case 2: return launch_wave<7, 4, 4>(a, kv, stream);
-    case 3: return launch_wave<7, 4, 1>(a, kv, stream);
-    case 4: return launch_wave<7, 2, 4>(a, kv, stream);
-    case 5: return launch_wave<7, 2, 1>(a, kv, stream);
-    case 6: return launch_wave<13, 1, 4>(a, kv, stream);
-    default: return launch_wave<13, 1, 1>(a, kv, stream);
+    case 0: return launch_wave<13, 2, 4>(a, stream);
+    case 1: return launch_wave<13, 2, 1>(a, stream);
+    case 2: return launch_wave<7, 4, 4>(a, stream);
+    case 3: return launch_wave<7, 4, 1>(a, stream);
+    case 4: return launch_wave<7, 2, 4>(a, stream);
+    case 5: return launch_wave<7, 2, 1>(a, stream);
+    case 6: return launch_wave<13, 1, 4>(a, stream);
+    default: return launch_wave<13, 1, 1>(a, stream);
   }
 }

@@ -545,11 +545,11 @@ constexpr int STEM_WIN = 36;
 constexpr int STEM_ROWS = STEM_KT * STEM_KH * STEM_WIN;   // 1260
 constexpr int STEM_MT = (STEM_ROWS + 15) / 16;            // 79
 
-// NW wavefronts per workgroup (4 or 8) share the ring; with 8, two wavefronts per SIMD cover each other's LDS
-// latencies and instruction issue (the f32 MFMA shares the vector ALUs with everything else a wavefront does).
-template <int NW>
-__global__ __launch_bounds__(64 * NW) void conv_wgrad_stem_pair_kernel(const StemArgs q) {
-  constexpr int STEM_NI2 = (STEM_MT + NW - 1) / NW;  // accumulator tiles per wavefront (20 / 10)
+// NW = 8 wavefronts per workgroup share the ring: two wavefronts per SIMD cover each other's LDS latencies and
+// instruction issue (the f32 MFMA shares the vector ALUs with everything else a wavefront does).
+__global__ __launch_bounds__(512) void conv_wgrad_stem_pair_kernel(const StemArgs q) {
+  constexpr int NW = 8;
+  constexpr int STEM_NI2 = (STEM_MT + NW - 1) / NW;  // accumulator tiles per wavefront (10)
   constexpr int NT = 64 * NW;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const WgradArgs& p = q.w;
@@ -699,8 +699,6 @@ __global__ __launch_bounds__(64 * NW) void conv_wgrad_stem_pair_kernel(const Ste
 
 // Does this problem take the stem kernel, and with how many workgroups (= partials)?
 static bool stem_plan(const sf_conv_desc* d, int dz_cs, StemArgs* q) {
-  static const bool off = [] { const char* e = getenv("SF_WGRAD_STEM"); return e && e[0] == '0'; }();
-  if (off) return false;
   if (d->kT != STEM_KT || d->kH != STEM_KH || d->kW != 1 || d->sT != 1 || d->sW != 1 || d->pH != 0 || d->pW != 0 ||
       d->dT != 1 || d->dH != 1 || d->dW != 1 || d->cin_pad != 32 || d->Cin > 32 || d->Cout > STEM_CO ||
       d->in_coff != 0 || (d->in_cs % 4) != 0 || d->To != d->Ti + 2 * d->pT - STEM_KT + 1)
@@ -712,13 +710,12 @@ static bool stem_plan(const sf_conv_desc* d, int dz_cs, StemArgs* q) {
   if (nblk * 16 * STEM_CO > 1024 || STEM_KH * rowf > 8 * 256 * 4) return false; // staging capacity per thread
   const long lds = ((long)STEM_KT * STEM_KH * rowf + (long)nblk * 16 * STEM_CO) * 4;
   if (lds > 160 * 1024 - 512) return false;
-  static const bool nopair = [] { const char* e = getenv("SF_STEM_PAIR"); return e && e[0] == '0'; }();
   // pair form: the window of the last pair (28 + 8 floats from its first position) stays inside the staged slab
   const int nk = ((d->Wo + 1) / 2 + 3) / 4;
   // (pair p starts at float 16 p of the row and reads 36 floats: 16 (npair - 1) + 36 <= rowf, else the last pair of
   // an odd-Wo row would run into the next kh row of the slab — fall back to the one-position form)
   const int npair = (d->Wo + 1) / 2;
-  const bool pair = !nopair && ps == 8 && d->Cin <= 28 && d->Cout <= STEM_CO && nk * 64 <= 1024 &&
+  const bool pair = ps == 8 && d->Cin <= 28 && d->Cout <= STEM_CO && nk * 64 <= 1024 &&
                     16L * (npair - 1) + 36 <= rowf;
   if (q) {
     q->rowf = rowf; q->ps = ps; q->nblk = pair ? nk : nblk;
@@ -920,10 +917,7 @@ static int tiled_wgrad_splits(const sf_conv_desc* d, int groups) {
   const long M = (long)d->N * d->To * d->Ho * d->Wo;
   const long tiles = (long)sf_cdiv(d->Cout, bco) * sf_cdiv(bco <= 32 ? d->cin_pad : d->Cin, bci) * d->kT * d->kH *
                      d->kW * groups;
-  static const long target = [] {
-    const char* e = getenv("SF_WGRAD_WGS");  // tuning aid
-    return e ? atol(e) : 768L;
-  }();
+  const long target = 768;
   // aim at ~768 workgroups (3 per CU): every workgroup writes its whole partial tile, so the partial traffic (and
   // the sum over S afterwards) grows with the split count — 1536 measured 75.5 ms per train step, 768 75.1, 256 76.0
   long S = (target + tiles - 1) / tiles;
@@ -1036,18 +1030,10 @@ extern "C" int sf_conv_wgrad(const sf_conv_desc* d, const float* x, const float*
     if (sq.pair && lds < (size_t)STEM_MT * 16 * 16 * sizeof(float)) lds = (size_t)STEM_MT * 16 * 16 * sizeof(float);
     static SfLdsAttr at0, at1;  // raise the dynamic-LDS cap once per device (129 KB of the CU's 160 KB)
     if (!sf_ensure_dyn_lds(at0, reinterpret_cast<const void*>(conv_wgrad_stem_kernel), 160 * 1024 - 512) ||
-        !sf_ensure_dyn_lds(at1, reinterpret_cast<const void*>(conv_wgrad_stem_pair_kernel<4>), 160 * 1024 - 512))
+        !sf_ensure_dyn_lds(at1, reinterpret_cast<const void*>(conv_wgrad_stem_pair_kernel), 160 * 1024 - 512))
       return SF_ELAUNCH;
-    static SfLdsAttr at2;
-    if (!sf_ensure_dyn_lds(at2, reinterpret_cast<const void*>(conv_wgrad_stem_pair_kernel<8>), 160 * 1024 - 512))
-      return SF_ELAUNCH;
-    static const int stem_nw = [] { const char* e = getenv("SF_STEM_NW"); return e ? atoi(e) : 8; }();
-    if (sq.pair && stem_nw == 8)
-      hipLaunchKernelGGL(conv_wgrad_stem_pair_kernel<8>, dim3(stem_workgroups(sq)), dim3(512), lds,
-                         (hipStream_t)stream, sq);
-    else if (sq.pair)
-      hipLaunchKernelGGL(conv_wgrad_stem_pair_kernel<4>, dim3(stem_workgroups(sq)), dim3(256), lds, (hipStream_t)stream,
-                         sq);
+    if (sq.pair)
+      hipLaunchKernelGGL(conv_wgrad_stem_pair_kernel, dim3(stem_workgroups(sq)), dim3(512), lds, (hipStream_t)stream, sq);
     else
       hipLaunchKernelGGL(conv_wgrad_stem_kernel, dim3(stem_workgroups(sq)), dim3(256), lds, (hipStream_t)stream, sq);
     SF_CHECK_LAUNCH();

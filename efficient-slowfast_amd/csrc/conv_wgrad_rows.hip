@@ -229,26 +229,17 @@ __global__ __launch_bounds__(256) void conv_wgrad_rows_kernel(const RowsArgs p) 
 // outside the clip and rows past the frame are out-of-range offsets: they land as zeros, so the loop needs NO validity
 // masks.  Loads are LDS-DMA pieces, PD steps ahead, behind a counted s_waitcnt vmcnt (every load of the loop is an
 // LDS-DMA and the loop stores nothing: the count is exact), raw s_barrier.
+constexpr int TRING_PD = 1;  // prefetch distance in frames (deeper rings measured no faster: profiles/r06_wgrad_tring_ab.txt)
 struct TringArgs {
   sf_conv_desc d;
   const float* x;
   const float* dz;
   float* part;           // [S][Cout][3][cin_pad], S = workgroups along x
   int dz_cs, dz_coff;
-  int L, nhb, nseg, tseg, PD;  // positions per block, blocks per frame, t segments, frames per segment, prefetch distance
+  int L, nhb, nseg, tseg;  // positions per block, blocks per frame, t segments, frames per segment
   int nb_ci, HW;
   unsigned x_bytes, z_bytes;
 };
-
-__device__ __forceinline__ void tring_vmwait(int n) {
-#define TR_VM(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-  switch (n) {
-    TR_VM(0) TR_VM(1) TR_VM(2) TR_VM(3) TR_VM(4) TR_VM(5) TR_VM(6) TR_VM(7) TR_VM(8) TR_VM(9) TR_VM(10) TR_VM(11)
-    TR_VM(12) TR_VM(13) TR_VM(14) TR_VM(15) TR_VM(16) TR_VM(17) TR_VM(18) TR_VM(19) TR_VM(20)
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-#undef TR_VM
-}
 
 template <int NCO, int ZW, int NCI, int XW>
 __global__ __launch_bounds__(256) void conv_wgrad_tring_kernel(const TringArgs p) {
@@ -264,7 +255,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_tring_kernel(const TringArgs p
   const int hb = col % p.nhb, n = col / p.nhb;
   const int bco = blockIdx.y / p.nb_ci, bci = blockIdx.y - bco * p.nb_ci;
   const int co0 = bco * BCO, ci0 = bci * BCI;
-  const int L = p.L, PD = p.PD, T = d.To;
+  constexpr int PD = TRING_PD;
+  const int L = p.L, T = d.To;
   const int t0 = seg * p.tseg, t1 = (t0 + p.tseg < T) ? t0 + p.tseg : T;
   const int NXS = 3 + PD, NZS = 1 + PD;             // ring slots
   const int xslot = L * XW, zslot = L * ZW;         // floats
@@ -275,7 +267,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_tring_kernel(const TringArgs p
   const __amdgpu_buffer_rsrc_t z_rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.dz, 0, p.z_bytes, 0x00020000);
   const int r_base = hb * L;                        // first row of the block within its frame
   // pieces this wavefront issues per step (x frame + dz frame): wave, wave + 4, ...
-  const int nper = ((nxb > wave) ? (nxb - wave + 3) / 4 : 0) + ((nzb > wave) ? (nzb - wave + 3) / 4 : 0);
 
   // frame f of x into ring slot (f + 1) % NXS (f >= -1); frame t of dz into slot t % NZS; f / t outside their ranges: zeros
   auto issue = [&](int fx, int xs, int tz, int zs) {
@@ -342,7 +333,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_tring_kernel(const TringArgs p
   int zs_cur = 0;  // ring slot of dz frame t
   for (int t = t0; t < t1; ++t) {
     // frames t - 1, t, t + 1 of x and frame t of dz have landed when only the loads of the PD - 1 younger steps remain
-    tring_vmwait((PD - 1) * nper);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (PD - 1 younger steps' loads outstanding: none)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -418,19 +409,11 @@ void magic(unsigned dv, unsigned* mul, unsigned* sh) {
 
 int g_rows_enable = 1;  // sf_conv_tune(10, e)
 
-bool rows_enabled() {
-  static const int env_on = [] {
-    const char* e = getenv("SF_WGRAD_ROWS");
-    return e ? atoi(e) : 1;
-  }();
-  return env_on && g_rows_enable;
-}
-
 int pow2_width(int c) { return c <= 8 ? 8 : (c <= 16 ? 16 : 32); }
 
 // Geometry + schedule for a problem this kernel covers; false = leave it to the other weight-gradient kernels.
 bool rows_plan(const sf_conv_desc* d, RowsArgs* a) {
-  if (!rows_enabled() || d->transposed) return false;
+  if (!g_rows_enable || d->transposed) return false;
   if (d->sT != 1 || d->sH != 1 || d->sW != 1 || d->dT != 1 || d->dH != 1 || d->dW != 1) return false;
   if (d->To != d->Ti || d->Ho != d->Hi || d->Wo != d->Wi) return false;
   int ntap;
@@ -483,30 +466,19 @@ bool rows_plan(const sf_conv_desc* d, RowsArgs* a) {
   return true;
 }
 
-int g_tring_enable = -1;  // sf_conv_tune(23, e): -1 = SF_WGRAD_TRING (default 1), 0 off, 1 on
-
-bool tring_enabled() {
-  static const int env_on = [] {
-    const char* e = getenv("SF_WGRAD_TRING");
-    return e ? atoi(e) : 1;
-  }();
-  return g_tring_enable < 0 ? env_on != 0 : g_tring_enable != 0;
-}
+int g_tring_enable = -1;  // sf_conv_tune(23, e): 0 off, 1 on, -1 the default (on)
 
 // Schedule of the ring-over-t form for a 3x1x1 problem rows_plan accepted (a holds its widths); false = not taken.
 bool tring_plan(const sf_conv_desc* d, const RowsArgs& a, TringArgs* t, size_t* lds) {
-  if (!tring_enabled()) return false;
+  if (!g_tring_enable) return false;
   if (!(d->kT == 3 && d->kH == 1 && d->kW == 1)) return false;
   const int HW = d->Hi * d->Wi, T = d->To, N = d->N;
   if (T < 2 || HW < 32) return false;
   const int bco = d->Cout <= 16 ? 16 : 32, bci = d->cin_pad <= 16 ? 16 : 32;
   const int blocks = sf_cdiv(d->Cout, bco) * a.nb_ci;
-  // positions per block: 128 for large frames, 64 otherwise (fewer padded rows in the last block of a frame)
-  static const int l_env = [] { const char* e = getenv("SF_WGRAD_TRING_L"); return e ? atoi(e) : 0; }();
   // positions per block: 64 (measured, profiles/r06_wgrad_tring_ab.txt: 128-position blocks 50.5 / 33.6 / 43.5 us where
   // 64-position ones take 45.0 / 28.8 / 31.0 — more workgroups per CU, fewer padded rows in a frame's last block)
   int L = 64;
-  if (l_env == 64 || l_env == 128) L = l_env;
   if (L * a.xw * 4 < 1024 || L * a.zw * 4 < 1024) L = 128;    // whole 1 KiB pieces (8-float rows)
   if ((L * a.xw) % 256 || (L * a.zw) % 256) return false;
   const int nhb = sf_cdiv(HW, L);
@@ -521,17 +493,10 @@ bool tring_plan(const sf_conv_desc* d, const RowsArgs& a, TringArgs* t, size_t* 
   t->L = L; t->nhb = nhb; t->nseg = nseg; t->tseg = tseg;
   t->nb_ci = a.nb_ci; t->HW = HW;
   t->x_bytes = a.x_bytes;
-  static const int pd_env = [] { const char* e = getenv("SF_WGRAD_TRING_PD"); return e ? atoi(e) : 1; }();  // (1: deeper rings measured no faster)
-  int PD = pd_env < 1 ? 1 : (pd_env > 4 ? 4 : pd_env);
-  size_t bytes;
-  for (;; --PD) {
-    bytes = ((size_t)(3 + PD) * L * a.xw + (size_t)(1 + PD) * L * a.zw) * sizeof(float);
-    static const int cap_kb = [] { const char* e = getenv("SF_WGRAD_TRING_KB"); return e ? atoi(e) : 76; }();
-    if (bytes <= (size_t)cap_kb * 1024 || PD == 1) break;
-  }
+  // ring of TRING_PD + 3 x slots and TRING_PD + 1 dz slots
+  const size_t bytes = ((size_t)(3 + TRING_PD) * L * a.xw + (size_t)(1 + TRING_PD) * L * a.zw) * sizeof(float);
   if (bytes > 150 * 1024) return false;
   const size_t red = (size_t)4 * bco * bci * sizeof(float);
-  t->PD = PD;
   *lds = bytes > red ? bytes : red;
   return true;
 }

@@ -245,18 +245,10 @@ int g_wg_target = 0;   // sf_conv_tune(12, n): workgroups to aim at (0: default)
 
 struct WgPlan { int na, nb, S; long chunk; int tiles_b, tiles; };
 
-static bool wg_enabled() {
-  static const int env_on = [] {
-    const char* e = getenv("SF_WGRAD_WAVE");
-    return e ? atoi(e) : 1;
-  }();
-  return env_on && g_wg_enable;
-}
-
 // Blocks per wavefront and position splits.  A (2, 1) / (1, 2) wavefront runs 32 MFMAs per 3 fragment loads; the
 // workgroup count aims at two rounds of 256 with the last round as full as the split count allows.
 static bool wg_plan(const sf_conv_desc* d, WgPlan* pl) {
-  if (!wg_enabled()) return false;
+  if (!g_wg_enable) return false;
   if (d->Cout < 64 || d->Cin < 64) return false;
   if ((d->Cin % 4) || (d->in_cs % 4) || (d->in_coff % 4) || (d->Cout % 4) || (d->cin_pad % 16)) return false;
   const long M = (long)d->N * d->To * d->Ho * d->Wo;
@@ -267,8 +259,7 @@ static bool wg_plan(const sf_conv_desc* d, WgPlan* pl) {
   int na = nco >= 2 ? 2 : 1, nb = na == 2 ? 1 : (ncb >= 2 ? 2 : 1);
   // 1x1x1 layers with a short reduction side (Cin <= 256): one block per wavefront — twice the tiles, half the
   // registers; measured 4-10 % faster than 2x1 / 1x2 on every such layer of cfg #3 (r02b_wgrad_wave_ab.txt)
-  static const bool rule11 = getenv("SF_WGRAD_11") == nullptr;  // SF_WGRAD_11=0: A/B
-  if (rule11 && ntaps == 1 && d->Cin <= 256) na = nb = 1;
+  if (ntaps == 1 && d->Cin <= 256) na = nb = 1;
   if (g_wg_force >= 0) { na = (g_wg_force & 1) + 1; nb = (g_wg_force >> 1) + 1; }
   pl->na = na; pl->nb = nb;
   pl->tiles_b = sf_cdiv(ncb, nb);

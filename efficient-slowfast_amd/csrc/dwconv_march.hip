@@ -505,10 +505,7 @@ int march_rows(int H, long columns, int groups) {
   return hc < 1 ? 1 : hc;
 }
 
-bool g_dwm_on = [] {
-  const char* e = getenv("SF_DW_MARCH");
-  return !(e && e[0] == '0');
-}();
+bool g_dwm_on = true;   // sf_conv_tune(30, e)
 
 bool shape_ok(const sf_conv_desc* d) {
   if (!g_dwm_on) return false;
@@ -521,10 +518,7 @@ bool shape_ok(const sf_conv_desc* d) {
 }
 
 // 1 x K x K (K = 3 | 5), stride (1, 2, 2), padding K / 2: the down-sampling depthwise layers
-bool g_dwm2_on = [] {
-  const char* e = getenv("SF_DW_MARCH_S2");
-  return !(e && e[0] == '0');
-}();
+bool g_dwm2_on = true;  // sf_conv_tune(31, e)
 bool shape2_ok(const sf_conv_desc* d) {
   if (!g_dwm_on || !g_dwm2_on) return false;
   if (d->kT != 1 || d->kH != d->kW || !(d->kH == 3 || d->kH == 5)) return false;

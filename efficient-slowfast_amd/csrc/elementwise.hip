@@ -841,21 +841,10 @@ inline int pow2ceil(int v) {
 // Ticket ring (common.h): 64 Ki zero-initialised counters per device, handed out in consecutive runs; a run is reused
 // only after 64 Ki counters' worth of later launches, and every last arriver leaves its counter at zero.
 #include <atomic>
-// OFF by default (SF_BN_TICKET=1 switches it on): measured on MI355X (profiles/README.md, round 2) the fused launches
-// are SLOWER than partial + final kernels — stats 2.5 -> 5.8 ms and BN-backward reductions 4.1 -> 7.2 ms per train
-// step (serial profile), 71.1 -> 73.8 ms per step: the last workgroup's walk over <= 512 write-through partials per
-// output is latency-bound on one CU, where the separate final kernel spreads it over S*C workgroups.
-bool sf_tickets_enabled() {
-  static const bool on = [] { const char* e = getenv("SF_BN_TICKET"); return e && e[0] == '1'; }();
-  return on;
-}
-// SF_BN_TICKET=2 (round 3, default; 0 = off): tickets only where the last arriver's walk is short — the BN backward
-// reduction of layers with >= 256 channels, cut into <= 64 row blocks (>= 4 channel groups of 64 keep >= 256 workgroups in
-// flight): one launch instead of partial + final on ~50 of the 114 BN layers of cfg #3, 67.8 -> 67.5 ms per step.
-int sf_tickets_level() {
-  static const int lv = [] { const char* e = getenv("SF_BN_TICKET"); return e ? atoi(e) : 2; }();  // default since round 3
-  return lv;
-}
+// Tickets are used only where the last arriver's walk is short (DESIGN.md has the measurements of the everywhere-fused
+// form, removed): the statistics and BN backward reductions of small tensors (<= 16 row blocks), and the BN backward
+// reduction of layers with >= 256 channels, cut into <= 64 row blocks (>= 4 channel groups of 64 keep >= 256 workgroups
+// in flight): one launch instead of partial + final on ~50 of the 114 BN layers of cfg #3, 67.8 -> 67.5 ms per step.
 namespace {
 constexpr int TICKET_RING = 1 << 16, TICKET_MAXDEV = 16;
 unsigned* g_ticket_ring[TICKET_MAXDEV] = {};
@@ -1043,14 +1032,9 @@ static int stats_launch(const float* x, int cs, int coff, int groups, long group
   const bool ring = sf_ticket_ring_ready(s);
   // small tensors (the launch-bound models: cfg #1's 16 384 .. 32 rows): the natural geometry has <= 16 row blocks, the
   // last arriver's walk is 16 partials per output at most and the final launch it replaces is a sixth of the layer's
-  // launches — fused whenever the tickets are not switched off (SF_BN_TICKET=0)
-  const bool small = ring && sf_tickets_level() >= 1 && S == 1 && groups == 1 &&
-                     group_rows / ((long)(TPB / (pow2ceil(cv) < TPB ? pow2ceil(cv) : TPB)) * 8) <= 16;
-  const bool fused = (sf_tickets_enabled() && ring) || small;
-  // fused launch of a LARGE tensor: <= 16 lanes (64 channels) per channel group, so that the group's last workgroup
-  // finishes few outputs while the groups finish in parallel, and <= 512 partials per output
-  const int cb_max = (fused && !small) ? 16 : TPB;
-  const int CB = pow2ceil(cv) < cb_max ? pow2ceil(cv) : cb_max;
+  // launches: fused through the ticket ring; every other tensor takes partial + final launches
+  const int CB = pow2ceil(cv) < TPB ? pow2ceil(cv) : TPB;
+  const bool fused = ring && S == 1 && groups == 1 && group_rows / ((long)(TPB / CB) * 8) <= 16;
   const int rpi = TPB / CB;
   const int max_p = fused ? 512 : STAT_MAX_P;
   if (groups > max_p) return SF_EINVAL;

@@ -381,13 +381,11 @@ def act_planes(a):
     return bx_planes(a.buf, a.rows, a.C, cs=a.cs, coff=a.coff)
 
 
-def _conv_launch(d, x_ptr, w_ptr, scale, bias, res_ptr, out_ptr, device, what, w_tensor=None, x_act=None,
-                 in_planes=None, keep=None):
+def _conv_launch(d, x_ptr, w_ptr, scale, bias, res_ptr, out_ptr, device, what, w_tensor=None, in_planes=None):
     """sf_conv_fwd, through the split-K schedule when the shape asks for it (workspace from the caching allocator).
     Trace tag: ("conv", output positions, taps * Cin, Cout) — 2 * product = the launch's algorithmic FLOPs.
     w_tensor: the packed weight as a tensor — lets the bf16-piece path (conv_bx.hip) keep its planes across calls.
-    in_planes: act_planes of the input view when the caller already has them; keep (a dict, with x_act): the planes this
-    call makes are left in keep["x"] for the layer's weight gradient."""
+    in_planes: act_planes of the input view when the caller already has them."""
     tag = ("conv", d.N * d.To * d.Ho * d.Wo, d.kT * d.kH * d.kW * d.Cin, d.Cout)
     if SPLIT_K and w_tensor is not None and w_tensor.shape[2] == d.Cin:
         n = lib().sf_conv_pw_ws_floats(ctypes.byref(d), 1)
@@ -399,9 +397,6 @@ def _conv_launch(d, x_ptr, w_ptr, scale, bias, res_ptr, out_ptr, device, what, w
             if rc not in (SF_EALIGN, SF_ENOTTAKEN):  # those two: refused before any launch -> the f32 kernels below
                 _check(rc, what)      # (SF_EINVAL — a genuinely inconsistent descriptor or a null pointer — raises)
                 return
-        if in_planes is None and keep is not None and x_act is not None and not BX_AF32 and \
-                lib().sf_conv_bx_ws_floats(ctypes.byref(d), 1, 1) > 0:
-            in_planes = keep["x"] = act_planes(x_act)
         n = lib().sf_conv_bx_ws_floats(ctypes.byref(d), 1 if in_planes is not None else 0, 1)
         if n > 0:
             planes = _weight_planes(w_tensor)
@@ -422,7 +417,7 @@ def _conv_launch(d, x_ptr, w_ptr, scale, bias, res_ptr, out_ptr, device, what, w
                                                       _stream())), what)
 
 
-SPLIT_K = os.environ.get("SF_SPLIT_K", "1") != "0"
+SPLIT_K = True  # False: one-pass f32 kernels only (tests compare the two schedules)
 
 
 def pack_conv_weight_pair(w):
@@ -550,12 +545,8 @@ def pack_dw_weight(w):
     return w.detach().reshape(c, -1).t().contiguous()
 
 
-CONV_STATS = os.environ.get("SF_CONV_STATS", "1") != "0"
-
-
 def conv(x, wp, kernel, stride=(1, 1, 1), padding=(0, 0, 0), dilation=(1, 1, 1), scale=None, bias=None,
-         relu=False, res=None, out=None, cin=None, out_cmul=1, out_reserve=(0, 0), out_thw=None, stats=False,
-         keep=None):
+         relu=False, res=None, out=None, cin=None, out_cmul=1, out_reserve=(0, 0), out_thw=None, stats=False):
     """Dense conv (implicit GEMM, sf_conv_fwd).  `wp` = pack_conv_weight(...).  `out`: Act to write into
     (a slice of a wider buffer) or None to allocate [.., before + Cout + after].
     stats=True returns (out, parts) with parts = (workspace, rows) of per-tile channel statistics of the output taken
@@ -581,7 +572,7 @@ def conv(x, wp, kernel, stride=(1, 1, 1), padding=(0, 0, 0), dilation=(1, 1, 1),
                  res.cs if res is not None else 0, res.coff if res is not None else 0, 0)
     if res is not None:
         assert res.rows == out.rows and res.C == cout
-    if stats and CONV_STATS and SPLIT_K and scale is None and res is None and not relu and out_cmul == 1 and \
+    if stats and SPLIT_K and scale is None and res is None and not relu and out_cmul == 1 and \
             wp.shape[2] == cin:
         n = lib().sf_conv_pw_stats_floats(ctypes.byref(d))
         if n > 0:  # pointwise layer on the bf16 pipe, statistics from its epilogue
@@ -595,8 +586,8 @@ def conv(x, wp, kernel, stride=(1, 1, 1), padding=(0, 0, 0), dilation=(1, 1, 1),
                                                              ctypes.byref(parts), _stream())), "sf_conv_fwd_pw")
             return out, ((st, parts.value) if parts.value > 0 else None)
     if stats:
-        n = lib().sf_conv_stats_ws_floats(ctypes.byref(d)) if (CONV_STATS and scale is None and res is None
-                                                              and not relu and out_cmul == 1) else 0
+        n = lib().sf_conv_stats_ws_floats(ctypes.byref(d)) if (scale is None and res is None and not relu
+                                                              and out_cmul == 1) else 0
         if n > 0:
             ws = torch.empty((n,), dtype=torch.float32, device=x.buf.device)
             parts = ctypes.c_int(0)
@@ -606,7 +597,7 @@ def conv(x, wp, kernel, stride=(1, 1, 1), padding=(0, 0, 0), dilation=(1, 1, 1),
                                                                 _stream())), "sf_conv_fwd_stats")
             return out, ((ws, parts.value) if parts.value > 0 else None)
     _conv_launch(d, x.ptr(), _ptr(wp), _ptr(scale), _ptr(bias), res.ptr() if res is not None else None, out.ptr(),
-                 x.buf.device, "sf_conv_fwd", w_tensor=wp, x_act=x if cin == x.C else None, keep=keep)
+                 x.buf.device, "sf_conv_fwd", w_tensor=wp)
     return (out, None) if stats else out
 
 
@@ -750,9 +741,6 @@ def channel_stats(x):
     return mean, var
 
 
-BN_MASK = os.environ.get("SF_BN_MASK", "1") != "0"  # byte masks instead of re-reading activations in BN backward
-
-
 def affine(x, scale=None, bias=None, res=None, relu=False, rep=1, out=None, out_reserve=(0, 0), out_cmul=1,
            nsplit=1, mask=None):
     """out = act(x*scale + bias + res), repeated `rep` times along T (nearest upsample).  nsplit > 1: scale/bias
@@ -768,7 +756,7 @@ def affine(x, scale=None, bias=None, res=None, relu=False, rep=1, out=None, out_
         assert out.coff + (x.C - 1) * out_cmul < out.cs and (out_cmul > 1 or out.C == x.C), (out, x)
     if res is not None:
         assert res.rows == x.rows and res.C == x.C
-    if (mask is not None and BN_MASK and relu and rep == 1 and nsplit == 1 and out_cmul == 1 and x.C % 4 == 0 and
+    if (mask is not None and relu and rep == 1 and nsplit == 1 and out_cmul == 1 and x.C % 4 == 0 and
             x.cs % 4 == 0 and x.coff % 4 == 0 and out.cs % 4 == 0 and out.coff % 4 == 0 and
             x.rows * (x.C // 4) < 2 ** 31 - 1 and scale is not None and
             (res is None or (res.cs % 4 == 0 and res.coff % 4 == 0))):
@@ -884,13 +872,6 @@ def _conv_dgrad_strided(dz, wt_packed, out, kernel, stride, padding, accumulate,
                 store = wt_packed.__dict__.setdefault("_sf_classes", {})
                 key = (at, ah, aw, tuple(kernel), tuple(stride), tuple(padding))
                 wsub = store.get(key)
-                if wsub is None and os.environ.get("SF_CLASS_GATHER", "1") == "0":
-                    taps_sel = tuple((a * kH + b) * kW + c for a in tt for b in th for c in tw)
-                    ikey = (taps_sel, str(wt_packed.device))
-                    idx = _TAP_INDEX.get(ikey)
-                    if idx is None:
-                        idx = _TAP_INDEX[ikey] = torch.tensor(taps_sel, dtype=torch.long, device=wt_packed.device)
-                    wsub = store[key] = wt_packed.index_select(1, idx)
                 if wsub is None:
                     wsub = _class_weights(wt_packed, store, kernel, stride, padding)[key]
                 d = ConvDesc(dz.N, dz.T, dz.H, dz.W, dz.C, dz.cs, dz.coff, dims[0], dims[1], dims[2], cin, out.cs,
@@ -903,35 +884,9 @@ def _conv_dgrad_strided(dz, wt_packed, out, kernel, stride, padding, accumulate,
 
 
 # ------------------------------------------------------------------------------------------------ backward
-# SF_CONV_BX_AF32 (default 1, read by conv_bx.hip too): forward / data-gradient launches of conv_bx.hip take their
-# activation operand as fp32 rows and split it after the LDS fragment read — no activation planes on those paths; the
-# weight gradient (whose transposing LDS reads need 16-bit elements) makes the planes of x and dz itself, inside its
-# own launch sequence on the companion stream.  0: planes made once per tensor on the pathway's stream and shared.
-BX_AF32 = os.environ.get("SF_CONV_BX_AF32", "1") != "0"
-
-
-def bx_backward_wants_dz_planes(x, dz, cout, kernel, stride, padding, dilation, cin=None, cin_pad=None,
-                                dgrad=True):
-    """True when the layer's weight gradient or (stride-1) data gradient runs on conv_bx.hip AND takes planes from the
-    caller (SF_CONV_BX_AF32=0): the caller then makes dz's planes ONCE (act_planes) and hands them to both."""
-    if BX_AF32:
-        return False
-    cin = x.C if cin is None else cin
-    cin_pad = (cin + 15) // 16 * 16 if cin_pad is None else cin_pad
-    if cin_pad != cin or not SPLIT_K:
-        return False
-    kT, kH, kW = kernel
-    d = ConvDesc(x.N, x.T, x.H, x.W, cin, x.cs, x.coff, dz.T, dz.H, dz.W, cout, 0, 0, 1,
-                 kT, kH, kW, stride[0], stride[1], stride[2], padding[0], padding[1], padding[2],
-                 dilation[0], dilation[1], dilation[2], cin_pad, ACT_NONE, 0, 0, 0)
-    if lib().sf_conv_wgrad_bx_ws_floats(ctypes.byref(d), 1, 1) > 0:
-        return True
-    if dgrad and max(stride) == 1 and cout % 16 == 0:
-        dt = ConvDesc(dz.N, dz.T, dz.H, dz.W, cout, dz.cs, dz.coff, x.T, x.H, x.W, cin, cin, 0, 1,
-                      kT, kH, kW, 1, 1, 1, padding[0], padding[1], padding[2], dilation[0], dilation[1], dilation[2],
-                      cout, ACT_NONE, 0, 0, 1)
-        return lib().sf_conv_bx_ws_floats(ctypes.byref(dt), 1, 1) > 0
-    return False
+# Forward / data-gradient launches of conv_bx.hip take their activation operand as fp32 rows and split it after the LDS
+# fragment read — no activation planes on those paths; the weight gradient (whose transposing LDS reads need 16-bit
+# elements) makes the planes of x and dz itself, inside its own launch sequence on the companion stream.
 
 
 def conv_wgrad(x, dz, cout, kernel, stride=(1, 1, 1), padding=(0, 0, 0), dilation=(1, 1, 1), cin=None,

@@ -348,24 +348,22 @@ def _colsum(act):
 
 
 def _record_conv(x, conv_weight, conv_bias, wp_shape, gsrc, kernel, stride, padding, dilation, x_needs_grad=True,
-                 cin=None, unpack=None, fold_kw=0, x_planes=None):
+                 cin=None, unpack=None, fold_kw=0):
     """Backward of a dense conv whose output gradient will be found in `gsrc` (an Act).  fold_kw: the stem layout
-    (packed channel = (kw, ci)); `unpack` maps the packed gradient to the parameter's layout on the autograd path.
-    x_planes: the bf16 piece planes of x the forward conv made (conv_bx.hip), reused by the weight gradient."""
+    (packed channel = (kw, ci)); `unpack` maps the packed gradient to the parameter's layout on the autograd path."""
     t = tape()
     if t is None:
         return
     cout = conv_weight.shape[0]
 
-    def wgrad(g, zp):
+    def wgrad(g):
         tgt = t.pgrad_target(conv_weight)
         if tgt is not None:  # partial sum + un-pack + accumulate into .grad in one kernel
             real_cin = conv_weight.shape[1]
             sfhip.conv_wgrad(x, g, cout, kernel, stride, padding, dilation, cin=cin, cin_pad=wp_shape[2],
-                             finish_into=(tgt, real_cin, fold_kw), x_planes=x_planes, dz_planes=zp)
+                             finish_into=(tgt, real_cin, fold_kw))
         else:
-            dwp = sfhip.conv_wgrad(x, g, cout, kernel, stride, padding, dilation, cin=cin, cin_pad=wp_shape[2],
-                                   x_planes=x_planes, dz_planes=zp)
+            dwp = sfhip.conv_wgrad(x, g, cout, kernel, stride, padding, dilation, cin=cin, cin_pad=wp_shape[2])
             t.add_pgrad(conv_weight, unpack(dwp) if unpack else sfhip.unpack_conv_weight_grad(dwp, conv_weight.shape))
         if conv_bias is not None:
             t.add_pgrad(conv_bias, _colsum(g))
@@ -373,12 +371,6 @@ def _record_conv(x, conv_weight, conv_bias, wp_shape, gsrc, kernel, stride, padd
     def bwd():
         g = gsrc() if callable(gsrc) else gsrc
         dev = x.buf.device
-        # dL/dz as bf16 piece planes, made once on this stream for the weight gradient and the data gradient when
-        # either runs on conv_bx.hip
-        zp = None
-        if fold_kw == 0 and sfhip.bx_backward_wants_dz_planes(x, g, cout, kernel, stride, padding, dilation, cin=cin,
-                                                               cin_pad=wp_shape[2], dgrad=x_needs_grad):
-            zp = sfhip.act_planes(g)
         # The fork costs two cross-stream hand-offs: ~15 us each on the device when launched eagerly
         # (tools/microbench/stream_latency.py) — worth it even for the small layers of cfg #3 (52.9 ms forking every
         # layer, 53.2 forking only those estimated above 30 .. 120 us) — but far more as edges of a captured hipGraph:
@@ -401,15 +393,12 @@ def _record_conv(x, conv_weight, conv_bias, wp_shape, gsrc, kernel, stride, padd
             wg = _companion_stream(cur)
             _sync_streams(cur, wg)
             with torch.cuda.stream(wg):
-                wgrad(g, zp)
+                wgrad(g)
             g.buf.record_stream(wg)  # e.g. the masked-gradient temporary of a bare ReLU dies with this closure
             x.buf.record_stream(wg)
-            for pl in (zp, x_planes):
-                if pl is not None:
-                    pl.record_stream(wg)
             t.joins.add(wg)
         else:
-            wgrad(g, zp)
+            wgrad(g)
         if x_needs_grad:
             if conv_weight.dim() == 5 and tuple(conv_weight.shape[2:]) == tuple(kernel):
                 wtp = _packed_pair(conv_weight)[1]
@@ -419,11 +408,9 @@ def _record_conv(x, conv_weight, conv_bias, wp_shape, gsrc, kernel, stride, padd
                                     conv_weight.shape[0], conv_weight.shape[1], *kernel).transpose(0, 1).contiguous()))
             fresh = t.grad_of_uninitialised(x)
             if fresh is not None:  # first consumer of x: write, do not accumulate
-                sfhip.conv_dgrad(g, wtp, x, kernel, stride, padding, dilation, out=fresh, accumulate=False,
-                                 dz_planes=zp)
+                sfhip.conv_dgrad(g, wtp, x, kernel, stride, padding, dilation, out=fresh, accumulate=False)
             else:
-                sfhip.conv_dgrad(g, wtp, x, kernel, stride, padding, dilation, out=t.grad_of(x), accumulate=True,
-                                 dz_planes=zp)
+                sfhip.conv_dgrad(g, wtp, x, kernel, stride, padding, dilation, out=t.grad_of(x), accumulate=True)
 
     t.record(bwd)
 
@@ -859,10 +846,9 @@ def conv_bn_act(x, conv, bn=None, relu=False, res=None, out=None, out_reserve=(0
         if conv.groups == 1:
             # plain BatchNorm3d: its batch statistics come out of the conv's epilogue (no extra pass over z)
             want = _plain_bn(bn) and bn.affine
-            keep = {} if tape() is not None else None
-            z = sfhip.conv(x, wp, k, s, p, d, bias=conv.bias, stats=want, keep=keep)
+            z = sfhip.conv(x, wp, k, s, p, d, bias=conv.bias, stats=want)
             z, st = z if want else (z, None)
-            _record_conv(x, conv.weight, conv.bias, wp.shape, z, k, s, p, d, x_planes=keep.get("x") if keep else None)
+            _record_conv(x, conv.weight, conv.bias, wp.shape, z, k, s, p, d)
         else:
             ones = _cached(conv, "_sf_ones", (conv.out_channels, str(x.buf.device)),
                            lambda: torch.ones(conv.out_channels, dtype=torch.float32, device=x.buf.device))

@@ -107,18 +107,25 @@ int sf_conv_fwd_grouped(const sf_conv_desc* d, int groups, int shuffle, const fl
 long sf_conv_stats_ws_floats(const sf_conv_desc* d);
 int sf_conv_fwd_stats(const sf_conv_desc* d, const float* in, const float* w_packed, const float* scale,
                       const float* bias, const float* res, float* out, float* stats_ws, int* parts, void* stream);
-/* Tuning knobs of the dense-conv launcher for microbenchmarks and A/B runs (process-wide, not used by the model code):
- * knob 0: value 0 routes every conv to the LDS-tiled kernels of conv_igemm.hip instead of the per-wavefront kernels of
- * conv_wave.hip; knob 1: force tile configuration `value` of conv_wave.hip (-1: planner); knob 2: force the rows per
- * M tile (0: planner); knob 3: value 1 selects 32-channel K steps; knob 4: the persistent
- * swapped-operand form (0 = never, 1 = the SF_CONV_WAVE_P level, 10 + L = level L: 1 every KS == 1 layer it covers,
- * 2 plain layers, 3 plain layers with <= 5 K steps); knob 6: conv_small.hip (bit 0 enable); knob 7: conv_bx.hip (0 off,
- * 1 where it wins, 2 every shape it covers); knob 8: its timing ablations; knobs 10 / 11 / 12: the weight-gradient kernels of
- * conv_wgrad_wave.hip — 10: value 0 routes every weight gradient to conv_wgrad.hip, 11: force the blocks per
- * wavefront (-1: planner), 12: workgroups to aim at (0: default); knob 30: the row-march depthwise kernels
- * (dwconv_march.hip) off / on, knob 31: its stride-(1,2,2) 1x3x3 / 1x5x5 marches alone; knobs 22 / 23: conv_rows.hip
- * (0 off, 1 the ring over t for 3x1x1 layers with <= 16 output channels, 2 every shape it covers) / the weight-gradient
- * ring over t of conv_wgrad_rows.hip (0 off, 1 on, -1 the environment's default).  Returns SF_EINVAL for an unknown knob. */
+/* Tuning knobs of the conv launchers for tests and microbenchmarks (process-wide, not used by the model code; the one
+ * way to force a form — the library reads no environment variable for this):
+ *   0: value 0 routes every conv to the LDS-tiled kernels of conv_igemm.hip instead of the per-wavefront kernels of
+ *      conv_wave.hip;  1: force tile configuration `value` of conv_wave.hip (-1: planner);  2: force the rows per M
+ *      tile (0: planner);  4: the persistent swapped-operand form (0 never, 1 the built-in default = level 3,
+ *      10 + L = level L: 1 every KS == 1 layer it covers, 2 plain layers, 3 plain layers with <= 5 K steps);
+ *   6: conv_small.hip (0 off, 1 by rule, 3 every shape it covers; values 0..3);
+ *   7: conv_bx.hip forward / data gradient (0 off, 1 where it wins, 2 every shape it covers);  9: its weight gradient
+ *      (same values);
+ *   10 / 11 / 12: the weight-gradient kernels of conv_wgrad_wave.hip / conv_wgrad_rows.hip — 10: value 0 routes every
+ *      weight gradient to conv_wgrad.hip, 11: force the blocks per wavefront (-1: planner), 12: workgroups to aim at
+ *      (0: default);
+ *   20: conv_wgrad_rows.hip off / on;  21: conv_pw_bx_kernel (0 off, 1 by model, 2 every shape it covers);
+ *   22: conv_rows.hip (0 off, 1 the built-in default: the ring over t for 3x1x1 layers with <= 16 output channels,
+ *      2 every shape it covers);  23: the weight-gradient ring over t of conv_wgrad_rows.hip (0 off, 1 on, -1 the
+ *      built-in default = on);
+ *   30: the row-march depthwise kernels (dwconv_march.hip) off / on;  31: its stride-(1,2,2) marches alone.
+ * Returns SF_EINVAL for any other knob (3, 5 and 8 were removed with the forms they selected) and for a value of knob
+ * 6 outside 0..3. */
 int sf_conv_tune(int knob, int value);
 /* ---- long reductions on the bf16 matrix pipe with fp32-exact operands (conv_bx.hip) --------------------------------
  * gfx950's f32-input MFMA runs at the vector rate, its bf16 MFMA at 16x that.  Every fp32 value is the EXACT sum of

@@ -105,7 +105,7 @@ def test_launch_planning_queries_are_host_only_and_fill_the_chip():
     assert 512 <= wg <= 1024 and wg / (-(-wg // 256) * 256) >= 0.94, (S, wg)
     assert L.sf_conv_fwd_ws_floats(ctypes.byref(d)) == 0                       # 1568 tiles: no split-K
     # res4 3x1x1 1024->256 at M = 12544 (K = 3072) on the bf16-piece kernel (conv_bx.hip): 49 tiles of 256 x 256 share
-    # their K steps between S workgroups that together fill the chip.  Default mode (SF_CONV_BX_AF32=1): the activation
+    # their K steps between S workgroups that together fill the chip.  The activation
     # operand travels as fp32 rows, so the workspace = the weight planes (unless handed in) + S partial tiles — no
     # activation planes whether or not the caller has them.  sf_conv_tune(7, 0): the per-wavefront kernel splits K inside
     # the workgroup (no workspace); the LDS-tiled fallback (sf_conv_tune(0, 0)): 196 tiles, 192 K steps -> split-K with a
@@ -127,6 +127,8 @@ def test_launch_planning_queries_are_host_only_and_fill_the_chip():
         assert L.sf_conv_bx_ws_floats(ctypes.byref(d4), 0, 1) == 0
         assert L.sf_conv_fwd_ws_floats(ctypes.byref(d4)) == 0
         assert L.sf_conv_tune(0, 0) == 0 and L.sf_conv_tune(99, 0) != 0
+        assert L.sf_conv_tune(3, 1) != 0 and L.sf_conv_tune(5, 1) != 0 and L.sf_conv_tune(8, 1) != 0  # removed knobs
+        assert L.sf_conv_tune(6, 16) != 0 and L.sf_conv_tune(6, 1) == 0                               # removed bits
         try:
             n = L.sf_conv_fwd_ws_floats(ctypes.byref(d4))
         finally:

@@ -47,7 +47,7 @@ def child_tol(outs):
     """Tight tolerance of one child: one flipped ReLU / max-pool position in an activation of P = N*T*H*W positions
     moves 1/sqrt(P) of a channel's gradient mass, and every tensor of the child downstream of it.  The deep Fast
     stages of the S = 64 fixtures have P = 1024 (s4) and 256 (s5): the SAME model run with three numerically
-    equivalent kernel selections (a per-tile online softmax in the attention forward, SF_CONV_WAVE=0, SF_STEM_PAIR=0:
+    equivalent kernel selections (a per-tile online softmax in the attention forward, the per-wavefront conv kernels off, the stem's pair form off:
     each re-associates a few sums)
     gave worst tensors of 4.4e-3, 5.7e-3, 6.2e-3 and — one unlucky flip — 3.8e-2 on dual_r50_subbn_s64.  So the tight
     bound is max(1e-2, 1.5 / sqrt(P_min)); the loose bound (25 %) on BOTH comparators stays what catches a wrong
