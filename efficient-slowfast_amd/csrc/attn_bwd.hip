@@ -1482,10 +1482,13 @@ int sf_attn_dq_reduce(const float* ws, float* dq, int dq_cs, int B, int N, int C
   return SF_OK;
 }
 
-// sf_attn_tune knobs (process-wide; the environment gives the initial values): keys per workgroup of the bf16-piece
-// backward sweeps (0 = by shape, 4 = 128 keys, 8 = 256 keys) and the number of sweep parts (0 = by fill)
-static int g_attn_nw = [] { const char* e = getenv("SF_ATTN_BX_NW"); return e ? atoi(e) : 0; }();
-static int g_sweep_parts = [] { const char* e = getenv("SF_SWEEP_PARTS"); return e ? atoi(e) : 0; }();
+// sf_attn_tune knobs (process-wide, 0 at load): wavefronts per workgroup of the backward sweeps that come in two
+// widths (0 = by shape, 4, 8: the bf16 d = 32 and d = 8 sweeps here, the d <= 4 one in attn_small_bwd.hip) and the
+// number of sweep parts (0 = by fill)
+static int g_attn_nw = 0;
+static int g_sweep_parts = 0;
+
+int sf_attn_nw() { return g_attn_nw; }
 
 extern "C" int sf_attn_tune(int knob, int value) {
   if (knob == 0 && (value == 0 || value == 4 || value == 8)) g_attn_nw = value;
@@ -1736,7 +1739,7 @@ extern "C" int sf_attn_bwd_fused(const float* q, int q_cs, const float* k, int k
     a.q_cs = q_cs; a.k_cs = k_cs; a.v_cs = v_cs; a.dz_cs = dz_cs; a.dq_cs = dq_cs; a.dk_cs = dk_cs; a.dv_cs = dv_cs;
     a.B = B; a.C = C; a.N = N; a.dqp = nullptr;
     // 128 keys per workgroup: the dQ planes are a quarter of the d = 32 ones, and 8-wavefront barriers cost more than
-    // halving them saves (N = 25 088, B = 8: 5.00 ms against 5.26).  SF_ATTN_BX_NW=8 forces the wide form.
+    // halving them saves (N = 25 088, B = 8: 5.00 ms against 5.26).  sf_attn_tune(0, 8) forces the wide form.
     const bool wide = g_attn_nw == 8;
     float* const bx_ws = ws + (sf_attn_bwd_fused_ws_floats(B, N, C) - sf_attn_bx_packed_elems(B, N));
     return wide ? launch_fused_bxp<8>(a, ws, bx_ws, (hipStream_t)stream)
@@ -1772,7 +1775,7 @@ extern "C" int sf_attn_bwd_fused(const float* q, int q_cs, const float* k, int k
                       sf_aligned16(dz) && sf_aligned16(dk) && sf_aligned16(dv);
     if (vec4) {
       // 256 keys (8 wavefronts, one workgroup per CU) per workgroup where that still fills the chip: half the dQ
-      // planes to write and to sum (N = 25 088, B = 8: 9.20 -> 8.70 ms).  SF_ATTN_BX_NW=4|8 forces either.
+      // planes to write and to sum (N = 25 088, B = 8: 9.20 -> 8.70 ms).  sf_attn_tune(0, 4 | 8) forces either.
       const bool wide = sf_attn_bx_wide(B, N);
       float* const bx_ws = ws + (sf_attn_bwd_fused_ws_floats(B, N, C) - sf_attn_bx_plane_elems(B, N));
       return wide ? launch_fused_bx<8>(a, ws, bx_ws, (hipStream_t)stream)

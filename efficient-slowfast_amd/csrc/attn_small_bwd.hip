@@ -760,8 +760,8 @@ int sf_attn_small_fused_dispatch(const float* q, int q_cs, const float* k, int k
   a.dq = dq; a.dk = dk; a.dv = dv;
   a.q_cs = q_cs; a.k_cs = k_cs; a.v_cs = v_cs; a.dz_cs = dz_cs; a.dq_cs = dq_cs; a.dk_cs = dk_cs; a.dv_cs = dv_cs;
   // 128 keys per workgroup (8 wavefronts) where that still leaves >= 2 workgroups per CU: half the dQ planes
-  static const int nw_env = [] { const char* e = getenv("SF_ATTN_SMALL_NW"); return e ? atoi(e) : 0; }();
-  const bool wide = C <= 4 && (nw_env == 8 || (nw_env != 4 && (long)B * sf_cdiv(N, 128) >= 2 * 256));
+  const int nw = sf_attn_nw();
+  const bool wide = C <= 4 && (nw == 8 || (nw != 4 && (long)B * sf_cdiv(N, 128) >= 2 * 256));
   a.B = B; a.C = C; a.N = N; a.nt = sf_cdiv(N, wide ? 128 : 64);
   a.zs = sf_sweep_parts((long)B * a.nt, sf_cdiv(N, ST));
   const int grid = B * a.zs * a.nt;

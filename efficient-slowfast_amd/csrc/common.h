@@ -36,9 +36,10 @@ static inline int sf_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // equal workgroups finishes when the busiest CU does: ceil(units / CUs) workgroup-times for units / CUs of work
 // (1568 workgroups on 256 CUs: 6.125 -> 7, 12.5 % of the chip idle in the tail).  Cutting the swept range into z
 // parts makes z-times more, z-times shorter units; pick the z <= SF_SWEEP_PARTS_MAX with the best fill, each part
-// keeping at least 8 tiles.  SF_SWEEP_PARTS=<z> overrides (1 = off).
+// keeping at least 8 tiles.  sf_attn_tune knob 1 = <z> overrides (1 = off).
 constexpr int SF_SWEEP_PARTS_MAX = 8;
 int sf_sweep_parts(long units, int tiles);  // attn_bwd.hip
+int sf_attn_nw();  // attn_bwd.hip: sf_attn_tune knob 0, wavefronts per backward workgroup (0 = by shape, 4, 8)
 
 // ---- last-workgroup tickets (a reduction's partial sums and its final step in ONE launch) ----------------------
 // Every workgroup of a reduction stores its partial sums write-through (sc1), drains, and takes a ticket; the workgroup

@@ -1157,13 +1157,10 @@ def act_bwd(dy, y, relu, dx, accumulate=True):
     return dx
 
 
-FUSED_ATTN_BWD = os.environ.get("SF_ATTN_BWD_SPLIT") != "1"  # single-sweep backward for 16 < C <= 64 (5 GB scratch at
-# N = 25088); SF_ATTN_BWD_SPLIT=1 selects the two-kernel form (no scratch)
-
-
-def attention_bwd(q, k, v, dz, o, lse, gamma, dq, dk, dv):
+def attention_bwd(q, k, v, dz, o, lse, gamma, dq, dk, dv, workspace=True):
     """dq/dk/dv (Act slices, overwritten) of the flash SpatialAttention; returns dvec[i] = <dz_i, O_i>
-    (its sum is dL/dgamma)."""
+    (its sum is dL/dgamma).  workspace: the single-sweep backward where it has one (16 < C <= 64: 5 GB scratch at
+    N = 25088); False, or no workspace for the shape, takes the two-kernel form (no scratch)."""
     B, n, C = o.shape
     o_act = Act(o.view(B, 1, 1, n, C))
     dvec = rowdot(Act(dz.buf.view(B, 1, 1, n, dz.cs), dz.coff, C), o_act)
@@ -1171,7 +1168,7 @@ def attention_bwd(q, k, v, dz, o, lse, gamma, dq, dk, dv):
     def base(a):
         return ctypes.c_void_p(a.buf.data_ptr() + 4 * a.coff)
 
-    nws = lib().sf_attn_bwd_fused_ws_floats(B, n, C) if FUSED_ATTN_BWD else 0
+    nws = lib().sf_attn_bwd_fused_ws_floats(B, n, C) if workspace else 0
     if nws > 0:  # one sweep: S and dP are recomputed once (5 products), dQ summed over key-block planes
         ws = torch.empty((nws,), dtype=torch.float32, device=o.device)
         _check(_traced(("attn_bwd_fused", B, n, C), lambda: lib().sf_attn_bwd_fused(

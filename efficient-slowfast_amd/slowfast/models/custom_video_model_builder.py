@@ -91,7 +91,7 @@ class FuseFastAndSlow(nn.Module):
         import torch.nn.modules.module as _tm
         hooked = bool(self._forward_hooks) or bool(_tm._global_forward_hooks)
         engine.run_paths([fast_to_slow, slow_to_fast], x_s.buf.device,
-                         defer_join=defer_join and engine.is_internal() and not hooked, fuse=True)
+                         defer_join=defer_join and engine.is_internal() and not hooked)
         return engine.leave([s_wide, f_wide])
 
 
@@ -132,7 +132,7 @@ class _EfficientTwoPathway(nn.Module):
                     x = m(x)
                 elif n.endswith("_fuse"):
                     nxt = names[i + 1] if i + 1 < len(names) else "head"
-                    x = m(x, defer_join=(nxt != "head") and engine.DEFER_JOIN)  # followed by a stage: the attention overlaps it
+                    x = m(x, defer_join=nxt != "head")  # followed by a stage: the attention overlaps it
                 else:
                     nxt = getattr(self, names[i + 1]) if i + 1 < len(names) else None
                     x = m(x, reserve=nxt.reserve(None) if isinstance(nxt, FuseFastAndSlow) else None)

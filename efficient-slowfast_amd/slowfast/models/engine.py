@@ -62,7 +62,6 @@ class Tape(object):
         self.input_grads = {}  # input index -> dL/d(clip), NCTHW (written by the stems' backward)
         self.joins = set()  # companion streams with weight-gradient work in flight (joined at the end of backward)
         self.model = None   # the model whose forward this tape records (milestone hooks are bound to it)
-        self.early = None   # backward: event a fusion region left for the next region's side stream (run_paths)
         self.capturing = False  # the backward is being captured into a hipGraph (no companion-stream forks then)
         self.arena = None   # backward of a small model: ONE zero-filled tensor the gradient buffers are cut from
         self.arena_off = 0
@@ -123,7 +122,7 @@ class Tape(object):
         multi-tensor launch instead of one small add per parameter (the q | k | v projections of an attention: six adds on
         the path between its weight gradient and its data gradient)."""
         tgts = [self.sink.get(p) if self.sink is not None else None for p in params]
-        if all(t is not None for t in tgts) and len(tgts) > 1 and os.environ.get("SF_FOREACH_PGRAD", "1") != "0":
+        if all(t is not None for t in tgts) and len(tgts) > 1:
             torch._foreach_add_(tgts, [g.reshape(p.shape) for p, g in zip(params, grads)])
             return
         for p, g in zip(params, grads):
@@ -163,11 +162,11 @@ class Tape(object):
         one backward come out of ONE zero-filled tensor — one fill launch instead of one per buffer.  Sized by what the
         previous backward of the same model asked for; made here, on the stream the backward starts on and before any
         side stream is forked, so every later use is ordered behind the fill.  Only models whose buffers total at most
-        64 MB (SF_GRAD_ARENA_MB) take it: a large model keeps one fill per buffer, which overlaps with the backward's
+        64 MB (ARENA_MAX_FLOATS) take it: a large model keeps one fill per buffer, which overlaps with the backward's
         kernels instead of delaying its first one (an arena for just the SMALL buffers of a large model was tried: cfg #3
         51.98 against 51.60 ms, two alternations on one box; cfg #5 at 2 clips unchanged)."""
         self.zero_floats = 0
-        if self.model is None or ARENA_MAX_FLOATS <= 0 or self.out_act is None:
+        if self.model is None or self.out_act is None:
             return
         want = self.model.__dict__.get("_sf_arena_floats", 0)
         if 0 < want <= ARENA_MAX_FLOATS:
@@ -219,10 +218,10 @@ _SIDE = {}
 def _side_stream(device):
     s = _SIDE.get(device)
     if s is None:
-        # priorities: SF_PRIO_SIDE / SF_PRIO_COMP (default 0 = normal).  High priority for this stream gained 0.25 ms of
-        # the eager train step but cost 13-70 % of the eval forward's hipGraph replay (442 -> 383 clips/s, cfg #1 2866
-        # -> 600): graph nodes captured on a high-priority stream replay through a slower path on this stack
-        s = _SIDE[device] = torch.cuda.Stream(device=device, priority=int(os.environ.get("SF_PRIO_SIDE", "0")))
+        # normal priority (also for the companion streams).  High priority for this stream gained 0.25 ms of the eager
+        # train step but cost 13-70 % of the eval forward's hipGraph replay (442 -> 383 clips/s, cfg #1 2866 -> 600):
+        # graph nodes captured on a high-priority stream replay through a slower path on this stack
+        s = _SIDE[device] = torch.cuda.Stream(device=device)
     return s
 
 
@@ -234,7 +233,7 @@ def _companion_stream(parent):
     key = (parent.device, parent.cuda_stream)
     s = _COMPANION.get(key)
     if s is None:
-        s = _COMPANION[key] = torch.cuda.Stream(device=parent.device, priority=int(os.environ.get("SF_PRIO_COMP", "0")))
+        s = _COMPANION[key] = torch.cuda.Stream(device=parent.device)
     return s
 
 
@@ -244,63 +243,28 @@ def _sync_streams(first, then):
     then.wait_event(ev)
 
 
-_FUSE = {}
-DEFER_JOIN = os.environ.get("SF_DEFER_JOIN", "1") != "0"  # forward: the Slow pathway's next stage starts beside the attention
-# SF_FUSE_STREAM=1 (default 0): the CMDA fusions' attention direction runs on a side stream of its own, so that in the
-# backward pass the Fast pathway's stage k (which does not depend on the attention's gradient) runs BESIDE the
-# attention backward of fusion k instead of queueing behind it on the shared side stream.  Measured (cfg #3, 8 clips,
-# one box, two alternations): 57.20 / 57.03 ms with it against 56.28 / 56.30 without — the attention sweeps hold 384 of
-# the 512 registers per lane, the Fast pathway's wavefronts that squeeze in beside them slow the sweep by more than
-# their own kernels were worth next to the Slow pathway's.  Kept as a switch (and in the stream-equivalence test).
-FUSE_STREAM = os.environ.get("SF_FUSE_STREAM", "0") == "1"
-
-
-def _fuse_stream(device):
-    s = _FUSE.get(device)
-    if s is None:
-        s = _FUSE[device] = torch.cuda.Stream(device=device, priority=int(os.environ.get("SF_PRIO_SIDE", "0")))
-    return s
-
-
-def run_paths(fns, device, defer_join=False, fuse=False):
+def run_paths(fns, device, defer_join=False):
     """[f() for f in fns] with fns[1] issued on the side stream (two callables on a CUDA device; otherwise serial).
     defer_join: do not make the caller's stream wait for the side stream at the end of the FORWARD region — only
     valid when the next work on the caller's stream does not read what fns[1] produced before the next region's
     join (a CMDA fusion followed by a stage: the attention keeps running beside the Slow pathway's next stage).
-    fuse: a CMDA fusion's region — fns[1] (the attention direction) gets the fusion stream.  Forward: the next
-    region's side stream waits for it (the Fast pathway reads the attention's output).  Backward: the caller's stream
-    leaves an event behind fns[0]'s gradient ops BEFORE it waits for the attention's, and the next region's side stream
-    (the Fast pathway's previous stage, which needs only those) starts from that event."""
+    The next region forks onto the same side stream, so it is ordered behind the deferred work without a join."""
     if not OVERLAP_PATHS or getattr(_tls, "serial", False) or len(fns) != 2 or device.type != "cuda":
         return [f() for f in fns]
     t = tape()
     if t is not None and t.side is not None:
         return [f() for f in fns]  # already inside a region
-    fuse = fuse and FUSE_STREAM
-    main, side = torch.cuda.current_stream(device), (_fuse_stream(device) if fuse else _side_stream(device))
+    main, side = torch.cuda.current_stream(device), _side_stream(device)
 
     def bwd_join():  # last op of the region's backward
-        cur = torch.cuda.current_stream(device)
-        if fuse:
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            t.early = ev
-        _sync_streams(side, cur)
+        _sync_streams(side, torch.cuda.current_stream(device))
 
     def bwd_fork():  # first op of the region's backward
-        cur = torch.cuda.current_stream(device)
-        ev, t.early = t.early, None
-        if ev is not None and not fuse:
-            side.wait_event(ev)
-        else:
-            _sync_streams(cur, side)
+        _sync_streams(torch.cuda.current_stream(device), side)
 
     if t is not None:
         t.record(bwd_join)
     _sync_streams(main, side)                                                       # forward: fork
-    pend = getattr(_tls, "pending_side", None)
-    if pend is not None and pend is not side:
-        _sync_streams(pend, side)            # ... and behind a deferred region on another stream (its output is read here)
     out0 = fns[0]()
     with torch.cuda.stream(side):
         if t is not None:
@@ -312,7 +276,7 @@ def run_paths(fns, device, defer_join=False, fuse=False):
                 t.side = None
     if not defer_join:
         _sync_streams(side, main)                                                   # forward: join
-        _tls.pending_side = None  # (a pending stream was waited for by `side` above: joined transitively)
+        _tls.pending_side = None  # (a deferred region ran on `side` too: joined here as well)
     else:
         _tls.pending_side = side
     if t is not None:
@@ -375,17 +339,8 @@ def _record_conv(x, conv_weight, conv_bias, wp_shape, gsrc, kernel, stride, padd
         # (tools/microbench/stream_latency.py) — worth it even for the small layers of cfg #3 (52.9 ms forking every
         # layer, 53.2 forking only those estimated above 30 .. 120 us) — but far more as edges of a captured hipGraph:
         # cfg #1's replay went from 9.65 to 6.03 ms, cfg #5's from 43.3 to 34.9 ms and cfg #3's own from 56.6 to 54.1 ms
-        # without them.  So: no companion stream while the backward is being CAPTURED; eagerly, every layer whose
-        # estimated weight gradient (2 rows Cin Cout taps FLOP at 80 TFLOP/s + both operands once at 3 TB/s) reaches
-        # SF_WGRAD_FORK_US (default 0: all).
-        fork = OVERLAP_PATHS and WGRAD_COMPANION and (WGRAD_FORK_IN_GRAPH or not t.capturing) and not t.serial and \
-            x_needs_grad and dev.type == "cuda"
-        if fork and WGRAD_FORK_US > 0:
-            rows_, cin_ = g.rows, (cin or x.C)
-            est_us = (2.0 * rows_ * cin_ * cout * (kernel[0] * kernel[1] * kernel[2])) / 80e6 + \
-                4.0 * (x.rows * cin_ + rows_ * cout) / 3e6
-            fork = est_us >= WGRAD_FORK_US
-        if fork:
+        # without them.  So: no companion stream while the backward is being CAPTURED; eagerly, every layer forks.
+        if OVERLAP_PATHS and not t.capturing and not t.serial and x_needs_grad and dev.type == "cuda":
             # the weight gradient only feeds the parameter's .grad: issue it on a companion stream so that it
             # overlaps the data gradient (both are short-grid GEMMs on the res4 / res5 layers); joined by
             # Tape.backward before the gradients are handed back
@@ -668,14 +623,10 @@ def norm_forward(bn, x):
     return leave([y])[0]
 
 
-ARENA_MAX_FLOATS = int(float(os.environ.get("SF_GRAD_ARENA_MB", "64")) * (1 << 18))  # 0: off
+ARENA_MAX_FLOATS = 64 << 18  # 64 MB: the largest gradient arena Tape._open_arena makes
 _GROUPS_OF = {}  # id(weight) -> groups, for the grouped convs (1 < groups < channels) packed by _group_pairs
 _PAIR_WEIGHTS = {}  # id(weight) -> weakref of the dense conv weights that have been packed as a pair (tensors compare
 # elementwise, so no WeakSet): repack_all's candidates
-BATCHED_REPACK = os.environ.get("SF_BATCH_REPACK", "1") != "0"
-WGRAD_COMPANION = os.environ.get("SF_WGRAD_COMPANION", "1") != "0"  # weight gradients on a companion stream
-WGRAD_FORK_US = float(os.environ.get("SF_WGRAD_FORK_US", "0"))       # ... when estimated to take at least this long
-WGRAD_FORK_IN_GRAPH = os.environ.get("SF_WGRAD_FORK_IN_GRAPH", "0") == "1"  # A/B: fork also while a hipGraph is captured
 
 
 def _packed_pair(weight):
@@ -694,8 +645,6 @@ def repack_all(model):
     (after an optimizer step: all of them — ~108 launches of ~6 us and 216 allocations otherwise; a grouped conv alone
     was G launches and two allocations).  The packed tensors are overwritten in place:
     the previous step's kernels that read them were joined before the optimizer ran."""
-    if not BATCHED_REPACK:
-        return
     cand = model.__dict__.get("_sf_pair_params")
     if cand is None or cand[0] != len(_PAIR_WEIGHTS):
         cand = (len(_PAIR_WEIGHTS), [p for p in model.parameters()

@@ -280,8 +280,9 @@ int sf_attn_bwd_fused(const float* q, int q_cs, const float* k, int k_cs, const 
  * 0 = shape not served).  The choice depends on the batch (B * ceil(N / 256) >= 256 selects the 8-wavefront form of
  * family 3, i.e. B >= 3 at N = 25 088): parity tests assert which one they exercised.                             */
 int sf_attn_bwd_variant(int B, int N, int C);
-/* Process-wide knobs of the attention launchers for tests: knob 0 = wavefronts per workgroup of the
- * bf16-piece backward (0 = by shape, 4, 8); knob 1 = parts every sweep is cut into (0 = by fill, 1..8).          */
+/* Process-wide knobs of the attention launchers for tests, 0 when the library loads: knob 0 = wavefronts per
+ * workgroup of the backward sweeps that come in two widths, the bf16 d = 32 and d = 8 ones and the f32 d <= 4 one
+ * (0 = by shape, 4, 8); knob 1 = parts every sweep is cut into (0 = by fill, 1..8).  Other values: SF_EINVAL.    */
 int sf_attn_tune(int knob, int value);
 
 /* ---- training-mode BatchNorm3d forward pieces (batchnorm_helper.py:15-34 -> nn.BatchNorm3d, training=True)

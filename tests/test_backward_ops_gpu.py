@@ -411,24 +411,50 @@ def test_attention_backward(c, thw):
     assert max(errs) < TOL, errs
 
 
-@pytest.mark.parametrize("parts", [3, 8])
-def test_attention_backward_query_parts(parts):
+@pytest.fixture(params=[3, 8])
+def forced_parts(request):
+    """Sweep parts forced through sf_attn_tune knob 1; 8 parts also force knob 0 = 8: the 8-wavefront (128 keys per
+    workgroup) form of the d <= 4 backward, which only large problems take by themselves.  The knobs are
+    process-wide: both go back to 0 (by shape) afterwards."""
+    import sfhip
+    L = sfhip.lib()
+    try:
+        assert L.sf_attn_tune(1, request.param) == 0
+        assert L.sf_attn_tune(0, 8 if request.param == 8 else 0) == 0
+        yield request.param
+    finally:
+        L.sf_attn_tune(0, 0)
+        L.sf_attn_tune(1, 0)
+
+
+def _cases(fn):
+    """The keyword arguments of every case of a test function (at most one parametrize mark)."""
+    marks = [m for m in getattr(fn, "pytestmark", []) if m.name == "parametrize"]
+    if not marks:
+        return [{}]
+    (mark,) = marks
+    names = [s.strip() for s in mark.args[0].split(",")]
+    return [dict(zip(names, v if len(names) > 1 else (v,))) for v in mark.args[1]]
+
+
+def test_attention_backward_query_parts(forced_parts):
     """The fused backward cuts the query sweep into parts to fill the chip's tail (sf_sweep_parts); the shapes above
-    are too small to be cut, so force the cut (SF_SWEEP_PARTS is read once per process -> child process).  8 parts of
-    a 5..7-tile sweep also leave parts EMPTY, which must contribute zero dK / dV."""
-    import subprocess
-    import sys
-    if os.environ.get("SF_SWEEP_PARTS"):
-        pytest.skip("already inside the forced-parts child")
-    env = dict(os.environ, SF_SWEEP_PARTS=str(parts))
-    if parts == 8:  # also the 8-wavefront (128 keys per workgroup) form of the d <= 4 backward, which only large
-        env["SF_ATTN_SMALL_NW"] = "8"   # problems take by themselves
-    fwd = os.path.join(os.path.dirname(__file__), "test_ops_gpu.py")  # its forward tests cut the KEY sweep alike
-    r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", __file__, fwd, "-k",
-                        "(test_attention_backward and not query_parts) or test_attention"], env=env,
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert "passed" in r.stdout
+    are too small to be cut, so force the cut and run every attention test of this file and of test_ops_gpu.py (its
+    forward tests cut the KEY sweep alike) under it.  8 parts of a 5..7-tile sweep also leave parts EMPTY, which must
+    contribute zero dK / dV."""
+    import test_ops_gpu
+    ran = 0
+    for ns in (globals(), vars(test_ops_gpu)):
+        for name, fn in sorted(ns.items()):
+            if not name.startswith("test_attention") or name == "test_attention_backward_query_parts":
+                continue
+            for kw in _cases(fn):
+                try:
+                    fn(**kw)
+                except AssertionError as e:
+                    raise AssertionError("%s %s with %d parts: %s" % (name, kw, forced_parts, e)) from e
+                ran += 1
+    assert ran >= 31, ran  # 12 backward + 19 forward cases at the time of writing
 
 
 @pytest.mark.parametrize("c,relu,use_res,wide", [(64, True, True, False), (8, True, False, True), (48, 6, False, False),

@@ -192,6 +192,33 @@ def test_launch_planning_queries_are_host_only_and_fill_the_chip():
     assert L.sf_attn_fwd_ws_floats(0, N, 32) == 0 and L.sf_attn_fwd_ws_floats(B, N, 129) == 0
 
 
+def test_attn_tune_accepts_its_knobs_only():
+    """sf_attn_tune knob 0 (wavefronts per backward workgroup) takes 0 / 4 / 8, knob 1 (sweep parts) 0 .. 8; any other
+    value or knob is refused.  Both start at 0 (by shape) and are process-wide, so the test hands them back at 0."""
+    import sfhip
+    L = sfhip.lib()
+    B, N = 8, 25088
+    try:
+        assert L.sf_attn_bwd_variant(B, N, 8) == 24
+        for v in (0, 4, 8):
+            assert L.sf_attn_tune(0, v) == 0, v
+        assert L.sf_attn_bwd_variant(B, N, 8) == 28  # the last accepted value (8) holds
+        for v in (-1, 1, 2, 3, 5, 6, 7, 9, 16):
+            assert L.sf_attn_tune(0, v) == sfhip.SF_EINVAL, v
+        assert L.sf_attn_bwd_variant(B, N, 8) == 28  # ... and a refused one changes nothing
+        for v in range(9):
+            assert L.sf_attn_tune(1, v) == 0, v
+        for v in (-1, 9, 16):
+            assert L.sf_attn_tune(1, v) == sfhip.SF_EINVAL, v
+        for knob in (-1, 2, 3, 10):
+            for v in (0, 4):
+                assert L.sf_attn_tune(knob, v) == sfhip.SF_EINVAL, (knob, v)
+    finally:
+        L.sf_attn_tune(0, 0)
+        L.sf_attn_tune(1, 0)
+    assert L.sf_attn_bwd_variant(B, N, 8) == 24
+
+
 def test_error_codes_match_header(repo_root):
     """The binding's SF_E* constants are the header's (SF_ENOTTAKEN, round 6: "not this entry point's shape" — the only
     code besides SF_EALIGN on which the binding falls back to a general entry point)."""

@@ -127,15 +127,10 @@ def test_attention_at_production_size_against_exact_fp64(c, thw, B):
                           save=save)
     grads = {}
     for mode, fused in (("fused", True), ("split", False)):
-        saved = sfhip.FUSED_ATTN_BWD
-        sfhip.FUSED_ATTN_BWD = fused
-        try:
-            d = sfhip.Act(torch.zeros(B, t, h, w, 3 * c, device=dev))
-            dvec = sfhip.attention_bwd(qkv.slice(0, c), qkv.slice(c, c), qkv.slice(2 * c, c),
-                                       sfhip.Act(dz.view(B, t, h, w, c)), save["o"], save["lse"], gamma,
-                                       d.slice(0, c), d.slice(c, c), d.slice(2 * c, c))
-        finally:
-            sfhip.FUSED_ATTN_BWD = saved
+        d = sfhip.Act(torch.zeros(B, t, h, w, 3 * c, device=dev))
+        dvec = sfhip.attention_bwd(qkv.slice(0, c), qkv.slice(c, c), qkv.slice(2 * c, c),
+                                   sfhip.Act(dz.view(B, t, h, w, c)), save["o"], save["lse"], gamma,
+                                   d.slice(0, c), d.slice(c, c), d.slice(2 * c, c), workspace=fused)
         grads[mode] = (d.buf.view(B, n, 3 * c).double(), dvec.double().sum())
     torch.cuda.synchronize()
 

@@ -3,8 +3,9 @@
 (v_mfma_f32_32x32x16_bf16: the matrix pipe) and a train of conv weight-gradient / forward launches
 (v_mfma_f32_*_f32: the vector pipe) are timed alone on one stream each, then together on two streams.  If the second
 number is near max(a, b) the two pipes overlap; near a + b they time-slice like two f32-MFMA streams do.
-SF_ATTN_BX_NW=4|8 picks the attention workgroup width (8: one 512-thread workgroup per CU, registers full).
-usage: tools/microbench/coexec_attn_conv.py"""
+nw = 4 | 8 picks the attention workgroup width through sf_attn_tune knob 0 (8: one 512-thread workgroup per CU,
+registers full); without it the launcher picks by shape.
+usage: tools/microbench/coexec_attn_conv.py [nw]"""
 import os
 import sys
 
@@ -14,6 +15,7 @@ import torch  # noqa: E402
 import sfhip  # noqa: E402
 
 dev = torch.device("cuda:0")
+assert sfhip.lib().sf_attn_tune(0, int(sys.argv[1]) if len(sys.argv) > 1 else 0) == 0
 B, (t, h, w), c = 8, (8, 56, 56), 32
 g = torch.Generator(device="cpu").manual_seed(3)
 qkv = sfhip.Act((torch.randn(B, t, h, w, 3 * c, generator=g) * 0.3).to(dev))
