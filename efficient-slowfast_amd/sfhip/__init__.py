@@ -62,11 +62,12 @@ EXPORTS = [
     "sf_conv_wgrad_bx_ws_floats", "sf_conv_wgrad_bx",
     "sf_conv_fwd_grouped", "sf_conv_wgrad_grouped_splits", "sf_conv_wgrad_grouped", "sf_channel_shuffle",
     "sf_dwconv_wgrad_param", "sf_roi_tpool_fwd", "sf_roi_align_max_fwd", "sf_roi_align_max_bwd", "sf_sigmoid_bwd",
+    "sf_xattn_accepts", "sf_xattn_bwd_ws_floats", "sf_xattn_fwd", "sf_xattn_bwd",
 ]
 _LONG_RET = ("sf_tmax_mean_ws_floats", "sf_channel_stats_ws_floats", "sf_bn_bwd_ws_floats",
              "sf_dwconv_wgrad_ws_floats", "sf_attn_bwd_fused_ws_floats", "sf_conv_fwd_ws_floats",
              "sf_attn_fwd_ws_floats", "sf_conv_stats_ws_floats", "sf_bx_planes_elems", "sf_conv_bx_ws_floats",
-             "sf_conv_wgrad_bx_ws_floats")
+             "sf_conv_wgrad_bx_ws_floats", "sf_xattn_bwd_ws_floats")
 
 
 def lib_path():
@@ -183,6 +184,12 @@ def lib():
         L.sf_roi_align_max_fwd.argtypes = [vp] + [ci] * 4 + [vp, ci, ci, cf, ci, vp, ci, ci, vp, vp]
         L.sf_roi_align_max_bwd.argtypes = [vp, ci, ci, vp, vp] + [ci] * 7 + [cf, ci, vp, ci, ci, ci, vp]
         L.sf_sigmoid_bwd.argtypes = [vp, vp, vp, cl, ci, vp]
+        L.sf_xattn_accepts.argtypes = [cl, cl, ci, ci]
+        L.sf_xattn_bwd_ws_floats.argtypes = [ci, cl, cl, ci, ci]
+        L.sf_xattn_bwd_ws_floats.restype = cl
+        L.sf_xattn_fwd.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, cl, cl, ci, ci, cf, vp]
+        L.sf_xattn_bwd.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, ci, ci, cl, cl, ci,
+                                   ci, cf, vp, vp]
         for name in EXPORTS:
             fn = getattr(L, name)
             if name != "sf_build_arch" and name not in _LONG_RET:
@@ -1180,6 +1187,51 @@ def attention_bwd(q, k, v, dz, o, lse, gamma, dq, dk, dv, workspace=True):
             base(q), q.cs, base(k), k.cs, base(v), v.cs, base(dz), dz.cs, _ptr(lse), _ptr(dvec),
             _ptr(gamma), base(dq), dq.cs, base(dk), dk.cs, base(dv), dv.cs, B, n, C, which, _stream())),
             "sf_attn_bwd")
+    return dvec
+
+
+def _slice_base(a):  # slice base pointer: buffer pointer + channel offset
+    return ctypes.c_void_p(a.buf.data_ptr() + 4 * a.coff)
+
+
+def xattn_accepts(q, k, v):
+    """True when the streaming cross-length kernels (attn_cross.hip) serve these views: shape inside
+    sf_xattn_accepts and float4-addressable rows."""
+    nq, nk = q.T * q.H * q.W, k.T * k.H * k.W
+    if not lib().sf_xattn_accepts(nq, nk, q.C, v.C):
+        return False
+    return all(a.cs % 4 == 0 and a.coff % 4 == 0 and a.buf.data_ptr() % 16 == 0 for a in (q, k, v))
+
+
+def cross_attention(q, k, v, sm_scale, save=None):
+    """Y = softmax(sm_scale q k^T) v per sample, streaming (no score matrix): q [N, ., d] queries, k [N, ., d] keys,
+    v [N, ., dv] values (any N_q, N_k).  Returns Y shaped like q with dv channels.
+    save: optional dict that receives 'lse' ([N, N_q], log2 domain) for cross_attention_bwd."""
+    _require_gpu(q.buf, "cross_attention")
+    B, nq, nk, d, dv = q.N, q.T * q.H * q.W, k.T * k.H * k.W, q.C, v.C
+    assert k.N == B and v.N == B and k.C == d and v.T * v.H * v.W == nk, (q, k, v)
+    y = new_act(q, B, q.T, q.H, q.W, dv)
+    lse = torch.empty((B, nq), dtype=torch.float32, device=q.buf.device)
+    if save is not None:
+        save["lse"] = lse
+    _check(_traced(("xattn_fwd", B, nq, nk, d, dv), lambda: lib().sf_xattn_fwd(
+        _slice_base(q), q.cs, _slice_base(k), k.cs, _slice_base(v), v.cs, _slice_base(y), y.cs, _ptr(lse), B, nq, nk,
+        d, dv, float(sm_scale), _stream())), "sf_xattn_fwd")
+    return y
+
+
+def cross_attention_bwd(q, k, v, y, dy, lse, sm_scale, dq, dk, dv, accumulate=(False, False, False)):
+    """dq / dk / dv (Act views) of cross_attention from y, dy and the saved lse; accumulate[i] True adds to the view,
+    False overwrites it.  Two launches (key-stationary dk, dv; query-stationary dq) after the <dy, y> row dots."""
+    B, nq, nk, d, dvw = q.N, q.T * q.H * q.W, k.T * k.H * k.W, q.C, v.C
+    dvec = rowdot(dy, y)
+    nws = lib().sf_xattn_bwd_ws_floats(B, nq, nk, d, dvw)
+    ws = torch.empty((nws,), dtype=torch.float32, device=q.buf.device) if nws > 0 else None
+    mask = sum(1 << i for i, on in enumerate(accumulate) if on)
+    _check(_traced(("xattn_bwd", B, nq, nk, d, dvw), lambda: lib().sf_xattn_bwd(
+        _slice_base(q), q.cs, _slice_base(k), k.cs, _slice_base(v), v.cs, _slice_base(dy), dy.cs, _ptr(lse),
+        _ptr(dvec), _slice_base(dq), dq.cs, _slice_base(dk), dk.cs, _slice_base(dv), dv.cs, mask, B, nq, nk, d, dvw,
+        float(sm_scale), _ptr(ws), _stream())), "sf_xattn_bwd")
     return dvec
 
 

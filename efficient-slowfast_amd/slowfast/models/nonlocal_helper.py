@@ -1,12 +1,16 @@
 """Non-local block (reference nonlocal_helper.py:8-148) on the HIP path.
 
 The block's attention runs over N_q <= 6272 positions against N_k <= 1568 max-pooled positions with d = 256 / 512
-channels — small enough to materialise one sample's score matrix, far outside the flash kernels' d <= 128 register
-tiling.  So the core is three launches per sample on the existing implicit-GEMM kernel, with ACTIVATIONS in the weight
-slot:  S = theta . phi^T (phi's NDHWC rows [N_k][d] already are the packed-weight layout), the normalisation
-(`sf_row_softmax_fwd`, or 1/N_k folded into the GEMM epilogue for "dot_product"), and Y = P . g (weights = g^T from
-the NDHWC->NCTHW kernel).  The backward is the same GEMMs transposed (data-gradient convs and weight-gradient
-reductions over the query positions)."""
+channels: different query and key lengths and widths far outside the flash kernels' d <= 128 register tiling.  The
+softmax form STREAMS through the cross-length kernels (`sf_xattn_fwd` / `sf_xattn_bwd`, attn_cross.hip): one forward
+launch for the whole batch that leaves the output and the log-sum-exp of every query, and a backward that recomputes
+the probabilities from it — no score matrix in memory, any key width that is a multiple of 4.
+
+"dot_product" (no softmax to stream) and views the streaming kernels refuse take the MATERIALISED path: three launches
+per sample on the implicit-GEMM kernel with ACTIVATIONS in the weight slot:  S = theta . phi^T (phi's NDHWC rows
+[N_k][d] already are the packed-weight layout), the normalisation (`sf_row_softmax_fwd`, or 1/N_k folded into the GEMM
+epilogue for "dot_product"), and Y = P . g (weights = g^T from the NDHWC->NCTHW kernel).  Its backward is the same
+GEMMs transposed (data-gradient convs and weight-gradient reductions over the query positions)."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -61,17 +65,37 @@ class Nonlocal(nn.Module):
 
 
 def dense_attention(theta, phi, g, softmax=True, sm_scale=1.0):
-    """Y = normalise(theta phi^T) g per sample with the score matrix MATERIALISED: softmax(sm_scale * S) over the keys,
-    or S / N_k (softmax=False: Nonlocal's "dot_product").  theta [N, ., d] queries, phi [N, ., d] keys, g [N, ., dv]
-    values, dense NDHWC buffers.  Taped.  Serves Nonlocal (d = 256 / 512) and SpatialAttention heads wider than the
-    flash kernels' 128 channels (SlowFastShuffleNet w2.0 / g3: d = 240 at s4_fuse, N <= 64 positions)."""
+    """Y = normalise(theta phi^T) g per sample: softmax(sm_scale * S) over the keys, or S / N_k (softmax=False:
+    Nonlocal's "dot_product").  theta [N, ., d] queries, phi [N, ., d] keys, g [N, ., dv] values, NDHWC views.  Taped.
+    Serves Nonlocal (d = 256 / 512) and SpatialAttention heads wider than the flash kernels' 128 channels
+    (SlowFastShuffleNet w2.0 / g3: d = 240 at s4_fuse, N <= 64 positions).  The softmax form streams through the
+    cross-length kernels wherever they accept the views (one launch forward, the score matrix never in memory); the
+    rest runs with the score matrix MATERIALISED."""
+    N, d, dv = theta.N, theta.C, g.C
+    nq, nk = theta.T * theta.H * theta.W, phi.T * phi.H * phi.W
+    assert phi.C == d and (g.T, g.H, g.W) == (phi.T, phi.H, phi.W)
+    if softmax and sfhip.xattn_accepts(theta, phi, g):
+        saved = {}
+        y = sfhip.cross_attention(theta, phi, g, sm_scale, save=saved)
+        t = engine.tape()
+        if t is not None:
+            def bwd_stream():
+                sfhip.cross_attention_bwd(theta, phi, g, y, t.grad_of(y), saved["lse"], sm_scale, t.grad_of(theta),
+                                          t.grad_of(phi), t.grad_of(g), accumulate=(True, True, True))
+            t.record(bwd_stream)
+        return y
+    return materialised_attention(theta, phi, g, softmax, sm_scale)
+
+
+def materialised_attention(theta, phi, g, softmax=True, sm_scale=1.0):
+    """dense_attention with one [N_q, N_k] score matrix per sample in memory (kept for the backward, which makes a
+    second one): "dot_product", and whatever the streaming kernels refuse.  Dense NDHWC buffers, d % 16 == 0."""
     N, d, dv = theta.N, theta.C, g.C
     nq, nk = theta.T * theta.H * theta.W, phi.T * phi.H * phi.W
     if d % 16 != 0:
         raise NotImplementedError("materialised attention needs a key width that is a multiple of 16 on the HIP "
                                   "path (got %d)" % d)
     assert theta.cs == d and phi.cs == d and g.cs == dv and theta.coff == phi.coff == g.coff == 0
-    assert phi.C == d and (g.T, g.H, g.W) == (phi.T, phi.H, phi.W)
     dev = theta.buf.device
     nk_pad = (nk + 15) // 16 * 16
     inv_nk = None if softmax else torch.full((max(nk, d),), 1.0 / nk, dtype=torch.float32, device=dev)

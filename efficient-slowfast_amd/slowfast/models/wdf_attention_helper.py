@@ -64,8 +64,9 @@ class SpatialAttention(nn.Module):
 
     def _run_wide(self, x, scale, bias, relu, alpha, out):
         """Heads wider than the flash kernels' 128 channels (SlowFastShuffleNet w2.0 / g3: C = 240 at s4_fuse, where
-        N = T*H*W <= 64): three dense 1x1x1 projections and the materialised-score attention of the Nonlocal block
-        (nonlocal_helper.dense_attention, no 1/sqrt(d)), then z = gamma * O + x (and the eval-mode BN affine / ReLU /
+        N = T*H*W <= 64): three dense 1x1x1 projections and the attention of the Nonlocal block
+        (nonlocal_helper.dense_attention with sm_scale = 1, i.e. no 1/sqrt(d): the streaming cross-length kernels of
+        attn_cross.hip, no score matrix in memory), then z = gamma * O + x (and the eval-mode BN affine / ReLU /
         nearest T-upsample as one more small pass)."""
         from .nonlocal_helper import dense_attention
         c = self.input_channel

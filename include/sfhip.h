@@ -285,6 +285,29 @@ int sf_attn_bwd_variant(int B, int N, int C);
  * (0 = by shape, 4, 8); knob 1 = parts every sweep is cut into (0 = by fill, 1..8).  Other values: SF_EINVAL.    */
 int sf_attn_tune(int knob, int value);
 
+/* ---- streaming cross-length attention (M/nonlocal_helper.py:105-148; attn_cross.hip) --------------------------------
+ *   Y[b,i,:] = sum_j softmax_j(sm_scale <Q[b,i,:], K[b,j,:]>) V[b,j,:]
+ * Q [B,Nq,d], K [B,Nk,d], V [B,Nk,dv], Y [B,Nq,dv] as (pointer, row pitch) views: pitch >= width, 16-byte aligned
+ * rows.  The Nq x Nk scores are never written to memory, forward or backward.  fp32 on v_mfma_f32_32x32x2_f32.
+ * sf_xattn_accepts (M/nonlocal_helper.py:105-148): 1 when the kernels serve the shape (1 <= Nq, Nk; 4 <= d, dv <= 512,
+ *   both multiples of 4), else 0.  Host only.
+ * sf_xattn_bwd_ws_floats (M/nonlocal_helper.py:105-148): workspace of sf_xattn_bwd in floats (0: every gradient element
+ *   has one owner, so there are no partial planes).  Host only.
+ * sf_xattn_fwd (M/nonlocal_helper.py:105-148): writes y and lse [B,Nq] (log2-domain log-sum-exp of every query row).
+ * sf_xattn_bwd (M/nonlocal_helper.py:105-148): dvec[b,i] = <dY_i, Y_i> (sf_rowdot); a key-stationary kernel writes
+ *   dk, dv_, a query-stationary one dq, both recomputing P from lse; no float atomics, bit-reproducible.
+ *   accumulate_mask: bit 0 / 1 / 2 set = dq / dk / dv_ is added to, clear = overwritten.  ws may be NULL.
+ * SF_EALIGN: a misaligned view; SF_ENOTTAKEN: a shape sf_xattn_accepts refuses; SF_EINVAL: anything else.  No
+ * allocation and no host synchronisation.                                                                        */
+int sf_xattn_accepts(long Nq, long Nk, int d, int dv);
+long sf_xattn_bwd_ws_floats(int B, long Nq, long Nk, int d, int dv);
+int sf_xattn_fwd(const float* q, int q_cs, const float* k, int k_cs, const float* v, int v_cs, float* y, int y_cs,
+                 float* lse, int B, long Nq, long Nk, int d, int dv, float sm_scale, void* stream);
+int sf_xattn_bwd(const float* q, int q_cs, const float* k, int k_cs, const float* v, int v_cs, const float* dy,
+                 int dy_cs, const float* lse, const float* dvec, float* dq, int dq_cs, float* dk, int dk_cs,
+                 float* dv_, int dv_cs, int accumulate_mask, int B, long Nq, long Nk, int d, int dv, float sm_scale,
+                 float* ws, void* stream);
+
 /* ---- training-mode BatchNorm3d forward pieces (batchnorm_helper.py:15-34 -> nn.BatchNorm3d, training=True)
  * sf_channel_stats: per-channel mean and BIASED variance over all rows of an NDHWC slice, reduced through
  *   a fixed number of fp32 partials combined in fp64 (bit-reproducible; ws = sf_channel_stats_ws_floats(C)).
