@@ -63,11 +63,12 @@ EXPORTS = [
     "sf_conv_fwd_grouped", "sf_conv_wgrad_grouped_splits", "sf_conv_wgrad_grouped", "sf_channel_shuffle",
     "sf_dwconv_wgrad_param", "sf_roi_tpool_fwd", "sf_roi_align_max_fwd", "sf_roi_align_max_bwd", "sf_sigmoid_bwd",
     "sf_xattn_accepts", "sf_xattn_bwd_ws_floats", "sf_xattn_fwd", "sf_xattn_bwd",
+    "sf_assoc_accepts", "sf_gram_splits", "sf_gram_ws_floats", "sf_gram", "sf_rowmat",
 ]
 _LONG_RET = ("sf_tmax_mean_ws_floats", "sf_channel_stats_ws_floats", "sf_bn_bwd_ws_floats",
              "sf_dwconv_wgrad_ws_floats", "sf_attn_bwd_fused_ws_floats", "sf_conv_fwd_ws_floats",
              "sf_attn_fwd_ws_floats", "sf_conv_stats_ws_floats", "sf_bx_planes_elems", "sf_conv_bx_ws_floats",
-             "sf_conv_wgrad_bx_ws_floats", "sf_xattn_bwd_ws_floats")
+             "sf_conv_wgrad_bx_ws_floats", "sf_xattn_bwd_ws_floats", "sf_gram_ws_floats")
 
 
 def lib_path():
@@ -190,6 +191,12 @@ def lib():
         L.sf_xattn_fwd.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, cl, cl, ci, ci, cf, vp]
         L.sf_xattn_bwd.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, ci, ci, cl, cl, ci,
                                    ci, cf, vp, vp]
+        L.sf_assoc_accepts.argtypes = [cl, cl, ci, ci]
+        L.sf_gram_splits.argtypes = [ci, cl, ci, ci]
+        L.sf_gram_ws_floats.argtypes = [ci, cl, ci, ci]
+        L.sf_gram_ws_floats.restype = cl
+        L.sf_gram.argtypes = [vp, ci, vp, ci, vp, vp, ci, cl, ci, ci, cf, vp, vp]
+        L.sf_rowmat.argtypes = [vp, ci, vp, vp, ci, ci, cl, ci, ci, cf, ci, vp]
         for name in EXPORTS:
             fn = getattr(L, name)
             if name != "sf_build_arch" and name not in _LONG_RET:
@@ -1233,6 +1240,50 @@ def cross_attention_bwd(q, k, v, y, dy, lse, sm_scale, dq, dk, dv, accumulate=(F
         _ptr(dvec), _slice_base(dq), dq.cs, _slice_base(dk), dk.cs, _slice_base(dv), dv.cs, mask, B, nq, nk, d, dvw,
         float(sm_scale), _ptr(ws), _stream())), "sf_xattn_bwd")
     return dvec
+
+
+def assoc_accepts(theta, phi, g):
+    """True when the associative "dot_product" kernels (attn_assoc.hip) serve these views: shape inside
+    sf_assoc_accepts and float4-addressable rows."""
+    nq, nk = theta.T * theta.H * theta.W, phi.T * phi.H * phi.W
+    if not lib().sf_assoc_accepts(nq, nk, theta.C, g.C):
+        return False
+    return all(a.cs % 4 == 0 and a.coff % 4 == 0 and a.buf.data_ptr() % 16 == 0 for a in (theta, phi, g))
+
+
+def gram(a, b, alpha, transposed=False):
+    """G[n] = alpha a[n]^T b[n] over the positions of the views a [N, ., da] and b [N, ., db]: a dense [N, da, db]
+    tensor, or (G, Gt) with Gt = G^T as [N, db, da] from the same launch when `transposed` is set."""
+    _require_gpu(a.buf, "gram")
+    B, R, da, db = a.N, a.T * a.H * a.W, a.C, b.C
+    assert b.N == B and b.T * b.H * b.W == R, (a, b)
+    dev = a.buf.device
+    G = torch.empty((B, da, db), dtype=torch.float32, device=dev)
+    Gt = torch.empty((B, db, da), dtype=torch.float32, device=dev) if transposed else None
+    nws = lib().sf_gram_ws_floats(B, R, da, db)
+    ws = torch.empty((nws,), dtype=torch.float32, device=dev) if nws > 0 else None
+    _check(_traced(("gram", B, R, da, db), lambda: lib().sf_gram(
+        _slice_base(a), a.cs, _slice_base(b), b.cs, _ptr(G), _ptr(Gt), B, R, da, db, float(alpha), _ptr(ws),
+        _stream())), "sf_gram")
+    return (G, Gt) if transposed else G
+
+
+def rowmat(x, w, alpha, out=None, accumulate=False):
+    """Y[n, r, j] = alpha sum_i x[n, r, i] w[n, j, i]: x [N, ., k] view, w dense [N, n, k]; `out` (a view shaped like
+    x with n channels, made when None) is overwritten, or added to when `accumulate` is set.  Returns it."""
+    _require_gpu(x.buf, "rowmat")
+    B, R, k = x.N, x.T * x.H * x.W, x.C
+    assert w.dim() == 3 and w.shape[0] == B and w.shape[2] == k and w.is_contiguous(), (x, tuple(w.shape))
+    _require_gpu(w, "rowmat")
+    n = w.shape[1]
+    if out is None:
+        assert not accumulate
+        out = new_act(x, B, x.T, x.H, x.W, n)
+    assert out.N == B and out.T * out.H * out.W == R and out.C == n, (x, out)
+    _check(_traced(("rowmat", B, R, k, n), lambda: lib().sf_rowmat(
+        _slice_base(x), x.cs, _ptr(w), _slice_base(out), out.cs, B, R, k, n, float(alpha), int(bool(accumulate)),
+        _stream())), "sf_rowmat")
+    return out
 
 
 def bn_train_stats(x, gamma, beta, eps, momentum, run_mean, run_var, nsplit=1):

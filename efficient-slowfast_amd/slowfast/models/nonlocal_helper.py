@@ -6,10 +6,16 @@ softmax form STREAMS through the cross-length kernels (`sf_xattn_fwd` / `sf_xatt
 launch for the whole batch that leaves the output and the log-sum-exp of every query, and a backward that recomputes
 the probabilities from it — no score matrix in memory, any key width that is a multiple of 4.
 
-"dot_product" (no softmax to stream) and views the streaming kernels refuse take the MATERIALISED path: three launches
-per sample on the implicit-GEMM kernel with ACTIVATIONS in the weight slot:  S = theta . phi^T (phi's NDHWC rows
-[N_k][d] already are the packed-weight layout), the normalisation (`sf_row_softmax_fwd`, or 1/N_k folded into the GEMM
-epilogue for "dot_product"), and Y = P . g (weights = g^T from the NDHWC->NCTHW kernel).  Its backward is the same
+"dot_product" has no softmax to stream, and without one the product is ASSOCIATIVE:  Y = (theta phi^T / N_k) g =
+theta (phi^T g / N_k).  It runs on the two batched kernels of attn_assoc.hip: `sfhip.gram` makes M = phi^T g / N_k (one
+d x dv matrix per sample, with its transpose) and `sfhip.rowmat` multiplies theta by it — two launches for the whole
+batch, 2 d dv (N_q + N_k) FLOP per sample instead of 2 N_q N_k (d + dv), no score matrix.  The backward keeps only M:
+D = theta^T dY (gram), then dtheta += dY M^T, dg += phi D / N_k and dphi += g D^T / N_k (three rowmat).
+
+Views neither pair of kernels accepts (a width above 512 or not a multiple of 4) take the MATERIALISED path: three
+launches per sample on the implicit-GEMM kernel with ACTIVATIONS in the weight slot:  S = theta . phi^T (phi's NDHWC
+rows [N_k][d] already are the packed-weight layout), the normalisation (`sf_row_softmax_fwd`, or 1/N_k folded into the
+GEMM epilogue for "dot_product"), and Y = P . g (weights = g^T from the NDHWC->NCTHW kernel).  Its backward is the same
 GEMMs transposed (data-gradient convs and weight-gradient reductions over the query positions)."""
 import torch
 import torch.nn as nn
@@ -69,8 +75,9 @@ def dense_attention(theta, phi, g, softmax=True, sm_scale=1.0):
     Nonlocal's "dot_product").  theta [N, ., d] queries, phi [N, ., d] keys, g [N, ., dv] values, NDHWC views.  Taped.
     Serves Nonlocal (d = 256 / 512) and SpatialAttention heads wider than the flash kernels' 128 channels
     (SlowFastShuffleNet w2.0 / g3: d = 240 at s4_fuse, N <= 64 positions).  The softmax form streams through the
-    cross-length kernels wherever they accept the views (one launch forward, the score matrix never in memory); the
-    rest runs with the score matrix MATERIALISED."""
+    cross-length kernels wherever they accept the views (one launch forward, the score matrix never in memory), the
+    dot-product form through the associative gram / rowmat kernels (two launches forward, four backward, only the
+    d x dv matrix M kept); views neither accepts run with the score matrix MATERIALISED."""
     N, d, dv = theta.N, theta.C, g.C
     nq, nk = theta.T * theta.H * theta.W, phi.T * phi.H * phi.W
     assert phi.C == d and (g.T, g.H, g.W) == (phi.T, phi.H, phi.W)
@@ -84,12 +91,26 @@ def dense_attention(theta, phi, g, softmax=True, sm_scale=1.0):
                                           t.grad_of(phi), t.grad_of(g), accumulate=(True, True, True))
             t.record(bwd_stream)
         return y
+    if not softmax and sfhip.assoc_accepts(theta, phi, g):
+        inv_nk = 1.0 / nk
+        Mt, M = sfhip.gram(g, phi, inv_nk, transposed=True)  # M^T = g^T phi / N_k [dv, d] and M [d, dv] per sample
+        y = sfhip.rowmat(theta, Mt, 1.0)
+        t = engine.tape()
+        if t is not None:
+            def bwd_assoc():  # D = theta^T dY; only M was kept
+                dy = t.grad_of(y)
+                D, Dt = sfhip.gram(theta, dy, 1.0, transposed=True)
+                sfhip.rowmat(dy, M, 1.0, out=t.grad_of(theta), accumulate=True)     # dtheta += dY M^T
+                sfhip.rowmat(phi, Dt, inv_nk, out=t.grad_of(g), accumulate=True)    # dg += phi D / N_k
+                sfhip.rowmat(g, D, inv_nk, out=t.grad_of(phi), accumulate=True)     # dphi += g D^T / N_k
+            t.record(bwd_assoc)
+        return y
     return materialised_attention(theta, phi, g, softmax, sm_scale)
 
 
 def materialised_attention(theta, phi, g, softmax=True, sm_scale=1.0):
     """dense_attention with one [N_q, N_k] score matrix per sample in memory (kept for the backward, which makes a
-    second one): "dot_product", and whatever the streaming kernels refuse.  Dense NDHWC buffers, d % 16 == 0."""
+    second one): whatever the streaming and the associative kernels refuse.  Dense NDHWC buffers, d % 16 == 0."""
     N, d, dv = theta.N, theta.C, g.C
     nq, nk = theta.T * theta.H * theta.W, phi.T * phi.H * phi.W
     if d % 16 != 0:

@@ -308,6 +308,36 @@ int sf_xattn_bwd(const float* q, int q_cs, const float* k, int k_cs, const float
                  float* dv_, int dv_cs, int accumulate_mask, int B, long Nq, long Nk, int d, int dv, float sm_scale,
                  float* ws, void* stream);
 
+/* ---- associative "dot_product" attention (M/nonlocal_helper.py:105-148; attn_assoc.hip) ------------------------------
+ *   Y = (theta phi^T / N_k) g = theta (phi^T g / N_k): without a softmax the product is associative, so the
+ *   N_q x N_k scores are never formed; M = phi^T g / N_k is one d x dv matrix per sample.  Two batched products on
+ *   v_mfma_f32_32x32x2_f32, fp32 in and out.  Views are (pointer, row pitch): pitch >= width, 16-byte aligned rows,
+ *   widths multiples of 4 in 4..512.  No float atomics: one owner per output element and a fixed summation order.
+ * sf_assoc_accepts (M/nonlocal_helper.py:105-148): 1 when the two kernels serve theta [Nq,d], phi [Nk,d], g [Nk,dv]
+ *   (1 <= Nq, Nk; 4 <= d, dv <= 512, both multiples of 4), else 0.  Host only.
+ * sf_gram_splits (M/nonlocal_helper.py:105-148): chunks S >= 1 the R rows of sf_gram are cut into (more than 1 only
+ *   where da x db has too few 32 x 32 tiles to fill the chip).  S depends on (R, da, db) alone, so the bits of one
+ *   sample do not depend on the batch it is in.  Host only.
+ * sf_gram_ws_floats (M/nonlocal_helper.py:105-148): workspace of sf_gram in floats, S B da db partial planes; 0 when
+ *   S == 1.  Host only.
+ * sf_gram (M/nonlocal_helper.py:105-148): G[b] = alpha A[b]^T B[b] for A [B,R,da], B [B,R,db] (views) into dense
+ *   G [B,da,db]; gt != NULL also receives G^T [B,db,da], element for element the same floats.  Rows past R and columns
+ *   past the width are never read.  ws: sf_gram_ws_floats floats, 16-byte aligned (may be NULL when that is 0); with
+ *   S > 1 a second launch sums the planes in chunk order.
+ * sf_rowmat (M/nonlocal_helper.py:105-148): Y[b,r,j] = alpha sum_i X[b,r,i] W[b,j,i] for X [B,R,k] (view), dense
+ *   W [B,n,k] ("weight layout": both operands reduce along contiguous floats) into the view Y [B,R,n]; accumulate != 0
+ *   adds to Y instead of overwriting it.
+ * SF_EALIGN: a misaligned pointer or a pitch that is not a multiple of 4; SF_ENOTTAKEN: a shape sf_assoc_accepts
+ *   refuses; SF_EINVAL: anything else (null pointers, B <= 0, R <= 0, pitch < width, a missing workspace).  No
+ *   allocation and no host synchronisation.                                                                        */
+int sf_assoc_accepts(long Nq, long Nk, int d, int dv);
+int sf_gram_splits(int B, long R, int da, int db);
+long sf_gram_ws_floats(int B, long R, int da, int db);
+int sf_gram(const float* a, int a_cs, const float* b, int b_cs, float* g, float* gt, int B, long R, int da, int db,
+            float alpha, float* ws, void* stream);
+int sf_rowmat(const float* x, int x_cs, const float* w, float* y, int y_cs, int B, long R, int k, int n, float alpha,
+              int accumulate, void* stream);
+
 /* ---- training-mode BatchNorm3d forward pieces (batchnorm_helper.py:15-34 -> nn.BatchNorm3d, training=True)
  * sf_channel_stats: per-channel mean and BIASED variance over all rows of an NDHWC slice, reduced through
  *   a fixed number of fp32 partials combined in fp64 (bit-reproducible; ws = sf_channel_stats_ws_floats(C)).

@@ -24,7 +24,8 @@ CSRC = os.path.join(ROOT, "efficient-slowfast_amd", "csrc")
 HOT = ("conv_rows_kernel", "conv_bx_kernel", "conv_pw_bx_kernel", "conv_bx_wgrad_kernel", "conv_wave_kernel", "conv_wgrad_wave_kernel",
        "attn_bwd_bx_kernel", "attn_bwd_bxp_kernel", "attn_bwd_bx2_kernel", "attn_fwd_bx_kernel", "attn_fwd_bxp_kernel",
        "attn_fwd_bx2_kernel", "conv_stem", "conv_wgrad_stem", "conv_wgrad_rows_kernel", "bn_bwd_", "affine_flat",
-       "roi_tpool_fwd_kernel", "roi_align_max_", "xattn_fwd_kernel", "xattn_bwd_dkv_kernel", "xattn_bwd_dq_kernel")
+       "roi_tpool_fwd_kernel", "roi_align_max_", "xattn_fwd_kernel", "xattn_bwd_dkv_kernel", "xattn_bwd_dq_kernel",
+       "gram_kernel", "gram_finish_kernel", "rowmat_kernel")
 # kernels that are allowed scratch: the f32-MFMA forms, which run only for views the bf16-piece forms reject
 # (C % 4 != 0, unaligned strides or pointers, sf_attn_fwd without a workspace, the public two-kernel sf_attn_bwd)
 EXEMPT = ("attn_bwd_fused_kernelILi64",    # fused f32 sweep for 32 < d <= 64
