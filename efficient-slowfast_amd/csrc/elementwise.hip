@@ -908,6 +908,7 @@ extern "C" int sf_ndhwc_to_ncthw(const float* src, int cs, int coff, float* dst,
 
 extern "C" int sf_pool_fwd(const sf_pool_desc* d, const float* in, float* out, void* stream) {
   if (!d || !in || !out || d->C <= 0 || d->kT <= 0 || d->kH <= 0 || d->kW <= 0) return SF_EINVAL;
+  if (d->N <= 0 || d->To <= 0 || d->Ho <= 0 || d->Wo <= 0) return SF_EINVAL;  // an empty grid is a launch error
   const bool vec4 = (d->C % 4 == 0) && (d->in_cs % 4 == 0) && (d->in_coff % 4 == 0) && (d->out_cs % 4 == 0) &&
                     (d->out_coff % 4 == 0) && sf_aligned16(in) && sf_aligned16(out);
   const long pos = (long)d->N * d->To * d->Ho * d->Wo;

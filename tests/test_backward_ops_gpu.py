@@ -32,11 +32,11 @@ def _back(a):
     return a.buf[..., a.coff:a.coff + a.C].permute(0, 4, 1, 2, 3).contiguous().cpu()
 
 
-def _report(name, err):
+def _report(name, err, fname="bwd_report.txt"):
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
     try:
         os.makedirs(out, exist_ok=True)
-        with open(os.path.join(out, "bwd_report.txt"), "a") as f:
+        with open(os.path.join(out, fname), "a") as f:
             f.write("%-50s %.3e\n" % (name, err))
     except OSError:
         pass
