@@ -82,6 +82,40 @@ __global__ void clip_prologue_kernel(const unsigned char* __restrict__ clip, int
   }
   *reinterpret_cast<f32x4*>(dst + idx * 4) = o;
 }
+// One-channel (grayscale) clip, uint8 [T,H,W]: the same arithmetic, one float per destination pixel — the one-channel
+// stem layout of conv_stem_gray.hip ([n_frames][crop + 2 ph][Wp], zero borders).
+__global__ void clip_prologue_gray_kernel(const unsigned char* __restrict__ clip, int T, int H, int W, int new_h,
+                                          int new_w, int y0, int x0, int crop, int flip, float mean, float stdv,
+                                          const int* __restrict__ frame_idx, int n_frames, float* __restrict__ dst,
+                                          int ph, int pw, int Wp, long total) {
+  const long idx = (long)blockIdx.x * TPB + threadIdx.x;
+  if (idx >= total) return;
+  const int Hp = crop + 2 * ph;
+  const int xp = (int)(idx % Wp);
+  long r = idx / Wp;
+  const int yp = (int)(r % Hp);
+  const int f = (int)(r / Hp);
+  float o = 0.f;
+  const int yy = yp - ph, xx = xp - pw;
+  if (yy >= 0 && yy < crop && xx >= 0 && xx < crop) {
+    const int t = min(max(frame_idx ? frame_idx[f] : f, 0), T - 1);
+    const int ys = y0 + yy;
+    const int xs = x0 + (flip ? crop - 1 - xx : xx);
+    const unsigned char* fr = clip + (long)t * H * W;
+    if (new_h == H && new_w == W) {
+      o = norm1(fr[(long)ys * W + xs], mean, stdv);
+    } else {
+      int ya, yb, xa, xb;
+      float ly0, ly1, lx0, lx1;
+      src_index((float)H / (float)new_h, ys, H, &ya, &yb, &ly0, &ly1);
+      src_index((float)W / (float)new_w, xs, W, &xa, &xb, &lx0, &lx1);
+      const float a = norm1(fr[(long)ya * W + xa], mean, stdv), b = norm1(fr[(long)ya * W + xb], mean, stdv);
+      const float d = norm1(fr[(long)yb * W + xa], mean, stdv), e = norm1(fr[(long)yb * W + xb], mean, stdv);
+      o = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * d + lx1 * e);
+    }
+  }
+  dst[idx] = o;
+}
 }  // namespace
 
 extern "C" int sf_clip_prologue(const unsigned char* clip, int T, int H, int W, int new_h, int new_w, int y0, int x0,
@@ -101,6 +135,21 @@ extern "C" int sf_clip_prologue(const unsigned char* clip, int T, int H, int W, 
   const long total = (long)n_frames * (crop + 2 * ph) * Wp;
   hipLaunchKernelGGL(clip_prologue_kernel, dim3(sf_cdiv(total, TPB)), dim3(TPB), 0, (hipStream_t)stream, clip, T, H, W,
                      new_h, new_w, y0, x0, crop, flip, reverse, nm, frame_idx, n_frames, dst, ph, pw, Wp, total);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_clip_prologue_gray(const unsigned char* clip, int T, int H, int W, int new_h, int new_w, int y0,
+                                     int x0, int crop, int flip, float mean, float stdv, const int* frame_idx,
+                                     int n_frames, float* dst, int ph, int pw, int Wp, void* stream) {
+  if (!clip || !dst || T <= 0 || H <= 0 || W <= 0 || new_h <= 0 || new_w <= 0 || crop <= 0 || n_frames <= 0 || ph < 0 ||
+      pw < 0)
+    return SF_EINVAL;
+  if (y0 < 0 || x0 < 0 || y0 + crop > new_h || x0 + crop > new_w || Wp < crop + 2 * pw) return SF_EINVAL;
+  if (!frame_idx && n_frames != T) return SF_EINVAL;
+  const long total = (long)n_frames * (crop + 2 * ph) * Wp;
+  hipLaunchKernelGGL(clip_prologue_gray_kernel, dim3(sf_cdiv(total, TPB)), dim3(TPB), 0, (hipStream_t)stream, clip, T, H,
+                     W, new_h, new_w, y0, x0, crop, flip, mean, stdv, frame_idx, n_frames, dst, ph, pw, Wp, total);
   SF_CHECK_LAUNCH();
   return SF_OK;
 }

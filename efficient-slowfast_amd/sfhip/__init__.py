@@ -64,11 +64,14 @@ EXPORTS = [
     "sf_dwconv_wgrad_param", "sf_roi_tpool_fwd", "sf_roi_align_max_fwd", "sf_roi_align_max_bwd", "sf_sigmoid_bwd",
     "sf_xattn_accepts", "sf_xattn_bwd_ws_floats", "sf_xattn_fwd", "sf_xattn_bwd",
     "sf_assoc_accepts", "sf_gram_splits", "sf_gram_ws_floats", "sf_gram", "sf_rowmat",
+    "sf_clip_prologue_gray", "sf_stem1_accepts", "sf_stem1_fwd", "sf_stem1_wgrad_ws_floats", "sf_stem1_wgrad",
+    "sf_ncthw1_pack",
 ]
 _LONG_RET = ("sf_tmax_mean_ws_floats", "sf_channel_stats_ws_floats", "sf_bn_bwd_ws_floats",
              "sf_dwconv_wgrad_ws_floats", "sf_attn_bwd_fused_ws_floats", "sf_conv_fwd_ws_floats",
              "sf_attn_fwd_ws_floats", "sf_conv_stats_ws_floats", "sf_bx_planes_elems", "sf_conv_bx_ws_floats",
-             "sf_conv_wgrad_bx_ws_floats", "sf_xattn_bwd_ws_floats", "sf_gram_ws_floats")
+             "sf_conv_wgrad_bx_ws_floats", "sf_xattn_bwd_ws_floats", "sf_gram_ws_floats",
+             "sf_stem1_wgrad_ws_floats")
 
 
 def lib_path():
@@ -197,6 +200,13 @@ def lib():
         L.sf_gram_ws_floats.restype = cl
         L.sf_gram.argtypes = [vp, ci, vp, ci, vp, vp, ci, cl, ci, ci, cf, vp, vp]
         L.sf_rowmat.argtypes = [vp, ci, vp, vp, ci, ci, cl, ci, ci, cf, ci, vp]
+        L.sf_clip_prologue_gray.argtypes = [vp] + [ci] * 9 + [cf, cf, vp, ci, vp, ci, ci, ci, vp]
+        L.sf_stem1_accepts.argtypes = [ci] * 4
+        L.sf_stem1_fwd.argtypes = [vp, ci, ci, ci, ci, vp, ci, ci, ci, vp, vp, ci, vp, ci, ci, vp]
+        L.sf_stem1_wgrad_ws_floats.argtypes = [ci] * 7
+        L.sf_stem1_wgrad_ws_floats.restype = cl
+        L.sf_stem1_wgrad.argtypes = [vp, ci, ci, ci, ci, vp, ci, ci, ci, ci, ci, vp, ci, vp, vp]
+        L.sf_ncthw1_pack.argtypes = [vp, vp] + [ci] * 7 + [vp]
         for name in EXPORTS:
             fn = getattr(L, name)
             if name != "sf_build_arch" and name not in _LONG_RET:
@@ -306,9 +316,13 @@ def from_ncthw(x, cpad=None, ph=0, pw=0, wp=None):
 
 class PackedClip(object):
     """A pathway input already in the stem's layout: buf [N, T, H+2*ph, Wp, 4] fp32 (channels padded to 4, zero
-    H/W borders).  Produced by `clip_prologue`; accepted by the model in place of an NCTHW tensor."""
+    H/W borders) — or, for a one-channel (grayscale) clip, [N, T, H+2*ph, Wp, 1]: one float per pixel.  Produced by
+    `clip_prologue`; accepted by the model in place of an NCTHW tensor."""
 
     def __init__(self, buf, channels, H, W, ph, pw):
+        if buf.dim() != 5 or buf.shape[4] != (1 if channels == 1 else 4):
+            raise ValueError("PackedClip: a %d-channel clip is packed as [N, T, H+2ph, Wp, %d], got %s" % (
+                channels, 1 if channels == 1 else 4, tuple(buf.shape)))
         self.buf, self.C, self.H, self.W, self.ph, self.pw = buf, channels, H, W, ph, pw
 
     @property
@@ -326,15 +340,26 @@ class PackedClip(object):
 
 def clip_prologue(clip_u8, dst, new_hw, yx, crop, flip, mean, std, frame_idx=None, reverse=False, ph=0, pw=0):
     """One decoded clip (uint8 [T,H,W,3], device) -> dst (float [n_frames, crop+2ph, Wp, 4] view of a PackedClip
-    buffer): normalise, bilinear short-side scale, crop, flip, frame selection in one kernel."""
+    buffer): normalise, bilinear short-side scale, crop, flip, frame selection in one kernel.  A grayscale clip (uint8
+    [T,H,W] or [T,H,W,1], one-element mean / std) -> dst [n_frames, crop+2ph, Wp, 1], the one-channel stem layout."""
     _require_gpu(dst, "clip_prologue")
     if not clip_u8.is_cuda:
         raise SfhipError("clip_prologue: the uint8 clip is on %s — copy it to the GPU first" % clip_u8.device)
-    assert clip_u8.dtype == torch.uint8 and clip_u8.dim() == 4 and clip_u8.shape[3] == 3 and clip_u8.is_contiguous()
-    assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.shape[3] == 4
-    T, H, W, _ = clip_u8.shape
+    assert clip_u8.dtype == torch.uint8 and clip_u8.dim() in (3, 4) and clip_u8.is_contiguous()
+    gray = clip_u8.dim() == 3 or clip_u8.shape[3] == 1
+    assert gray or clip_u8.shape[3] == 3
+    assert dst.dtype == torch.float32 and dst.is_contiguous() and dst.dim() == 4 and dst.shape[3] == (1 if gray else 4)
+    T, H, W = clip_u8.shape[:3]
     n = dst.shape[0]
     assert dst.shape[1] == crop + 2 * ph
+    if gray:
+        assert len(mean) == 1 and len(std) == 1, "a one-channel clip takes a one-element mean / std"
+        assert not reverse, "DATA.REVERSE_INPUT_CHANNEL has no meaning for a one-channel clip"
+        _check(lib().sf_clip_prologue_gray(_ptr(clip_u8), T, H, W, int(new_hw[0]), int(new_hw[1]), int(yx[0]),
+                                           int(yx[1]), int(crop), 1 if flip else 0, float(mean[0]), float(std[0]),
+                                           _ptr(frame_idx) if frame_idx is not None else None, n, _ptr(dst), ph, pw,
+                                           dst.shape[2], _stream()), "sf_clip_prologue_gray")
+        return dst
     m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
     s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
     _check(lib().sf_clip_prologue(_ptr(clip_u8), T, H, W, int(new_hw[0]), int(new_hw[1]), int(yx[0]), int(yx[1]),
@@ -342,6 +367,71 @@ def clip_prologue(clip_u8, dst, new_hw, yx, crop, flip, mean, std, frame_idx=Non
                                   _ptr(frame_idx) if frame_idx is not None else None, n, _ptr(dst), ph, pw,
                                   dst.shape[2], _stream()), "sf_clip_prologue")
     return dst
+
+
+# ------------------------------------------------------------------------------------------------ one-channel stem
+def ncthw1_pack(x, ph, pw, wp):
+    """[N,1,T,H,W] tensor -> the one-channel stem layout [N, T, H+2ph, Wp, 1] (zero borders)."""
+    _require_gpu(x, "ncthw1_pack")
+    x = x.contiguous()
+    N, C, T, H, W = x.shape
+    assert C == 1
+    buf = torch.empty((N, T, H + 2 * ph, wp, 1), dtype=torch.float32, device=x.device)
+    _check(lib().sf_ncthw1_pack(_ptr(x), _ptr(buf), N, T, H, W, ph, pw, wp, _stream()), "sf_ncthw1_pack")
+    return buf
+
+
+def stem1_accepts(Hp, Wp, cout, kernel, stride, dilation=(1, 1, 1), groups=1):
+    """Is nn.Conv3d(1, cout, kernel, stride) over rows of Wp floats in the range of sf_stem1_fwd / sf_stem1_wgrad?"""
+    return (tuple(kernel[1:]) == (7, 7) and tuple(stride) == (1, 2, 2) and tuple(dilation) == (1, 1, 1) and
+            groups == 1 and bool(lib().sf_stem1_accepts(int(Hp), int(Wp), int(cout), int(kernel[0]))))
+
+
+def stem1_out_thw(buf, kT, pT):
+    return buf.shape[1] + 2 * pT - kT + 1, (buf.shape[2] - 7) // 2 + 1, (buf.shape[3] - 7) // 2 + 1
+
+
+def stem1_fwd(buf, w, pT, scale=None, bias=None, relu=False, out=None, out_reserve=(0, 0)):
+    """Stem conv of a one-channel clip in the packed layout `buf` [N,T,Hp,Wp,1]; w: the nn.Conv3d weight
+    [Cout,1,kT,7,7] (stride (1,2,2), H/W padding in the layout).  -> Act [N,To,Ho,Wo,Cout]."""
+    _require_gpu(buf, "stem1_fwd")
+    _require_gpu(w, "stem1_fwd")
+    assert buf.dim() == 5 and buf.shape[4] == 1 and buf.is_contiguous()
+    assert w.dim() == 5 and w.shape[1] == 1 and tuple(w.shape[3:]) == (7, 7) and w.is_contiguous()
+    cout, kT = w.shape[0], w.shape[2]
+    N, T, Hp, Wp = buf.shape[:4]
+    To, Ho, Wo = stem1_out_thw(buf, kT, pT)
+    if out is None:
+        out = new_act(buf.device, N, To, Ho, Wo, cout, out_reserve[0], out_reserve[1])
+    assert (out.N, out.T, out.H, out.W, out.C) == (N, To, Ho, Wo, cout), (out, (N, To, Ho, Wo, cout))
+    for v in (scale, bias):
+        assert v is None or (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.numel() == cout)
+    _check(_traced("stem1_fwd", lambda: lib().sf_stem1_fwd(
+        _ptr(buf), N, T, Hp, Wp, _ptr(w), cout, kT, int(pT), _ptr(scale), _ptr(bias), _act(relu), out.ptr(), out.cs,
+        out.coff, _stream())), "sf_stem1_fwd")
+    return out
+
+
+def stem1_wgrad(buf, dz, kT, pT, into=None):
+    """dL/d(weight) [Cout,1,kT,7,7] of stem1_fwd from dz (Act shaped like its output); `into`: accumulate into this
+    contiguous gradient tensor instead of returning a new one.  Fixed summation order: bitwise reproducible."""
+    _require_gpu(buf, "stem1_wgrad")
+    assert buf.dim() == 5 and buf.shape[4] == 1 and buf.is_contiguous()
+    N, T, Hp, Wp = buf.shape[:4]
+    cout = dz.C
+    assert (dz.N, dz.T, dz.H, dz.W) == (N,) + stem1_out_thw(buf, kT, pT), (dz, tuple(buf.shape))
+    n_ws = lib().sf_stem1_wgrad_ws_floats(N, T, Hp, Wp, cout, int(kT), int(pT))
+    if n_ws <= 0:
+        raise SfhipError("stem1_wgrad: shape outside the one-channel stem kernels' range (sfhip.stem1_accepts)")
+    ws = torch.empty(n_ws, dtype=torch.float32, device=buf.device)
+    if into is not None:
+        assert into.is_cuda and into.dtype == torch.float32 and into.is_contiguous() and \
+            into.numel() == cout * kT * 49
+    dw = into if into is not None else torch.empty((cout, 1, kT, 7, 7), dtype=torch.float32, device=buf.device)
+    _check(_traced("stem1_wgrad", lambda: lib().sf_stem1_wgrad(
+        _ptr(buf), N, T, Hp, Wp, dz.ptr(), dz.cs, dz.coff, cout, int(kT), int(pT), _ptr(dw),
+        1 if into is not None else 0, _ptr(ws), _stream())), "sf_stem1_wgrad")
+    return dw
 
 
 def to_ncthw(a):

@@ -96,10 +96,13 @@ def tensor_normalize(tensor, mean, std):
 def gpu_input_step(clips, params, mean, std, alpha, reverse_input_channel=False, pad=(0, 0), wp=None):
     """The whole input step for a batch on the GPU.
 
-    clips:  list of B decoded clips, uint8 [T, H_i, W_i, 3] device tensors (sizes may differ between clips)
+    clips:  list of B decoded clips, uint8 [T, H_i, W_i, 3] device tensors (sizes may differ between clips); grayscale
+            clips are uint8 [T, H_i, W_i] or [T, H_i, W_i, 1] with a one-element mean / std
     params: list of B SpatialParams (same crop for all)
     pad/wp: the stem's (ph, pw) and row pitch, from `engine.stem_geometry(first_conv, crop, crop)`
-    Returns [slow, fast] as sfhip.PackedClip — pass them to the model in place of the NCTHW tensors."""
+    alpha:  SLOWFAST.ALPHA; None for a single-pathway model (MODEL.ARCH in SINGLE_PATHWAY_ARCH): no slow pathway
+    Returns [slow, fast] ([clip] with alpha=None) as sfhip.PackedClip — pass them to the model in place of the NCTHW
+    tensors."""
     B = len(clips)
     assert B == len(params) and B > 0
     crop = params[0].crop
@@ -107,15 +110,19 @@ def gpu_input_step(clips, params, mean, std, alpha, reverse_input_channel=False,
     ph, pw = pad
     wp = crop + 2 * pw if wp is None else wp
     dev = clips[0].device
-    idx = slow_frame_indices(T, alpha).to(device=dev, dtype=torch.int32)
-    slow = torch.empty((B, idx.numel(), crop + 2 * ph, wp, 4), dtype=torch.float32, device=dev)
-    fast = torch.empty((B, T, crop + 2 * ph, wp, 4), dtype=torch.float32, device=dev)
+    gray = clips[0].dim() == 3 or clips[0].shape[3] == 1
+    C, cpad = (1, 1) if gray else (3, 4)
+    paths = []  # (buffer, frame indices)
+    if alpha is not None:
+        idx = slow_frame_indices(T, alpha).to(device=dev, dtype=torch.int32)
+        paths.append((torch.empty((B, idx.numel(), crop + 2 * ph, wp, cpad), dtype=torch.float32, device=dev), idx))
+    paths.append((torch.empty((B, T, crop + 2 * ph, wp, cpad), dtype=torch.float32, device=dev), None))
     for b, (clip, p) in enumerate(zip(clips, params)):
         assert clip.shape[0] == T and p.crop == crop
-        for dst, fi in ((slow[b], idx), (fast[b], None)):
-            sfhip.clip_prologue(clip, dst, (p.new_h, p.new_w), (p.y, p.x), crop, p.flip, mean, std, frame_idx=fi,
+        for buf, fi in paths:
+            sfhip.clip_prologue(clip, buf[b], (p.new_h, p.new_w), (p.y, p.x), crop, p.flip, mean, std, frame_idx=fi,
                                 reverse=reverse_input_channel, ph=ph, pw=pw)
-    return [sfhip.PackedClip(slow, 3, crop, crop, ph, pw), sfhip.PackedClip(fast, 3, crop, crop, ph, pw)]
+    return [sfhip.PackedClip(buf, C, crop, crop, ph, pw) for buf, _ in paths]
 
 
 def stem_input_geometry(model, crop):

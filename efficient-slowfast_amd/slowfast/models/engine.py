@@ -872,9 +872,21 @@ def stem_conv_bn_relu(x, conv, bn, relu=True):
     wp_need = max(W + 2 * pW, (Wo - 1) * sW + kW)
     Wp = (wp_need + sW - 1) // sW * sW
     if isinstance(x, sfhip.PackedClip):  # produced by the GPU input step already in this layout
+        if x.C != conv.in_channels:
+            raise ValueError("a %d-channel PackedClip was handed to a stem that convolves %d channels" % (
+                x.C, conv.in_channels))
         if (x.ph, x.pw, x.Wp) != (pH, pW, Wp):
             raise ValueError("PackedClip geometry (ph, pw, Wp) = %s does not match this stem's %s; pack it with "
                              "engine.stem_geometry(conv, H, W)" % ((x.ph, x.pw, x.Wp), (pH, pW, Wp)))
+    if C == 1:  # grayscale clips: one float per pixel and the one-channel stem kernels, where they serve the conv
+        t = tape()
+        wants_grad = t is not None and isinstance(x, torch.Tensor) and id(x) in t.input_ids
+        if not wants_grad and sfhip.stem1_accepts(H + 2 * pH, Wp, conv.out_channels, conv.kernel_size, conv.stride,
+                                                  conv.dilation, conv.groups):
+            return _stem1_conv_bn_relu(x, conv, bn, relu, (pH, pW, Wp))
+        if isinstance(x, sfhip.PackedClip):  # out of the kernels' range: the padded route below, from the dense clip
+            x = x.to_ncthw()
+    if isinstance(x, sfhip.PackedClip):
         abuf = x.buf
     else:
         abuf = sfhip.from_ncthw(x, cpad=4, ph=pH, pw=pW, wp=Wp).buf
@@ -909,6 +921,40 @@ def stem_conv_bn_relu(x, conv, bn, relu=True):
     scale, bias = bn_affine(bn, conv.bias)
     return sfhip.conv(view, wp, (kT, kH, 1), (1, sH, 1), (pT, 0, 0), scale=scale, bias=bias, relu=relu,
                       cin=4 * kW, out_thw=thw)
+
+
+def _stem1_conv_bn_relu(x, conv, bn, relu, geom):
+    """stem_conv_bn_relu for a one-channel clip (tensor [N,1,T,H,W] or one-channel PackedClip) on sf_stem1_fwd: the
+    weights are read as the parameter holds them; training records the weight gradient (sf_stem1_wgrad) on the tape."""
+    pH, pW, Wp = geom
+    kT, pT = conv.kernel_size[0], conv.padding[0]
+    buf = x.buf if isinstance(x, sfhip.PackedClip) else sfhip.ncthw1_pack(x, pH, pW, Wp)
+    w = conv.weight.detach()
+    if bn.training:
+        z = sfhip.stem1_fwd(buf, w, pT, bias=conv.bias)
+        _record_stem1_wgrad(buf, conv, z)
+        return bn_train_apply(bn, z, relu=relu)
+    scale, bias = bn_affine(bn, conv.bias)
+    return sfhip.stem1_fwd(buf, w, pT, scale=scale, bias=bias, relu=relu)
+
+
+def _record_stem1_wgrad(buf, conv, z):
+    """dL/d(conv.weight) of the one-channel stem: its own step on the tape (the clip has no gradient on this route)."""
+    t = tape()
+    if t is None:
+        return
+    kT, pT = conv.kernel_size[0], conv.padding[0]
+
+    def bwd():  # z's buffer holds dL/dz after the BN backward
+        tgt = t.pgrad_target(conv.weight)
+        if tgt is not None:
+            sfhip.stem1_wgrad(buf, z, kT, pT, into=tgt)
+        else:
+            t.add_pgrad(conv.weight, sfhip.stem1_wgrad(buf, z, kT, pT))
+        if conv.bias is not None:
+            t.add_pgrad(conv.bias, _colsum(z))
+
+    t.record(bwd)
 
 
 def _record_stem_input_grad(x, conv, z, view, ncthw, geom, Wo):

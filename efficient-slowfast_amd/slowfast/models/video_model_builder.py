@@ -12,13 +12,14 @@ from .build import MODEL_REGISTRY
 _MODEL_STAGE_DEPTH = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 18: (2, 2, 2, 2), 34: (3, 4, 6, 3)}
 
 # [stage][pathway] temporal kernel basis; the fork's slowfast entry (custom_video_model_builder.py:155-163,
-# identical to video_model_builder.py:62-68)
+# identical to video_model_builder.py:62-68); "fast": the fork's Fast-only single pathway (video_model_builder.py:73-79, :89)
 _TEMPORAL_KERNEL_BASIS = {
     "c2d": [[[1]], [[1]], [[1]], [[1]], [[1]]],
     "c2d_nopool": [[[1]], [[1]], [[1]], [[1]], [[1]]],
     "i3d": [[[5]], [[3]], [[3, 1]], [[3, 1]], [[1, 3]]],
     "i3d_nopool": [[[5]], [[3]], [[3, 1]], [[3, 1]], [[1, 3]]],
     "slow": [[[1]], [[1]], [[1]], [[3]], [[3]]],
+    "fast": [[[5]], [[3]], [[3]], [[3]], [[3]]],
     "slowfast": [[[1], [5]], [[1], [3]], [[1], [3]], [[3], [3]], [[3], [3]]],
 }
 _POOL1 = {
@@ -27,6 +28,7 @@ _POOL1 = {
     "i3d": [[2, 1, 1]],
     "i3d_nopool": [[1, 1, 1]],
     "slow": [[1, 1, 1]],
+    "fast": [[1, 1, 1]],
     "slowfast": [[1, 1, 1], [1, 1, 1]],
 }
 

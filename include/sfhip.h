@@ -564,6 +564,35 @@ int sf_clip_prologue(const unsigned char* clip, int T, int H, int W, int new_h, 
                      int flip, int reverse, const float* mean3, const float* std3, const int* frame_idx,
                      int n_frames, float* dst, int ph, int pw, int Wp, void* stream);
 
+/* One-channel (grayscale) clips, uint8 [T,H,W] (the fork's configs/TIRED, configs/WHEEL: DATA.INPUT_CHANNEL_NUM [1],
+ * MEAN [0.45], STD [0.225]): the same arithmetic with a scalar mean / std, written to the ONE-channel stem layout
+ * dst [n_frames][crop+2ph][Wp] (one float per pixel, zero borders).                                               */
+int sf_clip_prologue_gray(const unsigned char* clip, int T, int H, int W, int new_h, int new_w, int y0, int x0,
+                          int crop, int flip, float mean, float stdv, const int* frame_idx, int n_frames, float* dst,
+                          int ph, int pw, int Wp, void* stream);
+
+/* ---- one-channel stem (csrc/conv_stem_gray.hip): nn.Conv3d(1, Cout, [kT,7,7], stride [1,2,2], padding [pT,3,3]) of
+ * ResNetBasicStem (stem_helper.py:157-164) and its weight gradient (autograd's conv backward for `conv.weight`) on
+ * the one-channel layout x [N][T][Hp][Wp] fp32, Hp = H + 2*3, zero H/W borders, Wp as for the RGB stem layout — what
+ * sf_ncthw1_pack makes of an [N,1,T,H,W] tensor (the permute the reference never needs: it convolves NCTHW) and
+ * sf_clip_prologue_gray of a decoded clip.  Output extents: To = T + 2 pT - kT + 1, Ho = (Hp - 7)/2 + 1,
+ * Wo = (Wp - 7)/2 + 1.  Weights w / dw are in the parameter's layout [Cout][1][kT][7][7].
+ * Range: Cout in {8, 16, 64}, kT <= 5, and a one-output-row band (7 kT input rows + the weights, forward; + that row's
+ * dz, weight gradient) that fits 128 KB of LDS — bands are sized for 64 KB (two workgroups per CU) where they can be
+ * (sf_stem1_accepts == 1; host only);
+ * anything else returns SF_ENOTTAKEN and launches nothing.
+ * sf_stem1_fwd:  out[n,t,ho,wo, out_coff + co] = act(scale[co] * z + bias[co]) (scale / bias may be NULL: 1 / 0).
+ * sf_stem1_wgrad: dw (+)= sum over positions of dz * x.  Per-workgroup partial sums go to ws
+ *   (sf_stem1_wgrad_ws_floats floats, caller-owned) and are added in workgroup order: no atomics, bitwise
+ *   reproducible.  accumulate == 0 overwrites dw.                                                                */
+int sf_stem1_accepts(int Hp, int Wp, int Cout, int kT);
+int sf_stem1_fwd(const float* x, int N, int T, int Hp, int Wp, const float* w, int Cout, int kT, int pT,
+                 const float* scale, const float* bias, int act, float* out, int out_cs, int out_coff, void* stream);
+long sf_stem1_wgrad_ws_floats(int N, int T, int Hp, int Wp, int Cout, int kT, int pT);
+int sf_stem1_wgrad(const float* x, int N, int T, int Hp, int Wp, const float* dz, int dz_cs, int dz_coff, int Cout,
+                   int kT, int pT, float* dw, int accumulate, float* ws, void* stream);
+int sf_ncthw1_pack(const float* src, float* dst, int N, int T, int H, int W, int ph, int pw, int Wp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
