@@ -65,7 +65,7 @@ EXPORTS = [
     "sf_xattn_accepts", "sf_xattn_bwd_ws_floats", "sf_xattn_fwd", "sf_xattn_bwd",
     "sf_assoc_accepts", "sf_gram_splits", "sf_gram_ws_floats", "sf_gram", "sf_rowmat",
     "sf_clip_prologue_gray", "sf_stem1_accepts", "sf_stem1_fwd", "sf_stem1_wgrad_ws_floats", "sf_stem1_wgrad",
-    "sf_ncthw1_pack",
+    "sf_ncthw1_pack", "sf_avgpool_win_fwd", "sf_avgpool_win_bwd",
 ]
 _LONG_RET = ("sf_tmax_mean_ws_floats", "sf_channel_stats_ws_floats", "sf_bn_bwd_ws_floats",
              "sf_dwconv_wgrad_ws_floats", "sf_attn_bwd_fused_ws_floats", "sf_conv_fwd_ws_floats",
@@ -207,6 +207,8 @@ def lib():
         L.sf_stem1_wgrad_ws_floats.restype = cl
         L.sf_stem1_wgrad.argtypes = [vp, ci, ci, ci, ci, vp, ci, ci, ci, ci, ci, vp, ci, vp, vp]
         L.sf_ncthw1_pack.argtypes = [vp, vp] + [ci] * 7 + [vp]
+        L.sf_avgpool_win_fwd.argtypes = [ctypes.POINTER(PoolDesc), vp, vp, vp]
+        L.sf_avgpool_win_bwd.argtypes = [ctypes.POINTER(PoolDesc), vp, ci, ci, vp, ci, ci, ci, vp]
         for name in EXPORTS:
             fn = getattr(L, name)
             if name != "sf_build_arch" and name not in _LONG_RET:
@@ -1452,7 +1454,7 @@ def gather_add(src, src_cmul, out, accumulate=True):
     return out
 
 
-# ------------------------------------------------------------------------------------------------ RoI head
+# ------------------------------------------------------------------------------------------------ RoI head, windowed pool
 def check_boxes(boxes, x):
     """boxes: [K, 5] float32 on x's device, rows (batch_idx, x1, y1, x2, y2).  Checks metadata only (no sync)."""
     if not isinstance(boxes, torch.Tensor) or boxes.dim() != 2 or boxes.shape[1] != 5:
@@ -1505,6 +1507,48 @@ def roi_align_max_bwd(dy, arg, boxes, resolution, spatial_scale, aligned, dx, ac
                                       dx.T, dx.H, dx.W, dx.C, int(resolution), float(spatial_scale),
                                       1 if aligned else 0, dx.ptr(), dx.cs, dx.coff, 1 if accumulate else 0,
                                       _stream()), "sf_roi_align_max_bwd")
+    return dx
+
+
+def _window_desc(x, kernel, out_cs=0, out_coff=0):
+    kt, kh, kw = (int(k) for k in kernel)
+    return PoolDesc(x.N, x.T, x.H, x.W, x.C, x.cs, x.coff, x.T - kt + 1, x.H - kh + 1, x.W - kw + 1, out_cs, out_coff,
+                    kt, kh, kw, 1, 1, 1, 0, 0, 0, 1)
+
+
+def avgpool_window(x, kernel, out=None):
+    """nn.AvgPool3d(kernel, stride=1) of the fully-convolutional head: Act [N,T,H,W,C] -> Act [N,T-kt+1,H-kh+1,W-kw+1,C]
+    (`out`: the pathway's slice of the concat buffer).  x is read once; bitwise reproducible."""
+    _require_gpu(x.buf, "avgpool_window")
+    assert len(kernel) == 3 and all(1 <= int(k) <= e for k, e in zip(kernel, (x.T, x.H, x.W))), (x, kernel)
+    d = _window_desc(x, kernel)
+    if out is None:
+        out = new_act(x, x.N, d.To, d.Ho, d.Wo, x.C)
+    else:
+        _require_gpu(out.buf, "avgpool_window")
+        assert (out.N, out.T, out.H, out.W, out.C) == (x.N, d.To, d.Ho, d.Wo, x.C), (x, kernel, out)
+    d.out_cs, d.out_coff = out.cs, out.coff
+    # trace tag: ("avgpool_window", algorithmic HBM bytes = the input once + the output once)
+    nbytes = 4 * (x.rows + out.rows) * x.C
+    _check(_traced(("avgpool_window", nbytes), lambda: lib().sf_avgpool_win_fwd(
+        ctypes.byref(d), x.ptr(), out.ptr(), _stream())), "sf_avgpool_win_fwd")
+    return out
+
+
+def avgpool_window_bwd(dy, dx, kernel, overwrite=False):
+    """dx [N,T,H,W,C] (+)= the backward of avgpool_window: 1/|kernel| * the sum of dy [N,T-kt+1,H-kh+1,W-kw+1,C] over
+    the windows that hold each element.  overwrite: dx is an uninitialised buffer this call is the first writer of
+    (every element is written, none read).  Bitwise reproducible (gather form)."""
+    _require_gpu(dx.buf, "avgpool_window_bwd")
+    _require_gpu(dy.buf, "avgpool_window_bwd")
+    assert len(kernel) == 3 and all(1 <= int(k) <= e for k, e in zip(kernel, (dx.T, dx.H, dx.W))), (dx, kernel)
+    d = _window_desc(dx, kernel, dy.cs, dy.coff)
+    assert (dy.N, dy.T, dy.H, dy.W, dy.C) == (dx.N, d.To, d.Ho, d.Wo, dx.C), (dy, dx, kernel)
+    # trace tag: algorithmic HBM bytes = dy once + dx written (read and written when accumulating)
+    nbytes = 4 * (dy.rows + dx.rows * (1 if overwrite else 2)) * dx.C
+    _check(_traced(("avgpool_window_bwd", nbytes), lambda: lib().sf_avgpool_win_bwd(
+        ctypes.byref(d), dy.ptr(), dy.cs, dy.coff, dx.ptr(), dx.cs, dx.coff, 1 if overwrite else 0, _stream())),
+        "sf_avgpool_win_bwd")
     return dx
 
 

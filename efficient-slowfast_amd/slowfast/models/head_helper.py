@@ -88,13 +88,25 @@ class ResNetBasicHead(nn.Module):
             assert (cat.T, cat.H, cat.W) == (to, ho, wo), "pathway pooled sizes differ"
             if (to, ho, wo) == (1, 1, 1):  # window == extent: a global mean (parallel tree reduction)
                 _global_mean(x, cat.slice(off, x.C))
-            else:
-                if engine.tape() is not None:
-                    raise NotImplementedError("training through a fully-convolutional head (pooled extent > 1)")
+            elif engine.tape() is None:
                 sfhip.pool(x, k, (1, 1, 1), avg=True, out=cat.slice(off, x.C))
+            else:  # training through the fully-convolutional head: logits [N, To*Ho*Wo*classes] (head_helper.py:198-223)
+                _window_pool(x, k, cat.slice(off, x.C))
             off += x.C
         logits = _project(cat, self.projection, getattr(self, "dropout", None), self.training)
         return _finish(logits, self.training, self._act_name)
+
+
+def _window_pool(x, k, piece):
+    """AvgPool3d(k, stride 1) of one pathway into its slice of the concat buffer, on the tape."""
+    sfhip.avgpool_window(x, k, out=piece)
+    t = engine.tape()
+
+    def bwd():
+        fresh = t.grad_of_uninitialised(x)  # first writer of x's gradient: write, no zero fill / read
+        sfhip.avgpool_window_bwd(t.grad_of(piece), fresh if fresh is not None else t.grad_of(x), k,
+                                 overwrite=fresh is not None)
+    t.record(bwd)
 
 
 class ROIAlign(nn.Module):

@@ -553,6 +553,26 @@ int sf_roi_align_max_bwd(const float* dy, int dy_cs, int dy_coff, const unsigned
                          int dx_cs, int dx_coff, int accumulate, void* stream);
 int sf_sigmoid_bwd(const float* y, const float* dy, float* dx, long n, int accumulate, void* stream);
 
+/* ---- fully-convolutional classification head (csrc/head_pool.hip): ResNetBasicHead's nn.AvgPool3d(pool_size, stride=1)
+ * per pathway (head_helper.py:174-179) and its concatenation (head_helper.py:203-207) when the window is smaller than
+ * res5 — the driver-monitoring YAMLs' RESNET.SPATIAL_STRIDES [[1,1],[1,1],[2,2],[2,2]]: a crop//32 window over a
+ * crop/16 map — and autograd's backward of that pool.  d: is_avg = 1, strides 1, padding 0, kT <= Ti (H, W likewise),
+ * To = Ti - kT + 1 (H, W likewise), divisor kT * kH * kW.  Null pointers, non-positive dims, a window larger than the
+ * input, any other stride / padding / output extent or a channel slice outside its pitch: SF_EINVAL, nothing launched.
+ * sf_avgpool_win_fwd: x channel slice (d->in_cs, d->in_coff) -> out[n,to,ho,wo, d->out_coff + c], the pathway's slice
+ *   of the concat buffer (pitch d->out_cs); channels outside the slice are not touched.  The window's frames are
+ *   summed first and that plane is box-filtered from LDS, so x is read once; a plane of more than 2048 positions
+ *   (8192 on the scalar path) goes to sf_pool_fwd's kernel instead.
+ * sf_avgpool_win_bwd: dx[n,t,h,w, dx_coff + c] (+)= 1/|k| * sum of dy[n,to,ho,wo, dy_coff + c] over to in
+ *   [max(0, t-kT+1), min(To-1, t)] (ho, wo likewise); d's own pitches / offsets are not read.  overwrite != 0: every
+ *   element of dx's slice is written (no zero fill, no read: the first writer of the gradient), else accumulated.
+ *   To == 1: the sum is formed once per (n, h, w, c) and stored to all Ti frames.
+ * Both: float4 kernels when C, both pitches and both offsets are multiples of 4 and both pointers 16-byte aligned,
+ * scalar kernels otherwise; fixed summation order and one owner per output element (no atomics): bitwise reproducible. */
+int sf_avgpool_win_fwd(const sf_pool_desc* d, const float* x, float* out, void* stream);
+int sf_avgpool_win_bwd(const sf_pool_desc* d, const float* dy, int dy_cs, int dy_coff, float* dx, int dx_cs,
+                       int dx_coff, int overwrite, void* stream);
+
 /* ---- input step (datasets/kinetics.py:230-248 -> datasets/utils.py:298-315 tensor_normalize, :151-203
  * spatial_sampling, :73-112 pack_pathway_output; transform.py:283-337 / 359-393 / 395-423 / 425-468).
  * clip: ONE decoded clip, uint8 [T,H,W,3] on the device.  The short side is scaled bilinearly to (new_h, new_w)
