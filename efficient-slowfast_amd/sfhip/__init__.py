@@ -66,12 +66,13 @@ EXPORTS = [
     "sf_assoc_accepts", "sf_gram_splits", "sf_gram_ws_floats", "sf_gram", "sf_rowmat",
     "sf_clip_prologue_gray", "sf_stem1_accepts", "sf_stem1_fwd", "sf_stem1_wgrad_ws_floats", "sf_stem1_wgrad",
     "sf_ncthw1_pack", "sf_avgpool_win_fwd", "sf_avgpool_win_bwd",
+    "sf_epilogue_bwd", "sf_head_act_mean_bwd", "sf_cam_weights", "sf_cam_map_ws_floats", "sf_cam_map",
 ]
 _LONG_RET = ("sf_tmax_mean_ws_floats", "sf_channel_stats_ws_floats", "sf_bn_bwd_ws_floats",
              "sf_dwconv_wgrad_ws_floats", "sf_attn_bwd_fused_ws_floats", "sf_conv_fwd_ws_floats",
              "sf_attn_fwd_ws_floats", "sf_conv_stats_ws_floats", "sf_bx_planes_elems", "sf_conv_bx_ws_floats",
              "sf_conv_wgrad_bx_ws_floats", "sf_xattn_bwd_ws_floats", "sf_gram_ws_floats",
-             "sf_stem1_wgrad_ws_floats")
+             "sf_stem1_wgrad_ws_floats", "sf_cam_map_ws_floats")
 
 
 def lib_path():
@@ -209,6 +210,12 @@ def lib():
         L.sf_ncthw1_pack.argtypes = [vp, vp] + [ci] * 7 + [vp]
         L.sf_avgpool_win_fwd.argtypes = [ctypes.POINTER(PoolDesc), vp, vp, vp]
         L.sf_avgpool_win_bwd.argtypes = [ctypes.POINTER(PoolDesc), vp, ci, ci, vp, ci, ci, ci, vp]
+        L.sf_epilogue_bwd.argtypes = [vp, ci, ci, vp, ci, ci] + [ci] * 6 + [vp, ci, vp, ci, ci, ci, vp, ci, ci, ci, vp]
+        L.sf_head_act_mean_bwd.argtypes = [vp, vp, ci, ci, ci, ci, vp, ci, vp]
+        L.sf_cam_weights.argtypes = [vp, ci, ci] + [ci] * 5 + [vp, vp]
+        L.sf_cam_map_ws_floats.argtypes = [ci] * 4
+        L.sf_cam_map_ws_floats.restype = cl
+        L.sf_cam_map.argtypes = [vp, ci, ci, vp] + [ci] * 5 + [vp, vp, vp, vp]
         for name in EXPORTS:
             fn = getattr(L, name)
             if name != "sf_build_arch" and name not in _LONG_RET:
@@ -1559,3 +1566,65 @@ def sigmoid_bwd(y, dy, dx, accumulate=True):
     _check(lib().sf_sigmoid_bwd(_ptr(y), _ptr(dy), _ptr(dx), y.numel(), 1 if accumulate else 0, _stream()),
            "sf_sigmoid_bwd")
     return dx
+
+
+# ------------------------------------------------------------------------------------------------ Grad-CAM
+def epilogue_bwd(dy, y, dz, scale=None, relu=False, rep=1, dz_accumulate=False, dres=None, dres_accumulate=False):
+    """Backward of the folded eval epilogue y = relu?(scale*z + bias + res) (repeated `rep` times along T):
+    dz (=|+=) scale * sum_r dy*[y > 0]; dres (=|+=) dy*[y > 0] in the same pass (rep 1 only).  dy / y: Acts with
+    dz.T * rep frames; y is only read when relu."""
+    _require_gpu(dy.buf, "epilogue_bwd")
+    _require_gpu(dz.buf, "epilogue_bwd")
+    assert relu in (False, True), "the eval epilogue's backward covers ReLU only"
+    assert (dy.N, dy.T, dy.H, dy.W, dy.C) == (dz.N, dz.T * rep, dz.H, dz.W, dz.C), (dy, dz, rep)
+    if relu:
+        _require_gpu(y.buf, "epilogue_bwd")
+        assert (y.N, y.T, y.H, y.W, y.C) == (dy.N, dy.T, dy.H, dy.W, dy.C), (y, dy)
+    if dres is not None:
+        _require_gpu(dres.buf, "epilogue_bwd")
+        assert rep == 1 and (dres.N, dres.T, dres.H, dres.W, dres.C) == (dz.N, dz.T, dz.H, dz.W, dz.C), (dres, dz)
+    assert scale is None or (scale.is_cuda and scale.dtype == torch.float32 and scale.is_contiguous() and
+                             scale.numel() == dz.C)
+    nbytes = 4 * dz.C * (dy.rows * (2 if relu else 1) + dz.rows * (2 if dz_accumulate else 1) +
+                         (dz.rows * (2 if dres_accumulate else 1) if dres is not None else 0))
+    _check(_traced(("epilogue_bwd", nbytes), lambda: lib().sf_epilogue_bwd(
+        dy.ptr(), dy.cs, dy.coff, y.ptr() if relu else None, y.cs if relu else 0, y.coff if relu else 0,
+        dz.N, dz.T, dz.H, dz.W, dz.C, rep, _ptr(scale), 1 if relu else 0, dz.ptr(), dz.cs, dz.coff,
+        1 if dz_accumulate else 0, dres.ptr() if dres is not None else None, dres.cs if dres is not None else 0,
+        dres.coff if dres is not None else 0, 1 if dres_accumulate else 0, _stream())), "sf_epilogue_bwd")
+    return dz
+
+
+def head_act_mean_bwd(logits, dout, act, dl, accumulate=False):
+    """dl (Act shaped like `logits`, dense) (=|+=) the backward of head_act_mean given dout [N, K]."""
+    _require_gpu(logits.buf, "head_act_mean_bwd")
+    _require_gpu(dout, "head_act_mean_bwd")
+    _require_gpu(dl.buf, "head_act_mean_bwd")
+    assert logits.coff == 0 and logits.C == logits.cs and dl.coff == 0 and dl.C == dl.cs
+    assert dl.buf.shape == logits.buf.shape and dout.is_contiguous() and tuple(dout.shape) == (logits.N, logits.C)
+    _check(lib().sf_head_act_mean_bwd(logits.ptr(), _ptr(dout), logits.N, logits.T * logits.H * logits.W, logits.C,
+                                      act, dl.ptr(), 1 if accumulate else 0, _stream()), "sf_head_act_mean_bwd")
+    return dl
+
+
+def cam_weights(g):
+    """w[n,t,c] = mean over h,w of the gradient view g -> torch [N, T, C]."""
+    _require_gpu(g.buf, "cam_weights")
+    w = torch.empty((g.N, g.T, g.C), dtype=torch.float32, device=g.buf.device)
+    _check(lib().sf_cam_weights(g.ptr(), g.cs, g.coff, g.N, g.T, g.H, g.W, g.C, _ptr(w), _stream()), "sf_cam_weights")
+    return w
+
+
+def cam_map(a, w, want_raw=False):
+    """Per-frame class-activation maps of the activation view `a` under the weights w [N,T,C]: torch [N,T,H,W] in
+    [0, 1] (min-max normalised per frame, zero-range frames give zeros); want_raw: (cam, the map before normalisation)."""
+    _require_gpu(a.buf, "cam_map")
+    _require_gpu(w, "cam_map")
+    assert w.is_contiguous() and tuple(w.shape) == (a.N, a.T, a.C), (tuple(w.shape), a)
+    dev = a.buf.device
+    ws = torch.empty((lib().sf_cam_map_ws_floats(a.N, a.H, a.W, a.C),), dtype=torch.float32, device=dev)
+    cam = torch.empty((a.N, a.T, a.H, a.W), dtype=torch.float32, device=dev)
+    raw = torch.empty_like(cam) if want_raw else None
+    _check(lib().sf_cam_map(a.ptr(), a.cs, a.coff, _ptr(w), a.N, a.T, a.H, a.W, a.C, _ptr(ws), _ptr(raw), _ptr(cam),
+                            _stream()), "sf_cam_map")
+    return (cam, raw) if want_raw else cam

@@ -63,8 +63,13 @@ class FuseFastAndSlow(nn.Module):
         else:
             f_wide = sfhip.new_act(x_f, x_f.N, x_f.T, x_f.H, x_f.W, x_f.C + self._c_s2f)
             sfhip.copy_channels(x_f, f_wide.slice(self._c_s2f, x_f.C))
+        unfused = isinstance(engine.tape(), engine.EvalTape)  # eval-mode tape: the forms that have a backward
+
         def fast_to_slow():
-            if self.bn_f2s.training:  # batch statistics sit between the gate and the ReLU: one extra pass
+            if unfused:
+                z = self.attention_channel_f2s.run(x_f, alpha=a)
+                engine.bn_eval_apply(self.bn_f2s, z, relu=True, out=s_wide.slice(x_s.C, self._c_f2s))
+            elif self.bn_f2s.training:  # batch statistics sit between the gate and the ReLU: one extra pass
                 z = self.attention_channel_f2s.run(x_f, alpha=a)
                 engine.bn_train_apply(self.bn_f2s, z, relu=True, out=s_wide.slice(x_s.C, self._c_f2s))
             else:
@@ -74,7 +79,10 @@ class FuseFastAndSlow(nn.Module):
 
         def slow_to_fast():
             y = engine.conv_bn_act(x_s, self.downsample_c_of_slow)
-            if self.bn_s2f.training:
+            if unfused:
+                z = self.attention_spatial_s2f.run(y)
+                engine.bn_eval_apply(self.bn_s2f, z, relu=True, rep=a, out=f_wide.slice(0, self._c_s2f))
+            elif self.bn_s2f.training:
                 z = self.attention_spatial_s2f.run(y)
                 engine.bn_train_apply(self.bn_s2f, z, relu=True, rep=a, out=f_wide.slice(0, self._c_s2f))
             else:

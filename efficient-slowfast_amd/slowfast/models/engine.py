@@ -66,6 +66,8 @@ class Tape(object):
         self.arena = None   # backward of a small model: ONE zero-filled tensor the gradient buffers are cut from
         self.arena_off = 0
         self.zero_floats = -1  # >= 0 while the backward runs: floats of zero-initialised buffers it has asked for
+        self.armed = True        # False: ops are not recorded yet (EvalTape before its target boundary)
+        self.param_grads = True  # False: weight / bias gradients are neither computed nor collected (EvalTape)
 
     def pgrad_target(self, param):
         """The tensor kernels may accumulate this parameter's gradient into directly, or None."""
@@ -175,7 +177,82 @@ class Tape(object):
 
 
 def tape():
-    return getattr(_tls, "tape", None)
+    t = getattr(_tls, "tape", None)
+    return t if t is None or t.armed else None
+
+
+class EvalTape(Tape):
+    """Tape of ONE eval-mode forward that yields ACTIVATION gradients only (models/gradcam.py; reference
+    wdf_visualization/gradcam_video.py:107-157).  Recording starts at the output boundary of the top-level child
+    `target` (engine.boundary): everything before it runs as the plain eval forward and leaves no closure, so the
+    replay ends at the target.  No weight-gradient kernel is launched, no parameter's .grad is read or written and no
+    gradient sink is consulted."""
+
+    def __init__(self, target):
+        super(EvalTape, self).__init__()
+        self.armed = False
+        self.param_grads = False
+        self.target = target
+        self.target_acts = None  # the target child's outputs (Acts), set when recording starts
+        self.out = None          # the head's eval output [N, classes]
+        self.dout = None         # dL/d(out), set by backward()
+
+    def pgrad_target(self, param):
+        return None
+
+    def add_pgrad(self, param, g):
+        pass
+
+    def add_pgrads(self, params, grads):
+        pass
+
+    def backward(self, dout):
+        """Replay from dL/d(out) = dout [N, classes] down to the target boundary; returns dL/d(target outputs) as
+        Acts (views of the gradient buffers, which then belong to the caller).  Every op runs on the stream it was
+        recorded on."""
+        if self.target_acts is None or self.out is None:
+            raise RuntimeError("the eval tape saw no boundary named %r, or no head output" % (self.target,))
+        self.dout = dout.contiguous()
+        try:
+            for fn, side in reversed(self.ops):
+                if side is None:
+                    fn()
+                else:
+                    with torch.cuda.stream(side):
+                        fn()
+            return [self.grad_of(a) for a in self.target_acts]
+        finally:
+            self.ops = []
+            self.gbuf = {}
+            self.dout = None
+
+
+class eval_taping(object):
+    """Context entered by models/gradcam.py only: the eval forward inside it records an EvalTape from the output of the
+    top-level child `target` on.  Nothing outside it changes: a plain eval forward and model.train() steps issue the
+    launches they always did."""
+
+    def __init__(self, target):
+        self.t = EvalTape(target)
+
+    def __enter__(self):
+        self.prev = getattr(_tls, "tape", None)
+        _tls.tape = self.t
+        return self.t
+
+    def __exit__(self, *a):
+        _tls.tape = self.prev
+
+
+def boundary(name, x):
+    """Called by the ResNet-family models' _forward_impl behind each top-level child with its outputs (Acts).  Under an
+    EvalTape whose target is `name` this is where recording starts; otherwise nothing happens."""
+    t = getattr(_tls, "tape", None)
+    if isinstance(t, EvalTape) and not t.armed and name == t.target:
+        join_pending(x[0].buf.device)  # a fusion's deferred join: the target's outputs are complete on this stream
+        t.target_acts = list(x)
+        t.armed = True
+    return x
 
 
 _MILESTONE_HOOKS = weakref.WeakKeyDictionary()  # model -> hook: a hook only ever sees the backward of ITS model
@@ -335,12 +412,14 @@ def _record_conv(x, conv_weight, conv_bias, wp_shape, gsrc, kernel, stride, padd
     def bwd():
         g = gsrc() if callable(gsrc) else gsrc
         dev = x.buf.device
+        if not t.param_grads:  # activation gradients only (EvalTape)
+            pass
         # The fork costs two cross-stream hand-offs: ~15 us each on the device when launched eagerly
         # (tools/microbench/stream_latency.py) — worth it even for the small layers of cfg #3 (52.9 ms forking every
         # layer, 53.2 forking only those estimated above 30 .. 120 us) — but far more as edges of a captured hipGraph:
         # cfg #1's replay went from 9.65 to 6.03 ms, cfg #5's from 43.3 to 34.9 ms and cfg #3's own from 56.6 to 54.1 ms
         # without them.  So: no companion stream while the backward is being CAPTURED; eagerly, every layer forks.
-        if OVERLAP_PATHS and not t.capturing and not t.serial and x_needs_grad and dev.type == "cuda":
+        elif OVERLAP_PATHS and not t.capturing and not t.serial and x_needs_grad and dev.type == "cuda":
             # the weight gradient only feeds the parameter's .grad: issue it on a companion stream so that it
             # overlaps the data gradient (both are short-grid GEMMs on the res4 / res5 layers); joined by
             # Tape.backward before the gradients are handed back
@@ -737,13 +816,15 @@ def _record_grouped_conv(x, conv, gsrc):
         g_all = gsrc() if callable(gsrc) else gsrc
         wp, wtp = _group_pairs(conv)
         tgt = t.pgrad_target(conv.weight)
-        if tgt is not None:
+        if not t.param_grads:  # activation gradients only (EvalTape)
+            pass
+        elif tgt is not None:
             sfhip.conv_wgrad_grouped(x, g_all, G, k, s, p, d, cin_pad=wp.shape[2], finish_into=tgt)
         else:
             dwp = sfhip.conv_wgrad_grouped(x, g_all, G, k, s, p, d, cin_pad=wp.shape[2])
             t.add_pgrad(conv.weight, sfhip.unpack_conv_weight_grad(dwp, tuple(conv.weight.shape)))
         sfhip.conv_dgrad_grouped(g_all, wtp, G, x, k, s, p, d, out=t.grad_of(x), accumulate=True)
-        if conv.bias is not None:
+        if conv.bias is not None and t.param_grads:
             t.add_pgrad(conv.bias, _colsum(g_all))
 
     t.record(bwd)
@@ -827,7 +908,9 @@ def conv_bn_act(x, conv, bn=None, relu=False, res=None, out=None, out_reserve=(0
         y = sfhip.conv(x, wp, k, s, p, d, scale=scale, bias=bias, relu=relu, res=res, out=out,
                        out_reserve=out_reserve, out_cmul=out_cmul)
         t = tape()
-        if t is not None:
+        if isinstance(t, EvalTape):
+            _record_eval_conv(t, x, conv, wp, y, scale, relu, res, out_cmul)
+        elif t is not None:
             if bn is not None or res is not None or out_cmul != 1:
                 raise NotImplementedError("taped conv with a folded (eval-mode) BN / residual epilogue")
             if relu:  # bare conv + ReLU (no BN): dL/dz = dL/dy masked by the activation's output
@@ -843,6 +926,40 @@ def conv_bn_act(x, conv, bn=None, relu=False, res=None, out=None, out_reserve=(0
         scale = torch.ones_like(bias)
     return sfhip.dwconv(x, wp, k, s, p, scale=scale, bias=bias, relu=relu, res=res, out=out, cout=cout,
                         out_cmul=out_cmul)
+
+
+def _record_eval_conv(t, x, conv, wp, y, scale, relu, res, out_cmul):
+    """Backward of the ONE-launch eval conv y = relu?(scale * conv(x) + bias + res) on an EvalTape: the epilogue's
+    backward (sf_epilogue_bwd: ReLU mask from y, the folded BN's scale, the residual's gradient in the same pass) into
+    a fresh dL/dz, then the data-gradient launch of the training tape.  No weight or bias gradient."""
+    if out_cmul != 1 or relu not in (False, True):
+        raise NotImplementedError("eval-mode tape: a channel-shuffled store or a ReLU6 epilogue has no backward here")
+    k, s, p, d = conv.kernel_size, conv.stride, conv.padding, conv.dilation
+    if scale is None and res is None and not relu:  # bare conv (+ bias): dL/dz is dL/dy
+        _record_conv(x, conv.weight, conv.bias, wp.shape, lambda: t.grad_of(y), k, s, p, d)
+        return
+
+    def dz_of_y():
+        dres, first = None, False
+        if res is not None:  # first writer of the residual branch's gradient: write it, no zero fill / read
+            fresh = t.grad_of_uninitialised(res)
+            dres, first = (fresh, True) if fresh is not None else (t.grad_of(res), False)
+        dz = sfhip.new_act(y, y.N, y.T, y.H, y.W, y.C)
+        return sfhip.epilogue_bwd(t.grad_of(y), y, dz, scale=scale, relu=relu, dres=dres, dres_accumulate=not first)
+
+    _record_conv(x, conv.weight, conv.bias, wp.shape, dz_of_y, k, s, p, d)
+
+
+def bn_eval_apply(bn, z, relu=False, rep=1, out=None):
+    """Eval-mode BatchNorm3d (+ ReLU) (+ nearest T-repeat) of the raw tensor z as ONE affine pass with bn_affine's
+    scale and bias — the un-fused form of the CMDA epilogues, taken under an EvalTape.  Its backward (sf_epilogue_bwd)
+    leaves dL/dz in z's own buffer, where the producer's backward looks for it (as bn_train_apply does)."""
+    sc, bi = bn_affine(bn)
+    y = sfhip.affine(z, sc, bi, relu=relu, rep=rep, out=out)
+    t = tape()
+    if t is not None:
+        t.record(lambda: sfhip.epilogue_bwd(t.grad_of(y), y, z, scale=sc, relu=relu, rep=rep))
+    return y
 
 
 def stem_geometry(conv, H, W):

@@ -43,7 +43,16 @@ def _finish(logits, training, act_name):
     if LOGITS_TAP is not None:
         LOGITS_TAP(logits.buf)
     if not training:
-        return sfhip.head_act_mean(logits, _act_code(act_name))
+        out = sfhip.head_act_mean(logits, _act_code(act_name))
+        t = engine.tape()
+        if isinstance(t, engine.EvalTape):  # Grad-CAM: the tape starts from dL/d(eval output), t.dout [N, classes]
+            def bwd():
+                fresh = t.grad_of_uninitialised(logits)
+                sfhip.head_act_mean_bwd(logits, t.dout, _act_code(act_name),
+                                        fresh if fresh is not None else t.grad_of(logits), accumulate=fresh is None)
+            t.record(bwd)
+            t.out = out
+        return out
     # train: the reference returns x.view(N, -1) of the raw projection (head_helper.py:222)
     return logits.buf.reshape(logits.N, -1)
 
@@ -90,6 +99,9 @@ class ResNetBasicHead(nn.Module):
                 _global_mean(x, cat.slice(off, x.C))
             elif engine.tape() is None:
                 sfhip.pool(x, k, (1, 1, 1), avg=True, out=cat.slice(off, x.C))
+            elif isinstance(engine.tape(), engine.EvalTape):  # the eval forward's pool, the windowed pool's backward
+                _window_pool(x, k, cat.slice(off, x.C),
+                             fwd=lambda x_, k_, out: sfhip.pool(x_, k_, (1, 1, 1), avg=True, out=out))
             else:  # training through the fully-convolutional head: logits [N, To*Ho*Wo*classes] (head_helper.py:198-223)
                 _window_pool(x, k, cat.slice(off, x.C))
             off += x.C
@@ -97,9 +109,9 @@ class ResNetBasicHead(nn.Module):
         return _finish(logits, self.training, self._act_name)
 
 
-def _window_pool(x, k, piece):
+def _window_pool(x, k, piece, fwd=sfhip.avgpool_window):
     """AvgPool3d(k, stride 1) of one pathway into its slice of the concat buffer, on the tape."""
-    sfhip.avgpool_window(x, k, out=piece)
+    fwd(x, k, out=piece)
     t = engine.tape()
 
     def bwd():

@@ -59,6 +59,8 @@ class Nonlocal(nn.Module):
 
     # ------------------------------------------------------------------------------------------------
     def run(self, x, reserve=(0, 0)):
+        if isinstance(engine.tape(), engine.EvalTape):
+            raise NotImplementedError("Grad-CAM (the eval-mode tape) does not cover Nonlocal blocks")
         theta = engine.conv_bn_act(x, self.conv_theta)
         xp = x
         if self.use_pool:

@@ -156,23 +156,24 @@ class _TwoPathwayResNet(nn.Module):
     def _forward_impl(self, x, bboxes=None):
         x = list(x)
         with engine.internal():
-            x = self.s1(x, reserve=self.s1_fuse.reserve(None))
-            x = self._fuse(self.s1_fuse, x)
-            x = self.s2(x, reserve=self.s2_fuse.reserve(None))
-            x = self._fuse(self.s2_fuse, x)
+            # engine.boundary: where an eval tape (models/gradcam.py) starts recording; nothing otherwise
+            x = engine.boundary("s1", self.s1(x, reserve=self.s1_fuse.reserve(None)))
+            x = engine.boundary("s1_fuse", self._fuse(self.s1_fuse, x))
+            x = engine.boundary("s2", self.s2(x, reserve=self.s2_fuse.reserve(None)))
+            x = engine.boundary("s2_fuse", self._fuse(self.s2_fuse, x))
             for pathway in range(self.num_pathways):
                 pool = getattr(self, "pathway{}_pool".format(pathway))
                 ks = pool.kernel_size if isinstance(pool.kernel_size, (list, tuple)) else [pool.kernel_size] * 3
                 if list(ks) != [1, 1, 1]:  # _POOL1["slowfast"] is the identity (elided)
                     x[pathway] = engine.maxpool(x[pathway], tuple(ks), tuple(ks))
             engine.milestone("s3")  # backward: the gradients of s3 .. head are complete here (chunked all-reduce)
-            x = self.s3(x, reserve=self.s3_fuse.reserve(None))
-            x = self._fuse(self.s3_fuse, x)
+            x = engine.boundary("s3", self.s3(x, reserve=self.s3_fuse.reserve(None)))
+            x = engine.boundary("s3_fuse", self._fuse(self.s3_fuse, x))
             engine.milestone("s4")
-            x = self.s4(x, reserve=self.s4_fuse.reserve(None))
-            x = self._fuse(self.s4_fuse, x)
+            x = engine.boundary("s4", self.s4(x, reserve=self.s4_fuse.reserve(None)))
+            x = engine.boundary("s4_fuse", self._fuse(self.s4_fuse, x))
             engine.milestone("s5")
-            x = self.s5(x)
+            x = engine.boundary("s5", self.s5(x))
             x = self.head(x, bboxes) if self.enable_detection else self.head(x)
         return x
 
@@ -266,17 +267,17 @@ class ResNet(nn.Module):
     def _forward_impl(self, x, bboxes=None):
         x = list(x)
         with engine.internal():
-            x = self.s1(x)
-            x = self.s2(x)
+            x = engine.boundary("s1", self.s1(x))
+            x = engine.boundary("s2", self.s2(x))
             ks = self.pathway0_pool.kernel_size
             ks = tuple(ks) if isinstance(ks, (list, tuple)) else (ks,) * 3
             if ks != (1, 1, 1):
                 x[0] = engine.maxpool(x[0], ks, ks)
             engine.milestone("s3")
-            x = self.s3(x)
+            x = engine.boundary("s3", self.s3(x))
             engine.milestone("s4")
-            x = self.s4(x)
+            x = engine.boundary("s4", self.s4(x))
             engine.milestone("s5")
-            x = self.s5(x)
+            x = engine.boundary("s5", self.s5(x))
             x = self.head(x, bboxes) if self.enable_detection else self.head(x)
         return x

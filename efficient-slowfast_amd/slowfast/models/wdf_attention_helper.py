@@ -52,11 +52,13 @@ class SpatialAttention(nn.Module):
 
             def bwd():  # merged q|k|v projection: one wgrad / dgrad, then split per conv
                 g = t.grad_of(qkv)
-                dwp = sfhip.conv_wgrad(x, g, 3 * c, (1, 1, 1), cin_pad=wp.shape[2])
-                dw = sfhip.unpack_conv_weight_grad(dwp, (3 * c, c, 1, 1, 1))
-                db = engine._colsum(g)
-                t.add_pgrads([cv.weight for cv in convs] + [cv.bias for cv in convs],
-                             [dw[i * c:i * c + nout[i]] for i in range(3)] + [db[i * c:i * c + nout[i]] for i in range(3)])
+                if t.param_grads:
+                    dwp = sfhip.conv_wgrad(x, g, 3 * c, (1, 1, 1), cin_pad=wp.shape[2])
+                    dw = sfhip.unpack_conv_weight_grad(dwp, (3 * c, c, 1, 1, 1))
+                    db = engine._colsum(g)
+                    t.add_pgrads([cv.weight for cv in convs] + [cv.bias for cv in convs],
+                                 [dw[i * c:i * c + nout[i]] for i in range(3)] +
+                                 [db[i * c:i * c + nout[i]] for i in range(3)])
                 sfhip.conv_dgrad(g, wtp, x, (1, 1, 1), out=t.grad_of(x), accumulate=True)
 
             t.record(bwd)
@@ -86,7 +88,8 @@ class SpatialAttention(nn.Module):
 
         def bwd():  # z's buffer holds dL/dz (the BN backward wrote it in place), as in run()
             gz = z if getattr(bwd, "grad_in_place", True) else t.grad_of(z)
-            t.add_pgrad(self.gamma, sfhip.rowdot(gz, o).sum().reshape(1))
+            if t.param_grads:
+                t.add_pgrad(self.gamma, sfhip.rowdot(gz, o).sum().reshape(1))
             sfhip.affine(gz, scale=self.gamma.detach().expand(c).contiguous(), bias=zero, out=t.grad_of(o))  # dO = gamma * dz
             sfhip.axpy(gz, t.grad_of(x), 1.0, accumulate=True)                                     # residual
 
@@ -111,7 +114,8 @@ class SpatialAttention(nn.Module):
                 dq = t.grad_of(qkv)
                 dvec = sfhip.attention_bwd(q, k, v, gz, save["o"], save["lse"], self.gamma, dq.slice(0, c),
                                            dq.slice(c, c), dq.slice(2 * c, c))
-                t.add_pgrad(self.gamma, dvec.sum().reshape(1))
+                if t.param_grads:
+                    t.add_pgrad(self.gamma, dvec.sum().reshape(1))
                 sfhip.axpy(gz, t.grad_of(x), 1.0, accumulate=True)  # residual: z = gamma*O + x
 
             t.record(bwd)

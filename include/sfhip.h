@@ -613,6 +613,44 @@ int sf_stem1_wgrad(const float* x, int N, int T, int Hp, int Wp, const float* dz
                    int kT, int pT, float* dw, int accumulate, float* ws, void* stream);
 int sf_ncthw1_pack(const float* src, float* dst, int N, int T, int H, int W, int ph, int pw, int Wp, void* stream);
 
+/* ---- Grad-CAM (csrc/gradcam.hip): the arithmetic of wdf_visualization/gradcam_video.py's GradVideoCam on the eval
+ * forward — the gradient of one class score with respect to a top-level child's output (gradcam_video.py:143-157:
+ * a one-hot vector back-propagated from the head's eval output) and the per-frame class-activation maps
+ * (gradcam_video.py:159-179).  Only ACTIVATION gradients: no entry here touches a parameter's gradient.
+ * All four: null pointers, non-positive sizes or a channel slice outside its pitch return SF_EINVAL with nothing
+ * launched; 64-bit element indices; one owner per output element and a fixed summation order (no atomics): bitwise
+ * reproducible.
+ *
+ * sf_epilogue_bwd: backward of the folded eval epilogue of sf_conv_fwd / sf_affine_fwd,
+ *     y = relu?(scale[c] * z + bias[c] + res), y repeated `rep` times along T (nn.Upsample nearest,
+ *     custom_video_model_builder.py:120-121):
+ *   dz[n,t,h,w,c] (=|+=) scale[c] * sum_{r<rep} dy[n, t*rep + r, h,w,c] * m,  m = [y[n, t*rep + r, h,w,c] > 0] when
+ *   relu != 0, else 1 (y is then not read and may be NULL); scale NULL means 1.  T is dz's frame count; dy and y hold
+ *   T * rep frames.  dres != NULL (rep must be 1): dres (=|+=) dy * m in the same pass — the residual branch's
+ *   gradient.  dz_accumulate / dres_accumulate == 0: every element of the slice is written (no zero fill needed).
+ *   dy and y are read once.  float4 kernel when C, every pitch and offset are multiples of 4 and every pointer is
+ *   16-byte aligned, scalar kernel otherwise.
+ * sf_head_act_mean_bwd: backward of sf_head_act_mean (head_helper.py:217-221), out[b,k] = mean_p act(logits[b,p,:])[k]:
+ *   given dout [B,K],  softmax: dl[b,p,k] = s[p,k] * (dout[k] - sum_j dout[j] * s[p,j]) / P;  sigmoid:
+ *   s (1 - s) dout[k] / P;  relu: [l > 0] dout[k] / P;  none: dout[k] / P.  The activation is recomputed from the
+ *   logits (max-subtracted softmax, as sf_head_act_mean); any K >= 1.  accumulate != 0 adds to dl.
+ * sf_cam_weights: w[n,t,c] = mean_{h,w} g[n,t,h,w, g_coff + c]  (gradcam_video.py:159-166), w dense [N*T, C].
+ * sf_cam_map: abar[n,h,w,c] = mean_t a[n,t,h,w, a_coff + c] (written to ws, sf_cam_map_ws_floats floats),
+ *   raw[n,t,h,w] = max(0, 1 + sum_c w[n,t,c] * abar[n,h,w,c]) (optional output, may be NULL),
+ *   cam[n,t,h,w] = (raw - min) / (max - min) over the frame (n,t)  (gradcam_video.py:167-179); a frame whose range is
+ *   zero gives zeros (the reference divides by zero there).  The normalisation is taken of max(-1, sum) — the same
+ *   map less its constant 1, summed from 0 — so a nearly flat map (sum of order 1e-3) is not first rounded at the
+ *   magnitude of the 1.  Two launches.                                                                             */
+int sf_epilogue_bwd(const float* dy, int dy_cs, int dy_coff, const float* y, int y_cs, int y_coff, int N, int T, int H,
+                    int W, int C, int rep, const float* scale, int relu, float* dz, int dz_cs, int dz_coff,
+                    int dz_accumulate, float* dres, int dres_cs, int dres_coff, int dres_accumulate, void* stream);
+int sf_head_act_mean_bwd(const float* logits, const float* dout, int B, int P, int K, int act, float* dl,
+                         int accumulate, void* stream);
+int sf_cam_weights(const float* g, int g_cs, int g_coff, int N, int T, int H, int W, int C, float* w, void* stream);
+long sf_cam_map_ws_floats(int N, int H, int W, int C);
+int sf_cam_map(const float* a, int a_cs, int a_coff, const float* w, int N, int T, int H, int W, int C, float* ws,
+               float* raw, float* cam, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
