@@ -1048,6 +1048,12 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_bx2_kernel(const BwdArgs p, f
           dp = mfma_split(da, vfb[blk][c], dp);
         }
       }
+      // a padded key (this lane's column, jrow >= N) has K = V = 0, so s = -lse there: P = 2^-lse, not 0.  Its dK / dV
+      // are dropped and dS * K = 0 — unless lse < -127, where P overflows and Inf * 0 puts a NaN into the row's dQ
+      if (!jok) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] = -POS_BIG;
+      }
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[r] = __builtin_amdgcn_exp2f(s[r]);  // P
       {

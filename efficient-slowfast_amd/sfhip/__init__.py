@@ -67,6 +67,7 @@ EXPORTS = [
     "sf_clip_prologue_gray", "sf_stem1_accepts", "sf_stem1_fwd", "sf_stem1_wgrad_ws_floats", "sf_stem1_wgrad",
     "sf_ncthw1_pack", "sf_avgpool_win_fwd", "sf_avgpool_win_bwd",
     "sf_epilogue_bwd", "sf_head_act_mean_bwd", "sf_cam_weights", "sf_cam_map_ws_floats", "sf_cam_map",
+    "sf_epilogue_bwd_act", "sf_dwconv_dgrad_epi",
 ]
 _LONG_RET = ("sf_tmax_mean_ws_floats", "sf_channel_stats_ws_floats", "sf_bn_bwd_ws_floats",
              "sf_dwconv_wgrad_ws_floats", "sf_attn_bwd_fused_ws_floats", "sf_conv_fwd_ws_floats",
@@ -211,6 +212,10 @@ def lib():
         L.sf_avgpool_win_fwd.argtypes = [ctypes.POINTER(PoolDesc), vp, vp, vp]
         L.sf_avgpool_win_bwd.argtypes = [ctypes.POINTER(PoolDesc), vp, ci, ci, vp, ci, ci, ci, vp]
         L.sf_epilogue_bwd.argtypes = [vp, ci, ci, vp, ci, ci] + [ci] * 6 + [vp, ci, vp, ci, ci, ci, vp, ci, ci, ci, vp]
+        L.sf_epilogue_bwd_act.argtypes = ([vp, ci, ci, vp, ci, ci] + [ci] * 6 +
+                                          [vp, ci, ci, vp, ci, ci, ci, vp, ci, ci, ci, vp])
+        L.sf_dwconv_dgrad_epi.argtypes = [ctypes.POINTER(ConvDesc), vp, ci, ci, vp, ci, ci, vp, vp, ci, vp, ci, ci, ci,
+                                          ci, vp]
         L.sf_head_act_mean_bwd.argtypes = [vp, vp, ci, ci, ci, ci, vp, ci, vp]
         L.sf_cam_weights.argtypes = [vp, ci, ci] + [ci] * 5 + [vp, vp]
         L.sf_cam_map_ws_floats.argtypes = [ci] * 4
@@ -1569,15 +1574,23 @@ def sigmoid_bwd(y, dy, dx, accumulate=True):
 
 
 # ------------------------------------------------------------------------------------------------ Grad-CAM
-def epilogue_bwd(dy, y, dz, scale=None, relu=False, rep=1, dz_accumulate=False, dres=None, dres_accumulate=False):
-    """Backward of the folded eval epilogue y = relu?(scale*z + bias + res) (repeated `rep` times along T):
-    dz (=|+=) scale * sum_r dy*[y > 0]; dres (=|+=) dy*[y > 0] in the same pass (rep 1 only).  dy / y: Acts with
-    dz.T * rep frames; y is only read when relu."""
+def epilogue_bwd(dy, y, dz, scale=None, relu=False, rep=1, dz_accumulate=False, dres=None, dres_accumulate=False,
+                 act=None, groups=1):
+    """Backward of the folded eval epilogue y = act(scale*z + bias + res) (repeated `rep` times along T):
+    dz (=|+=) scale * sum_r dy*m(y); dres (=|+=) dy*m(y) in the same pass (rep 1 only).  dy / y: Acts with dz.T * rep
+    frames; y is only read when there is an activation.  relu: False / True, the call sf_epilogue_bwd serves.  act
+    (False / True / 6 for ReLU6, overrides relu) or groups > 1 — dy and y hold the channel-shuffled store of a grouped
+    conv, dz channel g * C/groups + j reads channel j * groups + g — go to sf_epilogue_bwd_act."""
     _require_gpu(dy.buf, "epilogue_bwd")
     _require_gpu(dz.buf, "epilogue_bwd")
-    assert relu in (False, True), "the eval epilogue's backward covers ReLU only"
+    extended = act is not None or groups != 1
+    if act is None:
+        assert relu in (False, True), "relu is a flag: ReLU6 is act=6"
+        act = bool(relu)
+    assert act in (False, True, 6), act
+    assert groups >= 1 and dz.C % groups == 0 and (groups == 1 or (rep == 1 and dres is None)), (groups, dz, rep)
     assert (dy.N, dy.T, dy.H, dy.W, dy.C) == (dz.N, dz.T * rep, dz.H, dz.W, dz.C), (dy, dz, rep)
-    if relu:
+    if act:
         _require_gpu(y.buf, "epilogue_bwd")
         assert (y.N, y.T, y.H, y.W, y.C) == (dy.N, dy.T, dy.H, dy.W, dy.C), (y, dy)
     if dres is not None:
@@ -1585,14 +1598,45 @@ def epilogue_bwd(dy, y, dz, scale=None, relu=False, rep=1, dz_accumulate=False, 
         assert rep == 1 and (dres.N, dres.T, dres.H, dres.W, dres.C) == (dz.N, dz.T, dz.H, dz.W, dz.C), (dres, dz)
     assert scale is None or (scale.is_cuda and scale.dtype == torch.float32 and scale.is_contiguous() and
                              scale.numel() == dz.C)
-    nbytes = 4 * dz.C * (dy.rows * (2 if relu else 1) + dz.rows * (2 if dz_accumulate else 1) +
+    nbytes = 4 * dz.C * (dy.rows * (2 if act else 1) + dz.rows * (2 if dz_accumulate else 1) +
                          (dz.rows * (2 if dres_accumulate else 1) if dres is not None else 0))
-    _check(_traced(("epilogue_bwd", nbytes), lambda: lib().sf_epilogue_bwd(
-        dy.ptr(), dy.cs, dy.coff, y.ptr() if relu else None, y.cs if relu else 0, y.coff if relu else 0,
-        dz.N, dz.T, dz.H, dz.W, dz.C, rep, _ptr(scale), 1 if relu else 0, dz.ptr(), dz.cs, dz.coff,
-        1 if dz_accumulate else 0, dres.ptr() if dres is not None else None, dres.cs if dres is not None else 0,
-        dres.coff if dres is not None else 0, 1 if dres_accumulate else 0, _stream())), "sf_epilogue_bwd")
+    head = (dy.ptr(), dy.cs, dy.coff, y.ptr() if act else None, y.cs if act else 0, y.coff if act else 0,
+            dz.N, dz.T, dz.H, dz.W, dz.C, rep, _ptr(scale))
+    tail = (dz.ptr(), dz.cs, dz.coff, 1 if dz_accumulate else 0, dres.ptr() if dres is not None else None,
+            dres.cs if dres is not None else 0, dres.coff if dres is not None else 0, 1 if dres_accumulate else 0)
+    if extended:
+        _check(_traced(("epilogue_bwd", nbytes), lambda: lib().sf_epilogue_bwd_act(
+            *(head + (_act(act), groups) + tail + (_stream(),)))), "sf_epilogue_bwd_act")
+    else:
+        _check(_traced(("epilogue_bwd", nbytes), lambda: lib().sf_epilogue_bwd(
+            *(head + (1 if act else 0,) + tail + (_stream(),)))), "sf_epilogue_bwd")
     return dz
+
+
+def dwconv_dgrad_epi(x, dy, y, wp, kernel, stride, padding, dx, scale=None, relu=False, accumulate=True):
+    """dx (=|+=) the data gradient of the depthwise conv that made y [= act(scale * dwconv(x) + bias)] from x, given
+    dy = dL/dy: sf_dwconv_dgrad_epi masks and scales dy as it gathers it, so no dL/dz tensor is made.  x gives the input
+    geometry only; wp [taps, pitch >= C] as dwconv takes it; relu: False / True / 6; y is read only with an activation.
+    accumulate False: every element of dx is written (dx may be uninitialised)."""
+    _require_gpu(dy.buf, "dwconv_dgrad_epi")
+    _require_gpu(dx.buf, "dwconv_dgrad_epi")
+    assert relu in (False, True, 6), relu
+    assert (dx.N, dx.T, dx.H, dx.W, dx.C) == (x.N, x.T, x.H, x.W, x.C) and dy.C == x.C and dy.N == x.N, (dx, x, dy)
+    assert wp.is_cuda and wp.dtype == torch.float32 and wp.is_contiguous() and \
+        tuple(wp.shape) == (kernel[0] * kernel[1] * kernel[2], wp.shape[1]) and wp.shape[1] >= x.C, (wp.shape, x)
+    if relu:
+        _require_gpu(y.buf, "dwconv_dgrad_epi")
+        assert (y.N, y.T, y.H, y.W, y.C) == (dy.N, dy.T, dy.H, dy.W, dy.C), (y, dy)
+    assert scale is None or (scale.is_cuda and scale.dtype == torch.float32 and scale.is_contiguous() and
+                             scale.numel() == x.C)
+    d = _dw_desc(x, dy, kernel, stride, padding, wp.shape[1])
+    # trace tag: algorithmic HBM bytes = dy (and y) once + dx written (read and written when accumulating)
+    nbytes = 4 * x.C * (dy.rows * (2 if relu else 1) + dx.rows * (2 if accumulate else 1))
+    _check(_traced(("dwconv_dgrad_epi", nbytes), lambda: lib().sf_dwconv_dgrad_epi(
+        ctypes.byref(d), dy.ptr(), dy.cs, dy.coff, y.ptr() if relu else None, y.cs if relu else 0,
+        y.coff if relu else 0, _ptr(wp), _ptr(scale), _act(relu), dx.ptr(), dx.cs, dx.coff, x.C,
+        1 if accumulate else 0, _stream())), "sf_dwconv_dgrad_epi")
+    return dx
 
 
 def head_act_mean_bwd(logits, dout, act, dl, accumulate=False):

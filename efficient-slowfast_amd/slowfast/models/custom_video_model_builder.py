@@ -138,12 +138,14 @@ class _EfficientTwoPathway(nn.Module):
                     engine.milestone(n)
                 if n == "head":
                     x = m(x)
-                elif n.endswith("_fuse"):
+                    continue
+                if n.endswith("_fuse"):
                     nxt = names[i + 1] if i + 1 < len(names) else "head"
                     x = m(x, defer_join=nxt != "head")  # followed by a stage: the attention overlaps it
                 else:
                     nxt = getattr(self, names[i + 1]) if i + 1 < len(names) else None
                     x = m(x, reserve=nxt.reserve(None) if isinstance(nxt, FuseFastAndSlow) else None)
+                x = engine.boundary(n, x)  # Grad-CAM (models/gradcam.py): an eval tape starts behind its target child
         return x
 
 

@@ -864,10 +864,14 @@ def conv_bn_act(x, conv, bn=None, relu=False, res=None, out=None, out_reserve=(0
             y = bn_train_apply(bn, z, res=res, relu=relu)
             return channel_shuffle(y, conv.groups, out=out, out_reserve=out_reserve)
         scale, bias = bn_affine(bn, conv.bias) if bn is not None else (None, conv.bias)
-        if tape() is not None:
+        t = tape()
+        if t is not None and not isinstance(t, EvalTape):
             raise NotImplementedError("taped grouped conv with a folded (eval-mode) BN epilogue")
-        return grouped_conv(x, conv, scale=scale, bias=bias, relu=relu, res=res, out=out, out_reserve=out_reserve,
-                            shuffle=shuffle)
+        y = grouped_conv(x, conv, scale=scale, bias=bias, relu=relu, res=res, out=out, out_reserve=out_reserve,
+                         shuffle=shuffle)
+        if t is not None:
+            _record_eval_grouped_conv(t, x, conv, y, scale, relu, res, shuffle)
+        return y
     assert not shuffle or conv.groups == 1, "channel_shuffle of a depthwise conv's output is not used by any model"
     wp = packed_weight(conv)
     if bn is not None and bn.training:
@@ -924,16 +928,51 @@ def conv_bn_act(x, conv, bn=None, relu=False, res=None, out=None, out_reserve=(0
     assert d == (1, 1, 1)
     if scale is None and bias is not None:
         scale = torch.ones_like(bias)
-    return sfhip.dwconv(x, wp, k, s, p, scale=scale, bias=bias, relu=relu, res=res, out=out, cout=cout,
-                        out_cmul=out_cmul)
+    y = sfhip.dwconv(x, wp, k, s, p, scale=scale, bias=bias, relu=relu, res=res, out=out, cout=cout,
+                     out_cmul=out_cmul)
+    t = tape()
+    if isinstance(t, EvalTape):
+        if res is not None or out_cmul != 1 or (cout is not None and cout != x.C):
+            raise NotImplementedError("eval-mode tape: a depthwise conv with a residual, a channel-sliced or an "
+                                      "interleaved store has no backward here")
+
+        def bwd_dw_eval():  # epilogue backward and data gradient in ONE launch: no dL/dz tensor
+            fresh = t.grad_of_uninitialised(x)  # first writer of x's gradient: write, no zero fill / read
+            sfhip.dwconv_dgrad_epi(x, t.grad_of(y), y, packed_weight(conv), k, s, p,
+                                   fresh if fresh is not None else t.grad_of(x), scale=scale, relu=relu,
+                                   accumulate=fresh is None)
+
+        t.record(bwd_dw_eval)
+    return y
+
+
+def _record_eval_grouped_conv(t, x, conv, y, scale, relu, res, shuffle):
+    """_record_eval_conv for a grouped conv (1 < groups < channels): sf_epilogue_bwd_act into a fresh dL/dz — with
+    `groups` it also undoes the channel-shuffled store, so dL/dz is in the conv's own channel order — then the grouped
+    data gradient of the training tape.  No weight or bias gradient."""
+    if scale is None and res is None and not relu and not shuffle:  # bare conv (+ bias): dL/dz is dL/dy
+        _record_grouped_conv(x, conv, lambda: t.grad_of(y))
+        return
+
+    def dz_of_y():
+        dres, first = None, False
+        if res is not None:  # first writer of the residual branch's gradient: write it, no zero fill / read
+            fresh = t.grad_of_uninitialised(res)
+            dres, first = (fresh, True) if fresh is not None else (t.grad_of(res), False)
+        dz = sfhip.new_act(y, y.N, y.T, y.H, y.W, y.C)
+        return sfhip.epilogue_bwd(t.grad_of(y), y, dz, scale=scale, act=relu, groups=conv.groups if shuffle else 1,
+                                  dres=dres, dres_accumulate=not first)
+
+    _record_grouped_conv(x, conv, dz_of_y)
 
 
 def _record_eval_conv(t, x, conv, wp, y, scale, relu, res, out_cmul):
-    """Backward of the ONE-launch eval conv y = relu?(scale * conv(x) + bias + res) on an EvalTape: the epilogue's
-    backward (sf_epilogue_bwd: ReLU mask from y, the folded BN's scale, the residual's gradient in the same pass) into
-    a fresh dL/dz, then the data-gradient launch of the training tape.  No weight or bias gradient."""
-    if out_cmul != 1 or relu not in (False, True):
-        raise NotImplementedError("eval-mode tape: a channel-shuffled store or a ReLU6 epilogue has no backward here")
+    """Backward of the ONE-launch eval conv y = act(scale * conv(x) + bias + res) on an EvalTape: the epilogue's
+    backward (sf_epilogue_bwd, or sf_epilogue_bwd_act for ReLU6: mask from y, the folded BN's scale, the residual's
+    gradient in the same pass) into a fresh dL/dz, then the data-gradient launch of the training tape.  No weight or
+    bias gradient."""
+    if out_cmul != 1 or relu not in (False, True, 6):
+        raise NotImplementedError("eval-mode tape: an interleaved (out_cmul) store has no backward here")
     k, s, p, d = conv.kernel_size, conv.stride, conv.padding, conv.dilation
     if scale is None and res is None and not relu:  # bare conv (+ bias): dL/dz is dL/dy
         _record_conv(x, conv.weight, conv.bias, wp.shape, lambda: t.grad_of(y), k, s, p, d)
@@ -945,6 +984,8 @@ def _record_eval_conv(t, x, conv, wp, y, scale, relu, res, out_cmul):
             fresh = t.grad_of_uninitialised(res)
             dres, first = (fresh, True) if fresh is not None else (t.grad_of(res), False)
         dz = sfhip.new_act(y, y.N, y.T, y.H, y.W, y.C)
+        if relu == 6:
+            return sfhip.epilogue_bwd(t.grad_of(y), y, dz, scale=scale, act=6, dres=dres, dres_accumulate=not first)
         return sfhip.epilogue_bwd(t.grad_of(y), y, dz, scale=scale, relu=relu, dres=dres, dres_accumulate=not first)
 
     _record_conv(x, conv.weight, conv.bias, wp.shape, dz_of_y, k, s, p, d)

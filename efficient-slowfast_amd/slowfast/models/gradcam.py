@@ -1,12 +1,13 @@
 """Grad-CAM on the HIP path: the arithmetic of the reference's wdf_visualization/gradcam_video.py (GradVideoCam) for
-the two-pathway ResNet models and the single-pathway ResNet.
+the two-pathway ResNet models, the single-pathway ResNet and the two efficient backbones the reference tool defaults to
+(SlowFastShuffleNet, SlowFastMoibleNetV2).
 
 The reference puts the model in eval(), walks model._modules child by child, hooks the gradient of the [slow, fast]
 pair behind a chosen child, back-propagates a one-hot class vector from the head's eval output (:107-157) and builds
 one class-activation map per frame and pathway (:159-211).  Here the eval forward runs once under
 engine.eval_taping(target): everything up to the target child is the plain eval forward, everything after it records
-activation-gradient closures (folded conv epilogues through sf_epilogue_bwd, the head's softmax-mean through
-sf_head_act_mean_bwd), and the replay hands back d out[n, cls[n]] / d (target outputs).  No weight-gradient kernel
+activation-gradient closures (folded conv epilogues through sf_epilogue_bwd / sf_epilogue_bwd_act, depthwise convs with
+their epilogue through sf_dwconv_dgrad_epi, the head's softmax-mean through sf_head_act_mean_bwd), and the replay hands back d out[n, cls[n]] / d (target outputs).  No weight-gradient kernel
 runs and no parameter's .grad is touched."""
 import torch
 
@@ -21,14 +22,17 @@ def target_layers(model):
     """Names of the top-level children whose outputs class_gradients can differentiate to (the children in front of
     `head`; the identity pathway{p}_pool children are not targets).  Raises NotImplementedError for a model the
     eval-mode tape does not cover."""
-    from .custom_video_model_builder import SlowFastDualAttention
+    from .custom_video_model_builder import SlowFastDualAttention, SlowFastMoibleNetV2, SlowFastShuffleNet
     from .video_model_builder import ResNet, SlowFast
-    if not isinstance(model, (SlowFast, SlowFastDualAttention, ResNet)):
+    if not isinstance(model, (SlowFast, SlowFastDualAttention, ResNet, SlowFastShuffleNet, SlowFastMoibleNetV2)):
         raise NotImplementedError(
-            "Grad-CAM on the HIP path covers SlowFast, SlowFastDualAttention and ResNet; %s has no eval-mode backward"
-            % type(model).__name__)
+            "Grad-CAM on the HIP path covers SlowFast, SlowFastDualAttention, ResNet, SlowFastShuffleNet and "
+            "SlowFastMoibleNetV2; %s has no eval-mode backward" % type(model).__name__)
     if getattr(model, "enable_detection", False):
         raise NotImplementedError("Grad-CAM on the HIP path does not cover DETECTION.ENABLE models (ResNetRoIHead)")
+    if isinstance(model, (SlowFastShuffleNet, SlowFastMoibleNetV2)):  # forward = the registered children in order
+        names = [n for n, _ in model.named_children()]
+        return tuple(names[:names.index("head")])
     return _ONE_PATHWAY if isinstance(model, ResNet) else _TWO_PATHWAY
 
 

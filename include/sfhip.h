@@ -617,7 +617,7 @@ int sf_ncthw1_pack(const float* src, float* dst, int N, int T, int H, int W, int
  * forward — the gradient of one class score with respect to a top-level child's output (gradcam_video.py:143-157:
  * a one-hot vector back-propagated from the head's eval output) and the per-frame class-activation maps
  * (gradcam_video.py:159-179).  Only ACTIVATION gradients: no entry here touches a parameter's gradient.
- * All four: null pointers, non-positive sizes or a channel slice outside its pitch return SF_EINVAL with nothing
+ * All of them: null pointers, non-positive sizes or a channel slice outside its pitch return SF_EINVAL with nothing
  * launched; 64-bit element indices; one owner per output element and a fixed summation order (no atomics): bitwise
  * reproducible.
  *
@@ -644,6 +644,34 @@ int sf_ncthw1_pack(const float* src, float* dst, int N, int T, int H, int W, int
 int sf_epilogue_bwd(const float* dy, int dy_cs, int dy_coff, const float* y, int y_cs, int y_coff, int N, int T, int H,
                     int W, int C, int rep, const float* scale, int relu, float* dz, int dz_cs, int dz_coff,
                     int dz_accumulate, float* dres, int dres_cs, int dres_coff, int dres_accumulate, void* stream);
+/* sf_epilogue_bwd_act: sf_epilogue_bwd for the efficient backbones' epilogues (gradcam_video.py:143-157 back-propagates
+ * through them when the target is a child of SlowFastShuffleNet / SlowFastMoibleNetV2).
+ *   act is an activation CODE: SF_ACT_NONE, SF_ACT_RELU or SF_ACT_RELU6 (nn.ReLU6, mobilenetv2_helper.py:30-68); the
+ *   mask is taken from the output y as sf_act_bwd takes it: m = [0 < y], and [0 < y < 6] for ReLU6.
+ *   groups > 1 undoes the channel-shuffled store of sf_conv_fwd_grouped(shuffle = 1) (channel_shuffle behind the
+ *   grouped conv1 of shufflenet_helper.py:22-79): dz channel g * (C / groups) + j reads dy and y at channel
+ *   j * groups + g; scale is indexed by the dz channel.  It requires rep == 1, dres == NULL and C % groups == 0
+ *   (SF_EINVAL otherwise).  A thread owns contiguous dz channels and gathers the strided dy / y; dy and y are read
+ *   once, dz is written once.
+ *   groups == 1 and act in {SF_ACT_NONE, SF_ACT_RELU}: the same kernel and the same bits as sf_epilogue_bwd.
+ * sf_dwconv_dgrad_epi: data gradient of the depthwise conv `d` (as sf_dwconv_dgrad: Ti/Hi/Wi = dx's dims, To/Ho/Wo =
+ * dy's dims, which must be the conv's output dims; cin_pad = the pitch of w_packed [taps][cin_pad]) with the backward of
+ * its folded eval epilogue y = act(scale[c] * z + bias[c]) applied while dy is loaded — the depthwise 3x3x3 + BN + ReLU6
+ * of InvertedResidual (mobilenetv2_helper.py:30-68) and conv2 + bn2 of the ShuffleNet Bottleneck
+ * (shufflenet_helper.py:22-79; no activation, scale only):
+ *   dx[n,ti,hi,wi,c] (=|+=) scale[c] * sum_taps w[tap][c] * dy[pos(tap)] * m(y[pos(tap)]),  taps in (kt, kh, kw) order,
+ *   m as above.  No dL/dz tensor exists: against sf_epilogue_bwd_act followed by sf_dwconv_dgrad one write and one read
+ *   of a tensor the size of the layer's output are saved.  scale NULL means 1; y may be NULL when act is SF_ACT_NONE.
+ *   accumulate == 0 writes every element of the dx slice.  One thread per dx position and 4 channels (float4 form: C,
+ *   pitches, offsets and cin_pad multiples of 4, pointers 16-byte aligned) or per channel (scalar form).
+ * Both follow the rules above (SF_EINVAL before any launch, 64-bit element offsets, one owner, fixed order).        */
+int sf_epilogue_bwd_act(const float* dy, int dy_cs, int dy_coff, const float* y, int y_cs, int y_coff, int N, int T,
+                        int H, int W, int C, int rep, const float* scale, int act, int groups, float* dz, int dz_cs,
+                        int dz_coff, int dz_accumulate, float* dres, int dres_cs, int dres_coff, int dres_accumulate,
+                        void* stream);
+int sf_dwconv_dgrad_epi(const sf_conv_desc* d, const float* dy, int dy_cs, int dy_coff, const float* y, int y_cs,
+                        int y_coff, const float* w_packed, const float* scale, int act, float* dx, int dx_cs,
+                        int dx_coff, int C, int accumulate, void* stream);
 int sf_head_act_mean_bwd(const float* logits, const float* dout, int B, int P, int K, int act, float* dl,
                          int accumulate, void* stream);
 int sf_cam_weights(const float* g, int g_cs, int g_coff, int N, int T, int H, int W, int C, float* w, void* stream);
