@@ -26,6 +26,7 @@ def _act(relu):
 SF_EINVAL, SF_EALIGN, SF_ELAUNCH, SF_ENOTTAKEN = -1, -2, -3, -4
 _ERR = {-1: "SF_EINVAL (inconsistent descriptor)", -2: "SF_EALIGN", -3: "SF_ELAUNCH (hip launch failed)",
         -4: "SF_ENOTTAKEN (shape not served by this specialised entry point)"}
+_REFUSED = (SF_EALIGN, SF_ENOTTAKEN)  # a specialised entry point declined before any launch: take the general one
 
 
 class SfhipError(RuntimeError):
@@ -45,35 +46,138 @@ class PoolDesc(ctypes.Structure):
         "kT", "kH", "kW", "sT", "sH", "sW", "pT", "pH", "pW", "is_avg")]
 
 
-EXPORTS = [
-    "sf_abi_version", "sf_build_arch", "sf_ncthw_to_ndhwc", "sf_ndhwc_to_ncthw", "sf_conv_fwd", "sf_dwconv_fwd",
-    "sf_pool_fwd", "sf_maxpool_fwd_arg", "sf_maxpool_bwd_arg", "sf_tmax_mean_ws_floats", "sf_tmax_mean", "sf_gate_apply", "sf_attn_fwd", "sf_head_act_mean",
-    "sf_copy_channels", "sf_channel_stats_ws_floats", "sf_channel_stats", "sf_affine_fwd", "sf_bn_train_stats",
-    "sf_conv_wgrad_splits", "sf_conv_wgrad", "sf_bn_bwd_ws_floats", "sf_bn_bwd_reduce", "sf_bn_bwd_apply",
-    "sf_attn_bwd", "sf_maxpool_bwd", "sf_tmax_dot", "sf_eca_bwd_apply", "sf_eca_gate_bwd", "sf_bcast_add", "sf_rowdot", "sf_axpy", "sf_act_bwd",
-    "sf_dwconv_dgrad", "sf_dwconv_wgrad_ws_floats", "sf_dwconv_wgrad", "sf_gather_add",
-    "sf_bn_train_stats_split", "sf_affine_fwd_split", "sf_bn_bwd_reduce_split", "sf_bn_bwd_apply_split",
-    "sf_clip_prologue", "sf_conv_wgrad_finish", "sf_bn_bwd_reduce_acc", "sf_row_softmax_fwd", "sf_row_softmax_bwd",
-    "sf_attn_bwd_fused_ws_floats", "sf_attn_bwd_fused", "sf_pack_conv_weight", "sf_conv_fwd_ws_floats",
-    "sf_conv_fwd_ws", "sf_attn_fwd_ws_floats", "sf_attn_fwd_ws", "sf_affine_fwd_mask", "sf_bn_bwd_apply_first", "sf_maxpool_bwd_first",
-    "sf_conv_tune", "sf_conv_stats_ws_floats", "sf_conv_fwd_stats", "sf_bn_train_stats_merge",
-    "sf_attn_products_per_fp32", "sf_pack_conv_weights", "sf_attn_bwd_variant", "sf_attn_tune",
-    "sf_bx_planes_elems", "sf_bx_split", "sf_bx_split_batched", "sf_conv_rows_parts", "sf_conv_pw_ws_floats", "sf_conv_pw_stats_floats", "sf_conv_fwd_pw", "sf_conv_bx_ws_floats", "sf_conv_fwd_bx", "sf_conv_wgrad_bx_splits",
-    "sf_conv_wgrad_bx_ws_floats", "sf_conv_wgrad_bx",
-    "sf_conv_fwd_grouped", "sf_conv_wgrad_grouped_splits", "sf_conv_wgrad_grouped", "sf_channel_shuffle",
-    "sf_dwconv_wgrad_param", "sf_roi_tpool_fwd", "sf_roi_align_max_fwd", "sf_roi_align_max_bwd", "sf_sigmoid_bwd",
-    "sf_xattn_accepts", "sf_xattn_bwd_ws_floats", "sf_xattn_fwd", "sf_xattn_bwd",
-    "sf_assoc_accepts", "sf_gram_splits", "sf_gram_ws_floats", "sf_gram", "sf_rowmat",
-    "sf_clip_prologue_gray", "sf_stem1_accepts", "sf_stem1_fwd", "sf_stem1_wgrad_ws_floats", "sf_stem1_wgrad",
-    "sf_ncthw1_pack", "sf_avgpool_win_fwd", "sf_avgpool_win_bwd",
-    "sf_epilogue_bwd", "sf_head_act_mean_bwd", "sf_cam_weights", "sf_cam_map_ws_floats", "sf_cam_map",
-    "sf_epilogue_bwd_act", "sf_dwconv_dgrad_epi",
-]
-_LONG_RET = ("sf_tmax_mean_ws_floats", "sf_channel_stats_ws_floats", "sf_bn_bwd_ws_floats",
-             "sf_dwconv_wgrad_ws_floats", "sf_attn_bwd_fused_ws_floats", "sf_conv_fwd_ws_floats",
-             "sf_attn_fwd_ws_floats", "sf_conv_stats_ws_floats", "sf_bx_planes_elems", "sf_conv_bx_ws_floats",
-             "sf_conv_wgrad_bx_ws_floats", "sf_xattn_bwd_ws_floats", "sf_gram_ws_floats",
-             "sf_stem1_wgrad_ws_floats", "sf_cam_map_ws_floats")
+# The C ABI as ctypes sees it: symbol -> (restype, [argtypes]), one line per prototype of include/sfhip.h.  The header is
+# the authority — tests/test_cabi_cpu.py compares every line with its prototype, position by position (int -> c_int,
+# long -> c_long, float -> c_float, descriptor pointers -> POINTER(ConvDesc / PoolDesc), int* -> POINTER(c_int), every
+# other pointer -> c_void_p; mean3 / std3 of sf_clip_prologue are HOST arrays and stay POINTER(c_float)).
+_vp, _ci, _cl, _cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
+_CD, _PD, _pi, _pf = ctypes.POINTER(ConvDesc), ctypes.POINTER(PoolDesc), ctypes.POINTER(_ci), ctypes.POINTER(_cf)
+_VIEW = [_vp, _ci, _ci]  # a channel slice: pointer, pitch, offset
+_ATTN_FWD = [_vp, _ci, _vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _ci, _vp, _ci, _ci] + [_ci] * 6 + [_vp, _vp]
+_BN_BWD = _VIEW * 3 + [_ci] * 7 + [_vp] * 5        # dy, y, z views; N T H W C rep relu; mean invstd + three more
+_BN_BWD_SPLIT = _VIEW * 3 + [_ci] * 8 + [_vp] * 5  # ... with nsplit after C
+_BN_APPLY_TAIL = _VIEW * 2 + [_vp]                 # dz view, dres view, stream
+_SIGNATURES = {
+    "sf_abi_version": (_ci, []),
+    "sf_build_arch": (ctypes.c_char_p, []),
+    # layout, input step, one-channel stem
+    "sf_ncthw_to_ndhwc": (_ci, [_vp, _vp] + [_ci] * 9 + [_vp]),
+    "sf_ndhwc_to_ncthw": (_ci, [_vp, _ci, _ci, _vp] + [_ci] * 5 + [_vp]),
+    "sf_clip_prologue": (_ci, [_vp] + [_ci] * 10 + [_pf] * 2 + [_vp, _ci, _vp, _ci, _ci, _ci, _vp]),
+    "sf_clip_prologue_gray": (_ci, [_vp] + [_ci] * 9 + [_cf, _cf, _vp, _ci, _vp, _ci, _ci, _ci, _vp]),
+    "sf_ncthw1_pack": (_ci, [_vp, _vp] + [_ci] * 7 + [_vp]),
+    "sf_stem1_accepts": (_ci, [_ci] * 4),
+    "sf_stem1_fwd": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _ci, _ci, _vp]),
+    "sf_stem1_wgrad_ws_floats": (_cl, [_ci] * 7),
+    "sf_stem1_wgrad": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _vp, _vp]),
+    # dense, grouped and depthwise convs
+    "sf_conv_fwd": (_ci, [_CD] + [_vp] * 7),
+    "sf_conv_fwd_ws_floats": (_cl, [_CD]),
+    "sf_conv_fwd_ws": (_ci, [_CD] + [_vp] * 8),
+    "sf_conv_fwd_grouped": (_ci, [_CD, _ci, _ci] + [_vp] * 7),
+    "sf_conv_stats_ws_floats": (_cl, [_CD]),
+    "sf_conv_fwd_stats": (_ci, [_CD] + [_vp] * 7 + [_pi, _vp]),
+    "sf_conv_tune": (_ci, [_ci, _ci]),
+    "sf_bx_planes_elems": (_cl, [_cl, _ci]),
+    "sf_bx_split": (_ci, [_vp, _ci, _ci, _cl, _ci, _vp, _vp]),
+    "sf_bx_split_batched": (_ci, [_vp, _vp, _ci, _ci, _vp]),
+    "sf_conv_rows_parts": (_ci, [_CD]),
+    "sf_conv_pw_ws_floats": (_cl, [_CD, _ci]),
+    "sf_conv_pw_stats_floats": (_cl, [_CD]),
+    "sf_conv_fwd_pw": (_ci, [_CD] + [_vp] * 9 + [_pi, _vp]),
+    "sf_conv_bx_ws_floats": (_cl, [_CD, _ci, _ci]),
+    "sf_conv_fwd_bx": (_ci, [_CD] + [_vp] * 10),
+    "sf_pack_conv_weight": (_ci, [_vp, _ci, _ci, _ci, _vp, _ci, _vp, _ci, _vp]),
+    "sf_pack_conv_weights": (_ci, [_vp, _vp, _ci, _ci, _vp]),
+    "sf_dwconv_fwd": (_ci, [_CD] + [_vp] * 7),
+    "sf_conv_wgrad_splits": (_ci, [_CD]),
+    "sf_conv_wgrad": (_ci, [_CD, _vp, _vp, _ci, _ci, _vp, _vp]),
+    "sf_conv_wgrad_bx_splits": (_ci, [_CD]),
+    "sf_conv_wgrad_bx_ws_floats": (_cl, [_CD, _ci, _ci]),
+    "sf_conv_wgrad_bx": (_ci, [_CD, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp]),
+    "sf_conv_wgrad_grouped_splits": (_ci, [_CD, _ci]),
+    "sf_conv_wgrad_grouped": (_ci, [_CD, _ci, _vp, _vp, _ci, _ci, _vp, _vp]),
+    "sf_conv_wgrad_finish": (_ci, [_vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _ci, _vp]),
+    "sf_dwconv_dgrad": (_ci, [_CD, _vp, _ci, _ci, _vp, _vp, _ci, _ci, _ci, _vp]),
+    "sf_dwconv_wgrad_ws_floats": (_cl, [_CD, _ci]),
+    "sf_dwconv_wgrad": (_ci, [_CD, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp]),
+    "sf_dwconv_wgrad_param": (_ci, [_CD, _vp, _vp, _ci, _ci, _ci, _vp, _ci, _vp, _vp]),
+    "sf_dwconv_dgrad_epi": (_ci, [_CD] + _VIEW * 2 + [_vp, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _vp]),
+    # pooling
+    "sf_pool_fwd": (_ci, [_PD, _vp, _vp, _vp]),
+    "sf_maxpool_fwd_arg": (_ci, [_PD, _vp, _vp, _vp, _vp]),
+    "sf_maxpool_bwd_arg": (_ci, [_PD, _vp] + _VIEW * 2 + [_ci, _vp]),
+    "sf_maxpool_bwd": (_ci, [_PD, _vp, _vp] + _VIEW * 2 + [_vp]),
+    "sf_maxpool_bwd_first": (_ci, [_PD, _vp, _vp] + _VIEW * 2 + [_vp]),
+    "sf_avgpool_win_fwd": (_ci, [_PD, _vp, _vp, _vp]),
+    "sf_avgpool_win_bwd": (_ci, [_PD] + _VIEW * 2 + [_ci, _vp]),
+    # CMDA edges: ECA gate, SpatialAttention
+    "sf_tmax_mean_ws_floats": (_cl, [_ci, _ci]),
+    "sf_tmax_mean": (_ci, _VIEW + [_ci] * 6 + [_vp, _vp, _vp]),
+    "sf_gate_apply": (_ci, _VIEW + [_ci] * 6 + [_vp, _vp, _vp, _vp, _ci] + _VIEW + [_vp]),
+    "sf_tmax_dot": (_ci, _VIEW + [_ci] * 6 + _VIEW + [_vp, _vp, _vp]),
+    "sf_eca_bwd_apply": (_ci, _VIEW + [_ci] * 6 + _VIEW + [_vp, _vp] + _VIEW + [_vp]),
+    "sf_eca_gate_bwd": (_ci, [_vp, _vp, _vp, _ci, _ci, _cf, _vp, _vp, _vp, _vp]),
+    "sf_attn_fwd": (_ci, _ATTN_FWD + [_vp]),
+    "sf_attn_fwd_ws_floats": (_cl, [_ci] * 3),
+    "sf_attn_products_per_fp32": (_ci, [_ci]),
+    "sf_attn_fwd_ws": (_ci, _ATTN_FWD + [_vp, _vp]),
+    "sf_attn_bwd": (_ci, [_vp, _ci] * 4 + [_vp, _vp, _vp] + [_vp, _ci] * 3 + [_ci] * 4 + [_vp]),
+    "sf_attn_bwd_fused_ws_floats": (_cl, [_ci] * 3),
+    "sf_attn_bwd_fused": (_ci, [_vp, _ci] * 4 + [_vp, _vp, _vp] + [_vp, _ci] * 3 + [_ci] * 3 + [_vp, _vp]),
+    "sf_attn_bwd_variant": (_ci, [_ci] * 3),
+    "sf_attn_tune": (_ci, [_ci, _ci]),
+    # streaming cross-length and associative attention
+    "sf_xattn_accepts": (_ci, [_cl, _cl, _ci, _ci]),
+    "sf_xattn_bwd_ws_floats": (_cl, [_ci, _cl, _cl, _ci, _ci]),
+    "sf_xattn_fwd": (_ci, [_vp, _ci] * 4 + [_vp, _ci, _cl, _cl, _ci, _ci, _cf, _vp]),
+    "sf_xattn_bwd": (_ci, [_vp, _ci] * 4 + [_vp, _vp] + [_vp, _ci] * 3 + [_ci, _ci, _cl, _cl, _ci, _ci, _cf, _vp, _vp]),
+    "sf_assoc_accepts": (_ci, [_cl, _cl, _ci, _ci]),
+    "sf_gram_splits": (_ci, [_ci, _cl, _ci, _ci]),
+    "sf_gram_ws_floats": (_cl, [_ci, _cl, _ci, _ci]),
+    "sf_gram": (_ci, [_vp, _ci, _vp, _ci, _vp, _vp, _ci, _cl, _ci, _ci, _cf, _vp, _vp]),
+    "sf_rowmat": (_ci, [_vp, _ci, _vp, _vp, _ci, _ci, _cl, _ci, _ci, _cf, _ci, _vp]),
+    # BatchNorm forward / backward, affine
+    "sf_channel_stats_ws_floats": (_cl, [_ci]),
+    "sf_channel_stats": (_ci, _VIEW + [_cl, _ci, _vp, _vp, _vp, _vp]),
+    "sf_bn_train_stats": (_ci, _VIEW + [_cl, _ci, _vp, _vp, _cf, _cf] + [_vp] * 9),
+    "sf_bn_train_stats_split": (_ci, _VIEW + [_ci, _cl, _ci, _ci, _vp, _vp, _cf, _cf] + [_vp] * 9),
+    "sf_bn_train_stats_merge": (_ci, [_vp, _ci, _ci, _vp, _vp, _cf, _cf] + [_vp] * 8),
+    "sf_affine_fwd": (_ci, _VIEW + [_ci] * 5 + [_vp, _vp] + _VIEW + [_ci, _ci] + _VIEW + [_ci, _vp]),
+    "sf_affine_fwd_split": (_ci, _VIEW + [_ci] * 6 + [_vp, _vp] + _VIEW + [_ci, _ci] + _VIEW + [_ci, _vp]),
+    "sf_affine_fwd_mask": (_ci, _VIEW + [_ci] * 5 + [_vp, _vp] + _VIEW + [_ci] + _VIEW + [_vp, _vp]),
+    "sf_bn_bwd_ws_floats": (_cl, [_ci]),
+    "sf_bn_bwd_reduce": (_ci, _BN_BWD + [_vp]),
+    "sf_bn_bwd_reduce_acc": (_ci, _BN_BWD + [_vp, _vp, _vp]),
+    "sf_bn_bwd_reduce_split": (_ci, _BN_BWD_SPLIT + [_vp]),
+    "sf_bn_bwd_apply": (_ci, _BN_BWD + _BN_APPLY_TAIL),
+    "sf_bn_bwd_apply_first": (_ci, _BN_BWD + _BN_APPLY_TAIL),
+    "sf_bn_bwd_apply_split": (_ci, _BN_BWD_SPLIT + _BN_APPLY_TAIL),
+    # elementwise helpers, head, nonlocal softmax
+    "sf_head_act_mean": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _vp]),
+    "sf_head_act_mean_bwd": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _vp, _ci, _vp]),
+    "sf_copy_channels": (_ci, _VIEW * 2 + [_ci, _cl, _ci, _vp]),
+    "sf_channel_shuffle": (_ci, _VIEW * 2 + [_ci, _cl, _ci, _ci, _vp]),
+    "sf_gather_add": (_ci, _VIEW + [_ci] + _VIEW + [_cl, _ci, _ci, _vp]),
+    "sf_bcast_add": (_ci, _VIEW + [_ci, _cl, _ci, _vp, _cf, _vp]),
+    "sf_rowdot": (_ci, _VIEW * 2 + [_cl, _ci, _cf, _vp, _vp]),
+    "sf_axpy": (_ci, _VIEW + [_cf] + _VIEW + [_cl, _ci, _ci, _vp]),
+    "sf_act_bwd": (_ci, _VIEW * 2 + [_ci] + _VIEW + [_cl, _ci, _ci, _vp]),
+    "sf_sigmoid_bwd": (_ci, [_vp, _vp, _vp, _cl, _ci, _vp]),
+    "sf_row_softmax_fwd": (_ci, _VIEW + [_cl, _ci, _cf, _vp]),
+    "sf_row_softmax_bwd": (_ci, _VIEW * 2 + [_cl, _ci, _cf, _vp]),
+    # RoI head
+    "sf_roi_tpool_fwd": (_ci, _VIEW + [_ci] * 5 + [_vp, _vp]),
+    "sf_roi_align_max_fwd": (_ci, [_vp] + [_ci] * 4 + [_vp, _ci, _ci, _cf, _ci] + _VIEW + [_vp, _vp]),
+    "sf_roi_align_max_bwd": (_ci, _VIEW + [_vp, _vp] + [_ci] * 7 + [_cf, _ci] + _VIEW + [_ci, _vp]),
+    # Grad-CAM
+    "sf_epilogue_bwd": (_ci, _VIEW * 2 + [_ci] * 6 + [_vp, _ci] + _VIEW + [_ci] + _VIEW + [_ci, _vp]),
+    "sf_epilogue_bwd_act": (_ci, _VIEW * 2 + [_ci] * 6 + [_vp, _ci, _ci] + _VIEW + [_ci] + _VIEW + [_ci, _vp]),
+    "sf_cam_weights": (_ci, _VIEW + [_ci] * 5 + [_vp, _vp]),
+    "sf_cam_map_ws_floats": (_cl, [_ci] * 4),
+    "sf_cam_map": (_ci, _VIEW + [_vp] + [_ci] * 5 + [_vp, _vp, _vp, _vp]),
+}
+EXPORTS = list(_SIGNATURES)
 
 
 def lib_path():
@@ -81,7 +185,8 @@ def lib_path():
 
 
 def lib():
-    """Load libsfhip.so (built by `make -C efficient-slowfast_amd/csrc` / __graft_entry__.build())."""
+    """Load libsfhip.so (built by `make -C efficient-slowfast_amd/csrc` / __graft_entry__.build()) and hand ctypes the
+    signature of every entry point."""
     global _lib
     if _lib is None:
         if not os.path.exists(_LIB_PATH):
@@ -89,142 +194,13 @@ def lib():
                 "libsfhip.so not found at %s — build it with `make -C efficient-slowfast_amd/csrc` "
                 "(there is no CPU fallback for the SlowFast hot path)" % _LIB_PATH)
         L = ctypes.CDLL(_LIB_PATH)
-        vp, ci, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_long
-        L.sf_abi_version.restype = ci
-        L.sf_build_arch.restype = ctypes.c_char_p
-        L.sf_ncthw_to_ndhwc.argtypes = [vp, vp] + [ci] * 9 + [vp]
-        L.sf_ndhwc_to_ncthw.argtypes = [vp, ci, ci, vp] + [ci] * 5 + [vp]
-        L.sf_conv_fwd.argtypes = [ctypes.POINTER(ConvDesc)] + [vp] * 7
-        L.sf_dwconv_fwd.argtypes = [ctypes.POINTER(ConvDesc)] + [vp] * 7
-        L.sf_pool_fwd.argtypes = [ctypes.POINTER(PoolDesc), vp, vp, vp]
-        L.sf_maxpool_fwd_arg.argtypes = [ctypes.POINTER(PoolDesc), vp, vp, vp, vp]
-        L.sf_maxpool_bwd_arg.argtypes = [ctypes.POINTER(PoolDesc), vp, vp, ci, ci, vp, ci, ci, ci, vp]
-        L.sf_tmax_mean_ws_floats.argtypes = [ci, ci]
-        L.sf_tmax_mean_ws_floats.restype = cl
-        L.sf_tmax_mean.argtypes = [vp, ci, ci] + [ci] * 6 + [vp, vp, vp]
-        L.sf_gate_apply.argtypes = [vp, ci, ci] + [ci] * 6 + [vp, vp, vp, vp, ci, vp, ci, ci, vp]
-        L.sf_attn_fwd.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, ci] + [ci] * 6 + [vp, vp, vp]
-        L.sf_affine_fwd_mask.argtypes = [vp, ci, ci] + [ci] * 5 + [vp, vp, vp, ci, ci, ci, vp, ci, ci, vp, vp]
-        L.sf_attn_fwd_ws_floats.argtypes = [ci, ci, ci]
-        L.sf_attn_fwd_ws_floats.restype = cl
-        L.sf_attn_fwd_ws.argtypes = L.sf_attn_fwd.argtypes[:-1] + [vp, vp]
-        L.sf_attn_bwd.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, ci, vp, ci, vp, ci, ci, ci, ci, ci, vp]
-        L.sf_head_act_mean.argtypes = [vp, ci, ci, ci, ci, vp, vp]
-        L.sf_copy_channels.argtypes = [vp, ci, ci, vp, ci, ci, ci, cl, ci, vp]
-        L.sf_channel_shuffle.argtypes = [vp, ci, ci, vp, ci, ci, ci, cl, ci, ci, vp]
-        L.sf_channel_stats_ws_floats.argtypes = [ci]
-        L.sf_channel_stats_ws_floats.restype = cl
-        L.sf_channel_stats.argtypes = [vp, ci, ci, cl, ci, vp, vp, vp, vp]
-        L.sf_bn_train_stats.argtypes = [vp, ci, ci, cl, ci, vp, vp, ctypes.c_float, ctypes.c_float] + [vp] * 9
-        L.sf_affine_fwd.argtypes = [vp, ci, ci] + [ci] * 5 + [vp, vp, vp, ci, ci, ci, ci, vp, ci, ci, ci, vp]
-        cf = ctypes.c_float
-        L.sf_conv_wgrad_splits.argtypes = [ctypes.POINTER(ConvDesc)]
-        L.sf_conv_wgrad.argtypes = [ctypes.POINTER(ConvDesc), vp, vp, ci, ci, vp, vp]
-        L.sf_conv_fwd_grouped.argtypes = [ctypes.POINTER(ConvDesc), ci, ci] + [vp] * 7
-        L.sf_conv_wgrad_grouped_splits.argtypes = [ctypes.POINTER(ConvDesc), ci]
-        L.sf_conv_wgrad_grouped.argtypes = [ctypes.POINTER(ConvDesc), ci, vp, vp, ci, ci, vp, vp]
-        L.sf_bn_bwd_ws_floats.argtypes = [ci]
-        L.sf_bn_bwd_ws_floats.restype = cl
-        L.sf_bn_bwd_reduce.argtypes = [vp, ci, ci, vp, ci, ci, vp, ci, ci] + [ci] * 7 + [vp] * 5 + [vp]
-        L.sf_bn_bwd_apply.argtypes = ([vp, ci, ci, vp, ci, ci, vp, ci, ci] + [ci] * 7 + [vp] * 5 +
-                                      [vp, ci, ci, vp, ci, ci, vp])
-        L.sf_bn_bwd_apply_first.argtypes = L.sf_bn_bwd_apply.argtypes
-        L.sf_maxpool_bwd_first.argtypes = [ctypes.POINTER(PoolDesc), vp, vp, vp, ci, ci, vp, ci, ci, vp]
-        L.sf_maxpool_bwd.argtypes = [ctypes.POINTER(PoolDesc), vp, vp, vp, ci, ci, vp, ci, ci, vp]
-        L.sf_tmax_dot.argtypes = [vp, ci, ci] + [ci] * 6 + [vp, ci, ci, vp, vp, vp]
-        L.sf_eca_bwd_apply.argtypes = [vp, ci, ci] + [ci] * 6 + [vp, ci, ci, vp, vp, vp, ci, ci, vp]
-        L.sf_eca_gate_bwd.argtypes = [vp, vp, vp, ci, ci, cf, vp, vp, vp, vp]
-        L.sf_bcast_add.argtypes = [vp, ci, ci, ci, cl, ci, vp, cf, vp]
-        L.sf_rowdot.argtypes = [vp, ci, ci, vp, ci, ci, cl, ci, cf, vp, vp]
-        L.sf_axpy.argtypes = [vp, ci, ci, cf, vp, ci, ci, cl, ci, ci, vp]
-        L.sf_act_bwd.argtypes = [vp, ci, ci, vp, ci, ci, ci, vp, ci, ci, cl, ci, ci, vp]
-        L.sf_dwconv_dgrad.argtypes = [ctypes.POINTER(ConvDesc), vp, ci, ci, vp, vp, ci, ci, ci, vp]
-        L.sf_dwconv_wgrad_ws_floats.argtypes = [ctypes.POINTER(ConvDesc), ci]
-        L.sf_dwconv_wgrad_ws_floats.restype = cl
-        L.sf_dwconv_wgrad.argtypes = [ctypes.POINTER(ConvDesc), vp, vp, ci, ci, ci, vp, vp, vp]
-        L.sf_dwconv_wgrad_param.argtypes = [ctypes.POINTER(ConvDesc), vp, vp, ci, ci, ci, vp, ci, vp, vp]
-        L.sf_gather_add.argtypes = [vp, ci, ci, ci, vp, ci, ci, cl, ci, ci, vp]
-        L.sf_clip_prologue.argtypes = [vp] + [ci] * 10 + [ctypes.POINTER(ctypes.c_float)] * 2 + [vp, ci, vp, ci, ci, ci, vp]
-        L.sf_attn_bwd_fused_ws_floats.argtypes = [ci, ci, ci]
-        L.sf_attn_bwd_fused_ws_floats.restype = cl
-        L.sf_attn_bwd_fused.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, ci, vp, ci, vp, ci, ci, ci, ci,
-                                        vp, vp]
-        L.sf_conv_fwd_ws_floats.argtypes = [ctypes.POINTER(ConvDesc)]
-        L.sf_conv_fwd_ws_floats.restype = cl
-        L.sf_conv_stats_ws_floats.argtypes = [ctypes.POINTER(ConvDesc)]
-        L.sf_conv_stats_ws_floats.restype = cl
-        L.sf_conv_fwd_stats.argtypes = [ctypes.POINTER(ConvDesc)] + [vp] * 7 + [ctypes.POINTER(ctypes.c_int), vp]
-        L.sf_bn_train_stats_merge.argtypes = [vp, ci, ci, vp, vp, ctypes.c_float, ctypes.c_float] + [vp] * 8
-        L.sf_conv_fwd_ws.argtypes = [ctypes.POINTER(ConvDesc)] + [vp] * 8
-        L.sf_pack_conv_weight.argtypes = [vp, ci, ci, ci, vp, ci, vp, ci, vp]
-        L.sf_conv_tune.argtypes = [ci, ci]
-        L.sf_attn_tune.argtypes = [ci, ci]
-        L.sf_bx_planes_elems.argtypes = [cl, ci]
-        L.sf_bx_planes_elems.restype = cl
-        L.sf_bx_split.argtypes = [vp, ci, ci, cl, ci, vp, vp]
-        L.sf_bx_split_batched.argtypes = [vp, vp, ci, ci, vp]
-        L.sf_conv_pw_ws_floats.argtypes = [ctypes.POINTER(ConvDesc), ci]
-        L.sf_conv_pw_ws_floats.restype = cl
-        L.sf_conv_rows_parts.argtypes = [ctypes.POINTER(ConvDesc)]
-        L.sf_conv_pw_stats_floats.argtypes = [ctypes.POINTER(ConvDesc)]
-        L.sf_conv_pw_stats_floats.restype = cl
-        L.sf_conv_fwd_pw.argtypes = [ctypes.POINTER(ConvDesc)] + [vp] * 9 + [ctypes.POINTER(ctypes.c_int), vp]
-        L.sf_conv_bx_ws_floats.argtypes = [ctypes.POINTER(ConvDesc), ci, ci]
-        L.sf_conv_bx_ws_floats.restype = cl
-        L.sf_conv_fwd_bx.argtypes = [ctypes.POINTER(ConvDesc)] + [vp] * 10
-        L.sf_conv_wgrad_bx_splits.argtypes = [ctypes.POINTER(ConvDesc)]
-        L.sf_conv_wgrad_bx_ws_floats.argtypes = [ctypes.POINTER(ConvDesc), ci, ci]
-        L.sf_conv_wgrad_bx_ws_floats.restype = cl
-        L.sf_conv_wgrad_bx.argtypes = [ctypes.POINTER(ConvDesc), vp, vp, vp, ci, ci, vp, vp, vp, vp]
-        L.sf_attn_bwd_variant.argtypes = [ci, ci, ci]
-        L.sf_row_softmax_fwd.argtypes = [vp, ci, ci, cl, ci, cf, vp]
-        L.sf_row_softmax_bwd.argtypes = [vp, ci, ci, vp, ci, ci, cl, ci, cf, vp]
-        L.sf_conv_wgrad_finish.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, ci, vp]
-        L.sf_bn_bwd_reduce_acc.argtypes = [vp, ci, ci, vp, ci, ci, vp, ci, ci] + [ci] * 7 + [vp] * 5 + [vp, vp, vp]
-        L.sf_bn_train_stats_split.argtypes = [vp, ci, ci, ci, cl, ci, ci, vp, vp, cf, cf] + [vp] * 9
-        L.sf_affine_fwd_split.argtypes = [vp, ci, ci] + [ci] * 6 + [vp, vp, vp, ci, ci, ci, ci, vp, ci, ci, ci, vp]
-        L.sf_bn_bwd_reduce_split.argtypes = [vp, ci, ci, vp, ci, ci, vp, ci, ci] + [ci] * 8 + [vp] * 5 + [vp]
-        L.sf_bn_bwd_apply_split.argtypes = ([vp, ci, ci, vp, ci, ci, vp, ci, ci] + [ci] * 8 + [vp] * 5 +
-                                            [vp, ci, ci, vp, ci, ci, vp])
-        L.sf_roi_tpool_fwd.argtypes = [vp, ci, ci] + [ci] * 5 + [vp, vp]
-        L.sf_roi_align_max_fwd.argtypes = [vp] + [ci] * 4 + [vp, ci, ci, cf, ci, vp, ci, ci, vp, vp]
-        L.sf_roi_align_max_bwd.argtypes = [vp, ci, ci, vp, vp] + [ci] * 7 + [cf, ci, vp, ci, ci, ci, vp]
-        L.sf_sigmoid_bwd.argtypes = [vp, vp, vp, cl, ci, vp]
-        L.sf_xattn_accepts.argtypes = [cl, cl, ci, ci]
-        L.sf_xattn_bwd_ws_floats.argtypes = [ci, cl, cl, ci, ci]
-        L.sf_xattn_bwd_ws_floats.restype = cl
-        L.sf_xattn_fwd.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, cl, cl, ci, ci, cf, vp]
-        L.sf_xattn_bwd.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, vp, ci, ci, ci, cl, cl, ci,
-                                   ci, cf, vp, vp]
-        L.sf_assoc_accepts.argtypes = [cl, cl, ci, ci]
-        L.sf_gram_splits.argtypes = [ci, cl, ci, ci]
-        L.sf_gram_ws_floats.argtypes = [ci, cl, ci, ci]
-        L.sf_gram_ws_floats.restype = cl
-        L.sf_gram.argtypes = [vp, ci, vp, ci, vp, vp, ci, cl, ci, ci, cf, vp, vp]
-        L.sf_rowmat.argtypes = [vp, ci, vp, vp, ci, ci, cl, ci, ci, cf, ci, vp]
-        L.sf_clip_prologue_gray.argtypes = [vp] + [ci] * 9 + [cf, cf, vp, ci, vp, ci, ci, ci, vp]
-        L.sf_stem1_accepts.argtypes = [ci] * 4
-        L.sf_stem1_fwd.argtypes = [vp, ci, ci, ci, ci, vp, ci, ci, ci, vp, vp, ci, vp, ci, ci, vp]
-        L.sf_stem1_wgrad_ws_floats.argtypes = [ci] * 7
-        L.sf_stem1_wgrad_ws_floats.restype = cl
-        L.sf_stem1_wgrad.argtypes = [vp, ci, ci, ci, ci, vp, ci, ci, ci, ci, ci, vp, ci, vp, vp]
-        L.sf_ncthw1_pack.argtypes = [vp, vp] + [ci] * 7 + [vp]
-        L.sf_avgpool_win_fwd.argtypes = [ctypes.POINTER(PoolDesc), vp, vp, vp]
-        L.sf_avgpool_win_bwd.argtypes = [ctypes.POINTER(PoolDesc), vp, ci, ci, vp, ci, ci, ci, vp]
-        L.sf_epilogue_bwd.argtypes = [vp, ci, ci, vp, ci, ci] + [ci] * 6 + [vp, ci, vp, ci, ci, ci, vp, ci, ci, ci, vp]
-        L.sf_epilogue_bwd_act.argtypes = ([vp, ci, ci, vp, ci, ci] + [ci] * 6 +
-                                          [vp, ci, ci, vp, ci, ci, ci, vp, ci, ci, ci, vp])
-        L.sf_dwconv_dgrad_epi.argtypes = [ctypes.POINTER(ConvDesc), vp, ci, ci, vp, ci, ci, vp, vp, ci, vp, ci, ci, ci,
-                                          ci, vp]
-        L.sf_head_act_mean_bwd.argtypes = [vp, vp, ci, ci, ci, ci, vp, ci, vp]
-        L.sf_cam_weights.argtypes = [vp, ci, ci] + [ci] * 5 + [vp, vp]
-        L.sf_cam_map_ws_floats.argtypes = [ci] * 4
-        L.sf_cam_map_ws_floats.restype = cl
-        L.sf_cam_map.argtypes = [vp, ci, ci, vp] + [ci] * 5 + [vp, vp, vp, vp]
-        for name in EXPORTS:
-            fn = getattr(L, name)
-            if name != "sf_build_arch" and name not in _LONG_RET:
-                fn.restype = ci
+        for name, (restype, argtypes) in _SIGNATURES.items():
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                raise SfhipError("%s does not export %s — rebuild it with `make -C efficient-slowfast_amd/csrc`" % (
+                    _LIB_PATH, name))
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -247,6 +223,10 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _slice_base(a):  # slice base pointer: buffer pointer + channel offset
+    return ctypes.c_void_p(a.buf.data_ptr() + 4 * a.coff)
+
+
 EVENT_TRACE = None  # bench.py sets this to a list: (tag, start_event, end_event) per traced launch
 
 
@@ -260,6 +240,19 @@ def _traced(tag, fn):
     rc = fn()
     e1.record()
     EVENT_TRACE.append((tag, e0, e1))
+    return rc
+
+
+def _call(name, *args, tag=None, what=None, allow=()):
+    """One stream-taking entry point: `name`(*args, the current stream), under _traced when `tag` is given.  A code other
+    than 0 raises SfhipError labelled `what` (default: the symbol) unless it is in `allow`; the code is returned."""
+    fn = getattr(lib(), name)
+    if tag is None:
+        rc = fn(*args, _stream())
+    else:
+        rc = _traced(tag, lambda: fn(*args, _stream()))
+    if rc not in allow:
+        _check(rc, what or name)
     return rc
 
 
@@ -324,7 +317,7 @@ def from_ncthw(x, cpad=None, ph=0, pw=0, wp=None):
     cpad = C if cpad is None else cpad
     wp = W + 2 * pw if wp is None else wp
     buf = torch.empty((N, T, H + 2 * ph, wp, cpad), dtype=torch.float32, device=x.device)
-    _check(lib().sf_ncthw_to_ndhwc(_ptr(x), _ptr(buf), N, C, T, H, W, cpad, ph, pw, wp, _stream()), "sf_ncthw_to_ndhwc")
+    _call("sf_ncthw_to_ndhwc", _ptr(x), _ptr(buf), N, C, T, H, W, cpad, ph, pw, wp)
     return Act(buf, 0, cpad)
 
 
@@ -366,20 +359,16 @@ def clip_prologue(clip_u8, dst, new_hw, yx, crop, flip, mean, std, frame_idx=Non
     T, H, W = clip_u8.shape[:3]
     n = dst.shape[0]
     assert dst.shape[1] == crop + 2 * ph
+    head = (_ptr(clip_u8), T, H, W, int(new_hw[0]), int(new_hw[1]), int(yx[0]), int(yx[1]), int(crop), 1 if flip else 0)
+    tail = (_ptr(frame_idx), n, _ptr(dst), ph, pw, dst.shape[2])
     if gray:
         assert len(mean) == 1 and len(std) == 1, "a one-channel clip takes a one-element mean / std"
         assert not reverse, "DATA.REVERSE_INPUT_CHANNEL has no meaning for a one-channel clip"
-        _check(lib().sf_clip_prologue_gray(_ptr(clip_u8), T, H, W, int(new_hw[0]), int(new_hw[1]), int(yx[0]),
-                                           int(yx[1]), int(crop), 1 if flip else 0, float(mean[0]), float(std[0]),
-                                           _ptr(frame_idx) if frame_idx is not None else None, n, _ptr(dst), ph, pw,
-                                           dst.shape[2], _stream()), "sf_clip_prologue_gray")
+        _call("sf_clip_prologue_gray", *head, float(mean[0]), float(std[0]), *tail)
         return dst
     m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
     s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
-    _check(lib().sf_clip_prologue(_ptr(clip_u8), T, H, W, int(new_hw[0]), int(new_hw[1]), int(yx[0]), int(yx[1]),
-                                  int(crop), 1 if flip else 0, 1 if reverse else 0, m3, s3,
-                                  _ptr(frame_idx) if frame_idx is not None else None, n, _ptr(dst), ph, pw,
-                                  dst.shape[2], _stream()), "sf_clip_prologue")
+    _call("sf_clip_prologue", *head, 1 if reverse else 0, m3, s3, *tail)
     return dst
 
 
@@ -391,7 +380,7 @@ def ncthw1_pack(x, ph, pw, wp):
     N, C, T, H, W = x.shape
     assert C == 1
     buf = torch.empty((N, T, H + 2 * ph, wp, 1), dtype=torch.float32, device=x.device)
-    _check(lib().sf_ncthw1_pack(_ptr(x), _ptr(buf), N, T, H, W, ph, pw, wp, _stream()), "sf_ncthw1_pack")
+    _call("sf_ncthw1_pack", _ptr(x), _ptr(buf), N, T, H, W, ph, pw, wp)
     return buf
 
 
@@ -420,9 +409,8 @@ def stem1_fwd(buf, w, pT, scale=None, bias=None, relu=False, out=None, out_reser
     assert (out.N, out.T, out.H, out.W, out.C) == (N, To, Ho, Wo, cout), (out, (N, To, Ho, Wo, cout))
     for v in (scale, bias):
         assert v is None or (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.numel() == cout)
-    _check(_traced("stem1_fwd", lambda: lib().sf_stem1_fwd(
-        _ptr(buf), N, T, Hp, Wp, _ptr(w), cout, kT, int(pT), _ptr(scale), _ptr(bias), _act(relu), out.ptr(), out.cs,
-        out.coff, _stream())), "sf_stem1_fwd")
+    _call("sf_stem1_fwd", _ptr(buf), N, T, Hp, Wp, _ptr(w), cout, kT, int(pT), _ptr(scale), _ptr(bias), _act(relu),
+          out.ptr(), out.cs, out.coff, tag="stem1_fwd")
     return out
 
 
@@ -442,16 +430,14 @@ def stem1_wgrad(buf, dz, kT, pT, into=None):
         assert into.is_cuda and into.dtype == torch.float32 and into.is_contiguous() and \
             into.numel() == cout * kT * 49
     dw = into if into is not None else torch.empty((cout, 1, kT, 7, 7), dtype=torch.float32, device=buf.device)
-    _check(_traced("stem1_wgrad", lambda: lib().sf_stem1_wgrad(
-        _ptr(buf), N, T, Hp, Wp, dz.ptr(), dz.cs, dz.coff, cout, int(kT), int(pT), _ptr(dw),
-        1 if into is not None else 0, _ptr(ws), _stream())), "sf_stem1_wgrad")
+    _call("sf_stem1_wgrad", _ptr(buf), N, T, Hp, Wp, dz.ptr(), dz.cs, dz.coff, cout, int(kT), int(pT), _ptr(dw),
+          1 if into is not None else 0, _ptr(ws), tag="stem1_wgrad")
     return dw
 
 
 def to_ncthw(a):
     out = torch.empty(a.shape_ncthw, dtype=torch.float32, device=a.buf.device)
-    _check(lib().sf_ndhwc_to_ncthw(a.ptr(), a.cs, a.coff, _ptr(out), a.N, a.C, a.T, a.H, a.W, _stream()),
-           "sf_ndhwc_to_ncthw")
+    _call("sf_ndhwc_to_ncthw", a.ptr(), a.cs, a.coff, _ptr(out), a.N, a.C, a.T, a.H, a.W)
     return out
 
 
@@ -460,11 +446,35 @@ def _out_dim(i, k, s, p, d):
     return (i + 2 * p - d * (k - 1) - 1) // s + 1
 
 
+def _out_thw(x, kernel, stride, padding, dilation=(1, 1, 1)):
+    """(To, Ho, Wo) of a conv / pool window over the view x."""
+    return tuple(_out_dim(i, k, s, p, d) for i, k, s, p, d in zip((x.T, x.H, x.W), kernel, stride, padding, dilation))
+
+
+def _pad16(c):
+    """Channel count rounded up to the packed weights' multiple of 16."""
+    return (c + 15) // 16 * 16
+
+
+def _conv_desc(x, out_thw, out_cs, out_coff, cout, kernel, stride, padding, dilation=(1, 1, 1), *, cin_pad, cin=None,
+               act=ACT_NONE, res=None, out_cmul=1, transposed=0, scatter=()):
+    """sf_conv_desc, filled in the header's field order — the one place that is done.  x: the input view (dL/dz for a
+    data gradient); out_thw / out_cs / out_coff / cout: the output (pitch and offset 0 for the weight gradients, which
+    have none); cin: channels read per tap (default x.C); res: the residual view, whose pitch / offset the descriptor
+    carries (None: 0, 0); scatter: (os_T, os_H, os_W, oo_T, oo_H, oo_W, ob_T, ob_H, ob_W) of one residue class of a
+    strided data gradient (empty: a dense store)."""
+    kT, kH, kW = kernel
+    return ConvDesc(x.N, x.T, x.H, x.W, x.C if cin is None else cin, x.cs, x.coff, out_thw[0], out_thw[1], out_thw[2],
+                    cout, out_cs, out_coff, out_cmul, kT, kH, kW, stride[0], stride[1], stride[2],
+                    padding[0], padding[1], padding[2], dilation[0], dilation[1], dilation[2], cin_pad, act,
+                    res.cs if res is not None else 0, res.coff if res is not None else 0, transposed, *scatter)
+
+
 def pack_conv_weight(w, cin_pad=None):
     """[Cout, Cin, kT, kH, kW] -> [Cout, kT*kH*kW, cin_pad] (zero padded), contiguous."""
     cout, cin = w.shape[0], w.shape[1]
     taps = w.shape[2] * w.shape[3] * w.shape[4]
-    cin_pad = (cin + 15) // 16 * 16 if cin_pad is None else cin_pad
+    cin_pad = _pad16(cin) if cin_pad is None else cin_pad
     wp = torch.zeros((cout, taps, cin_pad), dtype=torch.float32, device=w.device)
     wp[:, :, :cin] = w.detach().reshape(cout, cin, taps).permute(0, 2, 1)
     return wp.contiguous()
@@ -473,7 +483,7 @@ def pack_conv_weight(w, cin_pad=None):
 def bx_planes(t, rows, C, cs=None, coff=0):
     """The bf16 piece planes [3][rows + 1][C] (uint16 tensor) of a [rows][cs] fp32 operand: sf_bx_split."""
     planes = torch.empty((lib().sf_bx_planes_elems(rows, C),), dtype=torch.int16, device=t.device)
-    _check(lib().sf_bx_split(_ptr(t), C if cs is None else cs, coff, rows, C, _ptr(planes), _stream()), "sf_bx_split")
+    _call("sf_bx_split", _ptr(t), C if cs is None else cs, coff, rows, C, _ptr(planes))
     return planes
 
 
@@ -487,8 +497,8 @@ def _weight_planes(wp):
         if pl is None:
             pl = bx_planes(wp, wp.shape[0], wp.shape[1] * wp.shape[2])
         else:  # same storage: pack_conv_weight_pairs' device-side tables keep pointing at it
-            _check(lib().sf_bx_split(_ptr(wp), wp.shape[1] * wp.shape[2], 0, wp.shape[0], wp.shape[1] * wp.shape[2],
-                                     _ptr(pl), _stream()), "sf_bx_split")
+            _call("sf_bx_split", _ptr(wp), wp.shape[1] * wp.shape[2], 0, wp.shape[0], wp.shape[1] * wp.shape[2],
+                  _ptr(pl))
         wp.__dict__["_sf_bx"] = pl
         wp.__dict__["_sf_bx_ver"] = wp._version
     return pl
@@ -510,29 +520,25 @@ def _conv_launch(d, x_ptr, w_ptr, scale, bias, res_ptr, out_ptr, device, what, w
         if n > 0:  # pointwise layers: activations split in registers, only the weight's planes are kept
             planes = _weight_planes(w_tensor)
             ws = torch.empty((n,), dtype=torch.float32, device=device)
-            rc = _traced(tag, lambda: lib().sf_conv_fwd_pw(ctypes.byref(d), x_ptr, w_ptr, _ptr(planes), scale, bias,
-                                                           res_ptr, out_ptr, _ptr(ws), None, None, _stream()))
-            if rc not in (SF_EALIGN, SF_ENOTTAKEN):  # those two: refused before any launch -> the f32 kernels below
-                _check(rc, what)      # (SF_EINVAL — a genuinely inconsistent descriptor or a null pointer — raises)
+            # _REFUSED: declined before any launch -> the f32 kernels below (SF_EINVAL — a genuinely inconsistent
+            # descriptor or a null pointer — raises)
+            if _call("sf_conv_fwd_pw", ctypes.byref(d), x_ptr, w_ptr, _ptr(planes), scale, bias, res_ptr, out_ptr,
+                     _ptr(ws), None, None, tag=tag, what=what, allow=_REFUSED) == 0:
                 return
         n = lib().sf_conv_bx_ws_floats(ctypes.byref(d), 1 if in_planes is not None else 0, 1)
         if n > 0:
             planes = _weight_planes(w_tensor)
             ws = torch.empty((n,), dtype=torch.float32, device=device)
-            rc = _traced(tag, lambda: lib().sf_conv_fwd_bx(ctypes.byref(d), x_ptr, _ptr(in_planes), w_ptr,
-                                                           _ptr(planes), scale, bias, res_ptr, out_ptr, _ptr(ws),
-                                                           _stream()))
-            if rc not in (SF_EALIGN, SF_ENOTTAKEN):
-                _check(rc, what)
+            if _call("sf_conv_fwd_bx", ctypes.byref(d), x_ptr, _ptr(in_planes), w_ptr, _ptr(planes), scale, bias,
+                     res_ptr, out_ptr, _ptr(ws), tag=tag, what=what, allow=_REFUSED) == 0:
                 return
     n = lib().sf_conv_fwd_ws_floats(ctypes.byref(d)) if SPLIT_K else 0
     if n > 0:
         ws = torch.empty((n,), dtype=torch.float32, device=device)
-        _check(_traced(tag, lambda: lib().sf_conv_fwd_ws(ctypes.byref(d), x_ptr, w_ptr, scale, bias, res_ptr, out_ptr,
-                                                         _ptr(ws), _stream())), what)
+        _call("sf_conv_fwd_ws", ctypes.byref(d), x_ptr, w_ptr, scale, bias, res_ptr, out_ptr, _ptr(ws), tag=tag,
+              what=what)
     else:
-        _check(_traced(tag, lambda: lib().sf_conv_fwd(ctypes.byref(d), x_ptr, w_ptr, scale, bias, res_ptr, out_ptr,
-                                                      _stream())), what)
+        _call("sf_conv_fwd", ctypes.byref(d), x_ptr, w_ptr, scale, bias, res_ptr, out_ptr, tag=tag, what=what)
 
 
 SPLIT_K = True  # False: one-pass f32 kernels only (tests compare the two schedules)
@@ -544,11 +550,10 @@ def pack_conv_weight_pair(w):
     w = w.detach().contiguous()
     cout, cin = w.shape[0], w.shape[1]
     taps = w.shape[2] * w.shape[3] * w.shape[4]
-    cin_pad, cout_pad = (cin + 15) // 16 * 16, (cout + 15) // 16 * 16
+    cin_pad, cout_pad = _pad16(cin), _pad16(cout)
     wp = torch.empty((cout, taps, cin_pad), dtype=torch.float32, device=w.device)
     wtp = torch.empty((cin, taps, cout_pad), dtype=torch.float32, device=w.device)
-    _check(lib().sf_pack_conv_weight(_ptr(w), cout, cin, taps, _ptr(wp), cin_pad, _ptr(wtp), cout_pad, _stream()),
-           "sf_pack_conv_weight")
+    _call("sf_pack_conv_weight", _ptr(w), cout, cin, taps, _ptr(wp), cin_pad, _ptr(wtp), cout_pad)
     return wp, wtp
 
 
@@ -562,14 +567,12 @@ def pack_grouped_weight_pair(w, groups):
     assert cout % groups == 0, (w.shape, groups)
     cout_g = cout // groups
     taps = w.shape[2] * w.shape[3] * w.shape[4]
-    cin_pad, cout_pad = (cin_g + 15) // 16 * 16, (cout_g + 15) // 16 * 16
+    cin_pad, cout_pad = _pad16(cin_g), _pad16(cout_g)
     wp = torch.empty((cout, taps, cin_pad), dtype=torch.float32, device=w.device)
     wtp = torch.empty((cin_g * groups, taps, cout_pad), dtype=torch.float32, device=w.device)
     for g in range(groups):
-        _check(lib().sf_pack_conv_weight(_ptr(w[g * cout_g:(g + 1) * cout_g]), cout_g, cin_g, taps,
-                                         _ptr(wp[g * cout_g:(g + 1) * cout_g]), cin_pad,
-                                         _ptr(wtp[g * cin_g:(g + 1) * cin_g]), cout_pad, _stream()),
-               "sf_pack_conv_weight")
+        _call("sf_pack_conv_weight", _ptr(w[g * cout_g:(g + 1) * cout_g]), cout_g, cin_g, taps,
+              _ptr(wp[g * cout_g:(g + 1) * cout_g]), cin_pad, _ptr(wtp[g * cin_g:(g + 1) * cin_g]), cout_pad)
     return wp, wtp
 
 
@@ -590,7 +593,7 @@ def pack_conv_weight_pairs(weights, outs):
         assert w.is_contiguous() and w.dtype == torch.float32
         cout, cin = w.shape[0], w.shape[1]
         taps = w.shape[2] * w.shape[3] * w.shape[4]
-        cin_pad, cout_pad = (cin + 15) // 16 * 16, (cout + 15) // 16 * 16
+        cin_pad, cout_pad = _pad16(cin), _pad16(cout)
         ok = (o is not None and o[0] is not None and o[1] is not None and
               all(t.device == w.device and t.dtype == torch.float32 and t.is_contiguous() for t in o) and
               tuple(o[0].shape) == (cout, taps, cin_pad) and tuple(o[1].shape) == (cin, taps, cout_pad))
@@ -615,13 +618,13 @@ def pack_conv_weight_pairs(weights, outs):
         for w, o in zip(weights, res):
             cout, cin = w.shape[0], w.shape[1]
             taps = w.shape[2] * w.shape[3] * w.shape[4]
-            _check(lib().sf_pack_conv_weight(_ptr(w), cout, cin, taps, _ptr(o[0]), o[0].shape[2], _ptr(o[1]),
-                                             o[1].shape[2], _stream()), "sf_pack_conv_weight")
+            _call("sf_pack_conv_weight", _ptr(w), cout, cin, taps, _ptr(o[0]), o[0].shape[2], _ptr(o[1]),
+                  o[1].shape[2])
             for t in o:
                 pl = t.__dict__.get("_sf_bx")
                 if pl is not None:
                     c = t.shape[1] * t.shape[2]
-                    _check(lib().sf_bx_split(_ptr(t), c, 0, t.shape[0], c, _ptr(pl), _stream()), "sf_bx_split")
+                    _call("sf_bx_split", _ptr(t), c, 0, t.shape[0], c, _ptr(pl))
                 t.__dict__.pop("_sf_classes", None)
         return res
     if tab is None or tab[0] != key:
@@ -630,7 +633,7 @@ def pack_conv_weight_pairs(weights, outs):
         starts = torch.tensor(blk0, dtype=torch.int32).to(dev)
         tab = (key, items, starts)
         _PACK_TABLES[dev] = tab
-    _check(lib().sf_pack_conv_weights(_ptr(tab[1]), _ptr(tab[2]), len(recs), nb, _stream()), "sf_pack_conv_weights")
+    _call("sf_pack_conv_weights", _ptr(tab[1]), _ptr(tab[2]), len(recs), nb)
     # packed weights overwritten in place: their bf16 piece planes (conv_bx.hip) follow, all in ONE launch
     recs, blk0, nb = [], [0], 0
     for o in res:
@@ -644,7 +647,7 @@ def pack_conv_weight_pairs(weights, outs):
             t.__dict__.pop("_sf_classes", None)  # tap-subset copies of the previous contents (strided data gradients)
     if len(recs) == 1:
         r = recs[0]
-        _check(lib().sf_bx_split(r[0], r[3], 0, r[2], r[3], r[1], _stream()), "sf_bx_split")
+        _call("sf_bx_split", r[0], r[3], 0, r[2], r[3], r[1])
     elif recs:
         key = tuple(recs)
         tab = _SPLIT_TABLES.get(dev)
@@ -653,7 +656,7 @@ def pack_conv_weight_pairs(weights, outs):
             tab = (key, torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(dev),
                    torch.tensor(blk0, dtype=torch.int32).to(dev))
             _SPLIT_TABLES[dev] = tab
-        _check(lib().sf_bx_split_batched(_ptr(tab[1]), _ptr(tab[2]), len(recs), nb, _stream()), "sf_bx_split_batched")
+        _call("sf_bx_split_batched", _ptr(tab[1]), _ptr(tab[2]), len(recs), nb)
     return res
 
 
@@ -672,10 +675,7 @@ def conv(x, wp, kernel, stride=(1, 1, 1), padding=(0, 0, 0), dilation=(1, 1, 1),
     _require_gpu(x.buf, "conv")
     cout, taps, cin_pad = wp.shape
     cin = x.C if cin is None else cin
-    kT, kH, kW = kernel
-    To = _out_dim(x.T, kT, stride[0], padding[0], dilation[0])
-    Ho = _out_dim(x.H, kH, stride[1], padding[1], dilation[1])
-    Wo = _out_dim(x.W, kW, stride[2], padding[2], dilation[2])
+    To, Ho, Wo = _out_thw(x, kernel, stride, padding, dilation)
     if out_thw is not None:  # caller restricts the output extent (stem trick: trailing columns are padding)
         assert out_thw[0] <= To and out_thw[1] <= Ho and out_thw[2] <= Wo
         To, Ho, Wo = out_thw
@@ -684,10 +684,8 @@ def conv(x, wp, kernel, stride=(1, 1, 1), padding=(0, 0, 0), dilation=(1, 1, 1),
     else:
         assert (out.N, out.T, out.H, out.W) == (x.N, To, Ho, Wo), (out, (x.N, To, Ho, Wo))
         assert out.coff + (cout - 1) * out_cmul < out.cs and (out_cmul > 1 or out.C == cout), (out, cout)
-    d = ConvDesc(x.N, x.T, x.H, x.W, cin, x.cs, x.coff, To, Ho, Wo, cout, out.cs, out.coff, out_cmul,
-                 kT, kH, kW, stride[0], stride[1], stride[2], padding[0], padding[1], padding[2],
-                 dilation[0], dilation[1], dilation[2], cin_pad, _act(relu),
-                 res.cs if res is not None else 0, res.coff if res is not None else 0, 0)
+    d = _conv_desc(x, (To, Ho, Wo), out.cs, out.coff, cout, kernel, stride, padding, dilation, cin=cin,
+                   cin_pad=cin_pad, act=_act(relu), res=res, out_cmul=out_cmul)
     if res is not None:
         assert res.rows == out.rows and res.C == cout
     if stats and SPLIT_K and scale is None and res is None and not relu and out_cmul == 1 and \
@@ -698,10 +696,9 @@ def conv(x, wp, kernel, stride=(1, 1, 1), padding=(0, 0, 0), dilation=(1, 1, 1),
             ws = torch.empty((lib().sf_conv_pw_ws_floats(ctypes.byref(d), 1),), dtype=torch.float32, device=x.buf.device)
             st = torch.empty((n,), dtype=torch.float32, device=x.buf.device)
             parts = ctypes.c_int(0)
-            tag = ("conv", d.N * d.To * d.Ho * d.Wo, d.Cin, d.Cout)
-            _check(_traced(tag, lambda: lib().sf_conv_fwd_pw(ctypes.byref(d), x.ptr(), _ptr(wp), _ptr(planes), None,
-                                                             _ptr(bias), None, out.ptr(), _ptr(ws), _ptr(st),
-                                                             ctypes.byref(parts), _stream())), "sf_conv_fwd_pw")
+            _call("sf_conv_fwd_pw", ctypes.byref(d), x.ptr(), _ptr(wp), _ptr(planes), None, _ptr(bias), None,
+                  out.ptr(), _ptr(ws), _ptr(st), ctypes.byref(parts),
+                  tag=("conv", d.N * d.To * d.Ho * d.Wo, d.Cin, d.Cout))
             return out, ((st, parts.value) if parts.value > 0 else None)
     if stats:
         n = lib().sf_conv_stats_ws_floats(ctypes.byref(d)) if (scale is None and res is None and not relu
@@ -709,10 +706,9 @@ def conv(x, wp, kernel, stride=(1, 1, 1), padding=(0, 0, 0), dilation=(1, 1, 1),
         if n > 0:
             ws = torch.empty((n,), dtype=torch.float32, device=x.buf.device)
             parts = ctypes.c_int(0)
-            tag = ("conv", d.N * d.To * d.Ho * d.Wo, d.kT * d.kH * d.kW * d.Cin, d.Cout)
-            _check(_traced(tag, lambda: lib().sf_conv_fwd_stats(ctypes.byref(d), x.ptr(), _ptr(wp), None, _ptr(bias),
-                                                                None, out.ptr(), _ptr(ws), ctypes.byref(parts),
-                                                                _stream())), "sf_conv_fwd_stats")
+            _call("sf_conv_fwd_stats", ctypes.byref(d), x.ptr(), _ptr(wp), None, _ptr(bias), None, out.ptr(),
+                  _ptr(ws), ctypes.byref(parts),
+                  tag=("conv", d.N * d.To * d.Ho * d.Wo, d.kT * d.kH * d.kW * d.Cin, d.Cout))
             return out, ((ws, parts.value) if parts.value > 0 else None)
     _conv_launch(d, x.ptr(), _ptr(wp), _ptr(scale), _ptr(bias), res.ptr() if res is not None else None, out.ptr(),
                  x.buf.device, "sf_conv_fwd", w_tensor=wp)
@@ -728,49 +724,45 @@ def dwconv(x, wp, kernel, stride=(1, 1, 1), padding=(0, 0, 0), scale=None, bias=
     c = x.C
     assert wpitch >= c, (wp.shape, x)
     cout = c if cout is None else cout
-    kT, kH, kW = kernel
-    To = _out_dim(x.T, kT, stride[0], padding[0], 1)
-    Ho = _out_dim(x.H, kH, stride[1], padding[1], 1)
-    Wo = _out_dim(x.W, kW, stride[2], padding[2], 1)
+    To, Ho, Wo = _out_thw(x, kernel, stride, padding)
     if out is None:
         out = new_act(x, x.N, To, Ho, Wo, cout)
     else:
         assert (out.N, out.T, out.H, out.W) == (x.N, To, Ho, Wo)
-    d = ConvDesc(x.N, x.T, x.H, x.W, c, x.cs, x.coff, To, Ho, Wo, cout, out.cs, out.coff, out_cmul,
-                 kT, kH, kW, stride[0], stride[1], stride[2], padding[0], padding[1], padding[2], 1, 1, 1,
-                 wpitch, _act(relu),
-                 res.cs if res is not None else 0, res.coff if res is not None else 0, 0)
+    d = _conv_desc(x, (To, Ho, Wo), out.cs, out.coff, cout, kernel, stride, padding, cin_pad=wpitch, act=_act(relu),
+                   res=res, out_cmul=out_cmul)
     # trace tag: ("dwconv", algorithmic HBM bytes = input + output (+ residual) rows once)
     nbytes = 4 * (x.rows * c + out.rows * cout * (2 if res is not None else 1))
-    _check(_traced(("dwconv", nbytes, taps, c), lambda: lib().sf_dwconv_fwd(
-        ctypes.byref(d), x.ptr(), _ptr(wp), _ptr(scale), _ptr(bias), res.ptr() if res is not None else None,
-        out.ptr(), _stream())), "sf_dwconv_fwd")
+    _call("sf_dwconv_fwd", ctypes.byref(d), x.ptr(), _ptr(wp), _ptr(scale), _ptr(bias),
+          res.ptr() if res is not None else None, out.ptr(), tag=("dwconv", nbytes, taps, c))
     return out
+
+
+def _pool_desc(x, out_thw, out_cs, out_coff, kernel, stride, padding, avg):
+    """sf_pool_desc in the header's field order; x: the input view."""
+    return PoolDesc(x.N, x.T, x.H, x.W, x.C, x.cs, x.coff, out_thw[0], out_thw[1], out_thw[2], out_cs, out_coff,
+                    kernel[0], kernel[1], kernel[2], stride[0], stride[1], stride[2],
+                    padding[0], padding[1], padding[2], 1 if avg else 0)
 
 
 def pool(x, kernel, stride, padding=(0, 0, 0), avg=False, out=None, out_reserve=(0, 0), want_arg=False):
     """want_arg (max pooling): also return the byte map of window winners for maxpool_bwd_arg — (out, arg), arg None
     when the views are not float4-addressable or the window has more than 255 taps."""
     _require_gpu(x.buf, "pool")
-    To = _out_dim(x.T, kernel[0], stride[0], padding[0], 1)
-    Ho = _out_dim(x.H, kernel[1], stride[1], padding[1], 1)
-    Wo = _out_dim(x.W, kernel[2], stride[2], padding[2], 1)
+    To, Ho, Wo = _out_thw(x, kernel, stride, padding)
     if out is None:
         out = new_act(x, x.N, To, Ho, Wo, x.C, out_reserve[0], out_reserve[1])
     else:
         assert (out.N, out.T, out.H, out.W, out.C) == (x.N, To, Ho, Wo, x.C)
-    d = PoolDesc(x.N, x.T, x.H, x.W, x.C, x.cs, x.coff, To, Ho, Wo, out.cs, out.coff,
-                 kernel[0], kernel[1], kernel[2], stride[0], stride[1], stride[2],
-                 padding[0], padding[1], padding[2], 1 if avg else 0)
+    d = _pool_desc(x, (To, Ho, Wo), out.cs, out.coff, kernel, stride, padding, avg)
     if want_arg and not avg:
         ok = (x.C % 4 == 0 and x.cs % 4 == 0 and x.coff % 4 == 0 and out.cs % 4 == 0 and out.coff % 4 == 0 and
               kernel[0] * kernel[1] * kernel[2] <= 255 and x.buf.data_ptr() % 16 == 0 and out.buf.data_ptr() % 16 == 0)
         if ok:
             arg = torch.empty((out.rows, x.C), dtype=torch.uint8, device=x.buf.device)
-            _check(lib().sf_maxpool_fwd_arg(ctypes.byref(d), x.ptr(), out.ptr(), _ptr(arg), _stream()),
-                   "sf_maxpool_fwd_arg")
+            _call("sf_maxpool_fwd_arg", ctypes.byref(d), x.ptr(), out.ptr(), _ptr(arg))
             return out, arg
-    _check(lib().sf_pool_fwd(ctypes.byref(d), x.ptr(), out.ptr(), _stream()), "sf_pool_fwd")
+    _call("sf_pool_fwd", ctypes.byref(d), x.ptr(), out.ptr())
     return (out, None) if want_arg else out
 
 
@@ -779,8 +771,7 @@ def tmax_mean(x, alpha):
     _require_gpu(x.buf, "tmax_mean")
     pooled = torch.empty((x.N, x.C), dtype=torch.float32, device=x.buf.device)
     ws = torch.empty((lib().sf_tmax_mean_ws_floats(x.N, x.C),), dtype=torch.float32, device=x.buf.device)
-    _check(lib().sf_tmax_mean(x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C, alpha, _ptr(pooled), _ptr(ws),
-                              _stream()), "sf_tmax_mean")
+    _call("sf_tmax_mean", x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C, alpha, _ptr(pooled), _ptr(ws))
     return pooled
 
 
@@ -790,9 +781,8 @@ def gate_apply(x, alpha, pooled, w3=None, scale=None, bias=None, relu=False, out
         out = new_act(x, x.N, x.T // alpha, x.H, x.W, x.C)
     else:
         assert (out.N, out.T, out.H, out.W, out.C) == (x.N, x.T // alpha, x.H, x.W, x.C), (out, x)
-    _check(lib().sf_gate_apply(x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C, alpha, _ptr(pooled), _ptr(w3),
-                               _ptr(scale), _ptr(bias), ACT_RELU if relu else ACT_NONE, out.ptr(), out.cs,
-                               out.coff, _stream()), "sf_gate_apply")
+    _call("sf_gate_apply", x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C, alpha, _ptr(pooled), _ptr(w3),
+          _ptr(scale), _ptr(bias), ACT_RELU if relu else ACT_NONE, out.ptr(), out.cs, out.coff)
     return out
 
 
@@ -804,10 +794,6 @@ def attention(q, k, v, x, gamma, scale=None, bias=None, relu=False, alpha=1, out
         out = new_act(x, x.N, x.T * alpha, x.H, x.W, x.C)
     else:
         assert (out.N, out.T, out.H, out.W, out.C) == (x.N, x.T * alpha, x.H, x.W, x.C), (out, x)
-
-    def base(a):  # slice base pointer: buffer pointer + channel offset
-        return ctypes.c_void_p(a.buf.data_ptr() + 4 * a.coff)
-
     o_save = lse_save = None
     if save is not None:
         n = x.T * x.H * x.W
@@ -816,10 +802,10 @@ def attention(q, k, v, x, gamma, scale=None, bias=None, relu=False, alpha=1, out
     # workspace for the key-range parts the launcher may cut the sweep into (sf_sweep_parts: fills the last round)
     ws = torch.empty((lib().sf_attn_fwd_ws_floats(x.N, x.T * x.H * x.W, x.C),), dtype=torch.float32,
                      device=x.buf.device)
-    _check(_traced(("attn", x.N, x.T * x.H * x.W, x.C), lambda: lib().sf_attn_fwd_ws(
-        base(q), q.cs, base(k), k.cs, base(v), v.cs, base(x), x.cs, _ptr(gamma), _ptr(scale),
-        _ptr(bias), ACT_RELU if relu else ACT_NONE, out.ptr(), out.cs, out.coff,
-        x.N, x.T, x.H, x.W, x.C, alpha, _ptr(o_save), _ptr(lse_save), _ptr(ws), _stream())), "sf_attn_fwd_ws")
+    _call("sf_attn_fwd_ws", _slice_base(q), q.cs, _slice_base(k), k.cs, _slice_base(v), v.cs, _slice_base(x), x.cs,
+          _ptr(gamma), _ptr(scale), _ptr(bias), ACT_RELU if relu else ACT_NONE, out.ptr(), out.cs, out.coff,
+          x.N, x.T, x.H, x.W, x.C, alpha, _ptr(o_save), _ptr(lse_save), _ptr(ws),
+          tag=("attn", x.N, x.T * x.H * x.W, x.C))
     return out
 
 
@@ -827,23 +813,21 @@ def head_act_mean(logits, act):
     """logits Act [N,T,H,W,K] (dense) -> torch [N, K] = mean_{t,h,w} act(logits)."""
     assert logits.coff == 0 and logits.C == logits.cs
     out = torch.empty((logits.N, logits.C), dtype=torch.float32, device=logits.buf.device)
-    _check(lib().sf_head_act_mean(logits.ptr(), logits.N, logits.T * logits.H * logits.W, logits.C, act, _ptr(out),
-                                  _stream()), "sf_head_act_mean")
+    _call("sf_head_act_mean", logits.ptr(), logits.N, logits.T * logits.H * logits.W, logits.C, act, _ptr(out))
     return out
 
 
 def copy_channels(x, out, out_cmul=1):
     assert x.rows == out.rows
-    _check(lib().sf_copy_channels(x.ptr(), x.cs, x.coff, out.ptr(), out.cs, out.coff, out_cmul, x.rows, x.C,
-                                  _stream()), "sf_copy_channels")
+    _call("sf_copy_channels", x.ptr(), x.cs, x.coff, out.ptr(), out.cs, out.coff, out_cmul, x.rows, x.C)
     return out
 
 
 def channel_shuffle(x, out, groups, accumulate=False):
     """out[.., j*G + g] (+)= x[.., g*(C/G) + j] in one launch (sf_channel_shuffle); groups = C/G inverts it."""
     assert x.rows == out.rows and x.C == out.C and x.C % groups == 0
-    _check(lib().sf_channel_shuffle(x.ptr(), x.cs, x.coff, out.ptr(), out.cs, out.coff, groups, x.rows, x.C,
-                                    1 if accumulate else 0, _stream()), "sf_channel_shuffle")
+    _call("sf_channel_shuffle", x.ptr(), x.cs, x.coff, out.ptr(), out.cs, out.coff, groups, x.rows, x.C,
+          1 if accumulate else 0)
     return out
 
 
@@ -854,8 +838,7 @@ def channel_stats(x):
     mean = torch.empty((x.C,), dtype=torch.float32, device=dev)
     var = torch.empty((x.C,), dtype=torch.float32, device=dev)
     ws = torch.empty((lib().sf_channel_stats_ws_floats(x.C),), dtype=torch.float32, device=dev)
-    _check(lib().sf_channel_stats(x.ptr(), x.cs, x.coff, x.rows, x.C, _ptr(mean), _ptr(var), _ptr(ws), _stream()),
-           "sf_channel_stats")
+    _call("sf_channel_stats", x.ptr(), x.cs, x.coff, x.rows, x.C, _ptr(mean), _ptr(var), _ptr(ws))
     return mean, var
 
 
@@ -874,25 +857,22 @@ def affine(x, scale=None, bias=None, res=None, relu=False, rep=1, out=None, out_
         assert out.coff + (x.C - 1) * out_cmul < out.cs and (out_cmul > 1 or out.C == x.C), (out, x)
     if res is not None:
         assert res.rows == x.rows and res.C == x.C
+    head = (x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C)
+    mid = (_ptr(scale), _ptr(bias), res.ptr() if res is not None else None, res.cs if res is not None else 0,
+           res.coff if res is not None else 0, _act(relu))
     if (mask is not None and relu and rep == 1 and nsplit == 1 and out_cmul == 1 and x.C % 4 == 0 and
             x.cs % 4 == 0 and x.coff % 4 == 0 and out.cs % 4 == 0 and out.coff % 4 == 0 and
             x.rows * (x.C // 4) < 2 ** 31 - 1 and scale is not None and
             (res is None or (res.cs % 4 == 0 and res.coff % 4 == 0))):
         mk = torch.empty((x.rows * (x.C // 4),), dtype=torch.uint8, device=x.buf.device)
-        _check(lib().sf_affine_fwd_mask(
-            x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C, _ptr(scale), _ptr(bias),
-            res.ptr() if res is not None else None, res.cs if res is not None else 0,
-            res.coff if res is not None else 0, _act(relu), out.ptr(), out.cs, out.coff, _ptr(mk), _stream()),
-            "sf_affine_fwd_mask")
+        _call("sf_affine_fwd_mask", *head, *mid, out.ptr(), out.cs, out.coff, _ptr(mk))
         mask["bytes"] = mk
         return out
-    tail = (_ptr(scale), _ptr(bias), res.ptr() if res is not None else None, res.cs if res is not None else 0,
-            res.coff if res is not None else 0, _act(relu), rep, out.ptr(), out.cs, out.coff, out_cmul, _stream())
+    tail = mid + (rep, out.ptr(), out.cs, out.coff, out_cmul)
     if nsplit == 1:
-        _check(lib().sf_affine_fwd(x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C, *tail), "sf_affine_fwd")
+        _call("sf_affine_fwd", *head, *tail)
     else:
-        _check(lib().sf_affine_fwd_split(x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C, nsplit, *tail),
-               "sf_affine_fwd_split")
+        _call("sf_affine_fwd_split", *head, nsplit, *tail)
     return out
 
 
@@ -908,10 +888,9 @@ def conv_dgrad(dz, wt_packed, x_like, kernel, stride=(1, 1, 1), padding=(0, 0, 0
     assert (out.N, out.T, out.H, out.W, out.C) == (x_like.N, x_like.T, x_like.H, x_like.W, cin), (out, x_like)
     if max(stride) > 1 and tuple(dilation) == (1, 1, 1) and (accumulate or (out.coff == 0 and out.cs == out.C)):
         return _conv_dgrad_strided(dz, wt_packed, out, kernel, stride, padding, accumulate, dz_planes)
-    d = ConvDesc(dz.N, dz.T, dz.H, dz.W, dz.C, dz.cs, dz.coff, out.T, out.H, out.W, cin, out.cs, out.coff, 1,
-                 kernel[0], kernel[1], kernel[2], stride[0], stride[1], stride[2], padding[0], padding[1],
-                 padding[2], dilation[0], dilation[1], dilation[2], cout_pad, ACT_NONE,
-                 out.cs if accumulate else 0, out.coff if accumulate else 0, 1)
+    # the residual is the output itself, and only when accumulating
+    d = _conv_desc(dz, (out.T, out.H, out.W), out.cs, out.coff, cin, kernel, stride, padding, dilation,
+                   cin_pad=cout_pad, res=out if accumulate else None, transposed=1)
     _conv_launch(d, dz.ptr(), _ptr(wt_packed), None, None, out.ptr() if accumulate else None, out.ptr(),
                  dz.buf.device, "sf_conv_fwd(transposed)", w_tensor=wt_packed, in_planes=dz_planes)
     return out
@@ -992,10 +971,11 @@ def _conv_dgrad_strided(dz, wt_packed, out, kernel, stride, padding, accumulate,
                 wsub = store.get(key)
                 if wsub is None:
                     wsub = _class_weights(wt_packed, store, kernel, stride, padding)[key]
-                d = ConvDesc(dz.N, dz.T, dz.H, dz.W, dz.C, dz.cs, dz.coff, dims[0], dims[1], dims[2], cin, out.cs,
-                             out.coff, 1, len(tt), len(th), len(tw), 1, 1, 1, -ot[0], -oh[0], -ow[0], 1, 1, 1,
-                             cout_pad, ACT_NONE, out.cs, out.coff, 0, stride[0], stride[1], stride[2], at, ah, aw,
-                             out.T, out.H, out.W)
+                # a dense stride-1 conv of the class's taps; the descriptor always carries the output's pitch / offset
+                # as the residual's (the pointer decides whether it is read)
+                d = _conv_desc(dz, dims, out.cs, out.coff, cin, (len(tt), len(th), len(tw)), (1, 1, 1),
+                               (-ot[0], -oh[0], -ow[0]), cin_pad=cout_pad, res=out,
+                               scatter=(stride[0], stride[1], stride[2], at, ah, aw, out.T, out.H, out.W))
                 _conv_launch(d, dz.ptr(), _ptr(wsub), None, None, out.ptr() if add else None, out.ptr(),
                              dz.buf.device, "sf_conv_fwd(strided dgrad class)", w_tensor=wsub, in_planes=dz_planes)
     return out
@@ -1014,37 +994,31 @@ def conv_wgrad(x, dz, cout, kernel, stride=(1, 1, 1), padding=(0, 0, 0), dilatio
     them into dst, a contiguous tensor in nn.Conv3d's [Cout, Cin, kT, kH, kW] layout (e.g. the weight's .grad)."""
     _require_gpu(x.buf, "conv_wgrad")
     cin = x.C if cin is None else cin
-    cin_pad = (cin + 15) // 16 * 16 if cin_pad is None else cin_pad
+    cin_pad = _pad16(cin) if cin_pad is None else cin_pad
     kT, kH, kW = kernel
-    d = ConvDesc(x.N, x.T, x.H, x.W, cin, x.cs, x.coff, dz.T, dz.H, dz.W, cout, 0, 0, 1,
-                 kT, kH, kW, stride[0], stride[1], stride[2], padding[0], padding[1], padding[2],
-                 dilation[0], dilation[1], dilation[2], cin_pad, ACT_NONE, 0, 0, 0)
+    d = _conv_desc(x, (dz.T, dz.H, dz.W), 0, 0, cout, kernel, stride, padding, dilation, cin=cin, cin_pad=cin_pad)
+    tag = ("conv", dz.rows, kT * kH * kW * cin, cout)
     nws = lib().sf_conv_wgrad_bx_ws_floats(ctypes.byref(d), 1 if x_planes is not None else 0,
                                            1 if dz_planes is not None else 0) if cin_pad == cin else 0
     if nws > 0:  # long reductions: the bf16-piece kernel of conv_bx.hip (operand planes handed in or made in ws)
         S = lib().sf_conv_wgrad_bx_splits(ctypes.byref(d))
         part = torch.empty((S, cout, kT * kH * kW, cin_pad), dtype=torch.float32, device=x.buf.device)
         ws = torch.empty((nws,), dtype=torch.float32, device=x.buf.device)
-        rc = _traced(("conv", dz.rows, kT * kH * kW * cin, cout), lambda: lib().sf_conv_wgrad_bx(
-            ctypes.byref(d), x.ptr(), _ptr(x_planes), dz.ptr(), dz.cs, dz.coff, _ptr(dz_planes), _ptr(part), _ptr(ws),
-            _stream()))
-        if rc in (SF_EALIGN, SF_ENOTTAKEN):  # a dz view the shape-only plan cannot see (odd channel offset / pitch)
+        # _REFUSED: a dz view the shape-only plan cannot see (odd channel offset / pitch)
+        if _call("sf_conv_wgrad_bx", ctypes.byref(d), x.ptr(), _ptr(x_planes), dz.ptr(), dz.cs, dz.coff,
+                 _ptr(dz_planes), _ptr(part), _ptr(ws), tag=tag, allow=_REFUSED) != 0:
             nws = 0
-        else:
-            _check(rc, "sf_conv_wgrad_bx")
     if nws <= 0:
         S = lib().sf_conv_wgrad_splits(ctypes.byref(d))
         part = torch.empty((S, cout, kT * kH * kW, cin_pad), dtype=torch.float32, device=x.buf.device)
-        _check(_traced(("conv", dz.rows, kT * kH * kW * cin, cout), lambda: lib().sf_conv_wgrad(
-            ctypes.byref(d), x.ptr(), dz.ptr(), dz.cs, dz.coff, _ptr(part), _stream())), "sf_conv_wgrad")
+        _call("sf_conv_wgrad", ctypes.byref(d), x.ptr(), dz.ptr(), dz.cs, dz.coff, _ptr(part), tag=tag)
     if finish_into is not None:
         dst, real_cin, fold_kw = finish_into
         assert dst.is_contiguous() and dst.dtype == torch.float32
         if S > 128 and cout * kT * kH * kW * cin_pad > 65536:  # long split lists of large weights (does not occur
             part, S = part.sum(0, keepdim=True), 1  # in the shipped models): a parallel tree sum first
         assert dst.numel() == cout * real_cin * kT * kH * kW * max(fold_kw, 1), (dst.shape, cout, real_cin, kernel)
-        _check(lib().sf_conv_wgrad_finish(_ptr(part), S, cout, kT * kH * kW, cin_pad, real_cin, fold_kw, _ptr(dst), 1,
-                                          _stream()), "sf_conv_wgrad_finish")
+        _call("sf_conv_wgrad_finish", _ptr(part), S, cout, kT * kH * kW, cin_pad, real_cin, fold_kw, _ptr(dst), 1)
         return None
     return part.sum(0) if S > 1 else part[0]
 
@@ -1057,24 +1031,18 @@ def conv_grouped(x, wp, groups, kernel, stride=(1, 1, 1), padding=(0, 0, 0), dil
     per-group packs one after the other).  shuffle: group g's channel j is stored at channel j*G + g."""
     _require_gpu(x.buf, "conv_grouped")
     cout, taps, cin_pad = wp.shape
-    kT, kH, kW = kernel
-    To = _out_dim(x.T, kT, stride[0], padding[0], dilation[0])
-    Ho = _out_dim(x.H, kH, stride[1], padding[1], dilation[1])
-    Wo = _out_dim(x.W, kW, stride[2], padding[2], dilation[2])
+    To, Ho, Wo = _out_thw(x, kernel, stride, padding, dilation)
     if out is None:
         out = new_act(x, x.N, To, Ho, Wo, cout, out_reserve[0], out_reserve[1])
     assert (out.N, out.T, out.H, out.W, out.C) == (x.N, To, Ho, Wo, cout), (out, (x.N, To, Ho, Wo, cout))
     assert x.C % groups == 0 and cout % groups == 0 and cin_pad >= x.C // groups, (x, wp.shape, groups)
-    d = ConvDesc(x.N, x.T, x.H, x.W, x.C, x.cs, x.coff, To, Ho, Wo, cout, out.cs, out.coff, 1,
-                 kT, kH, kW, stride[0], stride[1], stride[2], padding[0], padding[1], padding[2],
-                 dilation[0], dilation[1], dilation[2], cin_pad, _act(relu),
-                 res.cs if res is not None else 0, res.coff if res is not None else 0, 0)
+    d = _conv_desc(x, (To, Ho, Wo), out.cs, out.coff, cout, kernel, stride, padding, dilation, cin_pad=cin_pad,
+                   act=_act(relu), res=res)
     if res is not None:
         assert res.rows == out.rows and res.C == cout
-    tag = ("conv", d.N * d.To * d.Ho * d.Wo, taps * (x.C // groups), cout)
-    _check(_traced(tag, lambda: lib().sf_conv_fwd_grouped(
-        ctypes.byref(d), groups, 1 if shuffle else 0, x.ptr(), _ptr(wp), _ptr(scale), _ptr(bias),
-        res.ptr() if res is not None else None, out.ptr(), _stream())), "sf_conv_fwd_grouped")
+    _call("sf_conv_fwd_grouped", ctypes.byref(d), groups, 1 if shuffle else 0, x.ptr(), _ptr(wp), _ptr(scale),
+          _ptr(bias), res.ptr() if res is not None else None, out.ptr(),
+          tag=("conv", d.N * d.To * d.Ho * d.Wo, taps * (x.C // groups), cout))
     return out
 
 
@@ -1090,14 +1058,11 @@ def conv_dgrad_grouped(dz, wtp, groups, x_like, kernel, stride=(1, 1, 1), paddin
         accumulate = False
     assert (out.N, out.T, out.H, out.W, out.C) == (x_like.N, x_like.T, x_like.H, x_like.W, cin), (out, x_like)
     assert dz.C % groups == 0 and cin % groups == 0 and cout_pad >= dz.C // groups
-    d = ConvDesc(dz.N, dz.T, dz.H, dz.W, dz.C, dz.cs, dz.coff, out.T, out.H, out.W, cin, out.cs, out.coff, 1,
-                 kernel[0], kernel[1], kernel[2], stride[0], stride[1], stride[2], padding[0], padding[1],
-                 padding[2], dilation[0], dilation[1], dilation[2], cout_pad, ACT_NONE,
-                 out.cs if accumulate else 0, out.coff if accumulate else 0, 1)
-    tag = ("conv", dz.rows, taps * (dz.C // groups), cin)
-    _check(_traced(tag, lambda: lib().sf_conv_fwd_grouped(
-        ctypes.byref(d), groups, 0, dz.ptr(), _ptr(wtp), None, None, out.ptr() if accumulate else None, out.ptr(),
-        _stream())), "sf_conv_fwd_grouped(transposed)")
+    d = _conv_desc(dz, (out.T, out.H, out.W), out.cs, out.coff, cin, kernel, stride, padding, dilation,
+                   cin_pad=cout_pad, res=out if accumulate else None, transposed=1)
+    _call("sf_conv_fwd_grouped", ctypes.byref(d), groups, 0, dz.ptr(), _ptr(wtp), None, None,
+          out.ptr() if accumulate else None, out.ptr(), tag=("conv", dz.rows, taps * (dz.C // groups), cin),
+          what="sf_conv_fwd_grouped(transposed)")
     return out
 
 
@@ -1109,22 +1074,19 @@ def conv_wgrad_grouped(x, dz, groups, kernel, stride=(1, 1, 1), padding=(0, 0, 0
     _require_gpu(x.buf, "conv_wgrad_grouped")
     cin_g, cout = x.C // groups, dz.C
     assert x.C % groups == 0 and cout % groups == 0
-    cin_pad = (cin_g + 15) // 16 * 16 if cin_pad is None else cin_pad
+    cin_pad = _pad16(cin_g) if cin_pad is None else cin_pad
     kT, kH, kW = kernel
-    d = ConvDesc(x.N, x.T, x.H, x.W, x.C, x.cs, x.coff, dz.T, dz.H, dz.W, cout, 0, 0, 1,
-                 kT, kH, kW, stride[0], stride[1], stride[2], padding[0], padding[1], padding[2],
-                 dilation[0], dilation[1], dilation[2], cin_pad, ACT_NONE, 0, 0, 0)
+    d = _conv_desc(x, (dz.T, dz.H, dz.W), 0, 0, cout, kernel, stride, padding, dilation, cin_pad=cin_pad)
     S = lib().sf_conv_wgrad_grouped_splits(ctypes.byref(d), groups)
     if S <= 0:
         raise SfhipError("sf_conv_wgrad_grouped_splits: %d -> %d channels in %d groups" % (x.C, cout, groups))
     part = torch.empty((S, cout, kT * kH * kW, cin_pad), dtype=torch.float32, device=x.buf.device)
-    _check(_traced(("conv", dz.rows, kT * kH * kW * cin_g, cout), lambda: lib().sf_conv_wgrad_grouped(
-        ctypes.byref(d), groups, x.ptr(), dz.ptr(), dz.cs, dz.coff, _ptr(part), _stream())), "sf_conv_wgrad_grouped")
+    _call("sf_conv_wgrad_grouped", ctypes.byref(d), groups, x.ptr(), dz.ptr(), dz.cs, dz.coff, _ptr(part),
+          tag=("conv", dz.rows, kT * kH * kW * cin_g, cout))
     if finish_into is not None:
         dst = finish_into
         assert dst.is_contiguous() and dst.dtype == torch.float32 and dst.numel() == cout * cin_g * kT * kH * kW
-        _check(lib().sf_conv_wgrad_finish(_ptr(part), S, cout, kT * kH * kW, cin_pad, cin_g, 0, _ptr(dst), 1,
-                                          _stream()), "sf_conv_wgrad_finish")
+        _call("sf_conv_wgrad_finish", _ptr(part), S, cout, kT * kH * kW, cin_pad, cin_g, 0, _ptr(dst), 1)
         return None
     return part.sum(0) if S > 1 else part[0]
 
@@ -1157,22 +1119,22 @@ def bn_bwd(dy, y, z, mean, invstd, gamma, relu, rep=1, dres=None, dz_out=None, d
     head = (dy.ptr(), dy.cs, dy.coff, yp, ycs, yco, z.ptr(), z.cs, z.coff, z.N, z.T, z.H, z.W, C)
     tail = (rep, code, _ptr(mean), _ptr(invstd))
     split = (nsplit,) if nsplit > 1 else ()
-    reduce_fn = lib().sf_bn_bwd_reduce_split if nsplit > 1 else lib().sf_bn_bwd_reduce
-    apply_fn = lib().sf_bn_bwd_apply_split if nsplit > 1 else lib().sf_bn_bwd_apply
+    reduce_fn = "sf_bn_bwd_reduce_split" if nsplit > 1 else "sf_bn_bwd_reduce"
+    apply_fn = "sf_bn_bwd_apply_split" if nsplit > 1 else "sf_bn_bwd_apply"
     if dres_overwrite:  # dres is an uninitialised buffer this call is the first writer of (dres = g, not +=)
         assert dres is not None and nsplit == 1
-        apply_fn = lib().sf_bn_bwd_apply_first
+        apply_fn = "sf_bn_bwd_apply_first"
     if grad_sink is not None:  # (weight.grad[:C], bias.grad[:C]) accumulated by the reduction's final kernel
         assert nsplit == 1 and dgamma_out is None
-        _check(lib().sf_bn_bwd_reduce_acc(*head, *tail, _ptr(dbeta), _ptr(dgamma), _ptr(ws), _ptr(grad_sink[1]),
-                                          _ptr(grad_sink[0]), _stream()), "sf_bn_bwd_reduce_acc")
+        _call("sf_bn_bwd_reduce_acc", *head, *tail, _ptr(dbeta), _ptr(dgamma), _ptr(ws), _ptr(grad_sink[1]),
+              _ptr(grad_sink[0]))
     else:
-        _check(reduce_fn(*head, *split, *tail, _ptr(dbeta), _ptr(dgamma), _ptr(ws), _stream()), "sf_bn_bwd_reduce")
+        _call(reduce_fn, *head, *split, *tail, _ptr(dbeta), _ptr(dgamma), _ptr(ws))
     db_apply, dg_apply = (dbeta, dgamma) if sync is None else sync(dbeta, dgamma)
     out = z if dz_out is None else dz_out
-    _check(apply_fn(*head, *split, *tail, _ptr(gamma), _ptr(db_apply), _ptr(dg_apply), out.ptr(), out.cs, out.coff,
-                    dres.ptr() if dres is not None else None, dres.cs if dres is not None else 0,
-                    dres.coff if dres is not None else 0, _stream()), "sf_bn_bwd_apply")
+    _call(apply_fn, *head, *split, *tail, _ptr(gamma), _ptr(db_apply), _ptr(dg_apply), out.ptr(), out.cs, out.coff,
+          dres.ptr() if dres is not None else None, dres.cs if dres is not None else 0,
+          dres.coff if dres is not None else 0)
     if dgamma_out is not None:  # scatter into full-width parameter gradients (sliced BN, GhostModule)
         if nsplit > 1:
             dgamma_out[0][:C] = dgamma.view(nsplit, C).sum(0)
@@ -1185,12 +1147,9 @@ def bn_bwd(dy, y, z, mean, invstd, gamma, relu, rep=1, dres=None, dz_out=None, d
 
 def maxpool_bwd(x, y, dy, dx, kernel, stride, padding=(0, 0, 0), overwrite=False):
     """dx (+)= gathered dy; overwrite: dx is an uninitialised buffer this call is the first writer of."""
-    d = PoolDesc(x.N, x.T, x.H, x.W, x.C, x.cs, x.coff, y.T, y.H, y.W, y.cs, y.coff,
-                 kernel[0], kernel[1], kernel[2], stride[0], stride[1], stride[2],
-                 padding[0], padding[1], padding[2], 0)
-    fn = lib().sf_maxpool_bwd_first if overwrite else lib().sf_maxpool_bwd
-    _check(fn(ctypes.byref(d), x.ptr(), y.ptr(), dy.ptr(), dy.cs, dy.coff, dx.ptr(), dx.cs, dx.coff, _stream()),
-           "sf_maxpool_bwd")
+    d = _pool_desc(x, (y.T, y.H, y.W), y.cs, y.coff, kernel, stride, padding, False)
+    _call("sf_maxpool_bwd_first" if overwrite else "sf_maxpool_bwd", ctypes.byref(d), x.ptr(), y.ptr(), dy.ptr(),
+          dy.cs, dy.coff, dx.ptr(), dx.cs, dx.coff)
     return dx
 
 
@@ -1200,25 +1159,23 @@ def maxpool_bwd_arg(x_like, arg, dy, dx, kernel, stride, padding=(0, 0, 0), over
     if not (dy.cs % 4 == 0 and dy.coff % 4 == 0 and dx.cs % 4 == 0 and dx.coff % 4 == 0 and
             dy.buf.data_ptr() % 16 == 0 and dx.buf.data_ptr() % 16 == 0):
         return False
-    d = PoolDesc(x_like.N, x_like.T, x_like.H, x_like.W, x_like.C, x_like.cs, x_like.coff, dy.T, dy.H, dy.W, dy.cs,
-                 dy.coff, kernel[0], kernel[1], kernel[2], stride[0], stride[1], stride[2],
-                 padding[0], padding[1], padding[2], 0)
-    _check(lib().sf_maxpool_bwd_arg(ctypes.byref(d), _ptr(arg), dy.ptr(), dy.cs, dy.coff, dx.ptr(), dx.cs, dx.coff,
-                                    1 if overwrite else 0, _stream()), "sf_maxpool_bwd_arg")
+    d = _pool_desc(x_like, (dy.T, dy.H, dy.W), dy.cs, dy.coff, kernel, stride, padding, False)
+    _call("sf_maxpool_bwd_arg", ctypes.byref(d), _ptr(arg), dy.ptr(), dy.cs, dy.coff, dx.ptr(), dx.cs, dx.coff,
+          1 if overwrite else 0)
     return True
 
 
 def tmax_dot(x, alpha, dz):
     out = torch.empty((x.N, x.C), dtype=torch.float32, device=x.buf.device)
     ws = torch.empty((lib().sf_tmax_mean_ws_floats(x.N, x.C),), dtype=torch.float32, device=x.buf.device)
-    _check(lib().sf_tmax_dot(x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C, alpha, dz.ptr(), dz.cs, dz.coff,
-                             _ptr(out), _ptr(ws), _stream()), "sf_tmax_dot")
+    _call("sf_tmax_dot", x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C, alpha, dz.ptr(), dz.cs, dz.coff,
+          _ptr(out), _ptr(ws))
     return out
 
 
 def eca_bwd_apply(x, alpha, dz, gate, dpool, dx):
-    _check(lib().sf_eca_bwd_apply(x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C, alpha, dz.ptr(), dz.cs, dz.coff,
-                                  _ptr(gate), _ptr(dpool), dx.ptr(), dx.cs, dx.coff, _stream()), "sf_eca_bwd_apply")
+    _call("sf_eca_bwd_apply", x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C, alpha, dz.ptr(), dz.cs, dz.coff,
+          _ptr(gate), _ptr(dpool), dx.ptr(), dx.cs, dx.coff)
     return dx
 
 
@@ -1227,51 +1184,48 @@ def eca_gate_bwd(dg, pooled, w3, dpool_scale, dw3):
     n, c = pooled.shape
     gate = torch.empty_like(pooled)
     dpool = torch.empty_like(pooled)
-    _check(lib().sf_eca_gate_bwd(_ptr(dg), _ptr(pooled), _ptr(w3), n, c, float(dpool_scale), _ptr(gate), _ptr(dpool),
-                                 _ptr(dw3), _stream()), "sf_eca_gate_bwd")
+    _call("sf_eca_gate_bwd", _ptr(dg), _ptr(pooled), _ptr(w3), n, c, float(dpool_scale), _ptr(gate), _ptr(dpool),
+          _ptr(dw3))
     return gate, dpool
 
 
 def bcast_add(g, v, scale):
-    _check(lib().sf_bcast_add(g.ptr(), g.cs, g.coff, g.N, g.T * g.H * g.W, g.C, _ptr(v), float(scale), _stream()),
-           "sf_bcast_add")
+    _call("sf_bcast_add", g.ptr(), g.cs, g.coff, g.N, g.T * g.H * g.W, g.C, _ptr(v), float(scale))
     return g
 
 
 def rowdot(a, b, scale=1.0):
     out = torch.empty((a.rows,), dtype=torch.float32, device=a.buf.device)
-    _check(lib().sf_rowdot(a.ptr(), a.cs, a.coff, b.ptr(), b.cs, b.coff, a.rows, a.C, float(scale), _ptr(out),
-                           _stream()), "sf_rowdot")
+    _call("sf_rowdot", a.ptr(), a.cs, a.coff, b.ptr(), b.cs, b.coff, a.rows, a.C, float(scale), _ptr(out))
     return out
 
 
 def axpy(a, out, alpha=1.0, accumulate=True):
     assert a.rows == out.rows and a.C == out.C
-    _check(lib().sf_axpy(a.ptr(), a.cs, a.coff, float(alpha), out.ptr(), out.cs, out.coff, a.rows, a.C,
-                         1 if accumulate else 0, _stream()), "sf_axpy")
+    _call("sf_axpy", a.ptr(), a.cs, a.coff, float(alpha), out.ptr(), out.cs, out.coff, a.rows, a.C,
+          1 if accumulate else 0)
     return out
 
 
 def row_softmax(x, scale=1.0):
     """x <- softmax(scale * x) over the channel dimension, in place (one wavefront per row)."""
     _require_gpu(x.buf, "row_softmax")
-    _check(lib().sf_row_softmax_fwd(x.ptr(), x.cs, x.coff, x.rows, x.C, float(scale), _stream()), "sf_row_softmax_fwd")
+    _call("sf_row_softmax_fwd", x.ptr(), x.cs, x.coff, x.rows, x.C, float(scale))
     return x
 
 
 def row_softmax_bwd(p, dp, scale=1.0):
     """dp <- scale * p * (dp - <p, dp>) in place."""
     assert p.rows == dp.rows and p.C == dp.C
-    _check(lib().sf_row_softmax_bwd(p.ptr(), p.cs, p.coff, dp.ptr(), dp.cs, dp.coff, p.rows, p.C, float(scale),
-                                    _stream()), "sf_row_softmax_bwd")
+    _call("sf_row_softmax_bwd", p.ptr(), p.cs, p.coff, dp.ptr(), dp.cs, dp.coff, p.rows, p.C, float(scale))
     return dp
 
 
 def act_bwd(dy, y, relu, dx, accumulate=True):
     """dx (+)= dy * [0 < y (< 6)] — backward of a bare ReLU (relu=True) / ReLU6 (relu=6)."""
     assert dy.rows == y.rows == dx.rows and dy.C == y.C == dx.C
-    _check(lib().sf_act_bwd(dy.ptr(), dy.cs, dy.coff, y.ptr(), y.cs, y.coff, _act(relu), dx.ptr(), dx.cs, dx.coff,
-                            dy.rows, dy.C, 1 if accumulate else 0, _stream()), "sf_act_bwd")
+    _call("sf_act_bwd", dy.ptr(), dy.cs, dy.coff, y.ptr(), y.cs, y.coff, _act(relu), dx.ptr(), dx.cs, dx.coff,
+          dy.rows, dy.C, 1 if accumulate else 0)
     return dx
 
 
@@ -1282,27 +1236,16 @@ def attention_bwd(q, k, v, dz, o, lse, gamma, dq, dk, dv, workspace=True):
     B, n, C = o.shape
     o_act = Act(o.view(B, 1, 1, n, C))
     dvec = rowdot(Act(dz.buf.view(B, 1, 1, n, dz.cs), dz.coff, C), o_act)
-
-    def base(a):
-        return ctypes.c_void_p(a.buf.data_ptr() + 4 * a.coff)
-
+    args = (_slice_base(q), q.cs, _slice_base(k), k.cs, _slice_base(v), v.cs, _slice_base(dz), dz.cs, _ptr(lse),
+            _ptr(dvec), _ptr(gamma), _slice_base(dq), dq.cs, _slice_base(dk), dk.cs, _slice_base(dv), dv.cs, B, n, C)
     nws = lib().sf_attn_bwd_fused_ws_floats(B, n, C) if workspace else 0
     if nws > 0:  # one sweep: S and dP are recomputed once (5 products), dQ summed over key-block planes
         ws = torch.empty((nws,), dtype=torch.float32, device=o.device)
-        _check(_traced(("attn_bwd_fused", B, n, C), lambda: lib().sf_attn_bwd_fused(
-            base(q), q.cs, base(k), k.cs, base(v), v.cs, base(dz), dz.cs, _ptr(lse), _ptr(dvec), _ptr(gamma),
-            base(dq), dq.cs, base(dk), dk.cs, base(dv), dv.cs, B, n, C, _ptr(ws), _stream())), "sf_attn_bwd_fused")
+        _call("sf_attn_bwd_fused", *args, _ptr(ws), tag=("attn_bwd_fused", B, n, C))
         return dvec
     for which, tag in ((1, "attn_bwd_dq"), (2, "attn_bwd_dkv")):
-        _check(_traced((tag, B, n, C), lambda: lib().sf_attn_bwd(
-            base(q), q.cs, base(k), k.cs, base(v), v.cs, base(dz), dz.cs, _ptr(lse), _ptr(dvec),
-            _ptr(gamma), base(dq), dq.cs, base(dk), dk.cs, base(dv), dv.cs, B, n, C, which, _stream())),
-            "sf_attn_bwd")
+        _call("sf_attn_bwd", *args, which, tag=(tag, B, n, C))
     return dvec
-
-
-def _slice_base(a):  # slice base pointer: buffer pointer + channel offset
-    return ctypes.c_void_p(a.buf.data_ptr() + 4 * a.coff)
 
 
 def xattn_accepts(q, k, v):
@@ -1325,9 +1268,8 @@ def cross_attention(q, k, v, sm_scale, save=None):
     lse = torch.empty((B, nq), dtype=torch.float32, device=q.buf.device)
     if save is not None:
         save["lse"] = lse
-    _check(_traced(("xattn_fwd", B, nq, nk, d, dv), lambda: lib().sf_xattn_fwd(
-        _slice_base(q), q.cs, _slice_base(k), k.cs, _slice_base(v), v.cs, _slice_base(y), y.cs, _ptr(lse), B, nq, nk,
-        d, dv, float(sm_scale), _stream())), "sf_xattn_fwd")
+    _call("sf_xattn_fwd", _slice_base(q), q.cs, _slice_base(k), k.cs, _slice_base(v), v.cs, _slice_base(y), y.cs,
+          _ptr(lse), B, nq, nk, d, dv, float(sm_scale), tag=("xattn_fwd", B, nq, nk, d, dv))
     return y
 
 
@@ -1339,10 +1281,9 @@ def cross_attention_bwd(q, k, v, y, dy, lse, sm_scale, dq, dk, dv, accumulate=(F
     nws = lib().sf_xattn_bwd_ws_floats(B, nq, nk, d, dvw)
     ws = torch.empty((nws,), dtype=torch.float32, device=q.buf.device) if nws > 0 else None
     mask = sum(1 << i for i, on in enumerate(accumulate) if on)
-    _check(_traced(("xattn_bwd", B, nq, nk, d, dvw), lambda: lib().sf_xattn_bwd(
-        _slice_base(q), q.cs, _slice_base(k), k.cs, _slice_base(v), v.cs, _slice_base(dy), dy.cs, _ptr(lse),
-        _ptr(dvec), _slice_base(dq), dq.cs, _slice_base(dk), dk.cs, _slice_base(dv), dv.cs, mask, B, nq, nk, d, dvw,
-        float(sm_scale), _ptr(ws), _stream())), "sf_xattn_bwd")
+    _call("sf_xattn_bwd", _slice_base(q), q.cs, _slice_base(k), k.cs, _slice_base(v), v.cs, _slice_base(dy), dy.cs,
+          _ptr(lse), _ptr(dvec), _slice_base(dq), dq.cs, _slice_base(dk), dk.cs, _slice_base(dv), dv.cs, mask, B, nq,
+          nk, d, dvw, float(sm_scale), _ptr(ws), tag=("xattn_bwd", B, nq, nk, d, dvw))
     return dvec
 
 
@@ -1366,9 +1307,8 @@ def gram(a, b, alpha, transposed=False):
     Gt = torch.empty((B, db, da), dtype=torch.float32, device=dev) if transposed else None
     nws = lib().sf_gram_ws_floats(B, R, da, db)
     ws = torch.empty((nws,), dtype=torch.float32, device=dev) if nws > 0 else None
-    _check(_traced(("gram", B, R, da, db), lambda: lib().sf_gram(
-        _slice_base(a), a.cs, _slice_base(b), b.cs, _ptr(G), _ptr(Gt), B, R, da, db, float(alpha), _ptr(ws),
-        _stream())), "sf_gram")
+    _call("sf_gram", _slice_base(a), a.cs, _slice_base(b), b.cs, _ptr(G), _ptr(Gt), B, R, da, db, float(alpha),
+          _ptr(ws), tag=("gram", B, R, da, db))
     return (G, Gt) if transposed else G
 
 
@@ -1384,9 +1324,8 @@ def rowmat(x, w, alpha, out=None, accumulate=False):
         assert not accumulate
         out = new_act(x, B, x.T, x.H, x.W, n)
     assert out.N == B and out.T * out.H * out.W == R and out.C == n, (x, out)
-    _check(_traced(("rowmat", B, R, k, n), lambda: lib().sf_rowmat(
-        _slice_base(x), x.cs, _ptr(w), _slice_base(out), out.cs, B, R, k, n, float(alpha), int(bool(accumulate)),
-        _stream())), "sf_rowmat")
+    _call("sf_rowmat", _slice_base(x), x.cs, _ptr(w), _slice_base(out), out.cs, B, R, k, n, float(alpha),
+          int(bool(accumulate)), tag=("rowmat", B, R, k, n))
     return out
 
 
@@ -1398,15 +1337,12 @@ def bn_train_stats(x, gamma, beta, eps, momentum, run_mean, run_var, nsplit=1):
     dev = x.buf.device
     o = torch.empty((5, nsplit * x.C), dtype=torch.float32, device=dev)
     ws = torch.empty((lib().sf_channel_stats_ws_floats(x.C),), dtype=torch.float32, device=dev)
+    tail = (_ptr(gamma), _ptr(beta), float(eps), float(momentum), _ptr(run_mean), _ptr(run_var), _ptr(o[0]),
+            _ptr(o[1]), _ptr(o[2]), _ptr(o[3]), _ptr(o[4]), _ptr(ws))
     if nsplit == 1:
-        _check(lib().sf_bn_train_stats(x.ptr(), x.cs, x.coff, x.rows, x.C, _ptr(gamma), _ptr(beta), float(eps),
-                                       float(momentum), _ptr(run_mean), _ptr(run_var), _ptr(o[0]), _ptr(o[1]),
-                                       _ptr(o[2]), _ptr(o[3]), _ptr(o[4]), _ptr(ws), _stream()), "sf_bn_train_stats")
+        _call("sf_bn_train_stats", x.ptr(), x.cs, x.coff, x.rows, x.C, *tail)
     else:
-        _check(lib().sf_bn_train_stats_split(
-            x.ptr(), x.cs, x.coff, x.N, x.T * x.H * x.W, x.C, nsplit, _ptr(gamma), _ptr(beta), float(eps),
-            float(momentum), _ptr(run_mean), _ptr(run_var), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), _ptr(o[3]),
-            _ptr(o[4]), _ptr(ws), _stream()), "sf_bn_train_stats_split")
+        _call("sf_bn_train_stats_split", x.ptr(), x.cs, x.coff, x.N, x.T * x.H * x.W, x.C, nsplit, *tail)
     return o[0], o[2], o[3], o[4]
 
 
@@ -1415,16 +1351,14 @@ def bn_train_stats_merge(parts, C, gamma, beta, eps, momentum, run_mean, run_var
     over the activation.  Returns (mean, invstd, scale, shift)."""
     ws, rows = parts
     o = torch.empty((5, C), dtype=torch.float32, device=ws.device)
-    _check(lib().sf_bn_train_stats_merge(_ptr(ws), rows, C, _ptr(gamma), _ptr(beta), float(eps), float(momentum),
-                                         _ptr(run_mean), _ptr(run_var), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]),
-                                         _ptr(o[3]), _ptr(o[4]), _stream()), "sf_bn_train_stats_merge")
+    _call("sf_bn_train_stats_merge", _ptr(ws), rows, C, _ptr(gamma), _ptr(beta), float(eps), float(momentum),
+          _ptr(run_mean), _ptr(run_var), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), _ptr(o[3]), _ptr(o[4]))
     return o[0], o[2], o[3], o[4]
 
 
 def _dw_desc(x, dz, kernel, stride, padding, wpitch=None):
-    return ConvDesc(x.N, x.T, x.H, x.W, x.C, x.cs, x.coff, dz.T, dz.H, dz.W, x.C, 0, 0, 1,
-                    kernel[0], kernel[1], kernel[2], stride[0], stride[1], stride[2], padding[0], padding[1],
-                    padding[2], 1, 1, 1, x.C if wpitch is None else wpitch, ACT_NONE, 0, 0, 0)
+    return _conv_desc(x, (dz.T, dz.H, dz.W), 0, 0, x.C, kernel, stride, padding,
+                      cin_pad=x.C if wpitch is None else wpitch)
 
 
 def dwconv_bwd(x, dz, wp, kernel, stride, padding, dx=None, into=None):
@@ -1439,30 +1373,26 @@ def dwconv_bwd(x, dz, wp, kernel, stride, padding, dx=None, into=None):
         assert into.is_contiguous() and into.dtype == torch.float32 and \
             into.numel() == C * kernel[0] * kernel[1] * kernel[2], (into.shape, C, kernel)
         dw = None
-        _check(lib().sf_dwconv_wgrad_param(ctypes.byref(d), x.ptr(), dz.ptr(), dz.cs, dz.coff, C, _ptr(into), 1,
-                                           _ptr(ws), _stream()), "sf_dwconv_wgrad_param")
+        _call("sf_dwconv_wgrad_param", ctypes.byref(d), x.ptr(), dz.ptr(), dz.cs, dz.coff, C, _ptr(into), 1, _ptr(ws))
     else:
         dw = torch.empty((kernel[0] * kernel[1] * kernel[2], C), dtype=torch.float32, device=x.buf.device)
-        _check(lib().sf_dwconv_wgrad(ctypes.byref(d), x.ptr(), dz.ptr(), dz.cs, dz.coff, C, _ptr(dw), _ptr(ws),
-                                     _stream()), "sf_dwconv_wgrad")
+        _call("sf_dwconv_wgrad", ctypes.byref(d), x.ptr(), dz.ptr(), dz.cs, dz.coff, C, _ptr(dw), _ptr(ws))
     if dx is not None:
-        _check(lib().sf_dwconv_dgrad(ctypes.byref(d), dz.ptr(), dz.cs, dz.coff, _ptr(wp), dx.ptr(), dx.cs, dx.coff,
-                                     C, _stream()), "sf_dwconv_dgrad")
+        _call("sf_dwconv_dgrad", ctypes.byref(d), dz.ptr(), dz.cs, dz.coff, _ptr(wp), dx.ptr(), dx.cs, dx.coff, C)
     return dw
 
 
 def dwconv_dgrad(x, dz, wp, kernel, stride, padding, dx):
     """dx += transposed depthwise conv of dz (data gradient only: constant-weight pooling)."""
     d = _dw_desc(x, dz, kernel, stride, padding, wp.shape[1])
-    _check(lib().sf_dwconv_dgrad(ctypes.byref(d), dz.ptr(), dz.cs, dz.coff, _ptr(wp), dx.ptr(), dx.cs, dx.coff,
-                                 x.C, _stream()), "sf_dwconv_dgrad")
+    _call("sf_dwconv_dgrad", ctypes.byref(d), dz.ptr(), dz.cs, dz.coff, _ptr(wp), dx.ptr(), dx.cs, dx.coff, x.C)
     return dx
 
 
 def gather_add(src, src_cmul, out, accumulate=True):
     """out[r, c] (+)= src[r, src.coff + c*src_cmul]."""
-    _check(lib().sf_gather_add(src.ptr(), src.cs, src.coff, src_cmul, out.ptr(), out.cs, out.coff, out.rows, out.C,
-                               1 if accumulate else 0, _stream()), "sf_gather_add")
+    _call("sf_gather_add", src.ptr(), src.cs, src.coff, src_cmul, out.ptr(), out.cs, out.coff, out.rows, out.C,
+          1 if accumulate else 0)
     return out
 
 
@@ -1483,8 +1413,7 @@ def roi_tpool(x):
     """AvgPool3d([T,1,1], stride 1) + squeeze: Act [N,T,H,W,C] -> dense Act [N,1,H,W,C]."""
     _require_gpu(x.buf, "roi_tpool")
     out = new_act(x, x.N, 1, x.H, x.W, x.C)
-    _check(lib().sf_roi_tpool_fwd(x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C, out.ptr(), _stream()),
-           "sf_roi_tpool_fwd")
+    _call("sf_roi_tpool_fwd", x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C, out.ptr())
     return out
 
 
@@ -1499,9 +1428,8 @@ def roi_align_max(x, boxes, resolution, spatial_scale, aligned, out):
     assert (out.N, out.T, out.H, out.W, out.C) == (K, 1, 1, 1, x.C), (out, K, x)
     arg = torch.empty((K, x.C), dtype=torch.uint8, device=x.buf.device)
     if K > 0:
-        _check(lib().sf_roi_align_max_fwd(x.ptr(), x.N, x.H, x.W, x.C, _ptr(boxes), K, int(resolution),
-                                          float(spatial_scale), 1 if aligned else 0, out.ptr(), out.cs, out.coff,
-                                          _ptr(arg), _stream()), "sf_roi_align_max_fwd")
+        _call("sf_roi_align_max_fwd", x.ptr(), x.N, x.H, x.W, x.C, _ptr(boxes), K, int(resolution),
+              float(spatial_scale), 1 if aligned else 0, out.ptr(), out.cs, out.coff, _ptr(arg))
     return arg
 
 
@@ -1515,17 +1443,16 @@ def roi_align_max_bwd(dy, arg, boxes, resolution, spatial_scale, aligned, dx, ac
     assert (dy.N, dy.T, dy.H, dy.W, dy.C) == (K, 1, 1, 1, dx.C), (dy, dx)
     if K == 0 and accumulate:
         return dx
-    _check(lib().sf_roi_align_max_bwd(dy.ptr() if K else None, dy.cs, dy.coff, _ptr(arg), _ptr(boxes), K, dx.N,
-                                      dx.T, dx.H, dx.W, dx.C, int(resolution), float(spatial_scale),
-                                      1 if aligned else 0, dx.ptr(), dx.cs, dx.coff, 1 if accumulate else 0,
-                                      _stream()), "sf_roi_align_max_bwd")
+    _call("sf_roi_align_max_bwd", dy.ptr() if K else None, dy.cs, dy.coff, _ptr(arg), _ptr(boxes), K, dx.N, dx.T,
+          dx.H, dx.W, dx.C, int(resolution), float(spatial_scale), 1 if aligned else 0, dx.ptr(), dx.cs, dx.coff,
+          1 if accumulate else 0)
     return dx
 
 
 def _window_desc(x, kernel, out_cs=0, out_coff=0):
-    kt, kh, kw = (int(k) for k in kernel)
-    return PoolDesc(x.N, x.T, x.H, x.W, x.C, x.cs, x.coff, x.T - kt + 1, x.H - kh + 1, x.W - kw + 1, out_cs, out_coff,
-                    kt, kh, kw, 1, 1, 1, 0, 0, 0, 1)
+    kernel = tuple(int(k) for k in kernel)
+    return _pool_desc(x, _out_thw(x, kernel, (1, 1, 1), (0, 0, 0)), out_cs, out_coff, kernel, (1, 1, 1), (0, 0, 0),
+                      True)
 
 
 def avgpool_window(x, kernel, out=None):
@@ -1542,8 +1469,7 @@ def avgpool_window(x, kernel, out=None):
     d.out_cs, d.out_coff = out.cs, out.coff
     # trace tag: ("avgpool_window", algorithmic HBM bytes = the input once + the output once)
     nbytes = 4 * (x.rows + out.rows) * x.C
-    _check(_traced(("avgpool_window", nbytes), lambda: lib().sf_avgpool_win_fwd(
-        ctypes.byref(d), x.ptr(), out.ptr(), _stream())), "sf_avgpool_win_fwd")
+    _call("sf_avgpool_win_fwd", ctypes.byref(d), x.ptr(), out.ptr(), tag=("avgpool_window", nbytes))
     return out
 
 
@@ -1558,9 +1484,8 @@ def avgpool_window_bwd(dy, dx, kernel, overwrite=False):
     assert (dy.N, dy.T, dy.H, dy.W, dy.C) == (dx.N, d.To, d.Ho, d.Wo, dx.C), (dy, dx, kernel)
     # trace tag: algorithmic HBM bytes = dy once + dx written (read and written when accumulating)
     nbytes = 4 * (dy.rows + dx.rows * (1 if overwrite else 2)) * dx.C
-    _check(_traced(("avgpool_window_bwd", nbytes), lambda: lib().sf_avgpool_win_bwd(
-        ctypes.byref(d), dy.ptr(), dy.cs, dy.coff, dx.ptr(), dx.cs, dx.coff, 1 if overwrite else 0, _stream())),
-        "sf_avgpool_win_bwd")
+    _call("sf_avgpool_win_bwd", ctypes.byref(d), dy.ptr(), dy.cs, dy.coff, dx.ptr(), dx.cs, dx.coff,
+          1 if overwrite else 0, tag=("avgpool_window_bwd", nbytes))
     return dx
 
 
@@ -1568,8 +1493,7 @@ def sigmoid_bwd(y, dy, dx, accumulate=True):
     """dx (+)= dy * y * (1 - y) over dense tensors of one shape."""
     _require_gpu(y, "sigmoid_bwd")
     assert y.shape == dy.shape == dx.shape and y.is_contiguous() and dy.is_contiguous() and dx.is_contiguous()
-    _check(lib().sf_sigmoid_bwd(_ptr(y), _ptr(dy), _ptr(dx), y.numel(), 1 if accumulate else 0, _stream()),
-           "sf_sigmoid_bwd")
+    _call("sf_sigmoid_bwd", _ptr(y), _ptr(dy), _ptr(dx), y.numel(), 1 if accumulate else 0)
     return dx
 
 
@@ -1605,11 +1529,9 @@ def epilogue_bwd(dy, y, dz, scale=None, relu=False, rep=1, dz_accumulate=False, 
     tail = (dz.ptr(), dz.cs, dz.coff, 1 if dz_accumulate else 0, dres.ptr() if dres is not None else None,
             dres.cs if dres is not None else 0, dres.coff if dres is not None else 0, 1 if dres_accumulate else 0)
     if extended:
-        _check(_traced(("epilogue_bwd", nbytes), lambda: lib().sf_epilogue_bwd_act(
-            *(head + (_act(act), groups) + tail + (_stream(),)))), "sf_epilogue_bwd_act")
+        _call("sf_epilogue_bwd_act", *head, _act(act), groups, *tail, tag=("epilogue_bwd", nbytes))
     else:
-        _check(_traced(("epilogue_bwd", nbytes), lambda: lib().sf_epilogue_bwd(
-            *(head + (1 if act else 0,) + tail + (_stream(),)))), "sf_epilogue_bwd")
+        _call("sf_epilogue_bwd", *head, 1 if act else 0, *tail, tag=("epilogue_bwd", nbytes))
     return dz
 
 
@@ -1632,10 +1554,9 @@ def dwconv_dgrad_epi(x, dy, y, wp, kernel, stride, padding, dx, scale=None, relu
     d = _dw_desc(x, dy, kernel, stride, padding, wp.shape[1])
     # trace tag: algorithmic HBM bytes = dy (and y) once + dx written (read and written when accumulating)
     nbytes = 4 * x.C * (dy.rows * (2 if relu else 1) + dx.rows * (2 if accumulate else 1))
-    _check(_traced(("dwconv_dgrad_epi", nbytes), lambda: lib().sf_dwconv_dgrad_epi(
-        ctypes.byref(d), dy.ptr(), dy.cs, dy.coff, y.ptr() if relu else None, y.cs if relu else 0,
-        y.coff if relu else 0, _ptr(wp), _ptr(scale), _act(relu), dx.ptr(), dx.cs, dx.coff, x.C,
-        1 if accumulate else 0, _stream())), "sf_dwconv_dgrad_epi")
+    _call("sf_dwconv_dgrad_epi", ctypes.byref(d), dy.ptr(), dy.cs, dy.coff, y.ptr() if relu else None,
+          y.cs if relu else 0, y.coff if relu else 0, _ptr(wp), _ptr(scale), _act(relu), dx.ptr(), dx.cs, dx.coff, x.C,
+          1 if accumulate else 0, tag=("dwconv_dgrad_epi", nbytes))
     return dx
 
 
@@ -1646,8 +1567,8 @@ def head_act_mean_bwd(logits, dout, act, dl, accumulate=False):
     _require_gpu(dl.buf, "head_act_mean_bwd")
     assert logits.coff == 0 and logits.C == logits.cs and dl.coff == 0 and dl.C == dl.cs
     assert dl.buf.shape == logits.buf.shape and dout.is_contiguous() and tuple(dout.shape) == (logits.N, logits.C)
-    _check(lib().sf_head_act_mean_bwd(logits.ptr(), _ptr(dout), logits.N, logits.T * logits.H * logits.W, logits.C,
-                                      act, dl.ptr(), 1 if accumulate else 0, _stream()), "sf_head_act_mean_bwd")
+    _call("sf_head_act_mean_bwd", logits.ptr(), _ptr(dout), logits.N, logits.T * logits.H * logits.W, logits.C, act,
+          dl.ptr(), 1 if accumulate else 0)
     return dl
 
 
@@ -1655,7 +1576,7 @@ def cam_weights(g):
     """w[n,t,c] = mean over h,w of the gradient view g -> torch [N, T, C]."""
     _require_gpu(g.buf, "cam_weights")
     w = torch.empty((g.N, g.T, g.C), dtype=torch.float32, device=g.buf.device)
-    _check(lib().sf_cam_weights(g.ptr(), g.cs, g.coff, g.N, g.T, g.H, g.W, g.C, _ptr(w), _stream()), "sf_cam_weights")
+    _call("sf_cam_weights", g.ptr(), g.cs, g.coff, g.N, g.T, g.H, g.W, g.C, _ptr(w))
     return w
 
 
@@ -1669,6 +1590,5 @@ def cam_map(a, w, want_raw=False):
     ws = torch.empty((lib().sf_cam_map_ws_floats(a.N, a.H, a.W, a.C),), dtype=torch.float32, device=dev)
     cam = torch.empty((a.N, a.T, a.H, a.W), dtype=torch.float32, device=dev)
     raw = torch.empty_like(cam) if want_raw else None
-    _check(lib().sf_cam_map(a.ptr(), a.cs, a.coff, _ptr(w), a.N, a.T, a.H, a.W, a.C, _ptr(ws), _ptr(raw), _ptr(cam),
-                            _stream()), "sf_cam_map")
+    _call("sf_cam_map", a.ptr(), a.cs, a.coff, _ptr(w), a.N, a.T, a.H, a.W, a.C, _ptr(ws), _ptr(raw), _ptr(cam))
     return (cam, raw) if want_raw else cam

@@ -1,5 +1,6 @@
 """CPU-side checks of the C-ABI boundary: the library loads and exports every symbol include/sfhip.h
-declares (no compute calls without a GPU), and the product path refuses to run without a GPU."""
+declares (no compute calls without a GPU), the binding's signature table says what the header's prototypes say, and
+the product path refuses to run without a GPU."""
 import os
 import re
 
@@ -26,6 +27,80 @@ def test_library_exports_every_declared_symbol(repo_root):
     assert sorted(sfhip.EXPORTS) == syms
     assert L.sf_abi_version() == 1
     assert L.sf_build_arch() == b"gfx950"
+
+
+def _header_prototypes(root):
+    """{symbol: (return type, [(parameter type, parameter name), ...])} of every prototype in include/sfhip.h, types
+    spelled without spaces in front of the `*`."""
+    txt = open(os.path.join(root, "include", "sfhip.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = re.sub(r"typedef struct (\w+) \{.*?\} \1;", "", txt, flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"\b(const char\s*\*|int|long)\s+(sf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+        assert name not in protos, "%s is declared twice" % name
+        args = []
+        for p in (params.split(",") if params.strip() != "void" else []):
+            m = re.fullmatch(r"(.*?)(\w+)", " ".join(p.split()))
+            args.append((re.sub(r"\s*\*\s*", "*", m.group(1)).strip(), m.group(2)))
+        protos[name] = (re.sub(r"\s*\*", "*", ret), args)
+    return protos
+
+
+# host-side arrays the library reads during the call: the only `const float*` that may be POINTER(c_float)
+_HOST_FLOAT_ARRAYS = {("sf_clip_prologue", "mean3"), ("sf_clip_prologue", "std3")}
+
+
+def _ctype_of(sfhip, symbol, ctype, pname=None):
+    """What the binding's table must say for the header's type `ctype` (a list of permitted ctypes)."""
+    import ctypes
+    exact = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float,
+             "const sf_conv_desc*": ctypes.POINTER(sfhip.ConvDesc), "const sf_pool_desc*": ctypes.POINTER(sfhip.PoolDesc),
+             "int*": ctypes.POINTER(ctypes.c_int)}
+    if pname is None:  # a return type
+        exact["const char*"] = ctypes.c_char_p
+    if ctype in exact:
+        return [exact[ctype]]
+    assert ctype.endswith("*"), "%s: the header type %r has no rule" % (symbol, ctype)
+    if ctype == "const float*" and (symbol, pname) in _HOST_FLOAT_ARRAYS:
+        return [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    return [ctypes.c_void_p]
+
+
+def signature_mismatches(sfhip, protos, table):
+    """Symbols of `table` ({symbol: (restype, [argtypes])}) that differ from the header's prototypes, with the reason."""
+    bad = {}
+    for name, (ret, args) in protos.items():
+        if name not in table:
+            continue
+        restype, argtypes = table[name]
+        if restype not in _ctype_of(sfhip, name, ret):
+            bad[name] = "returns %s, the table says %r" % (ret, restype)
+        elif argtypes is None and args:  # (the table itself must hold a list, empty for `(void)`: asserted by the test)
+            bad[name] = "no argtypes"
+        elif len(argtypes or []) != len(args):
+            bad[name] = "%d parameters, the table has %d" % (len(args), len(argtypes))
+        else:
+            for i, ((ctype, pname), have) in enumerate(zip(args, argtypes or [])):
+                if have not in _ctype_of(sfhip, name, ctype, pname):
+                    bad[name] = "parameter %d (%s %s) is %r in the table" % (i, ctype, pname, have)
+                    break
+    return bad
+
+
+def test_signature_table_matches_header(repo_root):
+    """include/sfhip.h is the authority for the C ABI: every prototype's return type and every parameter, position by
+    position, is what the binding's signature table hands to ctypes.  Reads the header and the table only."""
+    import sfhip
+    protos = _header_prototypes(repo_root)
+    table = sfhip._SIGNATURES
+    assert len(protos) >= len(table) >= 100
+    assert set(protos) == set(table)
+    assert sorted(protos) == _header_symbols(repo_root)  # the prototype pattern missed no declaration
+    assert sfhip.EXPORTS == list(table)
+    for name, sig in table.items():
+        assert len(sig) == 2 and isinstance(sig[1], list), name
+    assert signature_mismatches(sfhip, protos, table) == {}
+    assert table["sf_abi_version"] == (sfhip.ctypes.c_int, []) and table["sf_build_arch"][1] == []
 
 
 def test_descriptor_structs_match_header(repo_root):

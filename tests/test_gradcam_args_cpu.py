@@ -75,7 +75,7 @@ def test_entries_are_declared_exported_and_bound(repo_root):
             want = ctypes.c_void_p if "*" in p else (ctypes.c_float if p.startswith("float ") else ctypes.c_int)
             assert a is want, (name, p, a)
         assert fn.restype is (ctypes.c_long if m.group(1) == "long" else ctypes.c_int), name
-    assert "sf_cam_map_ws_floats" in sfhip._LONG_RET
+    assert sfhip._SIGNATURES["sf_cam_map_ws_floats"][0] is ctypes.c_long
 
 
 def test_null_pointers_are_refused():
