@@ -153,6 +153,7 @@ _SIGNATURES = {
     "sf_bn_bwd_apply": (_ci, _BN_BWD + _BN_APPLY_TAIL),
     "sf_bn_bwd_apply_first": (_ci, _BN_BWD + _BN_APPLY_TAIL),
     "sf_bn_bwd_apply_split": (_ci, _BN_BWD_SPLIT + _BN_APPLY_TAIL),
+    "sf_bn_frozen_bwd": (_ci, _VIEW * 3 + [_ci] * 7 + [_vp] * 3 + _VIEW * 2 + [_ci] + [_vp] * 4),
     # elementwise helpers, head, nonlocal softmax
     "sf_head_act_mean": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _vp]),
     "sf_head_act_mean_bwd": (_ci, [_vp, _vp, _ci, _ci, _ci, _ci, _vp, _ci, _vp]),
@@ -1143,6 +1144,52 @@ def bn_bwd(dy, y, z, mean, invstd, gamma, relu, rep=1, dres=None, dz_out=None, d
             dgamma_out[0][:C] = dgamma
             dgamma_out[1][:C] = dbeta
     return out, dgamma, dbeta
+
+
+def bn_frozen_bwd(dy, y, z, mean, invstd, gamma, relu, rep=1, dres=None, dres_overwrite=False, dz_out=None,
+                  grads=None, mask=None):
+    """Backward of an eval-mode (frozen) BatchNorm3d epilogue y = act(gamma * (z - mean) * invstd + beta + res) under a
+    training tape, ONE pass (sf_bn_frozen_bwd): dz = gamma * invstd * g over z (or into dz_out), dres (= | +=) g,
+    g = sum over the `rep` T-copies of dy * mask.  mean / invstd: the running statistics as [C] tensors; gamma None: a BN
+    without affine.  grads = (dgamma, dbeta): [>= C] float32 tensors the per-channel sums are ACCUMULATED into (zero-filled
+    temporaries, or the parameters' .grad under the gradient sink); None: no parameter gradients.  relu: False / True /
+    6; mask: the byte mask affine(mask=...) left, read instead of y.  Returns dz."""
+    if dy is None or z is None or (relu and mask is None and y is None):
+        raise SfhipError("bn_frozen_bwd: dy, z and (with an activation) y or its mask are required")
+    for name, a in (("dy", dy), ("z", z), ("dz", dz_out), ("dres", dres), ("y", y if (relu and mask is None) else None)):
+        if a is not None:
+            _require_gpu(a.buf, "bn_frozen_bwd(%s)" % name)
+    C, dev = z.C, z.buf.device
+    if dres is not None and rep != 1:
+        raise SfhipError("bn_frozen_bwd: the residual's gradient is only defined without a T repeat (rep = %d)" % rep)
+    if (dy.N, dy.T, dy.H, dy.W, dy.C) != (z.N, z.T * rep, z.H, z.W, C):
+        raise SfhipError("bn_frozen_bwd: dy %r does not match z %r repeated %d times" % (dy, z, rep))
+    vecs = [("mean", mean), ("invstd", invstd)] + ([("gamma", gamma)] if gamma is not None else [])
+    for name, v in vecs:
+        _require_gpu(v, "bn_frozen_bwd(%s)" % name)
+        if v.numel() < C or not v.is_contiguous():
+            raise SfhipError("bn_frozen_bwd: %s must be a contiguous tensor of at least %d floats" % (name, C))
+    dgp = dbp = ws = None
+    if grads is not None:
+        for name, v in (("dgamma", grads[0]), ("dbeta", grads[1])):
+            _require_gpu(v, "bn_frozen_bwd(%s)" % name)
+            if v.numel() < C or not v.is_contiguous():
+                raise SfhipError("bn_frozen_bwd: %s must be a contiguous tensor of at least %d floats" % (name, C))
+        dgp, dbp = _ptr(grads[0]), _ptr(grads[1])
+        ws = torch.empty((lib().sf_bn_bwd_ws_floats(C),), dtype=torch.float32, device=dev)
+    yp, ycs, yco = (y.ptr(), y.cs, y.coff) if (y is not None and relu) else (None, 0, 0)
+    code = 2 if relu == 6 else (1 if relu else 0)
+    if mask is not None and relu:  # the byte mask affine(mask=...) left: read instead of the activation
+        if rep != 1 or mask.numel() != z.rows * (C // 4) or not mask.is_cuda:
+            raise SfhipError("bn_frozen_bwd: the byte mask holds rows * C/4 bytes of an un-repeated layer")
+        yp, ycs, yco, code = _ptr(mask), C // 4, 0, 3
+    out = z if dz_out is None else dz_out
+    _call("sf_bn_frozen_bwd", dy.ptr(), dy.cs, dy.coff, yp, ycs, yco, z.ptr(), z.cs, z.coff, z.N, z.T, z.H, z.W, C,
+          rep, code, _ptr(mean.detach()), _ptr(invstd.detach()), _ptr(gamma.detach()) if gamma is not None else None,
+          out.ptr(), out.cs, out.coff, dres.ptr() if dres is not None else None,
+          dres.cs if dres is not None else 0, dres.coff if dres is not None else 0, 0 if dres_overwrite else 1,
+          dbp, dgp, _ptr(ws))
+    return out
 
 
 def maxpool_bwd(x, y, dy, dx, kernel, stride, padding=(0, 0, 0), overwrite=False):

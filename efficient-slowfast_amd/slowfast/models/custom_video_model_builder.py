@@ -69,9 +69,9 @@ class FuseFastAndSlow(nn.Module):
             if unfused:
                 z = self.attention_channel_f2s.run(x_f, alpha=a)
                 engine.bn_eval_apply(self.bn_f2s, z, relu=True, out=s_wide.slice(x_s.C, self._c_f2s))
-            elif self.bn_f2s.training:  # batch statistics sit between the gate and the ReLU: one extra pass
-                z = self.attention_channel_f2s.run(x_f, alpha=a)
-                engine.bn_train_apply(self.bn_f2s, z, relu=True, out=s_wide.slice(x_s.C, self._c_f2s))
+            elif engine.bn_unfused(self.bn_f2s):  # batch statistics sit between the gate and the ReLU: one extra pass
+                z = self.attention_channel_f2s.run(x_f, alpha=a)  # (a frozen BN under a training tape: its own pass too)
+                engine.bn_apply(self.bn_f2s, z, relu=True, out=s_wide.slice(x_s.C, self._c_f2s))
             else:
                 sc, bi = engine.bn_affine(self.bn_f2s)
                 self.attention_channel_f2s.run(x_f, alpha=a, scale=sc, bias=bi, relu=True,
@@ -82,9 +82,9 @@ class FuseFastAndSlow(nn.Module):
             if unfused:
                 z = self.attention_spatial_s2f.run(y)
                 engine.bn_eval_apply(self.bn_s2f, z, relu=True, rep=a, out=f_wide.slice(0, self._c_s2f))
-            elif self.bn_s2f.training:
+            elif engine.bn_unfused(self.bn_s2f):
                 z = self.attention_spatial_s2f.run(y)
-                engine.bn_train_apply(self.bn_s2f, z, relu=True, rep=a, out=f_wide.slice(0, self._c_s2f))
+                engine.bn_apply(self.bn_s2f, z, relu=True, rep=a, out=f_wide.slice(0, self._c_s2f))
             else:
                 sc, bi = engine.bn_affine(self.bn_s2f)
                 self.attention_spatial_s2f.run(y, scale=sc, bias=bi, relu=True, alpha=a,

@@ -695,10 +695,97 @@ def bn_affine(bn, conv_bias=None):
     return _cached(bn, "_sf_affine", _key(w, b, stat.running_mean, stat.running_var, conv_bias), make)
 
 
+def _taped_training():
+    t = tape()
+    return t is not None and not isinstance(t, EvalTape)
+
+
+def bn_unfused(bn):
+    """The norm layer runs as its own pass behind a raw producer: in training mode (batch statistics), and in eval mode
+    under a TRAINING tape — a frozen BN (utils.misc.frozen_bn_stats, misc.py:246-254), whose gamma / beta still train.
+    A plain eval forward and an EvalTape keep the folded one-launch forms."""
+    return bn.training or _taped_training()
+
+
+def bn_apply(bn, z, conv_stats=None, **kw):
+    """bn_train_apply or bn_frozen_apply, by bn.training (the decision is per layer)."""
+    if bn.training:
+        return bn_train_apply(bn, z, conv_stats=conv_stats, **kw)
+    return bn_frozen_apply(bn, z, **kw)
+
+
+def _bn_frozen_stats(bn):
+    """(running mean, 1 / sqrt(running var + eps)) of an eval-mode norm layer, cached like bn_affine's pair."""
+    stat = bn.bn if _sub_bn(bn) else bn  # SubBatchNorm3d evaluates with the aggregated `bn` statistics
+    return _cached(bn, "_sf_frozen", _key(stat.running_mean, stat.running_var),
+                   lambda: (stat.running_mean.detach().float().contiguous(),
+                            (1.0 / torch.sqrt(stat.running_var + stat.eps)).detach().contiguous()))
+
+
+def bn_frozen_apply(bn, z, res=None, relu=False, rep=1, out=None, out_reserve=(0, 0), keep=None, out_cmul=1):
+    """Eval-mode (frozen) BatchNorm3d on the raw tensor z under a training tape: ONE affine(+residual)(+ReLU)(+T-repeat)
+    pass with bn_affine's scale and bias — the running statistics, which are not touched — leaving the byte mask for the
+    backward; the tape closure is ONE sf_bn_frozen_bwd pass that writes dL/dz over z (where the producer's backward
+    looks for it, as bn_train_apply), the residual's gradient, and accumulates dgamma / dbeta (gamma and beta stay
+    trainable: eval() does not freeze them).  Untaped it is the same affine pass and nothing else."""
+    check_bn(bn)
+    scale, shift = bn_affine(bn)
+    zz = z if keep is None else z.slice(0, keep)
+    nk = z.C if keep is None else keep
+    if keep is not None:  # channel-sliced BN (GhostModule [:oup])
+        scale, shift = scale[:keep].contiguous(), shift[:keep].contiguous()
+    t = tape()
+    shuffled = t is not None and out_cmul != 1
+    mk = {} if (t is not None and relu) else None
+    if shuffled:
+        # taped: a channel-shuffled store is an explicit (taped) strided copy of the dense result
+        y = sfhip.affine(zz, scale, shift, res=res, relu=relu, rep=rep, mask=mk)
+    else:
+        y = sfhip.affine(zz, scale, shift, res=res, relu=relu, rep=rep, out=out, out_reserve=out_reserve,
+                         out_cmul=out_cmul, mask=mk)
+    mask = mk.get("bytes") if mk else None
+    if t is not None:
+        mean, invstd = _bn_frozen_stats(bn)
+        weight, bias = getattr(bn, "weight", None), getattr(bn, "bias", None)
+
+        def bwd():
+            dres, first = None, False
+            if res is not None:  # first writer of the residual branch's gradient: write it, no zero fill / read
+                fresh = t.grad_of_uninitialised(res) if (res.C == zz.C and rep == 1) else None
+                dres, first = (fresh, True) if fresh is not None else (t.grad_of(res), False)
+            grads = dg_ = db_ = None
+            if weight is not None and bias is not None and t.param_grads:
+                wt, bt = t.pgrad_target(weight), t.pgrad_target(bias)
+                if wt is not None and bt is not None:  # the finish kernel accumulates into .grad
+                    grads = (wt, bt)
+                else:
+                    dg_ = torch.zeros(z.C, dtype=torch.float32, device=z.buf.device)
+                    db_ = torch.zeros(z.C, dtype=torch.float32, device=z.buf.device)
+                    grads = (dg_, db_)
+            sfhip.bn_frozen_bwd(t.grad_of(y), y, zz, mean, invstd, weight, relu, rep=rep, dres=dres,
+                                dres_overwrite=first, dz_out=zz, grads=grads, mask=mask)
+            if keep is not None and keep < z.C:  # sliced-away channels (GhostModule [:oup]) get no gradient
+                rest = z.slice(keep, z.C - keep)
+                sfhip.axpy(rest, rest, alpha=0.0, accumulate=False)
+            if dg_ is not None:
+                t.add_pgrad(weight, dg_)
+                t.add_pgrad(bias, db_)
+
+        t.record(bwd)  # afterwards z's buffer holds dL/dz for the producer's backward
+    if shuffled:  # recorded AFTER the BN op so that its backward (the gather) runs first
+        return copy_channels(y, out, out_cmul=out_cmul)
+    return y
+
+
 def norm_forward(bn, x):
     """A norm layer called on its own (NCTHW tensor or Act): the HIP statistics / normalise kernels."""
     (a,) = enter([x])
-    y = bn_train_apply(bn, a) if bn.training else sfhip.affine(a, *bn_affine(bn))
+    if bn.training:
+        y = bn_train_apply(bn, a)
+    elif _taped_training():
+        y = bn_frozen_apply(bn, a)
+    else:
+        y = sfhip.affine(a, *bn_affine(bn))
     return leave([y])[0]
 
 
@@ -852,21 +939,22 @@ def _is_grouped(conv):
 def conv_bn_act(x, conv, bn=None, relu=False, res=None, out=None, out_reserve=(0, 0), out_cmul=1, cout=None,
                 shuffle=False):
     """nn.Conv3d [+ BatchNorm3d] [+ residual] [+ ReLU].  Eval: ONE kernel launch (BN folded into the
-    epilogue).  Training: raw conv -> batch statistics -> one normalise/residual/ReLU pass.
+    epilogue).  Training: raw conv -> batch statistics -> one normalise/residual/ReLU pass.  A frozen BN (eval mode
+    under a training tape): raw conv -> bn_frozen_apply, the conv's own gradients recorded as in training.
     shuffle (grouped convs only): channel_shuffle(., conv.groups) applied to the result."""
     if _is_grouped(conv):
         assert out_cmul == 1 and cout is None, "grouped convs have their own shuffle"
-        if bn is not None and bn.training:
+        if bn is not None and bn_unfused(bn):  # training mode, or frozen (eval mode) under a training tape
             z = grouped_conv(x, conv, bias=conv.bias)
             _record_grouped_conv(x, conv, z)
             if not shuffle:
-                return bn_train_apply(bn, z, res=res, relu=relu, out=out, out_reserve=out_reserve)
-            y = bn_train_apply(bn, z, res=res, relu=relu)
+                return bn_apply(bn, z, res=res, relu=relu, out=out, out_reserve=out_reserve)
+            y = bn_apply(bn, z, res=res, relu=relu)
             return channel_shuffle(y, conv.groups, out=out, out_reserve=out_reserve)
         scale, bias = bn_affine(bn, conv.bias) if bn is not None else (None, conv.bias)
         t = tape()
-        if t is not None and not isinstance(t, EvalTape):
-            raise NotImplementedError("taped grouped conv with a folded (eval-mode) BN epilogue")
+        if t is not None and not isinstance(t, EvalTape):  # (bn is None here: no model has such a layer)
+            raise NotImplementedError("taped grouped conv without a norm layer behind it")
         y = grouped_conv(x, conv, scale=scale, bias=bias, relu=relu, res=res, out=out, out_reserve=out_reserve,
                          shuffle=shuffle)
         if t is not None:
@@ -874,12 +962,12 @@ def conv_bn_act(x, conv, bn=None, relu=False, res=None, out=None, out_reserve=(0
         return y
     assert not shuffle or conv.groups == 1, "channel_shuffle of a depthwise conv's output is not used by any model"
     wp = packed_weight(conv)
-    if bn is not None and bn.training:
+    if bn is not None and bn_unfused(bn):  # training mode, or frozen (eval mode) under a training tape
         k, s, p, d = conv.kernel_size, conv.stride, conv.padding, conv.dilation
         st = None
         if conv.groups == 1:
             # plain BatchNorm3d: its batch statistics come out of the conv's epilogue (no extra pass over z)
-            want = _plain_bn(bn) and bn.affine
+            want = bn.training and _plain_bn(bn) and bn.affine
             z = sfhip.conv(x, wp, k, s, p, d, bias=conv.bias, stats=want)
             z, st = z if want else (z, None)
             _record_conv(x, conv.weight, conv.bias, wp.shape, z, k, s, p, d)
@@ -901,8 +989,8 @@ def conv_bn_act(x, conv, bn=None, relu=False, res=None, out=None, out_reserve=(0
                         t.add_pgrad(conv.bias, _colsum(z))
 
                 t.record(bwd_dw)
-        return bn_train_apply(bn, z, res=res, relu=relu, out=out, out_reserve=out_reserve, keep=cout,
-                              out_cmul=out_cmul, conv_stats=st)
+        return bn_apply(bn, z, res=res, relu=relu, out=out, out_reserve=out_reserve, keep=cout, out_cmul=out_cmul,
+                        conv_stats=st)
     if bn is not None:
         scale, bias = bn_affine(bn, conv.bias)
     else:
@@ -915,8 +1003,8 @@ def conv_bn_act(x, conv, bn=None, relu=False, res=None, out=None, out_reserve=(0
         if isinstance(t, EvalTape):
             _record_eval_conv(t, x, conv, wp, y, scale, relu, res, out_cmul)
         elif t is not None:
-            if bn is not None or res is not None or out_cmul != 1:
-                raise NotImplementedError("taped conv with a folded (eval-mode) BN / residual epilogue")
+            if res is not None or out_cmul != 1:  # (bn is None here: a frozen BN took the un-fused branch above)
+                raise NotImplementedError("taped conv without a norm layer but with a residual or an interleaved store")
             if relu:  # bare conv + ReLU (no BN): dL/dz = dL/dy masked by the activation's output
                 def masked():
                     dz = sfhip.new_act(y, y.N, y.T, y.H, y.W, y.C)
@@ -1062,8 +1150,8 @@ def stem_conv_bn_relu(x, conv, bn, relu=True):
 
     wp = _cached(conv, "_sf_wp_stem", _key(conv.weight), make)
     thw = (T + 2 * pT - kT + 1, Ho, Wo)
-    if bn.training:
-        want = _plain_bn(bn) and bn.affine
+    if bn_unfused(bn):  # training mode, or frozen (eval mode) under a training tape
+        want = bn.training and _plain_bn(bn) and bn.affine
         z = sfhip.conv(view, wp, (kT, kH, 1), (1, sH, 1), (pT, 0, 0), bias=conv.bias, cin=4 * kW, out_thw=thw,
                        stats=want)
         z, st = z if want else (z, None)
@@ -1075,7 +1163,7 @@ def stem_conv_bn_relu(x, conv, bn, relu=True):
         _record_conv(view, conv.weight, conv.bias, wp.shape, z, (kT, kH, 1), (1, sH, 1), (pT, 0, 0), (1, 1, 1),
                      x_needs_grad=False, cin=4 * kW, unpack=unpack, fold_kw=kW)
         _record_stem_input_grad(x, conv, z, view, (N, C, T, H, W), (pH, pW, Wp), Wo)
-        return bn_train_apply(bn, z, relu=relu, conv_stats=st)
+        return bn_apply(bn, z, relu=relu, conv_stats=st)
     scale, bias = bn_affine(bn, conv.bias)
     return sfhip.conv(view, wp, (kT, kH, 1), (1, sH, 1), (pT, 0, 0), scale=scale, bias=bias, relu=relu,
                       cin=4 * kW, out_thw=thw)
@@ -1088,10 +1176,10 @@ def _stem1_conv_bn_relu(x, conv, bn, relu, geom):
     kT, pT = conv.kernel_size[0], conv.padding[0]
     buf = x.buf if isinstance(x, sfhip.PackedClip) else sfhip.ncthw1_pack(x, pH, pW, Wp)
     w = conv.weight.detach()
-    if bn.training:
+    if bn_unfused(bn):  # training mode, or frozen (eval mode) under a training tape
         z = sfhip.stem1_fwd(buf, w, pT, bias=conv.bias)
         _record_stem1_wgrad(buf, conv, z)
-        return bn_train_apply(bn, z, relu=relu)
+        return bn_apply(bn, z, relu=relu)
     scale, bias = bn_affine(bn, conv.bias)
     return sfhip.stem1_fwd(buf, w, pT, scale=scale, bias=bias, relu=relu)
 

@@ -82,7 +82,7 @@ class GhostModule(nn.Module):
         init = pc[0].out_channels
         keep = self.oup - init  # channels of the cheap half that survive the [:oup] slice
         out = sfhip.new_act(x, x.N, x.T, x.H, x.W, self.oup, reserve[0], reserve[1])
-        training = pc[1].training
+        training = engine.bn_unfused(pc[1])  # also a frozen BN under a training tape: the taped add below
         if res is None:
             x1 = engine.conv_bn_act(x, pc[0], pc[1], relu=self.relu, out=out.slice(0, init))
             engine.conv_bn_act(x1, co[0], co[1], relu=self.relu, out=out.slice(init, keep), cout=keep)

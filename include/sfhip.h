@@ -447,6 +447,26 @@ int sf_bn_bwd_apply_first(const float* dy, int dy_cs, int dy_coff, const float* 
                           const float* mean, const float* invstd, const float* gamma, const float* dbeta,
                           const float* dgamma, float* dz, int dz_cs, int dz_coff, float* dres, int dres_cs,
                           int dres_coff, void* stream);
+/* sf_bn_frozen_bwd: backward of an EVAL-mode BatchNorm3d epilogue under a training tape — the layers
+ * misc.frozen_bn_stats (misc.py:246-254) has put into eval() while the model trains; torch.nn.BatchNorm3d eval
+ * semantics: the running statistics are constants, gamma and beta stay trainable:
+ *     y = act(gamma * (z - mean) * invstd + beta + res),  mean = running_mean, invstd = 1 / sqrt(running_var + eps),
+ *     y repeated `rep` times along T;   g = sum_{q<rep} dy * m  (m: the activation's mask, as sf_bn_bwd_*: relu 0 / 1 /
+ *     2 / SF_BN_MASK_BYTES);   dz = gamma * invstd * g  (gamma NULL: 1; dz may alias z);   dres (=|+=) g  (rep must be
+ *     1; dres_accumulate == 0 writes every element: the first writer needs no zero fill);
+ *     dbeta[c] += sum g;   dgamma[c] += sum g * (z - mean) * invstd.
+ * dz does not depend on the sums, so ONE pass reads dy, the mask and z once, writes dz (and dres) and leaves per-block
+ * partial sums in ws (sf_bn_bwd_ws_floats(C) floats); a second small kernel adds them in a fixed order in fp64 and
+ * ACCUMULATES into dbeta / dgamma — zero-filled temporaries or the parameters' .grad.  dbeta == dgamma == NULL (a BN
+ * without affine): dz and dres only, ws may be NULL.  Null pointers, non-positive sizes, a slice outside its pitch or
+ * rep > 1 with dres return SF_EINVAL with nothing launched; 64-bit element offsets; float4 kernel when C, every pitch
+ * and offset are multiples of 4 and dy, y, z, dz, dres are 16-byte aligned, scalar kernel otherwise; no atomics, one
+ * owner per output element, fixed summation order: bitwise reproducible.                                          */
+int sf_bn_frozen_bwd(const float* dy, int dy_cs, int dy_coff, const float* y, int y_cs, int y_coff,
+                     const float* z, int z_cs, int z_coff, int N, int T, int H, int W, int C, int rep, int relu,
+                     const float* mean, const float* invstd, const float* gamma, float* dz, int dz_cs, int dz_coff,
+                     float* dres, int dres_cs, int dres_coff, int dres_accumulate, float* dbeta, float* dgamma,
+                     float* ws, void* stream);
 
 /* MaxPool3d backward (equality gather; dx accumulates).  `d` is the forward descriptor.                 */
 int sf_maxpool_bwd(const sf_pool_desc* d, const float* x, const float* y, const float* dy, int dy_cs,
