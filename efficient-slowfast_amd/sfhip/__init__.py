@@ -177,6 +177,14 @@ _SIGNATURES = {
     "sf_cam_weights": (_ci, _VIEW + [_ci] * 5 + [_vp, _vp]),
     "sf_cam_map_ws_floats": (_cl, [_ci] * 4),
     "sf_cam_map": (_ci, _VIEW + [_vp] + [_ci] * 5 + [_vp, _vp, _vp, _vp]),
+    # global-context pooling, per-sample affine (ContextBlock3D, ChannelAttention)
+    "sf_ctx_pool_parts": (_ci, [_cl]),
+    "sf_ctx_pool_ws_floats": (_cl, [_ci, _cl, _ci]),
+    "sf_ctx_pool_fwd": (_ci, _VIEW + [_ci, _cl, _ci] + [_vp] * 6),
+    "sf_ctx_pool_bwd": (_ci, _VIEW + [_ci, _cl, _ci] + [_vp] * 5 + _VIEW + [_ci, _vp, _vp, _ci, _vp, _vp]),
+    "sf_sample_affine_ws_floats": (_cl, [_ci, _cl, _ci]),
+    "sf_sample_affine_fwd": (_ci, _VIEW + [_ci, _cl, _ci, _vp, _vp] + _VIEW + [_vp]),
+    "sf_sample_affine_bwd": (_ci, _VIEW * 2 + [_ci, _cl, _ci, _vp] + _VIEW + [_ci, _vp, _vp, _vp, _vp]),
 }
 EXPORTS = list(_SIGNATURES)
 
@@ -1639,3 +1647,101 @@ def cam_map(a, w, want_raw=False):
     raw = torch.empty_like(cam) if want_raw else None
     _call("sf_cam_map", a.ptr(), a.cs, a.coff, _ptr(w), a.N, a.T, a.H, a.W, a.C, _ptr(ws), _ptr(raw), _ptr(cam))
     return (cam, raw) if want_raw else cam
+
+
+# ------------------------------------------------------------------------------------------------ context pooling
+def _vec_nc(v, n, c, what):
+    """A dense [N, C] float32 device vector set (or None)."""
+    if v is not None:
+        _require_gpu(v, what)
+        if not v.is_contiguous() or v.numel() != n * c:
+            raise SfhipError("%s: expected a contiguous tensor of %d x %d floats, got %s" % (what, n, c, tuple(v.shape)))
+    return v
+
+
+def ctx_pool(x, w, b=None):
+    """Global-context pooling of ContextBlock3D ('att'): per sample softmax over the T*H*W positions of the logits
+    w . x[pos] + b, ctx[n, c] = sum_pos p[pos] * x[n, pos, c] — ONE pass over the view x (sf_ctx_pool_fwd).
+    w: [C] (any shape of C floats), b: [1] or None.  -> (ctx [N, C], lse [N])."""
+    _require_gpu(x.buf, "ctx_pool")
+    _vec_nc(w, 1, x.C, "ctx_pool(w)")
+    _vec_nc(b, 1, 1, "ctx_pool(b)")
+    dev, rows = x.buf.device, x.T * x.H * x.W
+    ctx = torch.empty((x.N, x.C), dtype=torch.float32, device=dev)
+    lse = torch.empty((x.N,), dtype=torch.float32, device=dev)
+    ws = torch.empty((lib().sf_ctx_pool_ws_floats(x.N, rows, x.C),), dtype=torch.float32, device=dev)
+    _call("sf_ctx_pool_fwd", x.ptr(), x.cs, x.coff, x.N, rows, x.C, _ptr(w), _ptr(b), _ptr(ctx), _ptr(lse), _ptr(ws),
+          tag="ctx_pool")
+    return ctx, lse
+
+
+def ctx_pool_bwd(x, w, b, lse, ctx, dctx, dx, accumulate=True, dw=None, db=None, dw_accumulate=False, want_dw=True):
+    """Backward of ctx_pool in ONE pass (sf_ctx_pool_bwd): dx (+)= dL/dx (accumulate=False: dx is written, the first
+    writer needs no zero fill).  want_dw: also dL/dw, into `dw` ([C] floats; dw_accumulate: added to it, e.g. a
+    parameter's .grad) or a new tensor; `db` (one float) receives the exact 0 the shift-invariant softmax leaves.
+    Returns dw (None without want_dw)."""
+    _require_gpu(x.buf, "ctx_pool_bwd")
+    _require_gpu(dx.buf, "ctx_pool_bwd(dx)")
+    n, c, dev, rows = x.N, x.C, x.buf.device, x.T * x.H * x.W
+    if (dx.N, dx.T, dx.H, dx.W, dx.C) != (x.N, x.T, x.H, x.W, c):
+        raise SfhipError("ctx_pool_bwd: dx %r does not match x %r" % (dx, x))
+    _vec_nc(w, 1, c, "ctx_pool_bwd(w)")
+    _vec_nc(b, 1, 1, "ctx_pool_bwd(b)")
+    _vec_nc(lse, n, 1, "ctx_pool_bwd(lse)")
+    _vec_nc(ctx, n, c, "ctx_pool_bwd(ctx)")
+    _vec_nc(dctx, n, c, "ctx_pool_bwd(dctx)")
+    ws = None
+    if want_dw:
+        if dw is None:
+            assert not dw_accumulate
+            dw = torch.empty((c,), dtype=torch.float32, device=dev)
+        _vec_nc(dw, 1, c, "ctx_pool_bwd(dw)")
+        _vec_nc(db, 1, 1, "ctx_pool_bwd(db)")
+        ws = torch.empty((lib().sf_ctx_pool_ws_floats(n, rows, c),), dtype=torch.float32, device=dev)
+    else:
+        dw = db = None
+    _call("sf_ctx_pool_bwd", x.ptr(), x.cs, x.coff, n, rows, c, _ptr(w), _ptr(b), _ptr(lse), _ptr(ctx), _ptr(dctx),
+          dx.ptr(), dx.cs, dx.coff, 1 if accumulate else 0, _ptr(dw), _ptr(db), 1 if dw_accumulate else 0, _ptr(ws),
+          tag="ctx_pool_bwd")
+    return dw
+
+
+def sample_affine(x, mul=None, add=None, out=None):
+    """out[n, pos, c] = x[n, pos, c] * mul[n, c] + add[n, c] (mul / add: [N, C] tensors or None = 1 / 0): the broadcast
+    of a per-sample channel vector over an activation, one pass (sf_sample_affine_fwd)."""
+    _require_gpu(x.buf, "sample_affine")
+    if out is None:
+        out = new_act(x, x.N, x.T, x.H, x.W, x.C)
+    elif (out.N, out.T, out.H, out.W, out.C) != (x.N, x.T, x.H, x.W, x.C):
+        raise SfhipError("sample_affine: out %r does not match x %r" % (out, x))
+    _require_gpu(out.buf, "sample_affine(out)")
+    _vec_nc(mul, x.N, x.C, "sample_affine(mul)")
+    _vec_nc(add, x.N, x.C, "sample_affine(add)")
+    _call("sf_sample_affine_fwd", x.ptr(), x.cs, x.coff, x.N, x.T * x.H * x.W, x.C, _ptr(mul), _ptr(add), out.ptr(),
+          out.cs, out.coff, tag="sample_affine")
+    return out
+
+
+def sample_affine_bwd(dy, dx, x=None, mul=None, accumulate=True, want_dmul=False, want_dadd=False):
+    """Backward of sample_affine in one pass over dy (sf_sample_affine_bwd): dx (+)= dy * mul; with want_dmul (needs x)
+    dmul[n, c] = sum_pos dy * x; with want_dadd dadd[n, c] = sum_pos dy.  -> (dmul, dadd), None where not wanted."""
+    _require_gpu(dy.buf, "sample_affine_bwd")
+    _require_gpu(dx.buf, "sample_affine_bwd(dx)")
+    n, c, dev, rows = dy.N, dy.C, dy.buf.device, dy.T * dy.H * dy.W
+    if (dx.N, dx.T, dx.H, dx.W, dx.C) != (dy.N, dy.T, dy.H, dy.W, c):
+        raise SfhipError("sample_affine_bwd: dx %r does not match dy %r" % (dx, dy))
+    if want_dmul:
+        if x is None or (x.N, x.T, x.H, x.W, x.C) != (dy.N, dy.T, dy.H, dy.W, c):
+            raise SfhipError("sample_affine_bwd: dmul needs x shaped like dy %r, got %r" % (dy, x))
+        _require_gpu(x.buf, "sample_affine_bwd(x)")
+    _vec_nc(mul, n, c, "sample_affine_bwd(mul)")
+    dmul = torch.empty((n, c), dtype=torch.float32, device=dev) if want_dmul else None
+    dadd = torch.empty((n, c), dtype=torch.float32, device=dev) if want_dadd else None
+    ws = None
+    if want_dmul or want_dadd:
+        ws = torch.empty((lib().sf_sample_affine_ws_floats(n, rows, c),), dtype=torch.float32, device=dev)
+    xv = x if want_dmul else None
+    _call("sf_sample_affine_bwd", dy.ptr(), dy.cs, dy.coff, xv.ptr() if xv is not None else None,
+          xv.cs if xv is not None else 0, xv.coff if xv is not None else 0, n, rows, c, _ptr(mul), dx.ptr(), dx.cs,
+          dx.coff, 1 if accumulate else 0, _ptr(dmul), _ptr(dadd), _ptr(ws), tag="sample_affine_bwd")
+    return dmul, dadd

@@ -699,6 +699,52 @@ long sf_cam_map_ws_floats(int N, int H, int W, int C);
 int sf_cam_map(const float* a, int a_cs, int a_coff, const float* w, int N, int T, int H, int W, int C, float* ws,
                float* raw, float* cam, void* stream);
 
+/* ---- Global-context pooling and the per-sample affine: ContextBlock3D / ChannelAttention (ctx_pool.hip) ------------
+ * wdf_attention_helper.py:339-358 (spatial_pool, pooling_type 'att') per sample n, over its rows_per_sample = T*H*W
+ * positions of the channel slice x (NDHWC, pitch cs, offset coff):
+ *     l[pos] = sum_c w[c] * x[n,pos,c] + b[0];   p = softmax_pos(l);   ctx[n,c] = sum_pos p[pos] * x[n,pos,c];
+ *     lse[n] = log sum_pos exp(l[pos]).
+ * sf_ctx_pool_fwd reads x ONCE: every workgroup owns a contiguous run of one sample's positions, keeps a running
+ * (max, sum, acc[C]) — online softmax, the logits and the maximum in fp64 so that only the rounded difference l - max
+ * reaches expf — and leaves its partial in ws; a finish kernel merges the sf_ctx_pool_parts(rows_per_sample) partials
+ * of a sample in a fixed order with the usual max-rescale.  w [C] and b [1] are device arrays (b NULL: 0); ctx [N][C]
+ * and lse [N] are dense; ws: sf_ctx_pool_ws_floats(N, rows_per_sample, C) floats (0 for dimensions out of range).
+ * sf_ctx_pool_bwd, ONE pass again: l is recomputed, p = exp(l - lse[n]),
+ *     dl[pos] = p * (x[n,pos,:] . dctx[n,:] - ctx[n,:] . dctx[n,:]);
+ *     dx[n,pos,c] (=|+=) p * dctx[n,c] + dl * w[c]     (accumulate == 0 writes every element of the slice: the first
+ *                                                        writer needs no zero fill; else dx = prior + that value);
+ *     dw[c] (=|+=) sum_{n,pos} dl * x[n,pos,c]          (per-workgroup partial sums in ws, added in fp64 in a fixed order
+ *                                                        by a finish kernel; dw_accumulate != 0 accumulates, e.g. into
+ *                                                        the parameter's .grad);
+ *     db[0] = 0 exactly when dw_accumulate == 0 (the softmax is shift invariant: nothing is computed; untouched when
+ *     accumulating).  dw NULL: activation gradient only (db must be NULL too, ws may be NULL); db may be NULL.
+ * Both: 1 <= N <= 65535, 1 <= C <= 2048; null pointers, non-positive sizes or a slice outside its pitch return
+ * SF_EINVAL with nothing launched; no host synchronisation; 64-bit element offsets; float4 kernels when C, every pitch
+ * and offset are multiples of 4 and x (and dx) are 16-byte aligned, scalar kernels otherwise; no atomics, one owner per
+ * output element, fixed summation order: bitwise reproducible.                                                      */
+int sf_ctx_pool_parts(long rows_per_sample);
+long sf_ctx_pool_ws_floats(int N, long rows_per_sample, int C);
+int sf_ctx_pool_fwd(const float* x, int cs, int coff, int N, long rows_per_sample, int C, const float* w,
+                    const float* b, float* ctx, float* lse, float* ws, void* stream);
+int sf_ctx_pool_bwd(const float* x, int cs, int coff, int N, long rows_per_sample, int C, const float* w,
+                    const float* b, const float* lse, const float* ctx, const float* dctx, float* dx, int dx_cs,
+                    int dx_coff, int accumulate, float* dw, float* db, int dw_accumulate, float* ws, void* stream);
+/* sf_sample_affine_fwd: out[n,pos,c] = x[n,pos,c] * mul[n,c] + add[n,c], mul / add dense [N][C] device arrays, either
+ * may be NULL (1 / 0) — the broadcast fusion of ContextBlock3D.forward (wdf_attention_helper.py:371-378) and, with
+ * mul = 1 + sigmoid(e), ChannelAttention's x * y + x (:121-124).  out may alias x element for element.
+ * sf_sample_affine_bwd, one pass over dy (and over x when dmul is wanted):
+ *     dx[n,pos,c] (=|+=) dy[n,pos,c] * mul[n,c]   (accumulate as above);
+ *     dmul[n,c] = sum_pos dy * x;   dadd[n,c] = sum_pos dy    (written, not accumulated; either may be NULL; per-workgroup
+ *     partial sums in ws — sf_sample_affine_ws_floats floats, NULL allowed when both are NULL — added in fp64 in a
+ *     fixed order by a finish kernel).  x is only read when dmul != NULL.
+ * Limits, SF_EINVAL rules, float4 / scalar forms and reproducibility as for sf_ctx_pool_*.                          */
+long sf_sample_affine_ws_floats(int N, long rows_per_sample, int C);
+int sf_sample_affine_fwd(const float* x, int cs, int coff, int N, long rows_per_sample, int C, const float* mul,
+                         const float* add, float* out, int out_cs, int out_coff, void* stream);
+int sf_sample_affine_bwd(const float* dy, int dy_cs, int dy_coff, const float* x, int x_cs, int x_coff, int N,
+                         long rows_per_sample, int C, const float* mul, float* dx, int dx_cs, int dx_coff,
+                         int accumulate, float* dmul, float* dadd, float* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
