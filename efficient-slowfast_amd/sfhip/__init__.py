@@ -185,6 +185,10 @@ _SIGNATURES = {
     "sf_sample_affine_ws_floats": (_cl, [_ci, _cl, _ci]),
     "sf_sample_affine_fwd": (_ci, _VIEW + [_ci, _cl, _ci, _vp, _vp] + _VIEW + [_vp]),
     "sf_sample_affine_bwd": (_ci, _VIEW * 2 + [_ci, _cl, _ci, _vp] + _VIEW + [_ci, _vp, _vp, _vp, _vp]),
+    # stripe pooling, per-stripe broadcast add (Stripe_NonLocalBlock)
+    "sf_stripe_pool_fwd": (_ci, _VIEW + [_ci] * 7 + _VIEW + [_vp, _vp]),
+    "sf_stripe_add_fwd": (_ci, _VIEW * 2 + [_ci] * 6 + _VIEW + [_vp]),
+    "sf_stripe_pool_bwd": (_ci, _VIEW * 3 + [_vp] + [_ci] * 6 + _VIEW + [_ci, _vp]),
 }
 EXPORTS = list(_SIGNATURES)
 
@@ -1745,3 +1749,84 @@ def sample_affine_bwd(dy, dx, x=None, mul=None, accumulate=True, want_dmul=False
           xv.cs if xv is not None else 0, xv.coff if xv is not None else 0, n, rows, c, _ptr(mul), dx.ptr(), dx.cs,
           dx.coff, 1 if accumulate else 0, _ptr(dmul), _ptr(dadd), _ptr(ws), tag="sample_affine_bwd")
     return dmul, dadd
+
+
+# ------------------------------------------------------------------------------------------------ stripe pooling
+STRIPE_MODES = {"mean": 0, "max": 1, "meanmax": 2, "sum": 3}  # SF_STRIPE_*
+
+
+def _stripe_view(a, like, stripes, c, what):
+    """None, or the [N, T, S, 1, c] view `a` beside the activation `like`."""
+    if a is None:
+        return (None, 0, 0)
+    _require_gpu(a.buf, what)
+    if (a.N, a.T, a.H, a.W, a.C) != (like.N, like.T, stripes, 1, c):
+        raise SfhipError("%s: expected a [%d, %d, %d, 1, %d] view, got %r" % (what, like.N, like.T, stripes, c, a))
+    return (a.ptr(), a.cs, a.coff)
+
+
+def stripe_pool(x, stripes, mode="mean", out=None):
+    """Pooling over the `stripes` horizontal stripes of every frame of x [N,T,H,W,C] (H % stripes == 0), ONE pass over x
+    (sf_stripe_pool_fwd): mode 'mean', 'max', 'meanmax' (2C channels: mean | max) or 'sum'.
+    -> (out Act [N, T, stripes, 1, Cout], arg): arg is the int32 [N, T, stripes, C] position of every maximum inside
+    its stripe (the first of equal values), None for 'mean' / 'sum'."""
+    _require_gpu(x.buf, "stripe_pool")
+    if mode not in STRIPE_MODES:
+        raise SfhipError("stripe_pool: unknown mode %r" % (mode,))
+    stripes = int(stripes)
+    if stripes <= 0 or x.H % stripes != 0:
+        raise SfhipError("stripe_pool: %d stripes do not divide H = %d" % (stripes, x.H))
+    cout = 2 * x.C if mode == "meanmax" else x.C
+    if out is None:
+        out = new_act(x, x.N, x.T, stripes, 1, cout)
+    _stripe_view(out, x, stripes, cout, "stripe_pool(out)")
+    arg = None
+    if mode in ("max", "meanmax"):
+        arg = torch.empty((x.N, x.T, stripes, x.C), dtype=torch.int32, device=x.buf.device)
+    _call("sf_stripe_pool_fwd", x.ptr(), x.cs, x.coff, x.N, x.T, x.H, x.W, x.C, stripes, STRIPE_MODES[mode], out.ptr(),
+          out.cs, out.coff, _ptr(arg), tag="stripe_pool")
+    return out, arg
+
+
+def stripe_add(x, v, out=None):
+    """out[n,t,h,w,c] = x[n,t,h,w,c] + v[n,t,h // (H/S),c] for v [N,T,S,1,C]: the per-stripe broadcast add, one pass
+    (sf_stripe_add_fwd).  out: a view shaped like x (a slice of a wider buffer, or x itself), default a new one."""
+    _require_gpu(x.buf, "stripe_add")
+    _require_gpu(v.buf, "stripe_add(v)")
+    stripes = v.H
+    if stripes <= 0 or x.H % stripes != 0:
+        raise SfhipError("stripe_add: %d stripes do not divide H = %d" % (stripes, x.H))
+    vv = _stripe_view(v, x, stripes, x.C, "stripe_add(v)")
+    if out is None:
+        out = new_act(x, x.N, x.T, x.H, x.W, x.C)
+    elif (out.N, out.T, out.H, out.W, out.C) != (x.N, x.T, x.H, x.W, x.C):
+        raise SfhipError("stripe_add: out %r does not match x %r" % (out, x))
+    _require_gpu(out.buf, "stripe_add(out)")
+    _call("sf_stripe_add_fwd", x.ptr(), x.cs, x.coff, *vv, x.N, x.T, x.H, x.W, x.C, stripes, out.ptr(), out.cs,
+          out.coff, tag="stripe_add")
+    return out
+
+
+def stripe_pool_bwd(dx, stripes, dz=None, dmean=None, dmax=None, arg=None, accumulate=True):
+    """dx (+)= dz + dmean / (hs*W) + [position == arg] * dmax in one pass (sf_stripe_pool_bwd): the gradient of
+    z = x + broadcast(f(stripe_pool(x))) with respect to x, given dz (shaped like dx) and the gradients dmean / dmax
+    ([N,T,S,1,C] views) of the pooled values; each of the three may be None.  accumulate=False writes every element."""
+    _require_gpu(dx.buf, "stripe_pool_bwd(dx)")
+    stripes = int(stripes)
+    if stripes <= 0 or dx.H % stripes != 0:
+        raise SfhipError("stripe_pool_bwd: %d stripes do not divide H = %d" % (stripes, dx.H))
+    gz = (None, 0, 0)
+    if dz is not None:
+        _require_gpu(dz.buf, "stripe_pool_bwd(dz)")
+        if (dz.N, dz.T, dz.H, dz.W, dz.C) != (dx.N, dx.T, dx.H, dx.W, dx.C):
+            raise SfhipError("stripe_pool_bwd: dz %r does not match dx %r" % (dz, dx))
+        gz = (dz.ptr(), dz.cs, dz.coff)
+    gm = _stripe_view(dmean, dx, stripes, dx.C, "stripe_pool_bwd(dmean)")
+    gx = _stripe_view(dmax, dx, stripes, dx.C, "stripe_pool_bwd(dmax)")
+    if dmax is not None:
+        if arg is None or arg.dtype != torch.int32 or not arg.is_contiguous() or not arg.is_cuda or \
+                tuple(arg.shape) != (dx.N, dx.T, stripes, dx.C):
+            raise SfhipError("stripe_pool_bwd: dmax needs the int32 [N, T, S, C] positions stripe_pool returned")
+    _call("sf_stripe_pool_bwd", *gz, *gm, *gx, _ptr(arg) if dmax is not None else None, dx.N, dx.T, dx.H, dx.W, dx.C,
+          stripes, dx.ptr(), dx.cs, dx.coff, 1 if accumulate else 0, tag="stripe_pool_bwd")
+    return dx

@@ -1003,8 +1003,13 @@ def conv_bn_act(x, conv, bn=None, relu=False, res=None, out=None, out_reserve=(0
         if isinstance(t, EvalTape):
             _record_eval_conv(t, x, conv, wp, y, scale, relu, res, out_cmul)
         elif t is not None:
-            if res is not None or out_cmul != 1:  # (bn is None here: a frozen BN took the un-fused branch above)
-                raise NotImplementedError("taped conv without a norm layer but with a residual or an interleaved store")
+            if (res is not None and relu) or out_cmul != 1:  # (bn is None here: a frozen BN took the un-fused branch)
+                raise NotImplementedError("taped conv without a norm layer but with a residual behind an activation "
+                                          "or an interleaved store")
+            if res is not None:  # y = conv(x) + res (NonLocalBlock without its BN): dL/dres += dL/dy
+                def bwd_res():
+                    sfhip.axpy(t.grad_of(y), t.grad_of(res), 1.0, accumulate=True)
+                t.record(bwd_res)
             if relu:  # bare conv + ReLU (no BN): dL/dz = dL/dy masked by the activation's output
                 def masked():
                     dz = sfhip.new_act(y, y.N, y.T, y.H, y.W, y.C)

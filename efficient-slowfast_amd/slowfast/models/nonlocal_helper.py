@@ -72,10 +72,11 @@ class Nonlocal(nn.Module):
         return engine.conv_bn_act(y, self.conv_out, self.bn, relu=False, res=x, out_reserve=reserve)
 
 
-def dense_attention(theta, phi, g, softmax=True, sm_scale=1.0):
-    """Y = normalise(theta phi^T) g per sample: softmax(sm_scale * S) over the keys, or S / N_k (softmax=False:
-    Nonlocal's "dot_product").  theta [N, ., d] queries, phi [N, ., d] keys, g [N, ., dv] values, NDHWC views.  Taped.
-    Serves Nonlocal (d = 256 / 512) and SpatialAttention heads wider than the flash kernels' 128 channels
+def dense_attention(theta, phi, g, softmax=True, sm_scale=1.0, dot_scale=None):
+    """Y = normalise(theta phi^T) g per sample: softmax(sm_scale * S) over the keys, or S * dot_scale (softmax=False:
+    Nonlocal's "dot_product"; dot_scale None = 1 / N_k, Nonlocal's; NonLocalBlock and Stripe_NonLocalBlock of
+    wdf_attention_helper.py divide by the QUERY count).  theta [N, ., d] queries, phi [N, ., d] keys, g [N, ., dv] values,
+    NDHWC views.  Taped.  Serves Nonlocal (d = 256 / 512) and SpatialAttention heads wider than the flash kernels' 128 channels
     (SlowFastShuffleNet w2.0 / g3: d = 240 at s4_fuse, N <= 64 positions).  The softmax form streams through the
     cross-length kernels wherever they accept the views (one launch forward, the score matrix never in memory), the
     dot-product form through the associative gram / rowmat kernels (two launches forward, four backward, only the
@@ -94,7 +95,7 @@ def dense_attention(theta, phi, g, softmax=True, sm_scale=1.0):
             t.record(bwd_stream)
         return y
     if not softmax and sfhip.assoc_accepts(theta, phi, g):
-        inv_nk = 1.0 / nk
+        inv_nk = 1.0 / nk if dot_scale is None else float(dot_scale)
         Mt, M = sfhip.gram(g, phi, inv_nk, transposed=True)  # M^T = g^T phi / N_k [dv, d] and M [d, dv] per sample
         y = sfhip.rowmat(theta, Mt, 1.0)
         t = engine.tape()
@@ -107,10 +108,10 @@ def dense_attention(theta, phi, g, softmax=True, sm_scale=1.0):
                 sfhip.rowmat(g, D, inv_nk, out=t.grad_of(phi), accumulate=True)     # dphi += g D^T / N_k
             t.record(bwd_assoc)
         return y
-    return materialised_attention(theta, phi, g, softmax, sm_scale)
+    return materialised_attention(theta, phi, g, softmax, sm_scale, dot_scale)
 
 
-def materialised_attention(theta, phi, g, softmax=True, sm_scale=1.0):
+def materialised_attention(theta, phi, g, softmax=True, sm_scale=1.0, dot_scale=None):
     """dense_attention with one [N_q, N_k] score matrix per sample in memory (kept for the backward, which makes a
     second one): whatever the streaming and the associative kernels refuse.  Dense NDHWC buffers, d % 16 == 0."""
     N, d, dv = theta.N, theta.C, g.C
@@ -121,7 +122,8 @@ def materialised_attention(theta, phi, g, softmax=True, sm_scale=1.0):
     assert theta.cs == d and phi.cs == d and g.cs == dv and theta.coff == phi.coff == g.coff == 0
     dev = theta.buf.device
     nk_pad = (nk + 15) // 16 * 16
-    inv_nk = None if softmax else torch.full((max(nk, d),), 1.0 / nk, dtype=torch.float32, device=dev)
+    inv_nk = None if softmax else torch.full((max(nk, d),), 1.0 / nk if dot_scale is None else float(dot_scale),
+                                             dtype=torch.float32, device=dev)
 
     def transposed(a):  # [N, Tp, Hp, Wp, c] -> [N][c][nk_pad]: the packed weights of "multiply by a"
         t = sfhip.to_ncthw(a).view(N, a.C, nk)

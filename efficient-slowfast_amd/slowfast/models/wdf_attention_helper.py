@@ -4,8 +4,13 @@ the same kernels un-fused.
 
 ChannelAttention and ContextBlock3D (reference :97-124, :289-379) are the fork's swap-in alternatives for the CMDA
 halves and for stage-level context: same constructors, attributes and state_dict keys, forward on an NCTHW tensor or
-an Act (the same kind comes back), on the kernels of csrc/ctx_pool.hip.  The file's remaining two classes,
-NonLocalBlock and Stripe_NonLocalBlock, are out of scope: no model instantiates them."""
+an Act (the same kind comes back), on the kernels of csrc/ctx_pool.hip.
+
+NonLocalBlock and Stripe_NonLocalBlock (reference :129-195, :198-273) complete the file: the same constructors,
+attributes and state_dict keys, NCTHW tensor or Act in and the same kind out.  Their convs, max-pool and attention run
+on the kernels Nonlocal uses (engine.conv_bn_act, engine.maxpool, nonlocal_helper.dense_attention — with the scale rules
+of THIS file: softmax without 1/sqrt(d), 'dot' divided by the query count); the stripe pooling and the per-stripe
+broadcast add of Stripe_NonLocalBlock are the kernels of csrc/stripe_pool.hip.  Both are taped for training."""
 import torch
 import torch.nn as nn
 
@@ -239,8 +244,7 @@ class ContextBlock3D(nn.Module):
     library's GEMM kernels, the LayerNorm + ReLU between them (and their backward) are torch ops on [N, planes].
     'channel_mul': the reference builds nn.LayerNorm([planes, 1, 1]) for a [N, planes, 1, 1, 1] context, which
     PyTorch rejects unless planes == 1 — the constructor and the state_dict keys are kept, forward raises
-    NotImplementedError.  NonLocalBlock and Stripe_NonLocalBlock of the same reference file are out of scope (never
-    instantiated by any model)."""
+    NotImplementedError."""
 
     def __init__(self, inplanes, ratio=1., pooling_type='att', fusion_types=('channel_add',)):
         super(ContextBlock3D, self).__init__()
@@ -352,4 +356,164 @@ class ContextBlock3D(nn.Module):
     def forward(self, x, reserve=(0, 0)):
         if self.channel_mul_conv is not None:
             return self.run(x)  # raises before any tensor is touched
+        return _same_kind(self, x, reserve)
+
+
+def _block_attention(theta, phi, g, instance):
+    """f = theta phi^T; 'soft': softmax(f) g (no 1/sqrt(d)); 'dot': (f / f.shape[1]) g — f.shape[1] is the QUERY count
+    (wdf_attention_helper.py:185-190, :260-265), not Nonlocal's key count.  Through nonlocal_helper.dense_attention;
+    a key width none of its kernels takes raises — nothing here runs on torch."""
+    from .nonlocal_helper import dense_attention
+    soft = instance == 'soft'
+    if instance not in ('soft', 'dot'):
+        raise NotImplementedError("instance %r: the reference defines 'soft' and 'dot'" % (instance,))
+    taken = sfhip.xattn_accepts(theta, phi, g) if soft else sfhip.assoc_accepts(theta, phi, g)
+    if not taken and theta.C % 16 != 0:
+        raise NotImplementedError(
+            "no attention kernel takes a key width of %d (the streaming / associative kernels and the materialised "
+            "path, which needs a multiple of 16, all refuse): choose inter_channels as a multiple of 4" % theta.C)
+    nq = theta.T * theta.H * theta.W
+    return dense_attention(theta, phi, g, softmax=soft, sm_scale=1.0, dot_scale=1.0 / nq)
+
+
+def _refuse_eval_tape(name):
+    if isinstance(engine.tape(), engine.EvalTape):
+        raise NotImplementedError("Grad-CAM (the eval-mode tape) does not cover %s" % name)
+
+
+class NonLocalBlock(nn.Module):
+    """The fork's small non-local block (wdf_attention_helper.py:129-195, after STE-NVAN): theta / phi / g 1x1x1 convs,
+    f = theta phi^T over all T*H*W positions, softmax ('soft') or f / N_q ('dot'), y = f g, z = W(y) + x with W a conv +
+    zero-initialised BatchNorm3d (bn_layer) or a zero-initialised conv.  sub_sample wraps g and phi in
+    nn.Sequential(conv, MaxPool3d((1, 2, 2))) (keys g.0.* / phi.0.*): the keys and values are max-pooled (odd H / W
+    floored), so N_q = 4 N_k.  Convs through engine.conv_bn_act, the pool through engine.maxpool, the attention through
+    nonlocal_helper.dense_attention (streaming softmax / associative dot product), the residual in W's epilogue.  Taped
+    for training; the eval-mode tape raises, as Nonlocal's does."""
+
+    def __init__(self, in_channels, inter_channels=None, sub_sample=False, bn_layer=True, instance='soft'):
+        super(NonLocalBlock, self).__init__()
+        self.sub_sample = sub_sample
+        self.instance = instance
+        self.in_channels = in_channels
+        self.inter_channels = inter_channels
+        if self.inter_channels is None:
+            self.inter_channels = in_channels // 2
+            if self.inter_channels == 0:
+                self.inter_channels = 1
+        max_pool_layer = nn.MaxPool3d(kernel_size=(1, 2, 2))
+        self.g = nn.Conv3d(self.in_channels, self.inter_channels, kernel_size=1, stride=1, padding=0)
+        if bn_layer:
+            self.W = nn.Sequential(
+                nn.Conv3d(self.inter_channels, self.in_channels, kernel_size=1, stride=1, padding=0),
+                nn.BatchNorm3d(self.in_channels))
+            nn.init.constant_(self.W[1].weight, 0)
+            nn.init.constant_(self.W[1].bias, 0)
+        else:
+            self.W = nn.Conv3d(self.inter_channels, self.in_channels, kernel_size=1, stride=1, padding=0)
+            nn.init.constant_(self.W.weight, 0)
+            nn.init.constant_(self.W.bias, 0)
+        self.theta = nn.Conv3d(self.in_channels, self.inter_channels, kernel_size=1, stride=1, padding=0)
+        self.phi = nn.Conv3d(self.in_channels, self.inter_channels, kernel_size=1, stride=1, padding=0)
+        if sub_sample:
+            self.g = nn.Sequential(self.g, max_pool_layer)
+            self.phi = nn.Sequential(self.phi, max_pool_layer)
+
+    def run(self, x, reserve=(0, 0)):
+        _refuse_eval_tape("NonLocalBlock")
+        theta = engine.conv_bn_act(x, self.theta)
+        if self.sub_sample:  # conv, then the pool: the order of the reference's Sequential
+            ks = (1, 2, 2)
+            if x.H < 2 or x.W < 2:
+                raise ValueError("NonLocalBlock(sub_sample=True) needs H, W >= 2, got %r" % (x,))
+            phi = engine.maxpool(engine.conv_bn_act(x, self.phi[0]), ks, ks)
+            g = engine.maxpool(engine.conv_bn_act(x, self.g[0]), ks, ks)
+        else:
+            phi = engine.conv_bn_act(x, self.phi)
+            g = engine.conv_bn_act(x, self.g)
+        y = _block_attention(theta, phi, g, self.instance)
+        if isinstance(self.W, nn.Sequential):
+            return engine.conv_bn_act(y, self.W[0], self.W[1], res=x, out_reserve=reserve)
+        return engine.conv_bn_act(y, self.W, res=x, out_reserve=reserve)
+
+    def forward(self, x, reserve=(0, 0)):
+        return _same_kind(self, x, reserve)
+
+
+class Stripe_NonLocalBlock(nn.Module):
+    """Non-local attention between the horizontal stripes of all frames (wdf_attention_helper.py:198-273): every frame
+    is cut into `stripe` bands of H / stripe rows, each band pooled to one vector per channel ('mean', 'max', or
+    'meanmax': both, concatenated — the g / theta / phi convs then take 2C channels, the reference's in_channels *= 2),
+    the T * stripe vectors of a sample attend to each other ('soft' / 'dot', as NonLocalBlock), W = conv + zero-initialised
+    BatchNorm3d (batch statistics over the N * T * stripe vectors), and the result is added to every position of its
+    band.  The activation-sized steps are ONE pass each: sf_stripe_pool_fwd (x read once) and sf_stripe_add_fwd; the
+    backward is two passes over dL/dz — the 'sum' pool (the gradient of the broadcast) before the small attention's
+    backward, and sf_stripe_pool_bwd (residual + pooling gradient into dL/dx) after it.  Taped for training; the
+    eval-mode tape raises."""
+
+    def __init__(self, stripe, in_channels, inter_channels=None, pool_type='mean', instance='soft'):
+        super(Stripe_NonLocalBlock, self).__init__()
+        self.instance = instance
+        self.stripe = stripe
+        self.in_channels = in_channels
+        self.pool_type = pool_type
+        if pool_type == 'max':
+            self.pool = nn.AdaptiveMaxPool2d(1)
+        elif pool_type == 'mean':
+            self.pool = nn.AdaptiveAvgPool2d(1)
+        elif pool_type == 'meanmax':
+            self.avgpool = nn.AdaptiveAvgPool2d(1)
+            self.maxpool = nn.AdaptiveMaxPool2d(1)
+            self.in_channels *= 2
+        if inter_channels is None:
+            self.inter_channels = in_channels // 2
+        else:
+            self.inter_channels = inter_channels
+        self.g = nn.Conv3d(self.in_channels, self.inter_channels, kernel_size=1, stride=1, padding=0)
+        self.theta = nn.Conv3d(self.in_channels, self.inter_channels, kernel_size=1, stride=1, padding=0)
+        self.phi = nn.Conv3d(self.in_channels, self.inter_channels, kernel_size=1, stride=1, padding=0)
+        if pool_type == 'meanmax':
+            self.in_channels //= 2
+        self.W = nn.Sequential(
+            nn.Conv3d(self.inter_channels, self.in_channels, kernel_size=1, stride=1, padding=0),
+            nn.BatchNorm3d(self.in_channels))
+        nn.init.constant_(self.W[1].weight, 0)
+        nn.init.constant_(self.W[1].bias, 0)
+
+    def run(self, x, reserve=(0, 0)):
+        _refuse_eval_tape("Stripe_NonLocalBlock")
+        S, c = self.stripe, self.in_channels
+        if self.pool_type not in sfhip.STRIPE_MODES or self.pool_type == 'sum':
+            raise NotImplementedError("pool_type %r: the reference defines 'mean', 'max' and 'meanmax'" % (self.pool_type,))
+        assert x.C == c, "Stripe_NonLocalBlock(in_channels=%d) got %r" % (c, x)
+        assert S * (x.H // S) == x.H, "stripe = %d does not divide H = %d" % (S, x.H)
+        discri, arg = sfhip.stripe_pool(x, S, self.pool_type)
+        t = engine.tape()
+        held = {}
+        if t is not None:
+            def bwd_pool():  # the LAST op of the block's backward: dx (+)= dz + the pooling's gradient, one pass
+                dd = t.grad_of(discri)
+                dmean = dd.slice(0, c) if self.pool_type in ('mean', 'meanmax') else None
+                dmax = dd.slice(dd.C - c, c) if self.pool_type in ('max', 'meanmax') else None
+                fresh = t.grad_of_uninitialised(x)
+                sfhip.stripe_pool_bwd(fresh if fresh is not None else t.grad_of(x), S, dz=t.grad_of(held["z"]),
+                                      dmean=dmean, dmax=dmax, arg=arg, accumulate=fresh is None)
+
+            t.record(bwd_pool)
+        g = engine.conv_bn_act(discri, self.g)
+        theta = engine.conv_bn_act(discri, self.theta)
+        phi = engine.conv_bn_act(discri, self.phi)
+        y = _block_attention(theta, phi, g, self.instance)
+        wy = engine.conv_bn_act(y, self.W[0], self.W[1])
+        z = sfhip.stripe_add(x, wy, out=sfhip.new_act(x, x.N, x.T, x.H, x.W, c, reserve[0], reserve[1]))
+        if t is not None:
+            held["z"] = z
+
+            def bwd_add():  # the FIRST op: d(W_y)[n,t,s,:] = sum over the band of dz (the 'sum' pool)
+                dv, _ = sfhip.stripe_pool(t.grad_of(z), S, "sum")
+                sfhip.axpy(dv, t.grad_of(wy), 1.0, accumulate=True)
+
+            t.record(bwd_add)
+        return z
+
+    def forward(self, x, reserve=(0, 0)):
         return _same_kind(self, x, reserve)

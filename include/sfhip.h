@@ -745,6 +745,40 @@ int sf_sample_affine_bwd(const float* dy, int dy_cs, int dy_coff, const float* x
                          long rows_per_sample, int C, const float* mul, float* dx, int dx_cs, int dx_coff,
                          int accumulate, float* dmul, float* dadd, float* ws, void* stream);
 
+/* ---- Stripe pooling and the per-stripe broadcast add: Stripe_NonLocalBlock (stripe_pool.hip) ------------------------
+ * wdf_attention_helper.py:239-273.  A frame's H rows are cut into S stripes of hs = H / S rows (H % S == 0, the
+ * reference's assert at :242); stripe s is rows s*hs .. (s+1)*hs-1 and all W columns — what
+ * reshape(b*c*t, stripe, h//stripe, w) followed by AdaptiveAvg/MaxPool2d(1) selects (:243-254).  All views are NDHWC
+ * channel slices (pointer, pitch, offset); x, z, dz, dx are [N,T,H,W,C], the pooled tensors [N,T,S,1,.].
+ * sf_stripe_pool_fwd, x read ONCE: out[n,t,s,c] = mean | max | sum over the hs*W positions of the stripe; mode
+ *     SF_STRIPE_MEANMAX writes 2C channels, the mean in [0,C) and the max in [C,2C) — torch.cat([avg, max], dim=1) of
+ *     :250.  The max modes also write arg, a dense int32 [N][T][S][C]: the position h_in_stripe * W + w of the maximum,
+ *     of equal values the FIRST in (h, w) order (what PyTorch's adaptive max-pool backward routes the gradient to); a
+ *     NaN counts as the maximum.  arg may be NULL for mean / sum.  SF_STRIPE_SUM is the backward of the broadcast add:
+ *     dv[n,t,s,c] = sum_stripe dz.  One workgroup per (stripe, chunk of channels), lanes along channels; the positions
+ *     are split over the workgroup's remaining lanes and merged in LDS in lane order, sums in fp64.
+ * sf_stripe_add_fwd: z[n,t,h,w,c] = x[n,t,h,w,c] + v[n,t,h/hs,c] — W_y.repeat(...).reshape(b,c,t,h,w) + x of :269-271
+ *     without the repeated tensor.  z may alias x element for element.
+ * sf_stripe_pool_bwd, one pass: dx[n,t,h,w,c] (=|+=) dz[n,t,h,w,c] + dmean[n,t,s,c] / (hs*W)
+ *                                                     + [(h - s*hs)*W + w == arg[n,t,s,c]] * dmax[n,t,s,c]
+ *     — the residual's gradient and the pooling's in one pass.  dz, dmean and dmax may each be NULL (0); dmax needs
+ *     arg.  accumulate == 0 writes every element of the slice, else dx = prior + that value.
+ * All: null pointers, non-positive sizes, H % S != 0, an unknown mode or a slice outside its pitch return SF_EINVAL
+ * with nothing launched (also C > 2^20, N*T*S or hs*W >= 2^31); no host synchronisation; 64-bit element offsets;
+ * float4 kernels when C, every pitch and offset are multiples of 4 and every pointer is 16-byte aligned, scalar
+ * kernels otherwise; no atomics, one owner per output element, fixed summation order: bitwise reproducible.        */
+#define SF_STRIPE_MEAN 0
+#define SF_STRIPE_MAX 1
+#define SF_STRIPE_MEANMAX 2
+#define SF_STRIPE_SUM 3
+int sf_stripe_pool_fwd(const float* x, int cs, int coff, int N, int T, int H, int W, int C, int S, int mode,
+                       float* out, int out_cs, int out_coff, void* arg, void* stream);
+int sf_stripe_add_fwd(const float* x, int cs, int coff, const float* v, int v_cs, int v_coff, int N, int T, int H,
+                      int W, int C, int S, float* z, int z_cs, int z_coff, void* stream);
+int sf_stripe_pool_bwd(const float* dz, int dz_cs, int dz_coff, const float* dmean, int dmean_cs, int dmean_coff,
+                       const float* dmax, int dmax_cs, int dmax_coff, const void* arg, int N, int T, int H, int W,
+                       int C, int S, float* dx, int dx_cs, int dx_coff, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
