@@ -35,6 +35,46 @@ __device__ __forceinline__ void src_index(float scale, int dst, int n, int* i0, 
   *l0 = 1.f - l;
 }
 
+// The pixel arithmetic of the input step, shared by the per-clip kernels and the one-launch view sampler below (so the
+// two write the same bits): the value of the scaled frame at (ys, xs), taken from the decoded frame `fr`.
+// RGB: the three normalised channels in source order.
+__device__ __forceinline__ void sample_rgb(const unsigned char* __restrict__ fr, int H, int W, int new_h, int new_w,
+                                           int ys, int xs, const NormArgs& nm, float v[3]) {
+  if (new_h == H && new_w == W) {
+    const unsigned char* p = fr + ((long)ys * W + xs) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = norm1(p[c], nm.m[c], nm.s[c]);
+  } else {
+    int ya, yb, xa, xb;
+    float ly0, ly1, lx0, lx1;
+    src_index((float)H / (float)new_h, ys, H, &ya, &yb, &ly0, &ly1);
+    src_index((float)W / (float)new_w, xs, W, &xa, &xb, &lx0, &lx1);
+    const unsigned char* p00 = fr + ((long)ya * W + xa) * 3;
+    const unsigned char* p01 = fr + ((long)ya * W + xb) * 3;
+    const unsigned char* p10 = fr + ((long)yb * W + xa) * 3;
+    const unsigned char* p11 = fr + ((long)yb * W + xb) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float a = norm1(p00[c], nm.m[c], nm.s[c]), b = norm1(p01[c], nm.m[c], nm.s[c]);
+      const float d = norm1(p10[c], nm.m[c], nm.s[c]), e = norm1(p11[c], nm.m[c], nm.s[c]);
+      v[c] = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * d + lx1 * e);
+    }
+  }
+}
+
+// One-channel frame: one normalised value.
+__device__ __forceinline__ float sample_gray(const unsigned char* __restrict__ fr, int H, int W, int new_h, int new_w,
+                                             int ys, int xs, float mean, float stdv) {
+  if (new_h == H && new_w == W) return norm1(fr[(long)ys * W + xs], mean, stdv);
+  int ya, yb, xa, xb;
+  float ly0, ly1, lx0, lx1;
+  src_index((float)H / (float)new_h, ys, H, &ya, &yb, &ly0, &ly1);
+  src_index((float)W / (float)new_w, xs, W, &xa, &xb, &lx0, &lx1);
+  const float a = norm1(fr[(long)ya * W + xa], mean, stdv), b = norm1(fr[(long)ya * W + xb], mean, stdv);
+  const float d = norm1(fr[(long)yb * W + xa], mean, stdv), e = norm1(fr[(long)yb * W + xb], mean, stdv);
+  return ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * d + lx1 * e);
+}
+
 __global__ void clip_prologue_kernel(const unsigned char* __restrict__ clip, int T, int H, int W, int new_h,
                                      int new_w, int y0, int x0, int crop, int flip, int reverse, NormArgs nm,
                                      const int* __restrict__ frame_idx, int n_frames, float* __restrict__ dst, int ph,
@@ -52,28 +92,8 @@ __global__ void clip_prologue_kernel(const unsigned char* __restrict__ clip, int
     const int t = frame_idx ? frame_idx[f] : f;
     const int ys = y0 + yy;                            // row in the scaled image
     const int xs = x0 + (flip ? crop - 1 - xx : xx);   // column in the scaled image (flip is applied after the crop)
-    const unsigned char* fr = clip + (long)t * H * W * 3;
     float v[3];
-    if (new_h == H && new_w == W) {
-      const unsigned char* p = fr + ((long)ys * W + xs) * 3;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) v[c] = norm1(p[c], nm.m[c], nm.s[c]);
-    } else {
-      int ya, yb, xa, xb;
-      float ly0, ly1, lx0, lx1;
-      src_index((float)H / (float)new_h, ys, H, &ya, &yb, &ly0, &ly1);
-      src_index((float)W / (float)new_w, xs, W, &xa, &xb, &lx0, &lx1);
-      const unsigned char* p00 = fr + ((long)ya * W + xa) * 3;
-      const unsigned char* p01 = fr + ((long)ya * W + xb) * 3;
-      const unsigned char* p10 = fr + ((long)yb * W + xa) * 3;
-      const unsigned char* p11 = fr + ((long)yb * W + xb) * 3;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float a = norm1(p00[c], nm.m[c], nm.s[c]), b = norm1(p01[c], nm.m[c], nm.s[c]);
-        const float d = norm1(p10[c], nm.m[c], nm.s[c]), e = norm1(p11[c], nm.m[c], nm.s[c]);
-        v[c] = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * d + lx1 * e);
-      }
-    }
+    sample_rgb(clip + (long)t * H * W * 3, H, W, new_h, new_w, ys, xs, nm, v);
     if (reverse) {  // DATA.REVERSE_INPUT_CHANNEL: frames[[2, 1, 0]]
       o[0] = v[2]; o[1] = v[1]; o[2] = v[0];
     } else {
@@ -101,20 +121,129 @@ __global__ void clip_prologue_gray_kernel(const unsigned char* __restrict__ clip
     const int t = min(max(frame_idx ? frame_idx[f] : f, 0), T - 1);
     const int ys = y0 + yy;
     const int xs = x0 + (flip ? crop - 1 - xx : xx);
-    const unsigned char* fr = clip + (long)t * H * W;
-    if (new_h == H && new_w == W) {
-      o = norm1(fr[(long)ys * W + xs], mean, stdv);
-    } else {
-      int ya, yb, xa, xb;
-      float ly0, ly1, lx0, lx1;
-      src_index((float)H / (float)new_h, ys, H, &ya, &yb, &ly0, &ly1);
-      src_index((float)W / (float)new_w, xs, W, &xa, &xb, &lx0, &lx1);
-      const float a = norm1(fr[(long)ya * W + xa], mean, stdv), b = norm1(fr[(long)ya * W + xb], mean, stdv);
-      const float d = norm1(fr[(long)yb * W + xa], mean, stdv), e = norm1(fr[(long)yb * W + xb], mean, stdv);
-      o = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * d + lx1 * e);
-    }
+    o = sample_gray(clip + (long)t * H * W, H, W, new_h, new_w, ys, xs, mean, stdv);
   }
   dst[idx] = o;
+}
+
+// ---- all views of one decoded video, both pathways, in ONE launch (tools/test_net.py's protocol: TEST.NUM_ENSEMBLE_VIEWS
+// x TEST.NUM_SPATIAL_CROPS views per video).  The grid is (pixels of one padded frame, Fast frame, view): the view's
+// table row, the frame's index and the "is this Fast frame also a Slow frame" search are uniform per workgroup (scalar
+// loads), a thread owns one destination pixel of one Fast frame, computes it once with the per-clip kernels' arithmetic
+// and stores it to the Fast buffer and — when slow_idx names the frame — to the Slow buffer too.  Every element of both
+// buffers has exactly one owner (slow_idx holds distinct frames), consecutive threads write consecutive 16-byte chunks.
+constexpr int VIEW_ROW = 5;  // new_h, new_w, y0, x0, flip
+
+struct ViewGeo {
+  int new_h, new_w, y0, x0, flip, ok;
+};
+
+__device__ __forceinline__ ViewGeo view_row(const int* __restrict__ views, int v, int crop) {
+  const int* r = views + (long)v * VIEW_ROW;
+  ViewGeo g = {r[0], r[1], r[2], r[3], r[4], 0};
+  // the host entry checked its copy of the table; a row that differs on the device yields zeros, never a wild read
+  g.ok = g.new_h > 0 && g.new_w > 0 && g.y0 >= 0 && g.x0 >= 0 && g.y0 + crop <= g.new_h && g.x0 + crop <= g.new_w;
+  return g;
+}
+
+__global__ void clip_views_kernel(const unsigned char* __restrict__ video, int T, int H, int W,
+                                  const int* __restrict__ views, const int* __restrict__ frame_idx,
+                                  const int* __restrict__ slow_idx, int n_fast, int n_slow, int crop, int reverse,
+                                  NormArgs nm, float* __restrict__ fast, float* __restrict__ slow, int ph, int pw, int Wp,
+                                  int plane) {
+  const int p = blockIdx.x * TPB + threadIdx.x;
+  if (p >= plane) return;
+  const int f = blockIdx.y, v = blockIdx.z;
+  const ViewGeo g = view_row(views, v, crop);
+  const int yp = p / Wp, xp = p - yp * Wp;
+  f32x4 o = {0.f, 0.f, 0.f, 0.f};
+  const int yy = yp - ph, xx = xp - pw;
+  if (g.ok && yy >= 0 && yy < crop && xx >= 0 && xx < crop) {
+    const int t = min(max(frame_idx[(long)v * n_fast + f], 0), T - 1);
+    const int ys = g.y0 + yy;
+    const int xs = g.x0 + (g.flip ? crop - 1 - xx : xx);
+    float c[3];
+    sample_rgb(video + (long)t * H * W * 3, H, W, g.new_h, g.new_w, ys, xs, nm, c);
+    if (reverse) {
+      o[0] = c[2]; o[1] = c[1]; o[2] = c[0];
+    } else {
+      o[0] = c[0]; o[1] = c[1]; o[2] = c[2];
+    }
+  }
+  *reinterpret_cast<f32x4*>(fast + (((long)v * n_fast + f) * plane + p) * 4) = o;
+  for (int j = 0; j < n_slow; ++j)  // n_slow <= n_fast / alpha entries, wave-uniform
+    if (slow_idx[j] == f) *reinterpret_cast<f32x4*>(slow + (((long)v * n_slow + j) * plane + p) * 4) = o;
+}
+
+// One-channel video: VEC = 4 pixels of one row per thread (one 16-byte store; needs Wp % 4 == 0 and 16-byte aligned
+// buffers) or VEC = 1 (any pitch).  `plane` counts threads' units: Hp * Wp / VEC.
+template <int VEC>
+__global__ void clip_views_gray_kernel(const unsigned char* __restrict__ video, int T, int H, int W,
+                                       const int* __restrict__ views, const int* __restrict__ frame_idx,
+                                       const int* __restrict__ slow_idx, int n_fast, int n_slow, int crop, float mean,
+                                       float stdv, float* __restrict__ fast, float* __restrict__ slow, int ph, int pw,
+                                       int Wp, int plane) {
+  const int p = blockIdx.x * TPB + threadIdx.x;
+  if (p >= plane) return;
+  const int f = blockIdx.y, v = blockIdx.z;
+  const ViewGeo g = view_row(views, v, crop);
+  const int wq = Wp / VEC;
+  const int yp = p / wq, xp0 = (p - yp * wq) * VEC;
+  const int yy = yp - ph;
+  float o[VEC];
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) o[i] = 0.f;
+  if (g.ok && yy >= 0 && yy < crop) {
+    const int t = min(max(frame_idx[(long)v * n_fast + f], 0), T - 1);
+    const unsigned char* fr = video + (long)t * H * W;
+    const int ys = g.y0 + yy;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+      const int xx = xp0 + i - pw;
+      if (xx >= 0 && xx < crop)
+        o[i] = sample_gray(fr, H, W, g.new_h, g.new_w, ys, g.x0 + (g.flip ? crop - 1 - xx : xx), mean, stdv);
+    }
+  }
+  const long fo = (((long)v * n_fast + f) * plane + p) * VEC;
+  if constexpr (VEC == 4) {
+    const f32x4 q = {o[0], o[1], o[2], o[3]};
+    *reinterpret_cast<f32x4*>(fast + fo) = q;
+    for (int j = 0; j < n_slow; ++j)
+      if (slow_idx[j] == f) *reinterpret_cast<f32x4*>(slow + (((long)v * n_slow + j) * plane + p) * VEC) = q;
+  } else {
+    fast[fo] = o[0];
+    for (int j = 0; j < n_slow; ++j)
+      if (slow_idx[j] == f) slow[((long)v * n_slow + j) * plane + p] = o[0];
+  }
+}
+
+// Host-side check of the view table's host copy: rows [V][5], then frame indices [V][n_fast], then n_slow Slow indices.
+bool view_table_ok(const int* tab, int T, int V, int n_fast, int n_slow, int crop) {
+  for (int v = 0; v < V; ++v) {
+    const int* r = tab + (long)v * VIEW_ROW;
+    if (r[0] <= 0 || r[1] <= 0 || r[2] < 0 || r[3] < 0 || (long)r[2] + crop > r[0] || (long)r[3] + crop > r[1])
+      return false;
+  }
+  const int* fi = tab + (long)V * VIEW_ROW;
+  for (long i = 0; i < (long)V * n_fast; ++i)
+    if (fi[i] < 0 || fi[i] >= T) return false;
+  const int* si = fi + (long)V * n_fast;
+  for (int j = 0; j < n_slow; ++j)
+    if (si[j] < 0 || si[j] >= n_fast || (j > 0 && si[j] <= si[j - 1])) return false;  // distinct: one owner per Slow frame
+  return true;
+}
+
+// Shared argument checks of the two entries; on success *plane = (crop + 2 ph) * Wp.
+bool clip_views_args_ok(const void* video, int T, int H, int W, const int* table_host, const int* table, int V, int n_fast,
+                        int n_slow, int crop, const float* fast, const float* slow, int ph, int pw, int Wp, long* plane) {
+  if (!video || !table_host || !table || !fast || T <= 0 || H <= 0 || W <= 0 || V <= 0 || n_fast <= 0 || crop <= 0 ||
+      ph < 0 || pw < 0)
+    return false;
+  if (n_slow < 0 || n_slow > n_fast || (slow == nullptr) != (n_slow == 0)) return false;
+  if (V > 65535 || n_fast > 65535 || Wp < crop + 2 * pw) return false;
+  *plane = (long)(crop + 2 * ph) * Wp;
+  if (*plane > 0x7fffffffL / 4) return false;
+  return view_table_ok(table_host, T, V, n_fast, n_slow, crop);
 }
 }  // namespace
 
@@ -150,6 +279,48 @@ extern "C" int sf_clip_prologue_gray(const unsigned char* clip, int T, int H, in
   const long total = (long)n_frames * (crop + 2 * ph) * Wp;
   hipLaunchKernelGGL(clip_prologue_gray_kernel, dim3(sf_cdiv(total, TPB)), dim3(TPB), 0, (hipStream_t)stream, clip, T, H,
                      W, new_h, new_w, y0, x0, crop, flip, mean, stdv, frame_idx, n_frames, dst, ph, pw, Wp, total);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_clip_views(const unsigned char* video, int T, int H, int W, const int* table_host, const int* table,
+                             int V, int n_fast, int n_slow, int crop, int reverse, const float* mean3,
+                             const float* std3, float* fast, float* slow, int ph, int pw, int Wp, void* stream) {
+  long plane = 0;
+  if (!mean3 || !std3 ||
+      !clip_views_args_ok(video, T, H, W, table_host, table, V, n_fast, n_slow, crop, fast, slow, ph, pw, Wp, &plane))
+    return SF_EINVAL;
+  if (!sf_aligned16(fast) || !sf_aligned16(slow)) return SF_EINVAL;
+  NormArgs nm;
+  for (int c = 0; c < 3; ++c) {
+    nm.m[c] = mean3[c];   // HOST pointers: three floats each
+    nm.s[c] = std3[c];
+  }
+  const int* frame_idx = table + (long)V * VIEW_ROW;
+  hipLaunchKernelGGL(clip_views_kernel, dim3(sf_cdiv(plane, TPB), n_fast, V), dim3(TPB), 0, (hipStream_t)stream, video, T,
+                     H, W, table, frame_idx, frame_idx + (long)V * n_fast, n_fast, n_slow, crop, reverse, nm, fast, slow,
+                     ph, pw, Wp, (int)plane);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_clip_views_gray(const unsigned char* video, int T, int H, int W, const int* table_host,
+                                  const int* table, int V, int n_fast, int n_slow, int crop, float mean, float stdv,
+                                  float* fast, float* slow, int ph, int pw, int Wp, void* stream) {
+  long plane = 0;
+  if (!clip_views_args_ok(video, T, H, W, table_host, table, V, n_fast, n_slow, crop, fast, slow, ph, pw, Wp, &plane))
+    return SF_EINVAL;
+  const int* frame_idx = table + (long)V * VIEW_ROW;
+  const int* slow_idx = frame_idx + (long)V * n_fast;
+  if (Wp % 4 == 0 && sf_aligned16(fast) && sf_aligned16(slow)) {
+    hipLaunchKernelGGL(clip_views_gray_kernel<4>, dim3(sf_cdiv(plane / 4, TPB), n_fast, V), dim3(TPB), 0,
+                       (hipStream_t)stream, video, T, H, W, table, frame_idx, slow_idx, n_fast, n_slow, crop, mean, stdv,
+                       fast, slow, ph, pw, Wp, (int)(plane / 4));
+  } else {
+    hipLaunchKernelGGL(clip_views_gray_kernel<1>, dim3(sf_cdiv(plane, TPB), n_fast, V), dim3(TPB), 0,
+                       (hipStream_t)stream, video, T, H, W, table, frame_idx, slow_idx, n_fast, n_slow, crop, mean, stdv,
+                       fast, slow, ph, pw, Wp, (int)plane);
+  }
   SF_CHECK_LAUNCH();
   return SF_OK;
 }

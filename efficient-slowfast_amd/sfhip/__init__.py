@@ -65,6 +65,9 @@ _SIGNATURES = {
     "sf_ndhwc_to_ncthw": (_ci, [_vp, _ci, _ci, _vp] + [_ci] * 5 + [_vp]),
     "sf_clip_prologue": (_ci, [_vp] + [_ci] * 10 + [_pf] * 2 + [_vp, _ci, _vp, _ci, _ci, _ci, _vp]),
     "sf_clip_prologue_gray": (_ci, [_vp] + [_ci] * 9 + [_cf, _cf, _vp, _ci, _vp, _ci, _ci, _ci, _vp]),
+    "sf_clip_views": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp] + [_ci] * 5 + [_vp] * 4 + [_ci, _ci, _ci, _vp]),
+    "sf_clip_views_gray": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp] + [_ci] * 4 + [_cf, _cf, _vp, _vp, _ci, _ci, _ci, _vp]),
+    "sf_ensemble_update": (_ci, [_vp] * 4 + [_pi] * 3 + [_ci] * 4 + [_vp]),
     "sf_ncthw1_pack": (_ci, [_vp, _vp] + [_ci] * 7 + [_vp]),
     "sf_stem1_accepts": (_ci, [_ci] * 4),
     "sf_stem1_fwd": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _ci, _ci, _vp]),
@@ -383,6 +386,59 @@ def clip_prologue(clip_u8, dst, new_hw, yx, crop, flip, mean, std, frame_idx=Non
     s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
     _call("sf_clip_prologue", *head, 1 if reverse else 0, m3, s3, *tail)
     return dst
+
+
+def clip_views(video_u8, table_host, table, n_slow, crop, mean, std, fast, slow=None, reverse=False, ph=0, pw=0):
+    """All V views of one decoded video (uint8 [T,H,W,3], or [T,H,W] / [T,H,W,1] grayscale, device) in one launch ->
+    fast [V, n_fast, crop+2ph, Wp, 4 | 1] and slow [V, n_slow, ...] (None with n_slow == 0: single pathway), the
+    PackedClip layouts `clip_prologue` writes.  table_host: the int32 CPU view table (V rows new_h, new_w, y0, x0, flip;
+    V * n_fast frame indices; n_slow Slow positions), table: its device copy."""
+    _require_gpu(fast, "clip_views")
+    if not (video_u8.is_cuda and table.is_cuda) or table_host.is_cuda:
+        raise SfhipError("clip_views: the video and the view table's copy live on the GPU, table_host on the host")
+    assert video_u8.dtype == torch.uint8 and video_u8.dim() in (3, 4) and video_u8.is_contiguous()
+    gray = video_u8.dim() == 3 or video_u8.shape[3] == 1
+    assert gray or video_u8.shape[3] == 3
+    assert fast.is_contiguous() and fast.dim() == 5 and fast.shape[4] == (1 if gray else 4)
+    V, n_fast = fast.shape[:2]
+    assert table_host.dtype == torch.int32 and table.dtype == torch.int32 and table_host.is_contiguous()
+    assert table.is_contiguous() and table_host.numel() == table.numel() == V * (5 + n_fast) + n_slow
+    if slow is not None:
+        _require_gpu(slow, "clip_views")
+        assert slow.is_contiguous() and tuple(slow.shape) == (V, n_slow) + tuple(fast.shape[2:])
+    T, H, W = video_u8.shape[:3]
+    head = (_ptr(video_u8), T, H, W, _ptr(table_host), _ptr(table), V, n_fast, int(n_slow), int(crop))
+    tail = (_ptr(fast), _ptr(slow), ph, pw, fast.shape[3])
+    if gray:
+        assert len(mean) == 1 and len(std) == 1, "a one-channel video takes a one-element mean / std"
+        assert not reverse, "DATA.REVERSE_INPUT_CHANNEL has no meaning for a one-channel video"
+        _call("sf_clip_views_gray", *head, float(mean[0]), float(std[0]), *tail)
+    else:
+        m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
+        s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
+        _call("sf_clip_views", *head, 1 if reverse else 0, ctypes.cast(m3, _vp), ctypes.cast(s3, _vp), *tail)
+    return fast, slow
+
+
+def _iptr(t):  # a device int32 array where the header says `int*`
+    return ctypes.cast(ctypes.c_void_p(t.data_ptr()), _pi)
+
+
+def ensemble_update(preds, video_idx, labels, video_preds, video_labels, clip_count, bad_count, mode):
+    """TestMeter.update_stats on the device: preds [B,K] fp32, video_idx / labels int32 [B] (labels may be None) folded
+    into video_preds [Nv,K], video_labels / clip_count int32 [Nv]; mode 0 sum, 1 max.  bad_count: int32 [1], the number
+    of clips skipped because their video index was outside [0, Nv)."""
+    _require_gpu(preds, "ensemble_update")
+    _require_gpu(video_preds, "ensemble_update")
+    ints = (video_idx, video_labels, clip_count, bad_count) + (() if labels is None else (labels,))
+    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in ints)
+    assert preds.dim() == 2 and preds.is_contiguous() and video_preds.dim() == 2 and video_preds.is_contiguous()
+    B, K = preds.shape
+    Nv = video_preds.shape[0]
+    assert video_preds.shape[1] == K and video_idx.numel() == B and (labels is None or labels.numel() == B)
+    assert video_labels.numel() == Nv and clip_count.numel() == Nv and bad_count.numel() == 1
+    _call("sf_ensemble_update", _ptr(preds), _ptr(video_idx), _ptr(labels), _ptr(video_preds), _iptr(video_labels),
+          _iptr(clip_count), _iptr(bad_count), B, K, Nv, int(mode))
 
 
 # ------------------------------------------------------------------------------------------------ one-channel stem

@@ -125,6 +125,73 @@ def gpu_input_step(clips, params, mean, std, alpha, reverse_input_channel=False,
     return [sfhip.PackedClip(buf, C, crop, crop, ph, pw) for buf, _ in paths]
 
 
+def view_frame_indices(num_frames_total, clip_span, temporal_idx, num_clips, num_frames):
+    """The frames view `temporal_idx` of `num_clips` takes from a decoded video of `num_frames_total` frames:
+    decoder.py:55-83 (get_start_end_idx, uniform branch) and :35-52 (temporal_sampling).  int64 [num_frames]."""
+    delta = max(num_frames_total - clip_span, 0)
+    start = delta * temporal_idx / num_clips
+    end = start + clip_span - 1
+    index = torch.linspace(start, end, num_frames)
+    return torch.clamp(index, 0, num_frames_total - 1).long()
+
+
+def test_view_params(cfg, num_frames_total, height, width, fps=None):
+    """The TEST.NUM_ENSEMBLE_VIEWS * TEST.NUM_SPATIAL_CROPS views of one decoded video (num_frames_total frames of
+    height x width at `fps`; None: DATA.TARGET_FPS) in the order of the Kinetics dataset in test mode
+    (datasets/kinetics.py:95-109, :166-181): view i has temporal index i // NUM_SPATIAL_CROPS and spatial index
+    i % NUM_SPATIAL_CROPS.  Returns a list of (frame_indices int64 [DATA.NUM_FRAMES], SpatialParams).  Host arithmetic
+    only: no RNG, no GPU."""
+    n_views, n_crops = cfg.TEST.NUM_ENSEMBLE_VIEWS, cfg.TEST.NUM_SPATIAL_CROPS
+    fps = cfg.DATA.TARGET_FPS if fps is None else fps
+    span = cfg.DATA.NUM_FRAMES * cfg.DATA.SAMPLING_RATE * fps / cfg.DATA.TARGET_FPS  # decoder.py:449
+    crop = cfg.DATA.TEST_CROP_SIZE
+    views = []
+    for i in range(n_views * n_crops):
+        frames = view_frame_indices(num_frames_total, span, i // n_crops, n_views, cfg.DATA.NUM_FRAMES)
+        views.append((frames, sample_spatial_params(height, width, i % n_crops, crop, crop, crop)))
+    return views
+
+
+test_view_params.__test__ = False  # not a pytest function
+
+
+def view_table(views, n_slow_idx):
+    """The int32 host table sf_clip_views reads: V rows (new_h, new_w, y0, x0, flip), the V * n_fast frame indices,
+    then the Slow pathway's positions among the Fast frames (`n_slow_idx`: a tensor, possibly empty)."""
+    rows = torch.tensor([[p.new_h, p.new_w, p.y, p.x, int(p.flip)] for _, p in views], dtype=torch.int32)
+    frames = torch.stack([torch.as_tensor(f) for f, _ in views]).to(torch.int32)
+    return torch.cat([rows.flatten(), frames.flatten(), n_slow_idx.to(torch.int32).flatten()]).contiguous()
+
+
+def gpu_test_views(video, views, mean, std, alpha, reverse_input_channel=False, pad=(0, 0), wp=None):
+    """Every test view of ONE decoded video in one kernel launch (sf_clip_views).
+
+    video:  uint8 [T_total, H, W, 3] device tensor (grayscale: [T_total, H, W] or [T_total, H, W, 1])
+    views:  list of V (frame_indices, SpatialParams) from `test_view_params` (same crop and frame count for all)
+    the rest as `gpu_input_step`.  Returns [slow, fast] ([clip] with alpha=None) PackedClips of batch V holding the bits
+    `gpu_input_step` gives for the V gathered clips; a frame both pathways take is resampled once."""
+    V = len(views)
+    assert V > 0
+    crop = views[0][1].crop
+    n_fast = len(views[0][0])
+    assert all(p.crop == crop and len(f) == n_fast for f, p in views)
+    ph, pw = pad
+    wp = crop + 2 * pw if wp is None else wp
+    dev = video.device
+    gray = video.dim() == 3 or video.shape[3] == 1
+    C, cpad = (1, 1) if gray else (3, 4)
+    slow_idx = slow_frame_indices(n_fast, alpha) if alpha is not None else torch.zeros(0, dtype=torch.long)
+    n_slow = slow_idx.numel()
+    table_host = view_table(views, slow_idx)
+    table = table_host.to(dev)  # the one upload: rows, frame indices and Slow positions together
+    fast = torch.empty((V, n_fast, crop + 2 * ph, wp, cpad), dtype=torch.float32, device=dev)
+    slow = torch.empty((V, n_slow, crop + 2 * ph, wp, cpad), dtype=torch.float32, device=dev) if n_slow else None
+    sfhip.clip_views(video, table_host, table, n_slow, crop, mean, std, fast, slow, reverse=reverse_input_channel,
+                     ph=ph, pw=pw)
+    out = [sfhip.PackedClip(fast, C, crop, crop, ph, pw)]
+    return out if slow is None else [sfhip.PackedClip(slow, C, crop, crop, ph, pw)] + out
+
+
 def stem_input_geometry(model, crop):
     """(ph, pw, Wp) shared by the model's pathway stems (their first convolutions have the same H/W kernel,
     stride and padding) for crop x crop frames."""

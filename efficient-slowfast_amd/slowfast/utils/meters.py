@@ -88,3 +88,66 @@ class TestMeter(object):
         for k, c in zip(ks, correct):
             stats["top{}_acc".format(k)] = "{:.{prec}f}".format(float(c) / self.video_preds.size(0) * 100.0, prec=2)
         return stats
+
+
+class DeviceTestMeter(TestMeter):
+    """TestMeter whose ensemble is one `sf_ensemble_update` launch per batch: predictions, labels and clip ids stay on
+    the GPU, the per-video rows are folded in the host loop's order (the sum is TestMeter's bit for bit) and nothing
+    is copied to the host before `finalize_metrics`."""
+
+    def __init__(self, num_videos, num_clips, num_cls, overall_iters, multi_label=False, ensemble_method="sum",
+                 device="cuda"):
+        if ensemble_method not in ("sum", "max"):
+            raise NotImplementedError("Ensemble Method {} is not supported".format(ensemble_method))
+        self.num_clips = num_clips
+        self.overall_iters = overall_iters
+        self._tic, self._lap = time.perf_counter(), 0.0
+        self.multi_label = multi_label
+        self.ensemble_method = ensemble_method
+        self.device = torch.device(device)
+        self._shape = (num_videos, num_cls)
+        self.video_preds = self.video_labels = self.clip_count = self.bad_count = None  # allocated on first use
+
+    def _allocate(self):
+        n, k = self._shape
+        self.video_preds = torch.zeros((n, k), device=self.device)
+        self.video_labels = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        self.clip_count = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        self.bad_count = torch.zeros((1,), dtype=torch.int32, device=self.device)
+
+    def reset(self):
+        if self.video_preds is not None:
+            for t in (self.video_preds, self.video_labels, self.clip_count, self.bad_count):
+                t.zero_()
+
+    def update_stats(self, preds, labels, clip_ids):
+        """preds [N, C], labels [N], clip_ids [N], all on the device: video = clip_id // num_clips."""
+        if self.multi_label:
+            raise NotImplementedError("multi-label mAP (AVA/Charades) is outside the hot-path scope")
+        import sfhip
+        if self.video_preds is None:
+            self._allocate()
+        vid = torch.div(clip_ids, self.num_clips, rounding_mode="floor").to(torch.int32).contiguous()
+        sfhip.ensemble_update(preds.detach().float().contiguous(), vid, labels.to(torch.int32).contiguous(),
+                              self.video_preds, self.video_labels, self.clip_count, self.bad_count,
+                              0 if self.ensemble_method == "sum" else 1)
+
+    def finalize_metrics(self, ks=(1, 5)):
+        """One copy of the accumulators to the host, then TestMeter's statistics (through `topks_correct`)."""
+        if self.multi_label:
+            raise NotImplementedError("multi-label mAP (AVA/Charades) is outside the hot-path scope")
+        if self.video_preds is None:
+            self._allocate()
+        n, k = self._shape
+        packed = torch.cat([self.video_preds.flatten().view(torch.int32), self.video_labels, self.clip_count,
+                            self.bad_count]).cpu()  # the one device-to-host copy
+        video_preds = packed[:n * k].view(torch.float32).view(n, k)
+        video_labels, clip_count = packed[n * k:n * k + n].long(), packed[n * k + n:n * k + 2 * n].long()
+        bad = int(packed[-1])
+        if bad:
+            raise IndexError("{} clip(s) named a video outside [0, {}) and were skipped".format(bad, n))
+        stats = {"split": "test_final", "complete": bool((clip_count == self.num_clips).all())}
+        correct = topks_correct(video_preds, video_labels, ks)
+        for kk, c in zip(ks, correct):
+            stats["top{}_acc".format(kk)] = "{:.{prec}f}".format(float(c) / video_preds.size(0) * 100.0, prec=2)
+        return stats

@@ -611,6 +611,41 @@ int sf_clip_prologue_gray(const unsigned char* clip, int T, int H, int W, int ne
                           int crop, int flip, float mean, float stdv, const int* frame_idx, int n_frames, float* dst,
                           int ph, int pw, int Wp, void* stream);
 
+/* ---- multi-view testing (tools/test_net.py: TEST.NUM_ENSEMBLE_VIEWS x TEST.NUM_SPATIAL_CROPS views per video,
+ * datasets/kinetics.py:166-181 and decoder.py:35-83 decide which frames and which crop a view takes).
+ * sf_clip_views: ALL V views of ONE decoded video, uint8 [T,H,W,3] on the device, for both pathways in one launch.
+ *   The view table is V rows (new_h, new_w, y0, x0, flip), then V * n_fast frame indices (view-major), then the
+ *   n_slow Fast-frame positions the Slow pathway takes (datasets/utils.py:96-104; strictly increasing), all int32.
+ *   `table` is its device copy and `table_host` the host array it was uploaded from: the host copy is checked before
+ *   anything is launched, the kernel reads the device copy (a device row that fails the same check writes zeros).
+ *   fast [V][n_fast][crop+2ph][Wp][4] and slow [V][n_slow][crop+2ph][Wp][4] are the layouts sf_clip_prologue writes,
+ *   zero borders included, and hold the same bits: the pixel arithmetic is one device function.  Slow frame j of a
+ *   view is its Fast frame number table[slow j]; a frame that goes to both pathways is resampled once and stored twice.
+ *   slow == NULL with n_slow == 0: a single-pathway model.  One owner per output element, 16-byte stores, 64-bit
+ *   element offsets, no atomics.
+ *   SF_EINVAL, nothing launched: null pointers, V <= 0, non-positive sizes, a crop window outside its scaled frame, a
+ *   frame index outside [0, T), n_slow > n_fast, Slow positions outside [0, n_fast) or not increasing, slow given
+ *   without n_slow (or the reverse), Wp < crop + 2 pw, V or n_fast above 65535, buffers not 16-byte aligned.
+ * sf_clip_views_gray: the same for a one-channel video, uint8 [T,H,W]: one float per pixel ([V][n][crop+2ph][Wp]);
+ *   four pixels per 16-byte store when Wp % 4 == 0 and both buffers are 16-byte aligned, one pixel per store otherwise. */
+int sf_clip_views(const unsigned char* video, int T, int H, int W, const int* table_host, const int* table, int V,
+                  int n_fast, int n_slow, int crop, int reverse, const float* mean3, const float* std3, float* fast,
+                  float* slow, int ph, int pw, int Wp, void* stream);
+int sf_clip_views_gray(const unsigned char* video, int T, int H, int W, const int* table_host, const int* table, int V,
+                       int n_fast, int n_slow, int crop, float mean, float stdv, float* fast, float* slow, int ph,
+                       int pw, int Wp, void* stream);
+
+/* sf_ensemble_update (csrc/ensemble.hip): TestMeter.update_stats (utils/meters.py:283-317) on the device.  preds [B,K],
+ *   video_idx int32 [B] (clip id / clips per video), labels int32 [B] or NULL; video_preds [Nv,K], video_labels int32
+ *   [Nv], clip_count int32 [Nv] are the meter's accumulators.  mode 0: video_preds[video_idx[b]] += preds[b]; mode 1:
+ *   the elementwise maximum.  The first clip of a video in the batch owns that video's row for the call and folds the
+ *   batch in index order: the sum equals the host loop's bit for bit (no atomics).  video_labels takes the label of the
+ *   video's last clip in the batch, clip_count the number of its clips.  A video_idx outside [0, Nv) is skipped and
+ *   added to *bad_count (device int32).  Null pointers (labels excepted), non-positive sizes, another mode: SF_EINVAL. */
+int sf_ensemble_update(const float* preds, const int* video_idx, const int* labels, float* video_preds,
+                       int* video_labels, int* clip_count, int* bad_count, int B, int K, int Nv, int mode,
+                       void* stream);
+
 /* ---- one-channel stem (csrc/conv_stem_gray.hip): nn.Conv3d(1, Cout, [kT,7,7], stride [1,2,2], padding [pT,3,3]) of
  * ResNetBasicStem (stem_helper.py:157-164) and its weight gradient (autograd's conv backward for `conv.weight`) on
  * the one-channel layout x [N][T][Hp][Wp] fp32, Hp = H + 2*3, zero H/W borders, Wp as for the RGB stem layout — what
