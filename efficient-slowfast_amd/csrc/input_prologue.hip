@@ -245,6 +245,137 @@ bool clip_views_args_ok(const void* video, int T, int H, int W, const int* table
   if (*plane > 0x7fffffffL / 4) return false;
   return view_table_ok(table_host, T, V, n_fast, n_slow, crop);
 }
+
+// ---- all B clips of one TRAINING batch, both pathways, in ONE launch (datasets/kinetics.py:142-165, :186-189, :230-248
+// per sample; the loader's collate step stacks B of them).  Unlike the views of one video the B decoded spans are
+// separate allocations of their own T_i x H_i x W_i, so the table row carries the clip's device address and extents
+// beside its scale / crop / flip.  The grid is (pixels of one padded frame, Fast frame, clip); everything else is
+// clip_views_kernel: the row, the frame index and the Slow search are uniform per workgroup, a thread owns one
+// destination pixel of one Fast frame, computes it once with sample_rgb / sample_gray and stores it to the Fast buffer
+// and — when slow_idx names the frame — to the Slow buffer.
+constexpr int BATCH_ROW = 9;  // clip address, T, H, W, new_h, new_w, y0, x0, flip (int64 each)
+
+struct ClipGeo {
+  const unsigned char* clip;
+  int T, H, W, new_h, new_w, y0, x0, flip, ok;
+};
+
+// One row's check, shared by the host entry (its copy of the table) and the kernel (the device copy): a row that
+// fails yields zeros on the device, never a read.  Extents must fit an int: the pixel arithmetic is 32-bit per frame.
+__host__ __device__ __forceinline__ bool batch_row_ok(const long* r, int crop) {
+  const long lim = 0x7fffffffL;
+  return r[0] != 0 && r[1] > 0 && r[1] <= lim && r[2] > 0 && r[2] <= lim && r[3] > 0 && r[3] <= lim && r[4] > 0 &&
+         r[4] <= lim && r[5] > 0 && r[5] <= lim && r[6] >= 0 && r[6] <= lim && r[7] >= 0 && r[7] <= lim && r[6] + crop <= r[4] && r[7] + crop <= r[5];
+}
+
+__device__ __forceinline__ ClipGeo batch_row(const long* __restrict__ tab, int b, int crop) {
+  const long* r = tab + (long)b * BATCH_ROW;
+  ClipGeo g;
+  // the address names global memory (a hipMalloc'ed span): say so, or every tap becomes a flat load
+  g.clip = (const unsigned char*)(const __attribute__((address_space(1))) unsigned char*)(unsigned long)r[0];
+  g.T = (int)r[1]; g.H = (int)r[2]; g.W = (int)r[3];
+  g.new_h = (int)r[4]; g.new_w = (int)r[5]; g.y0 = (int)r[6]; g.x0 = (int)r[7];
+  g.flip = r[8] != 0;
+  g.ok = batch_row_ok(r, crop);
+  return g;
+}
+
+__global__ void clip_batch_kernel(const long* __restrict__ tab, const long* __restrict__ frame_idx,
+                                  const long* __restrict__ slow_idx, int n_fast, int n_slow, int crop, int reverse,
+                                  NormArgs nm, float* __restrict__ fast, float* __restrict__ slow, int ph, int pw, int Wp,
+                                  int plane) {
+  const int p = blockIdx.x * TPB + threadIdx.x;
+  if (p >= plane) return;
+  const int f = blockIdx.y, b = blockIdx.z;
+  const ClipGeo g = batch_row(tab, b, crop);
+  const int yp = p / Wp, xp = p - yp * Wp;
+  f32x4 o = {0.f, 0.f, 0.f, 0.f};
+  const int yy = yp - ph, xx = xp - pw;
+  if (g.ok && yy >= 0 && yy < crop && xx >= 0 && xx < crop) {
+    const long ft = frame_idx[(long)b * n_fast + f];
+    const int t = ft < 0 ? 0 : (ft > g.T - 1 ? g.T - 1 : (int)ft);  // clamped into [0, T_i)
+    const int ys = g.y0 + yy;
+    const int xs = g.x0 + (g.flip ? crop - 1 - xx : xx);
+    float c[3];
+    sample_rgb(g.clip + (long)t * g.H * g.W * 3, g.H, g.W, g.new_h, g.new_w, ys, xs, nm, c);
+    if (reverse) {
+      o[0] = c[2]; o[1] = c[1]; o[2] = c[0];
+    } else {
+      o[0] = c[0]; o[1] = c[1]; o[2] = c[2];
+    }
+  }
+  *reinterpret_cast<f32x4*>(fast + (((long)b * n_fast + f) * plane + p) * 4) = o;
+  for (int j = 0; j < n_slow; ++j)  // n_slow <= n_fast / alpha entries, wave-uniform
+    if (slow_idx[j] == f) *reinterpret_cast<f32x4*>(slow + (((long)b * n_slow + j) * plane + p) * 4) = o;
+}
+
+// One-channel clips: VEC as in clip_views_gray_kernel; `plane` counts threads' units: Hp * Wp / VEC.
+template <int VEC>
+__global__ void clip_batch_gray_kernel(const long* __restrict__ tab, const long* __restrict__ frame_idx,
+                                       const long* __restrict__ slow_idx, int n_fast, int n_slow, int crop, float mean,
+                                       float stdv, float* __restrict__ fast, float* __restrict__ slow, int ph, int pw,
+                                       int Wp, int plane) {
+  const int p = blockIdx.x * TPB + threadIdx.x;
+  if (p >= plane) return;
+  const int f = blockIdx.y, b = blockIdx.z;
+  const ClipGeo g = batch_row(tab, b, crop);
+  const int wq = Wp / VEC;
+  const int yp = p / wq, xp0 = (p - yp * wq) * VEC;
+  const int yy = yp - ph;
+  float o[VEC];
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) o[i] = 0.f;
+  if (g.ok && yy >= 0 && yy < crop) {
+    const long ft = frame_idx[(long)b * n_fast + f];
+    const int t = ft < 0 ? 0 : (ft > g.T - 1 ? g.T - 1 : (int)ft);  // clamped into [0, T_i)
+    const unsigned char* fr = g.clip + (long)t * g.H * g.W;
+    const int ys = g.y0 + yy;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+      const int xx = xp0 + i - pw;
+      if (xx >= 0 && xx < crop)
+        o[i] = sample_gray(fr, g.H, g.W, g.new_h, g.new_w, ys, g.x0 + (g.flip ? crop - 1 - xx : xx), mean, stdv);
+    }
+  }
+  const long fo = (((long)b * n_fast + f) * plane + p) * VEC;
+  if constexpr (VEC == 4) {
+    const f32x4 q = {o[0], o[1], o[2], o[3]};
+    *reinterpret_cast<f32x4*>(fast + fo) = q;
+    for (int j = 0; j < n_slow; ++j)
+      if (slow_idx[j] == f) *reinterpret_cast<f32x4*>(slow + (((long)b * n_slow + j) * plane + p) * VEC) = q;
+  } else {
+    fast[fo] = o[0];
+    for (int j = 0; j < n_slow; ++j)
+      if (slow_idx[j] == f) slow[((long)b * n_slow + j) * plane + p] = o[0];
+  }
+}
+
+// Host-side check of the batch table's host copy: rows [B][9], then frame indices [B][n_fast], then n_slow Slow positions.
+bool batch_table_ok(const long* tab, int B, int n_fast, int n_slow, int crop) {
+  for (int b = 0; b < B; ++b)
+    if (!batch_row_ok(tab + (long)b * BATCH_ROW, crop)) return false;
+  const long* fi = tab + (long)B * BATCH_ROW;
+  for (int b = 0; b < B; ++b) {
+    const long T = tab[(long)b * BATCH_ROW + 1];
+    for (int f = 0; f < n_fast; ++f)
+      if (fi[(long)b * n_fast + f] < 0 || fi[(long)b * n_fast + f] >= T) return false;
+  }
+  const long* si = fi + (long)B * n_fast;
+  for (int j = 0; j < n_slow; ++j)
+    if (si[j] < 0 || si[j] >= n_fast || (j > 0 && si[j] <= si[j - 1])) return false;  // distinct: one owner per Slow frame
+  return true;
+}
+
+// Shared argument checks of the two batch entries; on success *plane = (crop + 2 ph) * Wp.
+bool clip_batch_args_ok(const long* table_host, const long* table, int B, int n_fast, int n_slow, int crop,
+                        const float* fast, const float* slow, int ph, int pw, int Wp, long* plane) {
+  if (!table_host || !table || !fast || B <= 0 || n_fast <= 0 || crop <= 0 || ph < 0 || pw < 0) return false;
+  if (n_slow < 0 || n_slow > n_fast || (slow == nullptr) != (n_slow == 0)) return false;
+  if (B > 65535 || n_fast > 65535 || Wp < crop + 2 * pw) return false;
+  *plane = (long)(crop + 2 * ph) * Wp;
+  if (*plane > 0x7fffffffL / 4) return false;
+  return batch_table_ok(table_host, B, n_fast, n_slow, crop);
+}
 }  // namespace
 
 extern "C" int sf_clip_prologue(const unsigned char* clip, int T, int H, int W, int new_h, int new_w, int y0, int x0,
@@ -320,6 +451,48 @@ extern "C" int sf_clip_views_gray(const unsigned char* video, int T, int H, int 
     hipLaunchKernelGGL(clip_views_gray_kernel<1>, dim3(sf_cdiv(plane, TPB), n_fast, V), dim3(TPB), 0,
                        (hipStream_t)stream, video, T, H, W, table, frame_idx, slow_idx, n_fast, n_slow, crop, mean, stdv,
                        fast, slow, ph, pw, Wp, (int)plane);
+  }
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_clip_batch(const long* table_host, const long* table, int B, int n_fast, int n_slow, int crop,
+                             int reverse, const float* mean3, const float* std3, float* fast, float* slow, int ph,
+                             int pw, int Wp, void* stream) {
+  long plane = 0;
+  if (!mean3 || !std3 ||
+      !clip_batch_args_ok(table_host, table, B, n_fast, n_slow, crop, fast, slow, ph, pw, Wp, &plane))
+    return SF_EINVAL;
+  if (!sf_aligned16(fast) || !sf_aligned16(slow)) return SF_EINVAL;
+  NormArgs nm;
+  for (int c = 0; c < 3; ++c) {
+    nm.m[c] = mean3[c];   // HOST pointers: three floats each
+    nm.s[c] = std3[c];
+  }
+  const long* frame_idx = table + (long)B * BATCH_ROW;
+  hipLaunchKernelGGL(clip_batch_kernel, dim3(sf_cdiv(plane, TPB), n_fast, B), dim3(TPB), 0, (hipStream_t)stream, table,
+                     frame_idx, frame_idx + (long)B * n_fast, n_fast, n_slow, crop, reverse, nm, fast, slow, ph, pw, Wp,
+                     (int)plane);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_clip_batch_gray(const long* table_host, const long* table, int B, int n_fast, int n_slow, int crop,
+                                  float mean, float stdv, float* fast, float* slow, int ph, int pw, int Wp,
+                                  void* stream) {
+  long plane = 0;
+  if (!clip_batch_args_ok(table_host, table, B, n_fast, n_slow, crop, fast, slow, ph, pw, Wp, &plane)) return SF_EINVAL;
+  if (((uintptr_t)fast | (uintptr_t)slow) % sizeof(float)) return SF_EINVAL;  // not even a float's alignment
+  const long* frame_idx = table + (long)B * BATCH_ROW;
+  const long* slow_idx = frame_idx + (long)B * n_fast;
+  if (Wp % 4 == 0 && sf_aligned16(fast) && sf_aligned16(slow)) {
+    hipLaunchKernelGGL(clip_batch_gray_kernel<4>, dim3(sf_cdiv(plane / 4, TPB), n_fast, B), dim3(TPB), 0,
+                       (hipStream_t)stream, table, frame_idx, slow_idx, n_fast, n_slow, crop, mean, stdv, fast, slow, ph,
+                       pw, Wp, (int)(plane / 4));
+  } else {
+    hipLaunchKernelGGL(clip_batch_gray_kernel<1>, dim3(sf_cdiv(plane, TPB), n_fast, B), dim3(TPB), 0,
+                       (hipStream_t)stream, table, frame_idx, slow_idx, n_fast, n_slow, crop, mean, stdv, fast, slow, ph,
+                       pw, Wp, (int)plane);
   }
   SF_CHECK_LAUNCH();
   return SF_OK;

@@ -67,6 +67,8 @@ _SIGNATURES = {
     "sf_clip_prologue_gray": (_ci, [_vp] + [_ci] * 9 + [_cf, _cf, _vp, _ci, _vp, _ci, _ci, _ci, _vp]),
     "sf_clip_views": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp] + [_ci] * 5 + [_vp] * 4 + [_ci, _ci, _ci, _vp]),
     "sf_clip_views_gray": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp] + [_ci] * 4 + [_cf, _cf, _vp, _vp, _ci, _ci, _ci, _vp]),
+    "sf_clip_batch": (_ci, [_vp, _vp] + [_ci] * 5 + [_vp] * 4 + [_ci, _ci, _ci, _vp]),
+    "sf_clip_batch_gray": (_ci, [_vp, _vp] + [_ci] * 4 + [_cf, _cf, _vp, _vp, _ci, _ci, _ci, _vp]),
     "sf_ensemble_update": (_ci, [_vp] * 4 + [_pi] * 3 + [_ci] * 4 + [_vp]),
     "sf_ncthw1_pack": (_ci, [_vp, _vp] + [_ci] * 7 + [_vp]),
     "sf_stem1_accepts": (_ci, [_ci] * 4),
@@ -417,6 +419,35 @@ def clip_views(video_u8, table_host, table, n_slow, crop, mean, std, fast, slow=
         m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
         s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
         _call("sf_clip_views", *head, 1 if reverse else 0, ctypes.cast(m3, _vp), ctypes.cast(s3, _vp), *tail)
+    return fast, slow
+
+
+def clip_batch(table_host, table, n_slow, crop, mean, std, fast, slow=None, gray=False, reverse=False, ph=0, pw=0):
+    """All B clips of one training batch (B separate uint8 device spans, named by address in the table) in one launch ->
+    fast [B, n_fast, crop+2ph, Wp, 4 | 1] and slow [B, n_slow, ...] (None with n_slow == 0: single pathway), the
+    PackedClip layouts `clip_prologue` writes.  table_host: the int64 CPU batch table (B rows address, T, H, W, new_h,
+    new_w, y0, x0, flip; B * n_fast frame indices; n_slow Slow positions), table: its device copy.  The caller keeps the
+    spans alive until the launch has run.  gray: one-channel spans (the buffers' last extent is 1)."""
+    _require_gpu(fast, "clip_batch")
+    if not table.is_cuda or table_host.is_cuda:
+        raise SfhipError("clip_batch: the batch table's copy lives on the GPU, table_host on the host")
+    assert fast.is_contiguous() and fast.dim() == 5 and fast.shape[4] == (1 if gray else 4)
+    B, n_fast = fast.shape[:2]
+    assert table_host.dtype == torch.int64 and table.dtype == torch.int64 and table_host.is_contiguous()
+    assert table.is_contiguous() and table_host.numel() == table.numel() == B * (9 + n_fast) + n_slow
+    if slow is not None:
+        _require_gpu(slow, "clip_batch")
+        assert slow.is_contiguous() and tuple(slow.shape) == (B, n_slow) + tuple(fast.shape[2:])
+    head = (_ptr(table_host), _ptr(table), B, n_fast, int(n_slow), int(crop))
+    tail = (_ptr(fast), _ptr(slow), ph, pw, fast.shape[3])
+    if gray:
+        assert len(mean) == 1 and len(std) == 1, "one-channel clips take a one-element mean / std"
+        assert not reverse, "DATA.REVERSE_INPUT_CHANNEL has no meaning for one-channel clips"
+        _call("sf_clip_batch_gray", *head, float(mean[0]), float(std[0]), *tail)
+    else:
+        m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
+        s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
+        _call("sf_clip_batch", *head, 1 if reverse else 0, ctypes.cast(m3, _vp), ctypes.cast(s3, _vp), *tail)
     return fast, slow
 
 

@@ -5,12 +5,15 @@ Host side (this file) keeps what must stay on the host: the random draws of `spa
 pathway's frame indices (`pack_pathway_output`, datasets/utils.py:73-112).  The arithmetic — uint8 -> float
 normalise (`tensor_normalize`, :298-315), bilinear short-side scale, crop, flip, frame selection — runs as one HIP
 kernel per pathway (`sf_clip_prologue`) that writes the stems' input layout directly, so the decoded clip crosses
-PCIe as uint8 once instead of as two float NCTHW tensors."""
+PCIe as uint8 once instead of as two float NCTHW tensors.  Whole batches go in one launch for both pathways: the
+views of one test video (`test_view_params` -> `gpu_test_views` -> `sf_clip_views`) and the clips of one training
+batch, multigrid's short and long cycles included (`train_clip_params` -> `gpu_train_batch` -> `sf_clip_batch`)."""
 from slowfast._overlay import chain_module as _chain_module
 
 _chain_module(globals())  # the reference's namesake (when importable) supplies every name not defined below
 import collections
 import math
+import random
 
 import numpy as np
 import torch
@@ -187,6 +190,93 @@ def gpu_test_views(video, views, mean, std, alpha, reverse_input_channel=False, 
     fast = torch.empty((V, n_fast, crop + 2 * ph, wp, cpad), dtype=torch.float32, device=dev)
     slow = torch.empty((V, n_slow, crop + 2 * ph, wp, cpad), dtype=torch.float32, device=dev) if n_slow else None
     sfhip.clip_views(video, table_host, table, n_slow, crop, mean, std, fast, slow, reverse=reverse_input_channel,
+                     ph=ph, pw=pw)
+    out = [sfhip.PackedClip(fast, C, crop, crop, ph, pw)]
+    return out if slow is None else [sfhip.PackedClip(slow, C, crop, crop, ph, pw)] + out
+
+
+def get_random_sampling_rate(long_cycle_sampling_rate, sampling_rate):
+    """datasets/utils.py:318-327: with fewer frames in a long cycle the sampling rate is drawn from
+    [sampling_rate, long_cycle_sampling_rate] (Python's `random`), so that some clips cover the original span;
+    long_cycle_sampling_rate 0: `sampling_rate`, nothing drawn."""
+    if long_cycle_sampling_rate > 0:
+        assert long_cycle_sampling_rate >= sampling_rate
+        return random.randint(sampling_rate, long_cycle_sampling_rate)
+    return sampling_rate
+
+
+def train_clip_params(cfg, num_frames_total, height, width, short_cycle_idx=None, fps=None):
+    """The decisions of ONE training sample of the Kinetics / Jester loaders for a decoded span of num_frames_total
+    frames of height x width at `fps` (None: DATA.TARGET_FPS), without touching pixels:
+    the short-cycle crop and the jitter it implies (datasets/kinetics.py:146-165; short_cycle_idx 0 / 1: the crop is
+    MULTIGRID.SHORT_CYCLE_FACTORS[idx] * DEFAULT_S, anything else: DATA.TRAIN_CROP_SIZE), the sampling rate (:186-189),
+    the random temporal window (decoder.py:55-83 with clip_idx == -1 over the span of decoder.py:449), temporal_sampling
+    (:35-52) and the random scale / crop / flip of spatial_sampling.
+    Returns (frame_indices int64 [DATA.NUM_FRAMES], SpatialParams), the tuple `test_view_params` lists.
+    RNG order, the reference's: Python `random` for the sampling rate (only with MULTIGRID.LONG_CYCLE_SAMPLING_RATE > 0),
+    Python `random` for the window start, then numpy's global RNG for scale, crop y, crop x and flip."""
+    min_scale, max_scale = cfg.DATA.TRAIN_JITTER_SCALES[0], cfg.DATA.TRAIN_JITTER_SCALES[1]
+    crop_size = cfg.DATA.TRAIN_CROP_SIZE
+    if short_cycle_idx in [0, 1]:
+        crop_size = int(round(cfg.MULTIGRID.SHORT_CYCLE_FACTORS[short_cycle_idx] * cfg.MULTIGRID.DEFAULT_S))
+    if cfg.MULTIGRID.DEFAULT_S > 0:  # a smaller scale is a larger "span" of the sampling grid
+        min_scale = int(round(float(min_scale) * crop_size / cfg.MULTIGRID.DEFAULT_S))
+    sampling_rate = get_random_sampling_rate(cfg.MULTIGRID.LONG_CYCLE_SAMPLING_RATE, cfg.DATA.SAMPLING_RATE)
+    fps = cfg.DATA.TARGET_FPS if fps is None else fps
+    span = cfg.DATA.NUM_FRAMES * sampling_rate * fps / cfg.DATA.TARGET_FPS  # decoder.py:449
+    start = random.uniform(0, max(num_frames_total - span, 0))              # decoder.py:75-78
+    index = torch.linspace(start, start + span - 1, cfg.DATA.NUM_FRAMES)
+    frames = torch.clamp(index, 0, num_frames_total - 1).long()
+    params = sample_spatial_params(height, width, spatial_idx=-1, min_scale=min_scale, max_scale=max_scale,
+                                   crop_size=crop_size, random_horizontal_flip=cfg.DATA.RANDOM_FLIP,
+                                   inverse_uniform_sampling=cfg.DATA.INV_UNIFORM_SAMPLE)
+    return frames, params
+
+
+BATCH_ROW = 9  # clip address, T, H, W, new_h, new_w, y0, x0, flip
+
+
+def batch_table(videos, samples, n_slow_idx):
+    """The int64 host table sf_clip_batch reads: B rows (address of videos[b], T_b, H_b, W_b, new_h, new_w, y0, x0,
+    flip), the B * n_fast frame indices into each clip's own span (clip-major), then the Slow pathway's positions
+    among the Fast frames (`n_slow_idx`: a tensor, possibly empty)."""
+    rows = torch.tensor([[v.data_ptr(), v.shape[0], v.shape[1], v.shape[2], p.new_h, p.new_w, p.y, p.x, int(p.flip)]
+                         for v, (_, p) in zip(videos, samples)], dtype=torch.int64)
+    frames = torch.stack([torch.as_tensor(f) for f, _ in samples]).to(torch.int64)
+    return torch.cat([rows.flatten(), frames.flatten(), n_slow_idx.to(torch.int64).flatten()]).contiguous()
+
+
+def gpu_train_batch(videos, samples, mean, std, alpha, reverse_input_channel=False, pad=(0, 0), wp=None):
+    """The whole input step of ONE training batch in one kernel launch (sf_clip_batch), temporal sampling included.
+
+    videos:  list of B decoded spans, uint8 [T_i, H_i, W_i, 3] device tensors, each its own allocation and size
+             (grayscale: [T_i, H_i, W_i] or [T_i, H_i, W_i, 1]); they stay alive until the launch has run
+    samples: list of B (frame_indices, SpatialParams) from `train_clip_params` (same crop and frame count for all)
+    the rest as `gpu_input_step`.  One table upload, one launch.  Returns [slow, fast] ([clip] with alpha=None)
+    PackedClips of batch B holding the bits `gpu_input_step` gives for the B gathered clips; a frame both pathways
+    take is resampled once."""
+    B = len(videos)
+    assert B == len(samples) and B > 0
+    crop = samples[0][1].crop
+    n_fast = len(samples[0][0])
+    assert all(p.crop == crop and len(f) == n_fast for f, p in samples)
+    ph, pw = pad
+    wp = crop + 2 * pw if wp is None else wp
+    dev = videos[0].device
+    gray = videos[0].dim() == 3 or videos[0].shape[3] == 1
+    for v in videos:
+        if not v.is_cuda or v.device != dev:
+            raise sfhip.SfhipError("gpu_train_batch: every decoded span lives on one GPU, got %s" % v.device)
+        assert v.dtype == torch.uint8 and v.dim() in (3, 4) and v.is_contiguous()
+        assert (v.dim() == 3 or v.shape[3] == 1) == gray and (gray or v.shape[3] == 3)
+    C, cpad = (1, 1) if gray else (3, 4)
+    slow_idx = slow_frame_indices(n_fast, alpha) if alpha is not None else torch.zeros(0, dtype=torch.long)
+    n_slow = slow_idx.numel()
+    table_host = batch_table(videos, samples, slow_idx)
+    table = table_host.to(dev)  # the one upload: rows, frame indices and Slow positions together
+    fast = torch.empty((B, n_fast, crop + 2 * ph, wp, cpad), dtype=torch.float32, device=dev)
+    slow = torch.empty((B, n_slow, crop + 2 * ph, wp, cpad), dtype=torch.float32, device=dev) if n_slow else None
+    sfhip.clip_batch(table_host, table, n_slow, crop, mean, std, fast, slow, gray=gray, reverse=reverse_input_channel,
                      ph=ph, pw=pw)
     out = [sfhip.PackedClip(fast, C, crop, crop, ph, pw)]
     return out if slow is None else [sfhip.PackedClip(slow, C, crop, crop, ph, pw)] + out

@@ -635,6 +635,34 @@ int sf_clip_views_gray(const unsigned char* video, int T, int H, int W, const in
                        int n_fast, int n_slow, int crop, float mean, float stdv, float* fast, float* slow, int ph,
                        int pw, int Wp, void* stream);
 
+/* ---- training input step, one launch per batch (datasets/kinetics.py:146-165 short-cycle crop and jitter, :186-189
+ * sampling rate, :230-248 normalise / spatial_sampling / pack_pathway_output; decoder.py:55-83 random temporal window,
+ * :35-52 temporal_sampling, :449 the span; datasets/utils.py:318-327 get_random_sampling_rate).
+ * sf_clip_batch: ALL B clips of ONE training batch, for both pathways in one launch.  The B decoded spans are separate
+ *   device allocations, uint8 [T_i,H_i,W_i,3], each with its own scale, crop and flip.  The batch table is B rows
+ *   (clip device address, T_i, H_i, W_i, new_h, new_w, y0, x0, flip), then B * n_fast frame indices into each clip's
+ *   own span (clip-major; this is temporal_sampling's gather), then the n_slow Fast-frame positions the Slow pathway
+ *   takes (shared by the batch, strictly increasing), all int64.  `table` is its device copy and `table_host` the host
+ *   array it was uploaded from: the host copy is checked before anything is launched, the kernel reads the device copy
+ *   and re-checks its row — a device row that fails (zero address, non-positive or over-int extents, crop window
+ *   outside its scaled frame) writes zeros for that clip, and a device frame index is clamped into [0, T_i).
+ *   fast [B][n_fast][crop+2ph][Wp][4] and slow [B][n_slow][crop+2ph][Wp][4] are the layouts sf_clip_prologue writes,
+ *   zero borders included, and hold the same bits: the pixel arithmetic is one device function.  A frame that goes to
+ *   both pathways is resampled once and stored twice.  slow == NULL with n_slow == 0: a single-pathway model.  One
+ *   owner per output element, 16-byte stores, 64-bit element offsets, no atomics.
+ *   SF_EINVAL, nothing launched: null pointers, B <= 0, non-positive sizes, a zero clip address in the host table, a
+ *   crop window outside its scaled frame, a frame index outside [0, T_i), n_slow > n_fast, Slow positions outside
+ *   [0, n_fast) or not increasing, slow given without n_slow (or the reverse), Wp < crop + 2 pw, B or n_fast above
+ *   65535, buffers not 16-byte aligned.  mean3 / std3: HOST.
+ * sf_clip_batch_gray: the same for one-channel spans, uint8 [T_i,H_i,W_i]: one float per pixel ([B][n][crop+2ph][Wp]);
+ *   four pixels per 16-byte store when Wp % 4 == 0 and both buffers are 16-byte aligned, one pixel per store otherwise
+ *   (buffers that are not float-aligned: SF_EINVAL). */
+int sf_clip_batch(const long* table_host, const long* table, int B, int n_fast, int n_slow, int crop, int reverse,
+                  const float* mean3, const float* std3, float* fast, float* slow, int ph, int pw, int Wp,
+                  void* stream);
+int sf_clip_batch_gray(const long* table_host, const long* table, int B, int n_fast, int n_slow, int crop, float mean,
+                       float stdv, float* fast, float* slow, int ph, int pw, int Wp, void* stream);
+
 /* sf_ensemble_update (csrc/ensemble.hip): TestMeter.update_stats (utils/meters.py:283-317) on the device.  preds [B,K],
  *   video_idx int32 [B] (clip id / clips per video), labels int32 [B] or NULL; video_preds [Nv,K], video_labels int32
  *   [Nv], clip_count int32 [Nv] are the meter's accumulators.  mode 0: video_preds[video_idx[b]] += preds[b]; mode 1:
