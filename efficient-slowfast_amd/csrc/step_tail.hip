@@ -1,0 +1,251 @@
+// step_tail.hip — what follows the backward pass in tools/train_net.py:67-157: the loss with its gradient and the
+// meter's top-k counts in one launch (sf_ce_topk), torch.optim.SGD over every parameter of every group in one launch
+// (sf_sgd_step).  Nothing here needs the host: the statistics go to a ring in device memory that the meter drains once
+// per LOG_PERIOD, the hyper-parameters are read from device memory (the LR schedule is a 4-byte write a replayed graph
+// sees) and a non-finite loss switches the update off through a flag the loss kernel leaves.
+#include "common.h"
+
+#include <math.h>
+
+namespace {
+// ---------------------------------------------------------------------------------------------- loss + top-k
+// ONE workgroup: the real sizes are N = 2..64 rows of K = 27..700 logits (45k floats at most, read from L2 after the
+// first pass), so a second workgroup would only add a hand-over.  A wavefront owns rows w, w + 16, ...; a row is three
+// lane-strided sweeps (max + rank of the label, sum of exp, gradient).  exp / log / the sums run in fp64: at these sizes
+// that is free and every stored float is the rounded exact value.  Order of every sum is fixed (lane stride, xor
+// butterfly, rows in order per wavefront, wavefronts in order): equal bits run to run, no atomics.
+constexpr int CE_WAVES = 16;
+constexpr int CE_TPB = CE_WAVES * 64;
+constexpr int RING_ROW = 8;
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+__global__ __launch_bounds__(CE_TPB) void ce_topk_kernel(const float* __restrict__ logits, int ld,
+                                                         const long* __restrict__ labels, int N, int K, int k_hi,
+                                                         float* __restrict__ dlogits, float* __restrict__ ring,
+                                                         int* __restrict__ counter, int cap,
+                                                         float* __restrict__ loss_out) {
+  __shared__ double s_loss[CE_WAVES];
+  __shared__ int s_cnt[CE_WAVES][4];  // top-1 hits, top-k_hi hits, rows with a non-finite logit, bad labels
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const double inv_n = 1.0 / (double)N;
+  double loss = 0.0;
+  int hit1 = 0, hitk = 0, nonfinite = 0, bad = 0;
+  for (int r = wave; r < N; r += CE_WAVES) {
+    const float* x = logits + (long)r * ld;
+    float* dx = dlogits + (long)r * K;
+    const long l = labels[r];
+    const bool ok = l >= 0 && l < K;  // a label outside [0, K): no loss, no gradient, never a read
+    const float xl = ok ? x[l] : 0.f;
+    float m = -INFINITY;
+    int rank = 0, nf = 0;
+    for (int j = lane; j < K; j += 64) {
+      const float v = x[j];
+      m = fmaxf(m, v);
+      nf |= !isfinite(v);
+      rank += (v > xl || (v == xl && j < l)) ? 1 : 0;  // ties go to the lower index
+    }
+    m = wave_max(m);
+    rank = wave_sum(rank);
+    nf = wave_sum(nf) != 0;
+    double s = 0.0;
+    for (int j = lane; j < K; j += 64) s += exp((double)x[j] - (double)m);  // NaN / Inf propagate from here
+    s = wave_sum(s);
+    const double inv_s = 1.0 / s;
+    for (int j = lane; j < K; j += 64) {
+      const double p = exp((double)x[j] - (double)m) * inv_s;
+      dx[j] = ok ? (float)((p - (j == l ? 1.0 : 0.0)) * inv_n) : 0.f;
+    }
+    if (ok) {
+      loss += log(s) + (double)m - (double)xl;
+      if (!nf) {  // a row with a NaN or an Inf is wrong for every k
+        hit1 += rank < 1;
+        hitk += rank < k_hi;
+      }
+    } else {
+      bad += 1;
+    }
+    nonfinite += nf;
+  }
+  if (lane == 0) {
+    s_loss[wave] = loss;
+    s_cnt[wave][0] = hit1;
+    s_cnt[wave][1] = hitk;
+    s_cnt[wave][2] = nonfinite;
+    s_cnt[wave][3] = bad;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+    int c[4] = {0, 0, 0, 0};
+    for (int w = 0; w < CE_WAVES; ++w) {
+      tot += s_loss[w];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) c[i] += s_cnt[w][i];
+    }
+    const float mean = (float)(tot * inv_n);
+    const float flag = (c[2] != 0 || !isfinite(mean)) ? 1.f : 0.f;
+    const int step = counter[0];
+    const int slot = ((step % cap) + cap) % cap;
+    float* row = ring + (long)slot * RING_ROW;
+    const float n = (float)N;
+    row[0] = mean;
+    row[1] = (1.0f - (float)c[0] / n) * 100.0f;  // train_net.py:123-125, in float32 as there
+    row[2] = (1.0f - (float)c[1] / n) * 100.0f;
+    row[3] = flag;
+    row[4] = n;
+    row[5] = (float)c[3];
+    row[6] = 0.f;
+    row[7] = 0.f;
+    loss_out[0] = mean;
+    loss_out[1] = flag;
+    counter[0] = step + 1;  // the only writer: a plain store
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- SGD
+constexpr int SGD_TPB = 256;
+constexpr int SGD_CHUNK = 4096;  // elements per workgroup: four 16-byte accesses per thread and array
+constexpr int TAB_ROW = 6;       // parameter, gradient, momentum buffer (0: none), numel, group, first step
+constexpr int HYP_ROW = 5;       // lr, weight_decay, momentum, dampening, nesterov
+
+struct Hyper {
+  float lr, wd, mom, keep;  // keep = 1 - dampening
+  bool nesterov;
+};
+
+// torch/optim/sgd.py::_single_tensor_sgd for one element; returns the new parameter, *b the new momentum buffer.
+__device__ __forceinline__ float sgd1(float p, float g, float* b, const Hyper& h, bool has_buf, bool first) {
+  if (h.wd != 0.f) g = fmaf(h.wd, p, g);
+  if (has_buf) {
+    const float nb = first ? g : fmaf(h.mom, *b, h.keep * g);
+    *b = nb;
+    g = h.nesterov ? fmaf(h.mom, nb, g) : nb;
+  }
+  return fmaf(-h.lr, g, p);
+}
+
+__device__ __forceinline__ float* as_global(long addr) {
+  // the address names global memory (a hipMalloc'ed span): say so, or every access becomes a flat one
+  return (float*)(__attribute__((address_space(1))) float*)(unsigned long)addr;
+}
+
+__global__ __launch_bounds__(SGD_TPB) void sgd_step_kernel(const long* __restrict__ table,
+                                                           const long* __restrict__ chunks,
+                                                           const float* __restrict__ hyper,
+                                                           const float* __restrict__ guard, int n_tensors, int n_groups,
+                                                           int zero_grad) {
+  if (guard != nullptr && guard[0] != 0.f) return;  // the step's loss was not finite (or NaN itself): no update
+  const long* c = chunks + (long)blockIdx.x * 2;
+  const long ti = c[0], start = c[1];
+  // the host entry checked its copy of both tables; a device row that differs does nothing, never a wild access
+  if (ti < 0 || ti >= n_tensors) return;
+  const long* row = table + ti * TAB_ROW;
+  const long numel = row[3], grp = row[4];
+  if (row[0] == 0 || row[1] == 0 || start < 0 || start >= numel || grp < 0 || grp >= n_groups) return;
+  const float* hy = hyper + grp * HYP_ROW;
+  Hyper h;
+  h.lr = hy[0];
+  h.wd = hy[1];
+  h.mom = hy[2];
+  h.keep = 1.f - hy[3];
+  h.nesterov = hy[4] != 0.f;
+  const bool has_buf = row[2] != 0 && h.mom != 0.f;
+  const bool first = row[5] != 0;
+  float* p = as_global(row[0]) + start;
+  float* g = as_global(row[1]) + start;
+  float* b = as_global(has_buf ? row[2] : row[0]) + start;  // never dereferenced without has_buf
+  const int len = (int)(numel - start < SGD_CHUNK ? numel - start : SGD_CHUNK);
+  const unsigned long bits = (unsigned long)p | (unsigned long)g | (unsigned long)b;
+  if ((bits & 15) == 0) {
+    const int n4 = len >> 2;
+    for (int i = threadIdx.x; i < n4; i += SGD_TPB) {
+      f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+      const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+      f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+      if (has_buf && !first) bv = reinterpret_cast<f32x4*>(b)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float be = bv[e];
+        pv[e] = sgd1(pv[e], gv[e], &be, h, has_buf, first);
+        bv[e] = be;
+      }
+      reinterpret_cast<f32x4*>(p)[i] = pv;
+      if (has_buf) reinterpret_cast<f32x4*>(b)[i] = bv;
+      if (zero_grad) reinterpret_cast<f32x4*>(g)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const int i = (n4 << 2) + threadIdx.x;  // up to three elements left
+    if (i < len) {
+      float be = (has_buf && !first) ? b[i] : 0.f;
+      p[i] = sgd1(p[i], g[i], &be, h, has_buf, first);
+      if (has_buf) b[i] = be;
+      if (zero_grad) g[i] = 0.f;
+    }
+  } else {
+    for (int i = threadIdx.x; i < len; i += SGD_TPB) {
+      float be = (has_buf && !first) ? b[i] : 0.f;
+      p[i] = sgd1(p[i], g[i], &be, h, has_buf, first);
+      if (has_buf) b[i] = be;
+      if (zero_grad) g[i] = 0.f;
+    }
+  }
+}
+
+bool sgd_tables_ok(const long* tab, int n_tensors, const long* chunks, int n_chunks, const float* hyper, int n_groups) {
+  for (int t = 0; t < n_tensors; ++t) {
+    const long* r = tab + (long)t * TAB_ROW;
+    if (r[0] == 0 || r[1] == 0 || ((r[0] | r[1] | r[2]) & 3) != 0) return false;
+    if (r[3] <= 0 || r[4] < 0 || r[4] >= n_groups || (r[5] != 0 && r[5] != 1)) return false;
+    if (hyper[r[4] * HYP_ROW + 2] != 0.f && r[2] == 0) return false;  // momentum without a buffer
+  }
+  // the chunks tile the tensors exactly, in table order: (0, 0), (0, C), ..., (1, 0), ...
+  long t = 0, s = 0;
+  for (int i = 0; i < n_chunks; ++i) {
+    if (t >= n_tensors || chunks[2 * i] != t || chunks[2 * i + 1] != s) return false;
+    s += SGD_CHUNK;
+    if (s >= tab[t * TAB_ROW + 3]) {
+      ++t;
+      s = 0;
+    }
+  }
+  return t == n_tensors && s == 0;
+}
+}  // namespace
+
+extern "C" int sf_ce_topk(const float* logits, int ld, const long* labels, int N, int K, int k_hi, float* dlogits,
+                          float* ring, int* counter, int cap, float* loss_out, void* stream) {
+  if (!logits || !labels || !dlogits || !ring || !counter || !loss_out) return SF_EINVAL;
+  if (N <= 0 || K <= 0 || ld < K || cap <= 0 || k_hi < 1 || k_hi > K) return SF_EINVAL;
+  hipLaunchKernelGGL(ce_topk_kernel, dim3(1), dim3(CE_TPB), 0, (hipStream_t)stream, logits, ld, labels, N, K, k_hi,
+                     dlogits, ring, counter, cap, loss_out);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_sgd_chunk_elems(void) { return SGD_CHUNK; }
+
+extern "C" int sf_sgd_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host,
+                           const long* chunks, int n_chunks, const float* hyper_host, const float* hyper, int n_groups,
+                           const float* guard, int zero_grad, void* stream) {
+  if (!table_host || !table || !chunks_host || !chunks || !hyper_host || !hyper) return SF_EINVAL;
+  if (n_tensors <= 0 || n_chunks <= 0 || n_groups <= 0 || (zero_grad != 0 && zero_grad != 1)) return SF_EINVAL;
+  if (!sgd_tables_ok(table_host, n_tensors, chunks_host, n_chunks, hyper_host, n_groups)) return SF_EINVAL;
+  hipLaunchKernelGGL(sgd_step_kernel, dim3(n_chunks), dim3(SGD_TPB), 0, (hipStream_t)stream, table, chunks, hyper, guard,
+                     n_tensors, n_groups, zero_grad);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}

@@ -194,6 +194,10 @@ _SIGNATURES = {
     "sf_stripe_pool_fwd": (_ci, _VIEW + [_ci] * 7 + _VIEW + [_vp, _vp]),
     "sf_stripe_add_fwd": (_ci, _VIEW * 2 + [_ci] * 6 + _VIEW + [_vp]),
     "sf_stripe_pool_bwd": (_ci, _VIEW * 3 + [_vp] + [_ci] * 6 + _VIEW + [_ci, _vp]),
+    # training-step tail: loss + top-k, one-launch SGD
+    "sf_ce_topk": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp, _vp]),
+    "sf_sgd_chunk_elems": (_ci, []),
+    "sf_sgd_step": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _ci, _vp]),
 }
 EXPORTS = list(_SIGNATURES)
 

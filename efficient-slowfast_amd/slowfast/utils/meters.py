@@ -6,11 +6,14 @@ performs the ensemble, so the test loop never synchronises with the GPU until `f
 from slowfast._overlay import chain_module as _chain_module
 
 _chain_module(globals())  # the reference's namesake (when importable) supplies every name not defined below
+import collections
 import datetime
 import json
 import logging
+import math
 import time
 
+import numpy as np
 import torch
 
 _LOG = logging.getLogger(__name__)
@@ -150,4 +153,169 @@ class DeviceTestMeter(TestMeter):
         correct = topks_correct(video_preds, video_labels, ks)
         for kk, c in zip(ks, correct):
             stats["top{}_acc".format(kk)] = "{:.{prec}f}".format(float(c) / video_preds.size(0) * 100.0, prec=2)
+        return stats
+
+
+# ---------------------------------------------------------------------------------------------- training meter
+class _ScalarWindow(object):
+    """utils/meters.py:375-423 ScalarMeter: a window of the last `window_size` values plus the running total."""
+
+    def __init__(self, window_size):
+        self.deque = collections.deque(maxlen=window_size)
+        self.total = 0.0
+        self.count = 0
+
+    def reset(self):
+        self.deque.clear()
+        self.total = 0.0
+        self.count = 0
+
+    def add_value(self, value):
+        self.deque.append(value)
+        self.count += 1
+        self.total += value
+
+    def get_win_median(self):
+        return np.median(self.deque)
+
+    def get_win_avg(self):
+        return np.mean(self.deque)
+
+    def get_global_avg(self):
+        return self.total / self.count
+
+
+def format_json_stats(stats):
+    """The line utils/logging.py:84-96 log_json_stats writes: floats with six decimals, keys sorted."""
+    items = []
+    for k in sorted(stats):
+        v = stats[k]
+        items.append("%s: %s" % (json.dumps(k), "{:.6f}".format(v) if isinstance(v, float) else json.dumps(v)))
+    return "json_stats: {" + ", ".join(items) + "}"
+
+
+class DeviceTrainMeter(object):
+    """TrainMeter (utils/meters.py:426-554) for a loop that never reads the loss on the host: the loss kernel
+    (`models.step_tail.HipCrossEntropy`) leaves one row {loss, top-1 err, top-k err, non-finite flag, N, bad labels}
+    per step in a device ring of LOG_PERIOD rows, `update_stats(lr)` only records the host learning rate, and
+    `log_iter_stats` (on a LOG_PERIOD boundary) / `log_epoch_stats` drain the ring: one all-reduce of the block when
+    NUM_GPUS > 1 (train_net.py:128-131), ONE device-to-host copy, then TrainMeter.update_stats' arithmetic row by row —
+    the logged medians and averages are the reference's for the same values.  A drained row with the non-finite flag
+    raises misc.check_nan_losses' RuntimeWarning (late by at most LOG_PERIOD steps; `HipSGD.step(guard=...)` keeps
+    such a step from touching the parameters), a bad-label count raises ValueError."""
+
+    def __init__(self, epoch_iters, cfg, ring=None, device="cuda"):
+        from slowfast.models.step_tail import StatsRing
+        self._cfg = cfg
+        self.epoch_iters = epoch_iters
+        self.MAX_EPOCH = cfg.SOLVER.MAX_EPOCH * epoch_iters
+        self._tic, self._lap = time.perf_counter(), 0.0
+        self.ring = ring if ring is not None else StatsRing(cfg.LOG_PERIOD, device)
+        self._drained = 0  # ring.counter at the last drain
+        self.loss = _ScalarWindow(cfg.LOG_PERIOD)
+        self.mb_top1_err = _ScalarWindow(cfg.LOG_PERIOD)
+        self.mb_top5_err = _ScalarWindow(cfg.LOG_PERIOD)
+        self.reset()
+
+    def reset(self):
+        self.loss.reset()
+        self.loss_total = 0.0
+        self.lr = None
+        self.mb_top1_err.reset()
+        self.mb_top5_err.reset()
+        self.num_top1_mis = 0
+        self.num_top5_mis = 0
+        self.num_samples = 0
+
+    def iter_tic(self):
+        self._tic = time.perf_counter()
+
+    def iter_toc(self):
+        self._lap = time.perf_counter() - self._tic
+
+    def update_stats(self, lr):
+        self.lr = lr
+
+    def _fold(self, top1_err, top5_err, loss, mb_size):
+        """TrainMeter.update_stats (utils/meters.py:477-498) for one step's values."""
+        self.loss.add_value(loss)
+        self.loss_total += loss * mb_size
+        self.num_samples += mb_size
+        self.mb_top1_err.add_value(top1_err)
+        self.mb_top5_err.add_value(top5_err)
+        self.num_top1_mis += top1_err * mb_size
+        self.num_top5_mis += top5_err * mb_size
+
+    def drain(self):
+        """Fold the rows written since the last drain; returns how many there were."""
+        import slowfast.utils.distributed as du
+        ring = self.ring
+        world = max(int(self._cfg.NUM_GPUS), 1)
+        # the counter rides in the block (exact in float32 far beyond any epoch: the difference below is what is used)
+        block = torch.cat([ring.rows.flatten(), ring.counter.to(torch.float64).sub_(self._drained).float()])
+        if world > 1:
+            du.all_reduce([block])
+        host = block.cpu()  # the one device-to-host copy (the only synchronisation of the logging period)
+        fresh = int(round(float(host[-1])))
+        rows = host[:-1].view(ring.cap, -1)
+        if fresh < 0 or fresh > ring.cap:
+            raise RuntimeError("DeviceTrainMeter: {} steps since the last drain but the ring holds {} — drain at least "
+                               "every LOG_PERIOD steps".format(fresh, ring.cap))
+        for i in range(self._drained, self._drained + fresh):
+            loss, top1, top5, flag, n, bad = [float(v) for v in rows[i % ring.cap, :6]]
+            if bad != 0:
+                raise ValueError("DeviceTrainMeter: step {} had label(s) outside [0, classes) ({:g} per rank on "
+                                 "average)".format(i, bad))
+            if flag != 0 or math.isnan(loss):
+                raise RuntimeWarning("ERROR: Got NaN losses {}".format(datetime.datetime.now()))
+            self._fold(top1, top5, loss, int(round(n)) * world)
+        self._drained += fresh
+        return fresh
+
+    def _eta(self, iters_left):
+        return str(datetime.timedelta(seconds=int(self._lap * iters_left)))
+
+    @staticmethod
+    def _gpu_mem():
+        return (torch.cuda.max_memory_allocated() if torch.cuda.is_available() else 0) / 1024 ** 2
+
+    def log_iter_stats(self, cur_epoch, cur_iter):
+        if (cur_iter + 1) % self._cfg.LOG_PERIOD != 0:
+            return None
+        self.drain()
+        stats = {
+            "_type": "train_iter",
+            "epoch": "{}/{}".format(cur_epoch + 1, self._cfg.SOLVER.MAX_EPOCH),
+            "iter": "{}/{}".format(cur_iter + 1, self.epoch_iters),
+            "time_diff": self._lap,
+            "eta": self._eta(self.MAX_EPOCH - (cur_epoch * self.epoch_iters + cur_iter + 1)),
+            "loss": self.loss.get_win_median(),
+            "lr": self.lr,
+            "gpu_mem": "{:.2f} GB".format(self._gpu_mem()),
+            "top1_err": self.mb_top1_err.get_win_median(),
+            "top5_err": self.mb_top5_err.get_win_median(),
+        }
+        _LOG.info(format_json_stats(stats))
+        return stats
+
+    def log_epoch_stats(self, cur_epoch):
+        self.drain()
+        stats = {
+            "_type": "train_epoch",
+            "epoch": "{}/{}".format(cur_epoch + 1, self._cfg.SOLVER.MAX_EPOCH),
+            "time_diff": self._lap,
+            "eta": self._eta(self.MAX_EPOCH - (cur_epoch + 1) * self.epoch_iters),
+            "lr": self.lr,
+            "gpu_mem": "{:.2f} GB".format(self._gpu_mem()),
+        }
+        try:
+            import psutil
+            vram = psutil.virtual_memory()
+            stats["RAM"] = "{:.2f}/{:.2f} GB".format((vram.total - vram.available) / 1024 ** 3, vram.total / 1024 ** 3)
+        except ImportError:  # the reference needs psutil for this one field
+            pass
+        stats["top1_err"] = self.num_top1_mis / self.num_samples
+        stats["top5_err"] = self.num_top5_mis / self.num_samples
+        stats["loss"] = self.loss_total / self.num_samples
+        _LOG.info(format_json_stats(stats))
         return stats

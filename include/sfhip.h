@@ -842,6 +842,46 @@ int sf_stripe_pool_bwd(const float* dz, int dz_cs, int dz_coff, const float* dme
                        const float* dmax, int dmax_cs, int dmax_coff, const void* arg, int N, int T, int H, int W,
                        int C, int S, float* dx, int dx_cs, int dx_coff, int accumulate, void* stream);
 
+/* ---- the training step's tail (csrc/step_tail.hip): tools/train_net.py:87-138 and :93-96 without the host.
+ * sf_ce_topk: softmax cross-entropy with mean reduction (losses.py "cross_entropy", train_net.py:87), its gradient
+ *   and metrics.topks_correct for k = 1 and k = k_hi (TRAIN.TOPK; train_net.py:122-125) in ONE launch.
+ *   logits fp32 [N][K] with row stride ld >= K floats, labels int64 [N].  dlogits [N][K] (dense) = (softmax - onehot) / N.
+ *   ring is `float[cap][8]` and counter `int[1]`, both device memory: the kernel writes row (*counter % cap) as
+ *   {loss, top-1 error %, top-k_hi error %, non-finite flag, N, bad-label count, 0, 0} and then stores *counter + 1 —
+ *   one thread, a plain store; the slot comes from device memory, so a replayed graph advances it.  The errors are
+ *   (1 - correct / N) * 100 in float32.  loss_out is `float[2]`: the loss (the autograd result) and the same non-finite
+ *   flag at an address that does not move with the ring — what sf_sgd_step takes as `guard`.
+ *   Hit rule: row i is a top-k hit iff  #{j : x_j > x_l} + #{j < l : x_j == x_l} < k  (l = labels[i]): ties go to the
+ *   lower index.  A row holding a NaN or an Inf sets the flag and counts as wrong for every k; NaN propagates into the
+ *   loss and that row's gradient (the row maximum is subtracted before exp; a non-finite loss sets the flag too).  A
+ *   label outside [0, K): the row adds 0 to the loss, gets a zero gradient row, counts as wrong and is counted in the
+ *   bad-label field; nothing is read out of bounds.  exp, log and all sums run in fp64 in a fixed order (no atomics):
+ *   two runs give equal bits.  One workgroup; any N and K (the real sizes are N = 2..64, K = 27..700).
+ *   SF_EINVAL, nothing enqueued: a null pointer, N <= 0, K <= 0, ld < K, cap <= 0, k_hi < 1 or k_hi > K.
+ * sf_sgd_step: torch.optim.SGD's update (torch/optim/sgd.py::_single_tensor_sgd) of every parameter of every group in
+ *   ONE launch, per element and in that order:  g += wd * p;  buf = g on the tensor's first step, else
+ *   buf = m * buf + (1 - d) * g;  g = g + m * buf if nesterov else buf;  p -= lr * g  (buf steps skipped when m == 0).
+ *   table: int64 [n_tensors][6] = parameter address, gradient address, momentum-buffer address (0: the group has no
+ *   momentum), numel, group, first-step flag (0 / 1).  chunks: int64 [n_chunks][2] = tensor index, first element; a
+ *   chunk covers min(sf_sgd_chunk_elems(), numel - first) elements of ONE tensor and the chunks tile the tensors
+ *   exactly, in table order.  hyper: fp32 [n_groups][5] = lr, weight_decay, momentum, dampening, nesterov, read from
+ *   DEVICE memory by the kernel: a new learning rate is a 4-byte device write that a replayed graph sees.  The *_host
+ *   arguments are the host arrays the three were uploaded from: they are checked before anything is launched, and the
+ *   kernel re-checks the device row it reads (a row that fails is skipped, never dereferenced).
+ *   guard: NULL, or a device float; when it reads non-zero (NaN included) the launch updates nothing.
+ *   zero_grad = 1: zeros are stored to every gradient element after it is read.
+ *   A chunk whose three addresses are all 16-byte aligned moves 16 bytes per access, any other 4; one owner per
+ *   element, no atomics.
+ *   SF_EINVAL, nothing enqueued: a null pointer (guard excepted), non-positive counts, zero_grad outside {0, 1}, a
+ *   zero or 4-byte-misaligned address, numel <= 0, a group outside [0, n_groups), a first-step flag outside {0, 1}, a
+ *   momentum address of 0 in a group whose momentum is not 0, chunks that do not tile the tensors exactly. */
+int sf_ce_topk(const float* logits, int ld, const long* labels, int N, int K, int k_hi, float* dlogits, float* ring,
+               int* counter, int cap, float* loss_out, void* stream);
+int sf_sgd_chunk_elems(void);
+int sf_sgd_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
+                int n_chunks, const float* hyper_host, const float* hyper, int n_groups, const float* guard,
+                int zero_grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
