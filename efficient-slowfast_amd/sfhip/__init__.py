@@ -1201,6 +1201,18 @@ def unpack_conv_weight_grad(dwp, shape):
     return dwp[:, :, :cin].permute(0, 2, 1).reshape(cout, cin, kT, kH, kW).contiguous()
 
 
+def _bn_bwd_y(who, y, z, relu, mask, plain):
+    """(pointer, pitch, channel offset, activation code) of what a BN backward kernel takes its ReLU mask from: the
+    activation y, or — code 3 — the byte mask affine(mask=...) left, read instead of it.  plain: the layer is neither
+    T-repeated nor split, the only form a byte mask is made for."""
+    if mask is not None and relu:
+        if not plain or mask.numel() != z.rows * (z.C // 4) or not mask.is_cuda:
+            raise SfhipError("%s: the byte mask holds rows * C/4 bytes of an un-repeated, un-split layer" % who)
+        return _ptr(mask), z.C // 4, 0, 3
+    code = 2 if relu == 6 else (1 if relu else 0)
+    return (y.ptr(), y.cs, y.coff, code) if y is not None else (None, 0, 0, code)
+
+
 def bn_bwd(dy, y, z, mean, invstd, gamma, relu, rep=1, dres=None, dz_out=None, dgamma_out=None, nsplit=1,
            sync=None, grad_sink=None, mask=None, dres_overwrite=False):
     """Training BN backward (+ReLU mask, + residual fan-out, + upsample-copy sum).  Returns (dz, dgamma, dbeta);
@@ -1215,11 +1227,7 @@ def bn_bwd(dy, y, z, mean, invstd, gamma, relu, rep=1, dres=None, dz_out=None, d
     dbeta = torch.empty((nsplit * C,), dtype=torch.float32, device=dev)
     dgamma = torch.empty((nsplit * C,), dtype=torch.float32, device=dev)
     ws = torch.empty((lib().sf_bn_bwd_ws_floats(C),), dtype=torch.float32, device=dev)
-    yp, ycs, yco = (y.ptr(), y.cs, y.coff) if y is not None else (None, 0, 0)
-    code = 2 if relu == 6 else (1 if relu else 0)
-    if mask is not None and relu:  # the byte mask affine(mask=...) left: read instead of the activation
-        assert rep == 1 and nsplit == 1 and mask.numel() == z.rows * (C // 4)
-        yp, ycs, yco, code = _ptr(mask), C // 4, 0, 3
+    yp, ycs, yco, code = _bn_bwd_y("bn_bwd", y, z, relu, mask, rep == 1 and nsplit == 1)
     head = (dy.ptr(), dy.cs, dy.coff, yp, ycs, yco, z.ptr(), z.cs, z.coff, z.N, z.T, z.H, z.W, C)
     tail = (rep, code, _ptr(mean), _ptr(invstd))
     split = (nsplit,) if nsplit > 1 else ()
@@ -1280,12 +1288,7 @@ def bn_frozen_bwd(dy, y, z, mean, invstd, gamma, relu, rep=1, dres=None, dres_ov
                 raise SfhipError("bn_frozen_bwd: %s must be a contiguous tensor of at least %d floats" % (name, C))
         dgp, dbp = _ptr(grads[0]), _ptr(grads[1])
         ws = torch.empty((lib().sf_bn_bwd_ws_floats(C),), dtype=torch.float32, device=dev)
-    yp, ycs, yco = (y.ptr(), y.cs, y.coff) if (y is not None and relu) else (None, 0, 0)
-    code = 2 if relu == 6 else (1 if relu else 0)
-    if mask is not None and relu:  # the byte mask affine(mask=...) left: read instead of the activation
-        if rep != 1 or mask.numel() != z.rows * (C // 4) or not mask.is_cuda:
-            raise SfhipError("bn_frozen_bwd: the byte mask holds rows * C/4 bytes of an un-repeated layer")
-        yp, ycs, yco, code = _ptr(mask), C // 4, 0, 3
+    yp, ycs, yco, code = _bn_bwd_y("bn_frozen_bwd", y if relu else None, z, relu, mask, rep == 1)
     out = z if dz_out is None else dz_out
     _call("sf_bn_frozen_bwd", dy.ptr(), dy.cs, dy.coff, yp, ycs, yco, z.ptr(), z.cs, z.coff, z.N, z.T, z.H, z.W, C,
           rep, code, _ptr(mean.detach()), _ptr(invstd.detach()), _ptr(gamma.detach()) if gamma is not None else None,

@@ -96,16 +96,19 @@ class Tape(object):
     def has_grad(self, act):
         return act.buf.data_ptr() in self.gbuf
 
-    def grad_of_uninitialised(self, act):
-        """The gradient buffer of a whole-buffer activation that has no gradient yet, NOT zeroed: the caller must
-        overwrite every element (the first — usually only — consumer's data gradient), which saves the zero fill
-        and the read of an accumulate.  Returns None when the buffer already exists or `act` is a channel slice."""
+    def grad_dst(self, act, whole=True):
+        """(gradient buffer of `act`, accumulate) for a backward op about to issue dL/d(act) — the ONE statement of the
+        first-writer rule.  A whole-buffer activation that has no gradient yet (and `whole`: the op writes every
+        element of it) gets an UNINITIALISED buffer and accumulate=False: the caller is the first — usually only —
+        writer and must overwrite every element, which saves the zero fill and the read of an accumulate.  In every
+        other case (a channel slice, a buffer that already holds a fan-in sum, not `whole`) it is grad_of's
+        zero-initialised or existing buffer and accumulate=True."""
         key = act.buf.data_ptr()
-        if key in self.gbuf or act.coff != 0 or act.cs != act.C:
-            return None
+        if not whole or key in self.gbuf or act.coff != 0 or act.cs != act.C:
+            return self.grad_of(act), True
         g = torch.empty(act.buf.numel(), dtype=torch.float32, device=act.buf.device)
         self.gbuf[key] = g
-        return Act(g.view(act.buf.shape), 0, act.C)
+        return Act(g.view(act.buf.shape), 0, act.C), False
 
     def record(self, fn):
         self.ops.append((fn, self.side))
@@ -130,19 +133,22 @@ class Tape(object):
         for p, g in zip(params, grads):
             self.add_pgrad(p, g)
 
+    def _replay(self):
+        """The recorded ops in reverse, each on the stream it was recorded for: ops recorded inside run_paths on the
+        side stream run there again; the region's join / fork markers become the backward pass's fork / join."""
+        for fn, side in reversed(self.ops):
+            if side is None:
+                fn()
+            else:
+                with torch.cuda.stream(side):
+                    fn()
+
     def backward(self):
-        """Replay in reverse.  Ops recorded inside run_paths on the side stream run there again; the region's
-        join / fork markers become the backward pass's fork / join."""
         self._open_arena()
         self.capturing = bool(torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
         asked = -1
         try:
-            for fn, side in reversed(self.ops):
-                if side is None:
-                    fn()
-                else:
-                    with torch.cuda.stream(side):
-                        fn()
+            self._replay()
             for wg in self.joins:
                 _sync_streams(wg, torch.cuda.current_stream(wg.device))
             asked = self.zero_floats
@@ -208,18 +214,12 @@ class EvalTape(Tape):
 
     def backward(self, dout):
         """Replay from dL/d(out) = dout [N, classes] down to the target boundary; returns dL/d(target outputs) as
-        Acts (views of the gradient buffers, which then belong to the caller).  Every op runs on the stream it was
-        recorded on."""
+        Acts (views of the gradient buffers, which then belong to the caller)."""
         if self.target_acts is None or self.out is None:
             raise RuntimeError("the eval tape saw no boundary named %r, or no head output" % (self.target,))
         self.dout = dout.contiguous()
         try:
-            for fn, side in reversed(self.ops):
-                if side is None:
-                    fn()
-                else:
-                    with torch.cuda.stream(side):
-                        fn()
+            self._replay()
             return [self.grad_of(a) for a in self.target_acts]
         finally:
             self.ops = []
@@ -440,11 +440,8 @@ def _record_conv(x, conv_weight, conv_bias, wp_shape, gsrc, kernel, stride, padd
                 wtp = _cached_t(conv_weight, "_sf_wtp", _key(conv_weight),
                                 lambda: sfhip.pack_conv_weight(conv_weight.detach().reshape(
                                     conv_weight.shape[0], conv_weight.shape[1], *kernel).transpose(0, 1).contiguous()))
-            fresh = t.grad_of_uninitialised(x)
-            if fresh is not None:  # first consumer of x: write, do not accumulate
-                sfhip.conv_dgrad(g, wtp, x, kernel, stride, padding, dilation, out=fresh, accumulate=False)
-            else:
-                sfhip.conv_dgrad(g, wtp, x, kernel, stride, padding, dilation, out=t.grad_of(x), accumulate=True)
+            dx, acc = t.grad_dst(x)  # first consumer of x: write, do not accumulate
+            sfhip.conv_dgrad(g, wtp, x, kernel, stride, padding, dilation, out=dx, accumulate=acc)
 
     t.record(bwd)
 
@@ -613,6 +610,66 @@ def _bn_train_stats(bn, z, conv_stats=None):
     return mean, invstd, scale, shift, 1, bn.weight, None
 
 
+def _bn_epilogue(bn, z, scale, shift, make_backward, res, relu, rep, out, out_reserve, keep, out_cmul, nsplit=1,
+                 eager_sums=False, always_sums=False):
+    """The normalise(+residual)(+ReLU)(+T-repeat) pass of an un-fused norm layer on the raw tensor z, and its tape
+    closure — what bn_train_apply and bn_frozen_apply share.  keep: only the first `keep` channels are normalised
+    (GhostModule [:oup]); out_cmul: the channel-interleaved store (ShuffleNetV2).
+    make_backward() is called once, behind the forward pass of a TAPED layer, and returns
+    backward(dy, y, zz, dres, dres_accumulate, sink, sums, mask): the layer's one sfhip.*_bwd call, which leaves dL/dz
+    in zz (z's own buffer, where the producer's backward looks for it).  dgamma / dbeta go into sink = (weight.grad,
+    bias.grad) under the gradient sink, else into sums = two zero-filled [z.C] tensors that are then handed to the
+    tape; both are None when the layer owes no parameter gradient.  eager_sums: `sums` is made here, in the forward,
+    instead of in the closure; always_sums: the sums are taken even when no parameter receives them."""
+    zz = z if keep is None else z.slice(0, keep)
+    if keep is not None:
+        assert nsplit == 1, "channel-sliced BN (GhostModule) is only defined for plain BatchNorm3d"
+        scale, shift = scale[:keep], shift[:keep]
+    t = tape()
+    shuffled = t is not None and out_cmul != 1
+    # taped ReLU / ReLU6 layers: the normalise pass also leaves a byte per 4 channels for the backward's mask, which
+    # then reads that instead of the activation (1/16 of the bytes, twice per backward)
+    mk = {} if (t is not None and relu) else None
+    # taped: a channel-shuffled store is an explicit (taped) strided copy of the dense result
+    dst = {} if shuffled else dict(out=out, out_reserve=out_reserve, out_cmul=out_cmul)
+    y = sfhip.affine(zz, scale.contiguous(), shift.contiguous(), res=res, relu=relu, rep=rep, nsplit=nsplit, mask=mk,
+                     **dst)
+    if t is not None:
+        mask = mk.get("bytes") if mk else None
+        weight, bias = getattr(bn, "weight", None), getattr(bn, "bias", None)
+        affine = weight is not None and bias is not None
+        backward = make_backward()
+
+        def zeros():
+            return torch.zeros(z.C, dtype=torch.float32, device=z.buf.device)
+
+        made = (zeros(), zeros()) if eager_sums else None
+
+        def bwd():
+            dres, acc = None, True
+            if res is not None:  # first writer of the residual branch's gradient: write it, no zero fill / read
+                dres, acc = t.grad_dst(res, whole=nsplit == 1 and res.C == zz.C and rep == 1)
+            sink = sums = None
+            if always_sums or (affine and t.param_grads):
+                wt, bt = (t.pgrad_target(weight), t.pgrad_target(bias)) if (affine and nsplit == 1) else (None, None)
+                if wt is not None and bt is not None:  # dgamma / dbeta accumulate into .grad inside the reduction
+                    sink = (wt, bt)
+                else:
+                    sums = made or (zeros(), zeros())
+            backward(t.grad_of(y), y, zz, dres, acc, sink, sums, mask)
+            if keep is not None and keep < z.C:  # sliced-away channels (GhostModule [:oup]) get no gradient
+                rest = z.slice(keep, z.C - keep)
+                sfhip.axpy(rest, rest, alpha=0.0, accumulate=False)
+            if sums is not None and affine:
+                t.add_pgrad(weight, sums[0])
+                t.add_pgrad(bias, sums[1])
+
+        t.record(bwd)  # afterwards z's buffer holds dL/dz for the producer's backward
+    if shuffled:  # recorded AFTER the BN op so that its backward (the gather) runs first
+        return copy_channels(y, out, out_cmul=out_cmul)
+    return y
+
+
 def bn_train_apply(bn, z, res=None, relu=False, rep=1, out=None, out_reserve=(0, 0), keep=None, out_cmul=1,
                    conv_stats=None):
     """Training-mode BatchNorm3d on the raw tensor z: batch statistics (sf_channel_stats), running-stat update
@@ -620,59 +677,17 @@ def bn_train_apply(bn, z, res=None, relu=False, rep=1, out=None, out_reserve=(0,
     check_bn(bn)
     with torch.no_grad():
         mean, invstd, scale, shift, nsplit, gamma_b, sync = _bn_train_stats(bn, z, conv_stats)
-    zz = z if keep is None else z.slice(0, keep)
-    nk = z.C if keep is None else keep
-    if keep is not None:
-        assert nsplit == 1, "channel-sliced BN (GhostModule) is only defined for plain BatchNorm3d"
-        scale, shift = scale[:keep].contiguous(), shift[:keep].contiguous()
-    t = tape()
-    shuffled = t is not None and out_cmul != 1
-    # taped ReLU / ReLU6 layers: the normalise pass also leaves a byte per 4 channels for the backward's mask, which
-    # then reads that instead of the activation (1/16 of the bytes, twice per backward)
-    mk = {} if (t is not None and relu) else None
-    if shuffled:
-        # training: a channel-shuffled store is an explicit (taped) strided copy of the dense result
-        y = sfhip.affine(zz, scale.contiguous(), shift.contiguous(), res=res, relu=relu, rep=rep, nsplit=nsplit,
-                         mask=mk)
-    else:
-        y = sfhip.affine(zz, scale.contiguous(), shift.contiguous(), res=res, relu=relu, rep=rep, out=out,
-                         out_reserve=out_reserve, out_cmul=out_cmul, nsplit=nsplit, mask=mk)
-    mask = mk.get("bytes") if mk else None
-    if t is not None:
-        if _GRAD_SINK:
-            dg = db = None  # allocated lazily by the fallback below
-        else:
-            dg = torch.zeros(z.C, dtype=torch.float32, device=z.buf.device)
-            db = torch.zeros(z.C, dtype=torch.float32, device=z.buf.device)
-        sel = slice(None) if nsplit > 1 else slice(0, nk)
+    sel = slice(None) if nsplit > 1 else slice(0, z.C if keep is None else keep)
 
-        def bwd():
-            dres, first = None, False
-            if res is not None:  # first writer of the residual branch's gradient: write it, no zero fill / read
-                fresh = t.grad_of_uninitialised(res) if (nsplit == 1 and res.C == zz.C and rep == 1) else None
-                dres, first = (fresh, True) if fresh is not None else (t.grad_of(res), False)
-            wt = t.pgrad_target(bn.weight) if (nsplit == 1 and getattr(bn, "weight", None) is not None) else None
-            bt = t.pgrad_target(bn.bias) if wt is not None else None
-            if wt is not None and bt is not None:  # dgamma / dbeta accumulate into .grad inside the reduction
-                sfhip.bn_bwd(t.grad_of(y), y, zz, mean[sel], invstd[sel], gamma_b[sel], relu, rep=rep, dres=dres,
-                             dz_out=zz, sync=sync, grad_sink=(wt, bt), mask=mask, dres_overwrite=first)
-            else:
-                dg_ = dg if dg is not None else torch.zeros(z.C, dtype=torch.float32, device=z.buf.device)
-                db_ = db if db is not None else torch.zeros(z.C, dtype=torch.float32, device=z.buf.device)
-                sfhip.bn_bwd(t.grad_of(y), y, zz, mean[sel], invstd[sel], gamma_b[sel], relu, rep=rep, dres=dres,
-                             dz_out=zz, dgamma_out=(dg_, db_), nsplit=nsplit, sync=sync, mask=mask,
-                             dres_overwrite=first)
-            if keep is not None and keep < z.C:  # sliced-away channels (GhostModule [:oup]) get no gradient
-                rest = z.slice(keep, z.C - keep)
-                sfhip.axpy(rest, rest, alpha=0.0, accumulate=False)
-            if (wt is None or bt is None) and getattr(bn, "weight", None) is not None:
-                t.add_pgrad(bn.weight, dg_)
-                t.add_pgrad(bn.bias, db_)
+    def backward(dy, y, zz, dres, dres_accumulate, sink, sums, mask):
+        sfhip.bn_bwd(dy, y, zz, mean[sel], invstd[sel], gamma_b[sel], relu, rep=rep, dres=dres, dz_out=zz,
+                     dgamma_out=sums, nsplit=nsplit, sync=sync, grad_sink=sink, mask=mask,
+                     dres_overwrite=not dres_accumulate)
 
-        t.record(bwd)  # afterwards z's buffer holds dL/dz for the producer's backward
-    if shuffled:  # recorded AFTER the BN op so that its backward (the gather) runs first
-        return copy_channels(y, out, out_cmul=out_cmul)
-    return y
+    # without the gradient sink the dgamma / dbeta temporaries are made in the forward; with it, only by a layer whose
+    # parameters turn out to have no .grad to accumulate into
+    return _bn_epilogue(bn, z, scale, shift, lambda: backward, res, relu, rep, out, out_reserve, keep, out_cmul,
+                        nsplit=nsplit, eager_sums=not _GRAD_SINK, always_sums=True)
 
 
 def bn_affine(bn, conv_bias=None):
@@ -730,51 +745,19 @@ def bn_frozen_apply(bn, z, res=None, relu=False, rep=1, out=None, out_reserve=(0
     trainable: eval() does not freeze them).  Untaped it is the same affine pass and nothing else."""
     check_bn(bn)
     scale, shift = bn_affine(bn)
-    zz = z if keep is None else z.slice(0, keep)
-    nk = z.C if keep is None else keep
-    if keep is not None:  # channel-sliced BN (GhostModule [:oup])
-        scale, shift = scale[:keep].contiguous(), shift[:keep].contiguous()
-    t = tape()
-    shuffled = t is not None and out_cmul != 1
-    mk = {} if (t is not None and relu) else None
-    if shuffled:
-        # taped: a channel-shuffled store is an explicit (taped) strided copy of the dense result
-        y = sfhip.affine(zz, scale, shift, res=res, relu=relu, rep=rep, mask=mk)
-    else:
-        y = sfhip.affine(zz, scale, shift, res=res, relu=relu, rep=rep, out=out, out_reserve=out_reserve,
-                         out_cmul=out_cmul, mask=mk)
-    mask = mk.get("bytes") if mk else None
-    if t is not None:
+
+    def make_backward():
         mean, invstd = _bn_frozen_stats(bn)
-        weight, bias = getattr(bn, "weight", None), getattr(bn, "bias", None)
+        weight = getattr(bn, "weight", None)
 
-        def bwd():
-            dres, first = None, False
-            if res is not None:  # first writer of the residual branch's gradient: write it, no zero fill / read
-                fresh = t.grad_of_uninitialised(res) if (res.C == zz.C and rep == 1) else None
-                dres, first = (fresh, True) if fresh is not None else (t.grad_of(res), False)
-            grads = dg_ = db_ = None
-            if weight is not None and bias is not None and t.param_grads:
-                wt, bt = t.pgrad_target(weight), t.pgrad_target(bias)
-                if wt is not None and bt is not None:  # the finish kernel accumulates into .grad
-                    grads = (wt, bt)
-                else:
-                    dg_ = torch.zeros(z.C, dtype=torch.float32, device=z.buf.device)
-                    db_ = torch.zeros(z.C, dtype=torch.float32, device=z.buf.device)
-                    grads = (dg_, db_)
-            sfhip.bn_frozen_bwd(t.grad_of(y), y, zz, mean, invstd, weight, relu, rep=rep, dres=dres,
-                                dres_overwrite=first, dz_out=zz, grads=grads, mask=mask)
-            if keep is not None and keep < z.C:  # sliced-away channels (GhostModule [:oup]) get no gradient
-                rest = z.slice(keep, z.C - keep)
-                sfhip.axpy(rest, rest, alpha=0.0, accumulate=False)
-            if dg_ is not None:
-                t.add_pgrad(weight, dg_)
-                t.add_pgrad(bias, db_)
+        def backward(dy, y, zz, dres, dres_accumulate, sink, sums, mask):
+            sfhip.bn_frozen_bwd(dy, y, zz, mean, invstd, weight, relu, rep=rep, dres=dres,
+                                dres_overwrite=not dres_accumulate, dz_out=zz,
+                                grads=sink if sink is not None else sums, mask=mask)
 
-        t.record(bwd)  # afterwards z's buffer holds dL/dz for the producer's backward
-    if shuffled:  # recorded AFTER the BN op so that its backward (the gather) runs first
-        return copy_channels(y, out, out_cmul=out_cmul)
-    return y
+        return backward
+
+    return _bn_epilogue(bn, z, scale, shift, make_backward, res, relu, rep, out, out_reserve, keep, out_cmul)
 
 
 def norm_forward(bn, x):
@@ -1030,58 +1013,50 @@ def conv_bn_act(x, conv, bn=None, relu=False, res=None, out=None, out_reserve=(0
                                       "interleaved store has no backward here")
 
         def bwd_dw_eval():  # epilogue backward and data gradient in ONE launch: no dL/dz tensor
-            fresh = t.grad_of_uninitialised(x)  # first writer of x's gradient: write, no zero fill / read
-            sfhip.dwconv_dgrad_epi(x, t.grad_of(y), y, packed_weight(conv), k, s, p,
-                                   fresh if fresh is not None else t.grad_of(x), scale=scale, relu=relu,
-                                   accumulate=fresh is None)
+            dx, acc = t.grad_dst(x)  # first writer of x's gradient: write, no zero fill / read
+            sfhip.dwconv_dgrad_epi(x, t.grad_of(y), y, packed_weight(conv), k, s, p, dx, scale=scale, relu=relu,
+                                   accumulate=acc)
 
         t.record(bwd_dw_eval)
     return y
 
 
-def _record_eval_grouped_conv(t, x, conv, y, scale, relu, res, shuffle):
-    """_record_eval_conv for a grouped conv (1 < groups < channels): sf_epilogue_bwd_act into a fresh dL/dz — with
-    `groups` it also undoes the channel-shuffled store, so dL/dz is in the conv's own channel order — then the grouped
-    data gradient of the training tape.  No weight or bias gradient."""
-    if scale is None and res is None and not relu and not shuffle:  # bare conv (+ bias): dL/dz is dL/dy
-        _record_grouped_conv(x, conv, lambda: t.grad_of(y))
-        return
+def _eval_dz_of_y(t, y, scale, relu, res, groups=None):
+    """dz_of_y() for the eval-tape conv recorders: the backward of the folded epilogue y = act(scale * z + bias + res)
+    into a fresh dL/dz, the residual's gradient in the same pass.  groups None: a dense conv (sf_epilogue_bwd, and
+    sf_epilogue_bwd_act only for ReLU6); a number: a grouped conv, always sf_epilogue_bwd_act — with groups > 1 it also
+    undoes the channel-shuffled store, so dL/dz is in the conv's own channel order."""
+    act = relu if (groups is not None or relu == 6) else None
 
     def dz_of_y():
-        dres, first = None, False
+        dres, acc = None, True
         if res is not None:  # first writer of the residual branch's gradient: write it, no zero fill / read
-            fresh = t.grad_of_uninitialised(res)
-            dres, first = (fresh, True) if fresh is not None else (t.grad_of(res), False)
+            dres, acc = t.grad_dst(res)
         dz = sfhip.new_act(y, y.N, y.T, y.H, y.W, y.C)
-        return sfhip.epilogue_bwd(t.grad_of(y), y, dz, scale=scale, act=relu, groups=conv.groups if shuffle else 1,
-                                  dres=dres, dres_accumulate=not first)
+        return sfhip.epilogue_bwd(t.grad_of(y), y, dz, scale=scale, relu=relu, act=act, groups=groups or 1, dres=dres,
+                                  dres_accumulate=acc)
 
-    _record_grouped_conv(x, conv, dz_of_y)
+    return dz_of_y
+
+
+def _record_eval_grouped_conv(t, x, conv, y, scale, relu, res, shuffle):
+    """_record_eval_conv for a grouped conv (1 < groups < channels): the epilogue's backward, then the grouped data
+    gradient of the training tape.  No weight or bias gradient."""
+    bare = scale is None and res is None and not relu and not shuffle  # conv (+ bias): dL/dz is dL/dy
+    _record_grouped_conv(x, conv, (lambda: t.grad_of(y)) if bare else
+                         _eval_dz_of_y(t, y, scale, relu, res, groups=conv.groups if shuffle else 1))
 
 
 def _record_eval_conv(t, x, conv, wp, y, scale, relu, res, out_cmul):
     """Backward of the ONE-launch eval conv y = act(scale * conv(x) + bias + res) on an EvalTape: the epilogue's
-    backward (sf_epilogue_bwd, or sf_epilogue_bwd_act for ReLU6: mask from y, the folded BN's scale, the residual's
-    gradient in the same pass) into a fresh dL/dz, then the data-gradient launch of the training tape.  No weight or
-    bias gradient."""
+    backward (mask from y, the folded BN's scale, the residual's gradient in the same pass), then the data-gradient
+    launch of the training tape.  No weight or bias gradient."""
     if out_cmul != 1 or relu not in (False, True, 6):
         raise NotImplementedError("eval-mode tape: an interleaved (out_cmul) store has no backward here")
-    k, s, p, d = conv.kernel_size, conv.stride, conv.padding, conv.dilation
-    if scale is None and res is None and not relu:  # bare conv (+ bias): dL/dz is dL/dy
-        _record_conv(x, conv.weight, conv.bias, wp.shape, lambda: t.grad_of(y), k, s, p, d)
-        return
-
-    def dz_of_y():
-        dres, first = None, False
-        if res is not None:  # first writer of the residual branch's gradient: write it, no zero fill / read
-            fresh = t.grad_of_uninitialised(res)
-            dres, first = (fresh, True) if fresh is not None else (t.grad_of(res), False)
-        dz = sfhip.new_act(y, y.N, y.T, y.H, y.W, y.C)
-        if relu == 6:
-            return sfhip.epilogue_bwd(t.grad_of(y), y, dz, scale=scale, act=6, dres=dres, dres_accumulate=not first)
-        return sfhip.epilogue_bwd(t.grad_of(y), y, dz, scale=scale, relu=relu, dres=dres, dres_accumulate=not first)
-
-    _record_conv(x, conv.weight, conv.bias, wp.shape, dz_of_y, k, s, p, d)
+    bare = scale is None and res is None and not relu  # conv (+ bias): dL/dz is dL/dy
+    _record_conv(x, conv.weight, conv.bias, wp.shape,
+                 (lambda: t.grad_of(y)) if bare else _eval_dz_of_y(t, y, scale, relu, res),
+                 conv.kernel_size, conv.stride, conv.padding, conv.dilation)
 
 
 def bn_eval_apply(bn, z, relu=False, rep=1, out=None):
@@ -1252,13 +1227,12 @@ def maxpool(x, kernel, stride, padding=(0, 0, 0), out_reserve=(0, 0)):
     y, arg = sfhip.pool(x, kernel, stride, padding, out_reserve=out_reserve, want_arg=True)
     if t is not None:
         def bwd():
-            fresh = t.grad_of_uninitialised(x)  # first writer of x's gradient: write, no zero fill / read
-            dx = fresh if fresh is not None else t.grad_of(x)
+            dx, acc = t.grad_dst(x)  # first writer of x's gradient: write, no zero fill / read
             # the forward's winner map: no x / y reads, no tie search (else: the search form)
             if arg is not None and sfhip.maxpool_bwd_arg(x, arg, t.grad_of(y), dx, kernel, stride, padding,
-                                                         overwrite=fresh is not None):
+                                                         overwrite=not acc):
                 return
-            sfhip.maxpool_bwd(x, y, t.grad_of(y), dx, kernel, stride, padding, overwrite=fresh is not None)
+            sfhip.maxpool_bwd(x, y, t.grad_of(y), dx, kernel, stride, padding, overwrite=not acc)
 
         t.record(bwd)
     return y

@@ -47,9 +47,8 @@ def _finish(logits, training, act_name):
         t = engine.tape()
         if isinstance(t, engine.EvalTape):  # Grad-CAM: the tape starts from dL/d(eval output), t.dout [N, classes]
             def bwd():
-                fresh = t.grad_of_uninitialised(logits)
-                sfhip.head_act_mean_bwd(logits, t.dout, _act_code(act_name),
-                                        fresh if fresh is not None else t.grad_of(logits), accumulate=fresh is None)
+                dlogits, acc = t.grad_dst(logits)
+                sfhip.head_act_mean_bwd(logits, t.dout, _act_code(act_name), dlogits, accumulate=acc)
             t.record(bwd)
             t.out = out
         return out
@@ -115,9 +114,8 @@ def _window_pool(x, k, piece, fwd=sfhip.avgpool_window):
     t = engine.tape()
 
     def bwd():
-        fresh = t.grad_of_uninitialised(x)  # first writer of x's gradient: write, no zero fill / read
-        sfhip.avgpool_window_bwd(t.grad_of(piece), fresh if fresh is not None else t.grad_of(x), k,
-                                 overwrite=fresh is not None)
+        dx, acc = t.grad_dst(x)  # first writer of x's gradient: write, no zero fill / read
+        sfhip.avgpool_window_bwd(t.grad_of(piece), dx, k, overwrite=not acc)
     t.record(bwd)
 
 
@@ -196,10 +194,9 @@ class ResNetRoIHead(nn.Module):
             arg = sfhip.roi_align_max(pooled, boxes, R, roi.spatial_scale, roi.aligned, out=piece)
             if t is not None:
                 def bwd(x=x, piece=piece, arg=arg, R=R, roi=roi):
-                    fresh = t.grad_of_uninitialised(x)  # first writer of x's gradient: write, no zero fill / read
-                    dx = fresh if fresh is not None else t.grad_of(x)
+                    dx, acc = t.grad_dst(x)  # first writer of x's gradient: write, no zero fill / read
                     sfhip.roi_align_max_bwd(t.grad_of(piece), arg, boxes, R, roi.spatial_scale, roi.aligned, dx,
-                                            accumulate=fresh is None)
+                                            accumulate=acc)
                 t.record(bwd)
             off += x.C
         classes = self.projection.out_features

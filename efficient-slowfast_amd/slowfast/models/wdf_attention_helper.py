@@ -223,9 +223,8 @@ class ChannelAttention(nn.Module):
         t = engine.tape()
         if t is not None:
             def bwd():  # dx (+)= dy * (1 + gate) and sum_pos dy * x in one pass over dy and x
-                fresh = t.grad_of_uninitialised(x)
-                dmul, _ = sfhip.sample_affine_bwd(t.grad_of(y), fresh if fresh is not None else t.grad_of(x), x=x,
-                                                  mul=mul, accumulate=fresh is None, want_dmul=True)
+                dx, acc = t.grad_dst(x)
+                dmul, _ = sfhip.sample_affine_bwd(t.grad_of(y), dx, x=x, mul=mul, accumulate=acc, want_dmul=True)
                 de = (dmul * gate * (1.0 - gate)).contiguous()
                 sfhip.axpy(sfhip.Act(de.view(x.N, 1, 1, 1, x.C)), t.grad_of(e), 1.0, accumulate=True)
 
@@ -304,21 +303,19 @@ class ContextBlock3D(nn.Module):
         if t is not None:
             def bwd():  # one pass: l recomputed, dx (+)= p * dctx + dl * w, dw from per-workgroup partials
                 dctx = t.grad_of(context).buf.view(x.N, x.C)
-                fresh = t.grad_of_uninitialised(x)
-                dx = fresh if fresh is not None else t.grad_of(x)
+                dx, acc = t.grad_dst(x)
                 if not t.param_grads:
-                    sfhip.ctx_pool_bwd(x, w.detach(), b.detach(), lse, ctx, dctx, dx, accumulate=fresh is None,
-                                       want_dw=False)
+                    sfhip.ctx_pool_bwd(x, w.detach(), b.detach(), lse, ctx, dctx, dx, accumulate=acc, want_dw=False)
                     return
                 tgt = t.pgrad_target(w)
                 if tgt is not None:  # the finish kernel accumulates into the parameter's gradient
-                    sfhip.ctx_pool_bwd(x, w.detach(), b.detach(), lse, ctx, dctx, dx, accumulate=fresh is None,
-                                       dw=tgt, dw_accumulate=True)
+                    sfhip.ctx_pool_bwd(x, w.detach(), b.detach(), lse, ctx, dctx, dx, accumulate=acc, dw=tgt,
+                                       dw_accumulate=True)
                     if t.pgrad_target(b) is None:
                         t.add_pgrad(b, torch.zeros_like(b))
                     return
                 db = torch.empty_like(b)
-                dw = sfhip.ctx_pool_bwd(x, w.detach(), b.detach(), lse, ctx, dctx, dx, accumulate=fresh is None, db=db)
+                dw = sfhip.ctx_pool_bwd(x, w.detach(), b.detach(), lse, ctx, dctx, dx, accumulate=acc, db=db)
                 t.add_pgrad(w, dw)
                 t.add_pgrad(b, db)
 
@@ -345,9 +342,8 @@ class ContextBlock3D(nn.Module):
         t = engine.tape()
         if t is not None:
             def bwd():  # dx (+)= dy and sum_pos dy in one pass over dy
-                fresh = t.grad_of_uninitialised(x)
-                _, dadd = sfhip.sample_affine_bwd(t.grad_of(y), fresh if fresh is not None else t.grad_of(x),
-                                                  accumulate=fresh is None, want_dadd=True)
+                dx, acc = t.grad_dst(x)
+                _, dadd = sfhip.sample_affine_bwd(t.grad_of(y), dx, accumulate=acc, want_dadd=True)
                 sfhip.axpy(sfhip.Act(dadd.view(x.N, 1, 1, 1, x.C)), t.grad_of(term), 1.0, accumulate=True)
 
             t.record(bwd)
@@ -494,9 +490,8 @@ class Stripe_NonLocalBlock(nn.Module):
                 dd = t.grad_of(discri)
                 dmean = dd.slice(0, c) if self.pool_type in ('mean', 'meanmax') else None
                 dmax = dd.slice(dd.C - c, c) if self.pool_type in ('max', 'meanmax') else None
-                fresh = t.grad_of_uninitialised(x)
-                sfhip.stripe_pool_bwd(fresh if fresh is not None else t.grad_of(x), S, dz=t.grad_of(held["z"]),
-                                      dmean=dmean, dmax=dmax, arg=arg, accumulate=fresh is None)
+                dx, acc = t.grad_dst(x)
+                sfhip.stripe_pool_bwd(dx, S, dz=t.grad_of(held["z"]), dmean=dmean, dmax=dmax, arg=arg, accumulate=acc)
 
             t.record(bwd_pool)
         g = engine.conv_bn_act(discri, self.g)

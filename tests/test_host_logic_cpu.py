@@ -289,3 +289,30 @@ def test_bench_dump_outputs_are_float32_seeded_and_bounded(tmp_path):
     assert 5 * bench.DUMP_SAMPLE * 4 > bench.DUMP_LIMIT_BYTES >= 3 * bench.DUMP_SAMPLE * 4 + (1 << 20)
     with pytest.raises(AssertionError):
         bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+
+
+def test_tape_grad_dst_states_the_first_writer_rule():
+    """Tape.grad_dst hands the FIRST writer of a whole buffer's gradient an uninitialised buffer (accumulate False) and
+    everyone else — a second writer, a channel slice, a caller that does not write every element — the zero-filled or
+    existing one (accumulate True); backward() leaves the table empty."""
+    from sfhip import Act
+    from slowfast.models.engine import EvalTape, Tape
+    for t in (Tape(), EvalTape("s5")):
+        a = Act(torch.ones(1, 1, 2, 2, 8))
+        g1, acc1 = t.grad_dst(a)
+        assert acc1 is False and (g1.buf.shape, g1.coff, g1.C) == (a.buf.shape, 0, 8)
+        g1.buf.fill_(3.0)  # the first writer's every element
+        g2, acc2 = t.grad_dst(a)
+        assert acc2 is True and g2.buf.data_ptr() == g1.buf.data_ptr() and bool((g2.buf == 3.0).all())
+        assert t.grad_of(a).buf.data_ptr() == g1.buf.data_ptr()
+        piece = Act(torch.ones(1, 1, 2, 2, 8), 4, 4)  # channels 4..7 of another buffer: never a first writer
+        gp, accp = t.grad_dst(piece)
+        assert accp is True and (gp.coff, gp.C, gp.buf.shape) == (4, 4, piece.buf.shape) and not gp.buf.any()
+        b = Act(torch.ones(1, 1, 2, 2, 8))
+        gb, accb = t.grad_dst(b, whole=False)  # a fresh whole buffer, but the caller writes only part of it
+        assert accb is True and not gb.buf.any()
+        assert t.grad_dst(b)[1] is True and len(t.gbuf) == 3
+    t = Tape()
+    t.grad_dst(Act(torch.ones(1, 1, 2, 2, 8)))
+    t.backward()
+    assert t.gbuf == {} and t.ops == []
