@@ -1,11 +1,14 @@
 // step_tail.hip — what follows the backward pass in tools/train_net.py:67-157: the loss with its gradient and the
-// meter's top-k counts in one launch (sf_ce_topk), torch.optim.SGD over every parameter of every group in one launch
-// (sf_sgd_step).  Nothing here needs the host: the statistics go to a ring in device memory that the meter drains once
+// meter's top-k counts in one launch (sf_ce_topk; sf_bce for the multi-label and detection losses), torch.optim.SGD over
+// every parameter of every group in one launch (sf_sgd_step), torch.optim.Adam in two (sf_adam_step: the step counts,
+// then the update).  Nothing here needs the host: the statistics go to a ring in device memory that the meter drains once
 // per LOG_PERIOD, the hyper-parameters are read from device memory (the LR schedule is a 4-byte write a replayed graph
 // sees) and a non-finite loss switches the update off through a flag the loss kernel leaves.
 #include "common.h"
 
 #include <math.h>
+
+#include <cmath>
 
 namespace {
 // ---------------------------------------------------------------------------------------------- loss + top-k
@@ -117,6 +120,89 @@ __global__ __launch_bounds__(CE_TPB) void ce_topk_kernel(const float* __restrict
   }
 }
 
+// ---------------------------------------------------------------------------------------------- BCE
+// nn.BCELoss / nn.BCEWithLogitsLoss (mean) with the gradient, a ring row and the flag.  ONE workgroup as above: the real
+// sizes are boxes x 80 (AVA) or clips x 157 (Charades), ~1e4 elements.  Thread i owns elements i, i + 1024, ... of the
+// flattened [N][K]; log / exp / log1p and the sums in fp64, fixed order (thread stride, xor butterfly, wavefronts in
+// order): equal bits run to run, no atomics.
+constexpr float KIND_BCE = 1.f;  // row[6]: which loss wrote the row (0: cross-entropy)
+
+__global__ __launch_bounds__(CE_TPB) void bce_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ y,
+                                                     int ldy, int N, int K, int from_logits, float* __restrict__ dx,
+                                                     float* __restrict__ ring, int* __restrict__ counter, int cap,
+                                                     float* __restrict__ loss_out) {
+  __shared__ double s_loss[CE_WAVES];
+  __shared__ int s_cnt[CE_WAVES][2];  // elements with a NaN / Inf input, elements outside [0, 1]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long total = (long)N * K;
+  const double inv = 1.0 / (double)total;
+  double loss = 0.0;
+  int nonfinite = 0, bad = 0;
+  for (long e = threadIdx.x; e < total; e += CE_TPB) {
+    const long r = e / K;
+    const int j = (int)(e - r * K);
+    const float xf = x[r * ldx + j], yf = y[r * ldy + j];
+    const double xv = (double)xf, yv = (double)yf;
+    const bool nf = !isfinite(xf) || !isfinite(yf);
+    double l, d;
+    if (from_logits) {
+      const double t = exp(-fabs(xv));  // in (0, 1]: no overflow at any x; log1p keeps it where 1 + t == 1
+      l = fmax(xv, 0.0) - xv * yv + log1p(t);
+      d = ((xv >= 0.0 ? 1.0 / (1.0 + t) : t / (1.0 + t)) - yv) * inv;
+    } else if (nf || (xf >= 0.f && xf <= 1.f && yf >= 0.f && yf <= 1.f)) {
+      // torch's binary_cross_entropy: both logs clamped at -100, the gradient's denominator at 1e-12
+      l = -(yv * fmax(log(xv), -100.0) + (1.0 - yv) * fmax(log(1.0 - xv), -100.0));
+      double den = xv * (1.0 - xv);
+      den = den < 1e-12 ? 1e-12 : den;  // (a NaN stays one)
+      d = (xv - yv) / den * inv;
+    } else {  // where torch asserts on the device: no loss, no gradient; the divisor stays N * K
+      l = 0.0;
+      d = 0.0;
+      bad += 1;
+    }
+    if (nf) {  // fmax drops a NaN: say it outright
+      l = (double)NAN;
+      nonfinite += 1;
+    }
+    loss += l;
+    dx[e] = (float)d;
+  }
+  loss = wave_sum(loss);
+  nonfinite = wave_sum(nonfinite);
+  bad = wave_sum(bad);
+  if (lane == 0) {
+    s_loss[wave] = loss;
+    s_cnt[wave][0] = nonfinite;
+    s_cnt[wave][1] = bad;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+    int c[2] = {0, 0};
+    for (int w = 0; w < CE_WAVES; ++w) {
+      tot += s_loss[w];
+      c[0] += s_cnt[w][0];
+      c[1] += s_cnt[w][1];
+    }
+    const float mean = (float)(tot * inv);
+    const float flag = (c[0] != 0 || !isfinite(mean)) ? 1.f : 0.f;
+    const int step = counter[0];
+    const int slot = ((step % cap) + cap) % cap;
+    float* row = ring + (long)slot * RING_ROW;
+    row[0] = mean;
+    row[1] = 0.f;
+    row[2] = 0.f;
+    row[3] = flag;
+    row[4] = (float)N;
+    row[5] = (float)c[1];
+    row[6] = KIND_BCE;
+    row[7] = 0.f;
+    loss_out[0] = mean;
+    loss_out[1] = flag;
+    counter[0] = step + 1;  // the only writer: a plain store
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- SGD
 constexpr int SGD_TPB = 256;
 constexpr int SGD_CHUNK = 4096;  // elements per workgroup: four 16-byte accesses per thread and array
@@ -205,6 +291,20 @@ __global__ __launch_bounds__(SGD_TPB) void sgd_step_kernel(const long* __restric
   }
 }
 
+// the chunks tile the tensors exactly, in table order: (0, 0), (0, C), ..., (1, 0), ... (numel: column `col` of a row)
+bool chunks_tile(const long* tab, int row, int col, int n_tensors, const long* chunks, int n_chunks) {
+  long t = 0, s = 0;
+  for (int i = 0; i < n_chunks; ++i) {
+    if (t >= n_tensors || chunks[2 * i] != t || chunks[2 * i + 1] != s) return false;
+    s += SGD_CHUNK;
+    if (s >= tab[t * row + col]) {
+      ++t;
+      s = 0;
+    }
+  }
+  return t == n_tensors && s == 0;
+}
+
 bool sgd_tables_ok(const long* tab, int n_tensors, const long* chunks, int n_chunks, const float* hyper, int n_groups) {
   for (int t = 0; t < n_tensors; ++t) {
     const long* r = tab + (long)t * TAB_ROW;
@@ -212,17 +312,134 @@ bool sgd_tables_ok(const long* tab, int n_tensors, const long* chunks, int n_chu
     if (r[3] <= 0 || r[4] < 0 || r[4] >= n_groups || (r[5] != 0 && r[5] != 1)) return false;
     if (hyper[r[4] * HYP_ROW + 2] != 0.f && r[2] == 0) return false;  // momentum without a buffer
   }
-  // the chunks tile the tensors exactly, in table order: (0, 0), (0, C), ..., (1, 0), ...
-  long t = 0, s = 0;
-  for (int i = 0; i < n_chunks; ++i) {
-    if (t >= n_tensors || chunks[2 * i] != t || chunks[2 * i + 1] != s) return false;
-    s += SGD_CHUNK;
-    if (s >= tab[t * TAB_ROW + 3]) {
-      ++t;
-      s = 0;
+  return chunks_tile(tab, TAB_ROW, 3, n_tensors, chunks, n_chunks);
+}
+
+// ---------------------------------------------------------------------------------------------- Adam
+constexpr int ADAM_TAB_ROW = 7;  // parameter, gradient, exp_avg, exp_avg_sq, step (one float), numel, group
+constexpr int ADAM_HYP_ROW = 5;  // lr, beta1, beta2, eps, weight_decay — fp64, what torch's Python floats are
+
+// the step counts first, in a launch of their own: the update's chunks of one tensor all read the new value
+__global__ __launch_bounds__(SGD_TPB) void adam_tick_kernel(const long* __restrict__ table,
+                                                            const float* __restrict__ guard, int n_tensors) {
+  if (guard != nullptr && guard[0] != 0.f) return;
+  for (int t = threadIdx.x; t < n_tensors; t += SGD_TPB) {
+    const long a = table[(long)t * ADAM_TAB_ROW + 4];
+    if (a == 0) continue;
+    float* s = as_global(a);
+    s[0] += 1.f;
+  }
+}
+
+struct AdamScalars {
+  float w1, b2, w2, step_size, inv_bc2_sqrt, eps, wd;  // w_i = 1 - beta_i
+  int ok;
+};
+
+// torch/optim/adam.py::_single_tensor_adam (amsgrad = maximize = False) for one element; returns the new parameter.
+__device__ __forceinline__ float adam1(float p, float g, float* m, float* v, const AdamScalars& a) {
+  if (a.wd != 0.f) g = fmaf(a.wd, p, g);
+  const float dm = g - *m;
+  const float nm = a.w1 < 0.5f ? fmaf(a.w1, dm, *m) : g - dm * (1.f - a.w1);  // exp_avg.lerp_(grad, 1 - beta1)
+  const float nv = fmaf(a.w2 * g, g, a.b2 * *v);
+  *m = nm;
+  *v = nv;
+  const float denom = fmaf(sqrtf(nv), a.inv_bc2_sqrt, a.eps);
+  return fmaf(-a.step_size, nm / denom, p);
+}
+
+__global__ __launch_bounds__(SGD_TPB) void adam_step_kernel(const long* __restrict__ table,
+                                                            const long* __restrict__ chunks,
+                                                            const double* __restrict__ hyper,
+                                                            const float* __restrict__ guard, int n_tensors,
+                                                            int n_groups, int zero_grad) {
+  __shared__ AdamScalars s_a;
+  if (guard != nullptr && guard[0] != 0.f) return;  // as in sgd_step_kernel: nothing moves
+  const long* c = chunks + (long)blockIdx.x * 2;
+  const long ti = c[0], start = c[1];
+  if (ti < 0 || ti >= n_tensors) return;
+  const long* row = table + ti * ADAM_TAB_ROW;
+  const long numel = row[5], grp = row[6];
+  if (row[0] == 0 || row[1] == 0 || row[2] == 0 || row[3] == 0 || row[4] == 0) return;
+  if (start < 0 || start >= numel || grp < 0 || grp >= n_groups) return;
+  if (threadIdx.x == 0) {  // the bias corrections once per workgroup, in fp64 as torch's Python floats
+    const double* hy = hyper + grp * ADAM_HYP_ROW;
+    const double lr = hy[0], b1 = hy[1], b2 = hy[2];
+    const double t = (double)as_global(row[4])[0];
+    const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
+    AdamScalars a;
+    a.w1 = (float)(1.0 - b1);
+    a.b2 = (float)b2;
+    a.w2 = (float)(1.0 - b2);
+    a.step_size = (float)(lr / bc1);
+    a.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+    a.eps = (float)hy[3];
+    a.wd = (float)hy[4];
+    a.ok = t >= 1.0 && bc1 > 0.0 && bc2 > 0.0;  // a step count nobody advanced: leave the chunk alone
+    s_a = a;
+  }
+  __syncthreads();
+  const AdamScalars a = s_a;
+  if (!a.ok) return;
+  float* p = as_global(row[0]) + start;
+  float* g = as_global(row[1]) + start;
+  float* m = as_global(row[2]) + start;
+  float* v = as_global(row[3]) + start;
+  const int len = (int)(numel - start < SGD_CHUNK ? numel - start : SGD_CHUNK);
+  const unsigned long bits = (unsigned long)p | (unsigned long)g | (unsigned long)m | (unsigned long)v;
+  if ((bits & 15) == 0) {
+    const int n4 = len >> 2;
+    for (int i = threadIdx.x; i < n4; i += SGD_TPB) {
+      f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+      const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+      f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
+      f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float me = mv[e], ve = vv[e];
+        pv[e] = adam1(pv[e], gv[e], &me, &ve, a);
+        mv[e] = me;
+        vv[e] = ve;
+      }
+      reinterpret_cast<f32x4*>(p)[i] = pv;
+      reinterpret_cast<f32x4*>(m)[i] = mv;
+      reinterpret_cast<f32x4*>(v)[i] = vv;
+      if (zero_grad) reinterpret_cast<f32x4*>(g)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const int i = (n4 << 2) + threadIdx.x;  // up to three elements left
+    if (i < len) {
+      float me = m[i], ve = v[i];
+      p[i] = adam1(p[i], g[i], &me, &ve, a);
+      m[i] = me;
+      v[i] = ve;
+      if (zero_grad) g[i] = 0.f;
+    }
+  } else {
+    for (int i = threadIdx.x; i < len; i += SGD_TPB) {
+      float me = m[i], ve = v[i];
+      p[i] = adam1(p[i], g[i], &me, &ve, a);
+      m[i] = me;
+      v[i] = ve;
+      if (zero_grad) g[i] = 0.f;
     }
   }
-  return t == n_tensors && s == 0;
+}
+
+bool adam_tables_ok(const long* tab, int n_tensors, const long* chunks, int n_chunks, const double* hyper,
+                    int n_groups) {
+  for (int g = 0; g < n_groups; ++g) {
+    const double* h = hyper + (long)g * ADAM_HYP_ROW;
+    for (int i = 0; i < ADAM_HYP_ROW; ++i)
+      if (!std::isfinite(h[i])) return false;
+    if (h[1] < 0.0 || h[1] >= 1.0 || h[2] < 0.0 || h[2] >= 1.0) return false;  // torch's own range: 1 - beta^t > 0
+  }
+  for (int t = 0; t < n_tensors; ++t) {
+    const long* r = tab + (long)t * ADAM_TAB_ROW;
+    for (int i = 0; i < 5; ++i)
+      if (r[i] == 0 || (r[i] & 3) != 0) return false;
+    if (r[5] <= 0 || r[6] < 0 || r[6] >= n_groups) return false;
+  }
+  return chunks_tile(tab, ADAM_TAB_ROW, 5, n_tensors, chunks, n_chunks);
 }
 }  // namespace
 
@@ -246,6 +463,30 @@ extern "C" int sf_sgd_step(const long* table_host, const long* table, int n_tens
   if (!sgd_tables_ok(table_host, n_tensors, chunks_host, n_chunks, hyper_host, n_groups)) return SF_EINVAL;
   hipLaunchKernelGGL(sgd_step_kernel, dim3(n_chunks), dim3(SGD_TPB), 0, (hipStream_t)stream, table, chunks, hyper, guard,
                      n_tensors, n_groups, zero_grad);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_bce(const float* x, int ldx, const float* y, int ldy, int N, int K, int from_logits, float* dx,
+                      float* ring, int* counter, int cap, float* loss_out, void* stream) {
+  if (!x || !y || !dx || !ring || !counter || !loss_out) return SF_EINVAL;
+  if (N <= 0 || K <= 0 || ldx < K || ldy < K || cap <= 0 || (from_logits != 0 && from_logits != 1)) return SF_EINVAL;
+  hipLaunchKernelGGL(bce_kernel, dim3(1), dim3(CE_TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, N, K, from_logits, dx,
+                     ring, counter, cap, loss_out);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_adam_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host,
+                            const long* chunks, int n_chunks, const double* hyper_host, const double* hyper,
+                            int n_groups, const float* guard, int zero_grad, void* stream) {
+  if (!table_host || !table || !chunks_host || !chunks || !hyper_host || !hyper) return SF_EINVAL;
+  if (n_tensors <= 0 || n_chunks <= 0 || n_groups <= 0 || (zero_grad != 0 && zero_grad != 1)) return SF_EINVAL;
+  if (!adam_tables_ok(table_host, n_tensors, chunks_host, n_chunks, hyper_host, n_groups)) return SF_EINVAL;
+  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(SGD_TPB), 0, (hipStream_t)stream, table, guard, n_tensors);
+  SF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(adam_step_kernel, dim3(n_chunks), dim3(SGD_TPB), 0, (hipStream_t)stream, table, chunks, hyper,
+                     guard, n_tensors, n_groups, zero_grad);
   SF_CHECK_LAUNCH();
   return SF_OK;
 }

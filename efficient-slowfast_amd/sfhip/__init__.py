@@ -198,6 +198,9 @@ _SIGNATURES = {
     "sf_ce_topk": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp, _vp]),
     "sf_sgd_chunk_elems": (_ci, []),
     "sf_sgd_step": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _ci, _vp]),
+    # multi-label / detection loss, one-call Adam
+    "sf_bce": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp, _vp]),
+    "sf_adam_step": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _ci, _vp]),
 }
 EXPORTS = list(_SIGNATURES)
 

@@ -1,13 +1,19 @@
 """The training iteration behind the backward pass (reference tools/train_net.py:67-157) on libsfhip kernels.
 
 * `StatsRing` — device memory the loss kernel writes one row of statistics into per step (loss, top-1 / top-k error,
-  non-finite flag, batch size, bad-label count); `utils.meters.DeviceTrainMeter` drains it once per LOG_PERIOD.
+  non-finite flag, batch size, bad-label count, loss kind); `utils.meters.DeviceTrainMeter` drains it once per LOG_PERIOD.
 * `HipCrossEntropy(topk, ring)` — `loss_fun(preds, labels)` of train_net.py:84-87, `misc.check_nan_losses` (:90) and
   `metrics.topks_correct` (:122-125) as ONE launch (`sf_ce_topk`) with no host read.
+* `HipBCE(ring)` / `HipBCEWithLogits(ring)` — `nn.BCELoss(reduction="mean")` on probabilities (detection, losses.py
+  "bce") and `nn.BCEWithLogitsLoss(reduction="mean")` on logits (multi-label classification, "bce_logit") with the
+  NaN check as ONE launch (`sf_bce`); `get_hip_loss_func(cfg, ring)` picks by `MODEL.LOSS_FUNC`.
 * `HipSGD` — `torch.optim.SGD` whose `step()` is ONE launch over every parameter of every group (`sf_sgd_step`), with the
   hyper-parameters in device memory: `optim.set_lr` (:68-69) stays a host assignment, `step()` / `upload_hyper()` turn a
   change into one small copy, and a captured step follows the schedule.
-* `construct_hip_optimizer(model, cfg)` — models/optimizer.py:26-58 for `sgd`.
+* `HipAdam` — `torch.optim.Adam` the same way (`sf_adam_step`: the step counts live in device memory and advance in a
+  launch of their own in front of the update, so a replayed step keeps counting).
+* `construct_hip_solver(model, cfg)` — models/optimizer.py:26-69: `construct_hip_optimizer` for `sgd`,
+  `construct_hip_adam` for `adam`.
 There is no fallback: tensors that are not fp32 on the current GPU are refused."""
 import ctypes
 
@@ -17,8 +23,10 @@ import sfhip
 
 RING_ROW = 8
 TAB_ROW, HYP_ROW = 6, 5
+ADAM_TAB_ROW, ADAM_HYP_ROW = 7, 5
 STAGE_SLOTS = 16
-ROW_LOSS, ROW_TOP1, ROW_TOPK, ROW_FLAG, ROW_N, ROW_BAD = 0, 1, 2, 3, 4, 5
+ROW_LOSS, ROW_TOP1, ROW_TOPK, ROW_FLAG, ROW_N, ROW_BAD, ROW_KIND = 0, 1, 2, 3, 4, 5, 6
+KIND_CE, KIND_BCE = 0, 1  # ROW_KIND: which loss kernel wrote the row
 
 
 class StatsRing(object):
@@ -37,6 +45,13 @@ def _vp(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _rows_view(t, N, K):
+    """A [N, K] tensor the kernels can read in place (unit column stride, row stride >= K) and that row stride."""
+    if N > 0 and K > 0 and (t.stride(1) != 1 or (N > 1 and t.stride(0) < K)):
+        t = t.contiguous()
+    return t, (t.stride(0) if N > 1 else K)
+
+
 def ce_topk(preds, labels, k_hi, ring, out, dlogits=None):
     """One `sf_ce_topk` launch.  preds fp32 [N, K] (unit column stride, row stride >= K), labels int64 [N], out fp32 [2]
     (loss, non-finite flag).  Returns dlogits [N, K]."""
@@ -46,9 +61,7 @@ def ce_topk(preds, labels, k_hi, ring, out, dlogits=None):
     if labels.dtype != torch.int64 or not labels.is_cuda:
         raise ValueError("ce_topk: labels must be int64 on the GPU, got %s on %s" % (labels.dtype, labels.device))
     N, K = preds.shape
-    if N > 0 and K > 0 and (preds.stride(1) != 1 or (N > 1 and preds.stride(0) < K)):
-        preds = preds.contiguous()
-    ld = preds.stride(0) if N > 1 else K
+    preds, ld = _rows_view(preds, N, K)
     labels = labels.contiguous()
     if dlogits is None:
         dlogits = torch.empty((N, K), dtype=torch.float32, device=preds.device)
@@ -59,10 +72,35 @@ def ce_topk(preds, labels, k_hi, ring, out, dlogits=None):
     return dlogits
 
 
-class _CEFunction(torch.autograd.Function):
+def bce(preds, targets, from_logits, ring, out, dgrad=None):
+    """One `sf_bce` launch.  preds fp32 [N, K] (probabilities, or logits with from_logits), targets [N, K] of any
+    real dtype (the reference's label tensors are float64 or integer: converted to float32), both as row views (unit
+    column stride, row stride >= K); out fp32 [2] (loss, non-finite flag).  Returns d loss / d preds [N, K]."""
+    sfhip._require_gpu(preds, "bce")
+    if preds.dim() != 2 or tuple(targets.shape) != tuple(preds.shape):
+        raise ValueError("bce: preds [N, K] and targets [N, K], got %s and %s" % (tuple(preds.shape),
+                                                                                 tuple(targets.shape)))
+    if not targets.is_cuda:
+        raise sfhip.SfhipError("bce: targets are on %s — the loss kernel runs on the GPU only" % targets.device)
+    if targets.dtype != torch.float32:
+        targets = targets.float()
+    sfhip._require_gpu(targets, "bce")
+    N, K = preds.shape
+    preds, ldx = _rows_view(preds, N, K)
+    targets, ldy = _rows_view(targets, N, K)
+    if dgrad is None:
+        dgrad = torch.empty((N, K), dtype=torch.float32, device=preds.device)
+    assert dgrad.is_contiguous() and tuple(dgrad.shape) == (N, K) and out.numel() >= 2
+    cnt = ctypes.cast(ctypes.c_void_p(ring.counter.data_ptr()), sfhip._pi)
+    sfhip._call("sf_bce", _vp(preds), int(ldx), _vp(targets), int(ldy), N, K, 1 if from_logits else 0, _vp(dgrad),
+                _vp(ring.rows), cnt, ring.cap, _vp(out), tag="bce")
+    return dgrad
+
+
+class _LossFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, preds, labels, owner):
-        d = ce_topk(preds.detach(), labels, owner.topk, owner.ring, owner.out)
+        d = owner._launch(preds.detach(), labels)
         owner.dlogits = d
         ctx.save_for_backward(d)
         return owner.out[0].clone() if owner.keep_loss else owner.out[0]
@@ -73,151 +111,191 @@ class _CEFunction(torch.autograd.Function):
         return d * grad_output, None, None
 
 
-class HipCrossEntropy(object):
-    """`loss = HipCrossEntropy(cfg.TRAIN.TOPK, ring)(preds, labels)`; `loss.backward()` as in the reference, or
-    `.backward_direct(preds)` to hand the stored gradient to autograd without the multiply by grad_output (= 1).
-    `guard` is the step's non-finite flag at a fixed address: `HipSGD.step(guard=loss_fun.guard)`.  The returned loss
-    is a view of a buffer the next call overwrites (keep_loss=True returns a copy, one more launch)."""
+class _HipLoss(object):
+    """A loss whose value, gradient, ring row and flag come from one launch: `loss = loss_fun(preds, labels)`;
+    `loss.backward()` as in the reference, or `.backward_direct(preds)` to hand the stored gradient to autograd without
+    the multiply by grad_output (= 1).  `guard` is the step's non-finite flag at a fixed address:
+    `optimizer.step(guard=loss_fun.guard)`.  The returned loss is a view of a buffer the next call overwrites
+    (keep_loss=True returns a copy, one more launch)."""
 
-    def __init__(self, topk, ring, keep_loss=False):
-        if int(topk) < 1:
-            raise ValueError("HipCrossEntropy: topk must be at least 1, got %r" % (topk,))
-        self.topk, self.ring, self.keep_loss = int(topk), ring, bool(keep_loss)
+    def __init__(self, ring, keep_loss=False):
+        self.ring, self.keep_loss = ring, bool(keep_loss)
         self.out = torch.zeros((2,), dtype=torch.float32, device=ring.rows.device)
-        self.dlogits = None
+        self.dlogits = None  # d loss / d preds of the last call
 
     @property
     def guard(self):
         return self.out[1:2]
 
     def __call__(self, preds, labels):
-        return _CEFunction.apply(preds, labels, self)
+        return _LossFunction.apply(preds, labels, self)
 
     def backward_direct(self, preds):
         if self.dlogits is None or tuple(self.dlogits.shape) != tuple(preds.shape):
-            raise RuntimeError("HipCrossEntropy.backward_direct: call the loss on these predictions first")
+            raise RuntimeError("%s.backward_direct: call the loss on these predictions first" % type(self).__name__)
         preds.backward(gradient=self.dlogits)
 
 
-# ---------------------------------------------------------------------------------------------------------- SGD
+class HipCrossEntropy(_HipLoss):
+    """`HipCrossEntropy(cfg.TRAIN.TOPK, ring)`: softmax cross-entropy with the meter's top-1 / top-k errors."""
+
+    def __init__(self, topk, ring, keep_loss=False):
+        if int(topk) < 1:
+            raise ValueError("HipCrossEntropy: topk must be at least 1, got %r" % (topk,))
+        super().__init__(ring, keep_loss)
+        self.topk = int(topk)
+
+    def _launch(self, preds, labels):
+        return ce_topk(preds, labels, self.topk, self.ring, self.out)
+
+
+class HipBCE(_HipLoss):
+    """`nn.BCELoss(reduction="mean")` on probabilities [N, K] (the detection head's output).  A batch without boxes
+    ([0, K]) raises ValueError: the reference computes NaN there and stops on check_nan_losses."""
+    from_logits = False
+
+    def _launch(self, preds, labels):
+        if preds.dim() == 2 and preds.shape[0] * preds.shape[1] == 0:
+            raise ValueError("%s: empty batch %s (a detection batch without boxes?) — the mean over no elements is "
+                             "NaN" % (type(self).__name__, tuple(preds.shape)))
+        return bce(preds, labels, self.from_logits, self.ring, self.out)
+
+
+class HipBCEWithLogits(HipBCE):
+    """`nn.BCEWithLogitsLoss(reduction="mean")` on raw logits [N, K] (multi-label classification in training mode)."""
+    from_logits = True
+
+
+def get_hip_loss_func(cfg, ring):
+    """models/losses.py:20-28 by `cfg.MODEL.LOSS_FUNC`, on the kernels above."""
+    name = cfg.MODEL.LOSS_FUNC
+    if name == "cross_entropy":
+        return HipCrossEntropy(cfg.TRAIN.TOPK, ring)
+    if name == "bce":
+        return HipBCE(ring)
+    if name == "bce_logit":
+        return HipBCEWithLogits(ring)
+    raise NotImplementedError("Loss {} is not supported".format(name))
+
+
+# ---------------------------------------------------------------------------------------------- address tables
+def _build_tables(entries, chunk, row, numel_col):
+    table = torch.tensor([list(map(int, e)) for e in entries], dtype=torch.int64).reshape(-1, row)
+    rows = []
+    for i, e in enumerate(entries):
+        rows += [(i, s) for s in range(0, int(e[numel_col]), chunk)]
+    return table, torch.tensor(rows, dtype=torch.int64).reshape(-1, 2)
+
+
 def build_sgd_tables(entries, chunk):
     """entries: (parameter address, gradient address, momentum address, numel, group, first) per tensor ->
     (table int64 [n, 6], chunks int64 [n_chunks, 2]): a chunk is (tensor index, first element) and covers at most
     `chunk` elements of one tensor; the chunks tile the tensors in order."""
-    table = torch.tensor([list(map(int, e)) for e in entries], dtype=torch.int64).reshape(-1, TAB_ROW)
-    rows = []
-    for i, e in enumerate(entries):
-        rows += [(i, s) for s in range(0, int(e[3]), chunk)]
-    return table, torch.tensor(rows, dtype=torch.int64).reshape(-1, 2)
+    return _build_tables(entries, chunk, TAB_ROW, 3)
+
+
+def build_adam_tables(entries, chunk):
+    """entries: (parameter, gradient, exp_avg, exp_avg_sq, step address, numel, group) per tensor -> (table int64
+    [n, 7], chunks int64 [n_chunks, 2]), tiled as build_sgd_tables does."""
+    return _build_tables(entries, chunk, ADAM_TAB_ROW, 5)
+
+
+def _table_step(symbol, dtype, table_host, table, chunks_host, chunks, hyper_host, hyper, guard, zero_grad):
+    for h, d in ((table_host, table), (chunks_host, chunks)):
+        assert h.dtype == d.dtype == torch.int64 and h.is_contiguous() and d.is_contiguous() and not h.is_cuda
+        assert h.shape == d.shape
+    assert hyper_host.dtype == hyper.dtype == dtype and hyper_host.shape == hyper.shape and hyper.is_contiguous()
+    tag = symbol[3:]
+    if not (table.is_cuda and chunks.is_cuda and hyper.is_cuda):
+        raise sfhip.SfhipError("%s: table, chunks and hyper live on the GPU — there is no CPU fallback" % tag)
+    sfhip._call(symbol, _vp(table_host), _vp(table), table_host.shape[0], _vp(chunks_host), _vp(chunks),
+                chunks_host.shape[0], _vp(hyper_host), _vp(hyper), hyper_host.shape[0], _vp(guard),
+                1 if zero_grad else 0, tag=tag)
 
 
 def sgd_step(table_host, table, chunks_host, chunks, hyper_host, hyper, guard=None, zero_grad=False):
     """One `sf_sgd_step` launch; the host tensors are what the device ones were uploaded from."""
-    for h, d in ((table_host, table), (chunks_host, chunks)):
-        assert h.dtype == d.dtype == torch.int64 and h.is_contiguous() and d.is_contiguous() and not h.is_cuda
-        assert h.shape == d.shape
-    assert hyper_host.dtype == hyper.dtype == torch.float32 and hyper_host.shape == hyper.shape and hyper.is_contiguous()
-    if not (table.is_cuda and chunks.is_cuda and hyper.is_cuda):
-        raise sfhip.SfhipError("sgd_step: table, chunks and hyper live on the GPU — there is no CPU fallback")
-    sfhip._call("sf_sgd_step", _vp(table_host), _vp(table), table_host.shape[0], _vp(chunks_host), _vp(chunks),
-                chunks_host.shape[0], _vp(hyper_host), _vp(hyper), hyper_host.shape[0], _vp(guard),
-                1 if zero_grad else 0, tag="sgd_step")
+    _table_step("sf_sgd_step", torch.float32, table_host, table, chunks_host, chunks, hyper_host, hyper, guard,
+                zero_grad)
 
 
-class HipSGD(torch.optim.SGD):
-    """torch.optim.SGD (same constructor, param_groups and state_dict) with a one-launch `step()`.
+def adam_step(table_host, table, chunks_host, chunks, hyper_host, hyper, guard=None, zero_grad=False):
+    """One `sf_adam_step` call (two launches); hyper is float64 [n_groups, 5]."""
+    _table_step("sf_adam_step", torch.float64, table_host, table, chunks_host, chunks, hyper_host, hyper, guard,
+                zero_grad)
 
-    Momentum buffers are 16-byte aligned views of one allocation owned by the optimizer, exposed as
-    `state[p]["momentum_buffer"]` from a parameter's first step on (as torch does).  `step(guard=, zero_grad=)`: guard
-    is a device float that switches the update off when non-zero; zero_grad stores zeros to the gradients read.  (A
-    guarded-off step still counts as a parameter's first: its momentum buffer then starts from zeros instead of the
-    next gradient — the loop is about to stop on the meter's NaN warning anyway.)"""
 
-    def __init__(self, params, *args, **kwargs):
-        super().__init__(params, *args, **kwargs)
-        for g in self.param_groups:
-            if g.get("maximize") or g.get("differentiable"):
-                raise ValueError("HipSGD: maximize / differentiable are not supported — use torch.optim.SGD")
-        self._slots = {}          # parameter -> its view of a momentum allocation
-        self._blocks = []         # the allocations (one, unless groups or momentum were added later)
+class _TableOptimizer(object):
+    """What HipSGD and HipAdam share, mixed in in front of torch's optimizer: the parameter checks, 16-byte aligned
+    state slots carved from allocations the optimizer owns, the address table cached by a cheap signature, the pinned
+    staging ring of the hyper-parameter uploads, and the step around the one native call.  A subclass supplies
+    `_REFUSED` (group options the kernel does not do), `_TORCH`, `_HYP_DTYPE`, `_KEY_COLS`, `_hyper_values`,
+    `_check_hyper`, `_sig_extra`, `_entries`, `_build`, `_launch` and `_after_fresh`."""
+
+    def _init_tables(self):
+        self._refuse_groups()
+        self._slots = {}          # parameter -> its view(s) of a state allocation
+        self._blocks = []         # the allocations (one, unless groups or state were added later)
         self._key = None
         self._table = self._chunks = self._table_dev = self._chunks_dev = None
         self._hyper = self._hyper_dev = self._hyper_vals = None
         self._stage = None        # pinned staging rows of the hyper-parameter uploads
         self._sig = self._plist = None  # what the table was built from; the flat parameter list
         self._check_params()
-        self._allocate([p for g in self.param_groups if g["momentum"] != 0 for p in g["params"]])
 
-    # ---- construction-time checks and momentum storage
+    def _refuse_groups(self):
+        for g in self.param_groups:
+            if any(g.get(k) for k in self._REFUSED):
+                raise ValueError("%s: %s are not supported — use %s" % (self._NAME, " / ".join(self._REFUSED),
+                                                                        self._TORCH))
+
     def _check_params(self):
         for g in self.param_groups:
             for p in g["params"]:
                 if p.dtype != torch.float32:
-                    raise ValueError("HipSGD: parameter of dtype %s — float32 only" % p.dtype)
+                    raise ValueError("%s: parameter of dtype %s — float32 only" % (self._NAME, p.dtype))
                 if not p.is_contiguous():
-                    raise ValueError("HipSGD: parameters must be contiguous")
+                    raise ValueError("%s: parameters must be contiguous" % self._NAME)
 
-    def _allocate(self, params):
-        params = [p for p in params if p not in self._slots]
-        if not params:
-            return
+    def _carve(self, numels, device):
+        """One zero-filled allocation holding a flat view of each of `numels` elements, every view on 16 bytes."""
         offs, n = [], 0
-        for p in params:
+        for k in numels:
             offs.append(n)
-            n += (p.numel() + 3) // 4 * 4  # every buffer starts on 16 bytes
-        block = torch.zeros((n,), dtype=torch.float32, device=params[0].device)
+            n += (k + 3) // 4 * 4
+        block = torch.zeros((n,), dtype=torch.float32, device=device)
         self._blocks.append(block)
-        for p, o in zip(params, offs):
-            self._slots[p] = block[o:o + p.numel()].view_as(p)
+        return [block[o:o + k] for o, k in zip(offs, numels)]
+
+    def _invalidate(self):
+        self._key = self._sig = self._plist = None
 
     def add_param_group(self, group):
         super().add_param_group(group)
         if hasattr(self, "_slots"):
+            self._refuse_groups()
             self._check_params()
-            self._key = self._sig = self._plist = None
-
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        for g in self.param_groups:
-            if g.get("maximize") or g.get("differentiable"):
-                raise ValueError("HipSGD: maximize / differentiable are not supported — use torch.optim.SGD")
-        for g in self.param_groups:
-            for p in g["params"]:
-                buf = self.state.get(p, {}).get("momentum_buffer")
-                if buf is None:
-                    continue
-                self._allocate([p])
-                slot = self._slots[p]
-                if buf.data_ptr() != slot.data_ptr():
-                    slot.copy_(buf.to(device=slot.device, dtype=torch.float32).view_as(slot))
-                    self.state[p]["momentum_buffer"] = slot
-        self._key = self._sig = self._plist = None
+            self._invalidate()
 
     # ---- hyper-parameters in device memory
-    def _hyper_values(self):
-        return tuple((float(g["lr"]), float(g["weight_decay"]), float(g["momentum"]), float(g["dampening"]),
-                      1.0 if g["nesterov"] else 0.0) for g in self.param_groups)
-
     def upload_hyper(self):
-        """Copy the groups' lr / weight_decay / momentum / dampening / nesterov to the device if they changed since the
-        last upload: one small copy on the current stream from a pinned staging row, so the host does not wait for
-        the work already queued there.  Call it before `engine.replay(graph)`: a replayed step reads the values from
-        device memory.  Returns whether anything was copied."""
+        """Copy the groups' hyper-parameters to the device if they changed since the last upload: one small copy on the
+        current stream from a pinned staging row, so the host does not wait for the work already queued there.  Call
+        it before `engine.replay(graph)`: a replayed step reads the values from device memory.  Returns whether
+        anything was copied."""
         vals = self._hyper_values()
         if vals == self._hyper_vals:
             return False
-        for g in self.param_groups:
-            if g["nesterov"] and (g["momentum"] <= 0 or g["dampening"] != 0):
-                raise ValueError("Nesterov momentum requires a momentum and zero dampening")
-        rows = torch.tensor(vals, dtype=torch.float32).reshape(-1, HYP_ROW)
+        self._check_hyper()
+        rows = torch.tensor(vals, dtype=self._HYP_DTYPE).reshape(len(vals), -1)
         dev = self.param_groups[0]["params"][0].device
         if self._hyper_dev is None or self._hyper_dev.shape != rows.shape:
-            self._hyper_dev = torch.empty(rows.shape, dtype=torch.float32, device=dev)
+            self._hyper_dev = torch.empty(rows.shape, dtype=self._HYP_DTYPE, device=dev)
         # the copy reads the staging row when the stream gets there, not now: every upload takes the next of STAGE_SLOTS
         # pinned rows and leaves an event behind it, and a row is written again only after its event has passed (the
         # host would have to run STAGE_SLOTS learning rates ahead of the device to wait here)
         if self._stage is None or self._stage.shape[1:] != rows.shape:
-            self._stage = torch.empty((STAGE_SLOTS,) + tuple(rows.shape), dtype=torch.float32).pin_memory()
+            self._stage = torch.empty((STAGE_SLOTS,) + tuple(rows.shape), dtype=self._HYP_DTYPE).pin_memory()
             self._stage_events, self._stage_next = [None] * STAGE_SLOTS, 0
         i = self._stage_next
         self._stage_next = (i + 1) % STAGE_SLOTS
@@ -230,21 +308,134 @@ class HipSGD(torch.optim.SGD):
         self._hyper, self._hyper_vals = rows, vals
         return True
 
+    def _check_hyper(self):
+        pass
+
     # ---- the step
+    def _checked_grad(self, p):
+        """p.grad if the kernel can read it (None: the parameter is absent from this step, as in torch)."""
+        if p.grad is None:
+            return None
+        if not p.is_cuda:
+            raise ValueError("%s: parameter on %s — the update kernel runs on the GPU only" % (self._NAME, p.device))
+        if p.grad.is_sparse:
+            raise ValueError("%s: sparse gradients are not supported — use %s" % (self._NAME, self._TORCH))
+        if p.grad.dtype != torch.float32 or not p.grad.is_cuda or not p.grad.is_contiguous():
+            raise ValueError("%s: gradients must be contiguous float32 tensors on the GPU" % self._NAME)
+        return p.grad
+
+    def _signature(self):
+        """What the address table depends on, cheaply: every parameter's and gradient's address, the subclass's extra
+        (which groups have momentum) and how many parameters have state.  Equal to the signature the table was built
+        from = the table still holds (a state tensor re-assigned by hand is only seen at the next rebuild;
+        load_state_dict and add_param_group force one)."""
+        plist = self._plist
+        if plist is None:
+            plist = self._plist = [p for g in self.param_groups for p in g["params"]]
+        grads = [p.grad for p in plist]
+        return ([p.data_ptr() for p in plist], [0 if g is None else g.data_ptr() for g in grads],
+                self._sig_extra(), len(self.state))
+
+    @torch.no_grad()
+    def step(self, closure=None, guard=None, zero_grad=False):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        sig = self._signature()
+        if sig != self._sig:  # first call, or an address / a group changed: check everything and rebuild the table
+            entries, fresh = self._entries()
+            if not entries:
+                return loss
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("%s.step under stream capture needs a new address table or a parameter's first "
+                                   "step, which take host-to-device copies — warm up eagerly first (run the same step "
+                                   "outside the capture until every parameter has had one)" % self._NAME)
+            key = tuple(e[:self._KEY_COLS] for e in entries)
+            self._table, chunks = self._build(entries, sfhip.lib().sf_sgd_chunk_elems())
+            dev = self.param_groups[0]["params"][0].device
+            self._table_dev = self._table.to(dev)
+            if key != self._key:
+                self._chunks, self._chunks_dev = chunks, chunks.to(dev)
+            self._key = key
+        else:
+            fresh = ()
+        if not torch.cuda.is_current_stream_capturing():
+            self.upload_hyper()
+        elif self._hyper_dev is None:
+            raise RuntimeError("%s.step under stream capture: warm up eagerly first" % self._NAME)
+        if guard is not None and (not guard.is_cuda or guard.dtype != torch.float32):
+            raise ValueError("%s.step: guard is a float32 tensor on the GPU" % self._NAME)
+        self._launch(self._table, self._table_dev, self._chunks, self._chunks_dev, self._hyper, self._hyper_dev, guard,
+                     zero_grad)
+        if fresh:
+            self._after_fresh(fresh)
+            sig = self._signature()  # the state grew
+        self._sig = sig
+        return loss
+
+
+# ---------------------------------------------------------------------------------------------------------- SGD
+class HipSGD(_TableOptimizer, torch.optim.SGD):
+    """torch.optim.SGD (same constructor, param_groups and state_dict) with a one-launch `step()`.
+
+    Momentum buffers are 16-byte aligned views of one allocation owned by the optimizer, exposed as
+    `state[p]["momentum_buffer"]` from a parameter's first step on (as torch does).  `step(guard=, zero_grad=)`: guard
+    is a device float that switches the update off when non-zero; zero_grad stores zeros to the gradients read.  (A
+    guarded-off step still counts as a parameter's first: its momentum buffer then starts from zeros instead of the
+    next gradient — the loop is about to stop on the meter's NaN warning anyway.)"""
+    _NAME, _TORCH, _REFUSED = "HipSGD", "torch.optim.SGD", ("maximize", "differentiable")
+    _HYP_DTYPE, _KEY_COLS = torch.float32, 5
+    _build = staticmethod(build_sgd_tables)
+    _launch = staticmethod(sgd_step)
+
+    def __init__(self, params, *args, **kwargs):
+        super().__init__(params, *args, **kwargs)
+        self._init_tables()
+        self._allocate([p for g in self.param_groups if g["momentum"] != 0 for p in g["params"]])
+
+    def _allocate(self, params):
+        params = [p for p in params if p not in self._slots]
+        if not params:
+            return
+        for p, v in zip(params, self._carve([p.numel() for p in params], params[0].device)):
+            self._slots[p] = v.view_as(p)
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._refuse_groups()
+        for g in self.param_groups:
+            for p in g["params"]:
+                buf = self.state.get(p, {}).get("momentum_buffer")
+                if buf is None:
+                    continue
+                self._allocate([p])
+                slot = self._slots[p]
+                if buf.data_ptr() != slot.data_ptr():
+                    slot.copy_(buf.to(device=slot.device, dtype=torch.float32).view_as(slot))
+                    self.state[p]["momentum_buffer"] = slot
+        self._invalidate()
+
+    def _hyper_values(self):
+        return tuple((float(g["lr"]), float(g["weight_decay"]), float(g["momentum"]), float(g["dampening"]),
+                      1.0 if g["nesterov"] else 0.0) for g in self.param_groups)
+
+    def _check_hyper(self):
+        for g in self.param_groups:
+            if g["nesterov"] and (g["momentum"] <= 0 or g["dampening"] != 0):
+                raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+
+    def _sig_extra(self):
+        return [g["momentum"] != 0 for g in self.param_groups]
+
     def _entries(self):
         entries, firsts = [], []
+        self._refuse_groups()
         for gi, g in enumerate(self.param_groups):
-            if g.get("maximize") or g.get("differentiable"):
-                raise ValueError("HipSGD: maximize / differentiable are not supported — use torch.optim.SGD")
             for p in g["params"]:
-                if p.grad is None:
+                grad = self._checked_grad(p)
+                if grad is None:
                     continue  # absent: left untouched, as torch does
-                if not p.is_cuda:
-                    raise ValueError("HipSGD: parameter on %s — the update kernel runs on the GPU only" % p.device)
-                if p.grad.is_sparse:
-                    raise ValueError("HipSGD: sparse gradients are not supported — use torch.optim.SGD")
-                if p.grad.dtype != torch.float32 or not p.grad.is_cuda or not p.grad.is_contiguous():
-                    raise ValueError("HipSGD: gradients must be contiguous float32 tensors on the GPU")
                 buf, first = 0, 0
                 if g["momentum"] != 0:
                     if p not in self._slots:
@@ -256,68 +447,109 @@ class HipSGD(torch.optim.SGD):
                     elif have.data_ptr() != buf:  # a buffer somebody assigned by hand: adopt its values
                         self._slots[p].copy_(have)
                         self.state[p]["momentum_buffer"] = self._slots[p]
-                entries.append((p.data_ptr(), p.grad.data_ptr(), buf, p.numel(), gi, first))
+                entries.append((p.data_ptr(), grad.data_ptr(), buf, p.numel(), gi, first))
                 if first:
                     firsts.append(p)
         return entries, firsts
 
-    def _signature(self):
-        """What the address table depends on, cheaply: every parameter's and gradient's address, which groups have
-        momentum and how many parameters have state.  Equal to the signature the table was built from = the table
-        still holds (a momentum buffer re-assigned by hand is only seen at the next rebuild; load_state_dict and
-        add_param_group force one)."""
-        plist = self._plist
-        if plist is None:
-            plist = self._plist = [p for g in self.param_groups for p in g["params"]]
-        grads = [p.grad for p in plist]
-        return ([p.data_ptr() for p in plist], [0 if g is None else g.data_ptr() for g in grads],
-                [g["momentum"] != 0 for g in self.param_groups], len(self.state))
-
-    @torch.no_grad()
-    def step(self, closure=None, guard=None, zero_grad=False):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        sig = self._signature()
-        if sig != self._sig:  # first call, or an address / a group changed: check everything and rebuild the table
-            entries, firsts = self._entries()
-            if not entries:
-                return loss
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("HipSGD.step under stream capture needs a new address table or a first momentum "
-                                   "step, which take host-to-device copies — warm up eagerly first (run the same step "
-                                   "outside the capture until every parameter has had one)")
-            key = tuple(e[:5] for e in entries)
-            self._table, chunks = build_sgd_tables(entries, sfhip.lib().sf_sgd_chunk_elems())
-            dev = self.param_groups[0]["params"][0].device
-            self._table_dev = self._table.to(dev)
-            if key != self._key:
-                self._chunks, self._chunks_dev = chunks, chunks.to(dev)
-            self._key = key
-        else:
-            firsts = ()
-        if not torch.cuda.is_current_stream_capturing():
-            self.upload_hyper()
-        elif self._hyper_dev is None:
-            raise RuntimeError("HipSGD.step under stream capture: warm up eagerly first")
-        if guard is not None and (not guard.is_cuda or guard.dtype != torch.float32):
-            raise ValueError("HipSGD.step: guard is a float32 tensor on the GPU")
-        sgd_step(self._table, self._table_dev, self._chunks, self._chunks_dev, self._hyper, self._hyper_dev, guard,
-                 zero_grad)
-        if firsts:  # the first-step flags are spent: the table in device memory says so before the next launch
-            for p in firsts:
-                self.state[p]["momentum_buffer"] = self._slots[p]
-            self._table[:, 5] = 0
-            self._table_dev = self._table.to(self._table_dev.device)
-            sig = self._signature()  # the state grew
-        self._sig = sig
-        return loss
+    def _after_fresh(self, firsts):
+        # the first-step flags are spent: the table in device memory says so before the next launch
+        for p in firsts:
+            self.state[p]["momentum_buffer"] = self._slots[p]
+        self._table[:, 5] = 0
+        self._table_dev = self._table.to(self._table_dev.device)
 
 
-def construct_hip_optimizer(model, cfg):
-    """models/optimizer.py:26-58 for SOLVER.OPTIMIZING_METHOD == "sgd": BatchNorm parameters ("bn" in the name) get
-    BN.WEIGHT_DECAY, the rest SOLVER.WEIGHT_DECAY."""
+# ---------------------------------------------------------------------------------------------------------- Adam
+class HipAdam(_TableOptimizer, torch.optim.Adam):
+    """torch.optim.Adam (same constructor, param_groups and state_dict keys) whose `step()` is ONE native call over every
+    parameter of every group (`sf_adam_step`).
+
+    `exp_avg`, `exp_avg_sq` and `step` are 16-byte aligned views of one allocation owned by the optimizer; `step` is a
+    float32 scalar in DEVICE memory per parameter (torch keeps it on the host), advanced by the call itself, so a
+    captured step keeps counting when it is replayed.  They appear in `state[p]` from the parameter's first step on;
+    a parameter whose `.grad` is None is left untouched and gets no state.  `step(guard=, zero_grad=)` as in HipSGD: a
+    guarded-off step moves nothing — parameters, moments, step counts, gradients."""
+    _NAME, _TORCH = "HipAdam", "torch.optim.Adam"
+    _REFUSED = ("amsgrad", "maximize", "differentiable", "decoupled_weight_decay")
+    _HYP_DTYPE, _KEY_COLS = torch.float64, 7
+    _build = staticmethod(build_adam_tables)
+    _launch = staticmethod(adam_step)
+
+    def __init__(self, params, *args, **kwargs):
+        super().__init__(params, *args, **kwargs)
+        self._init_tables()
+        self._allocate([p for g in self.param_groups for p in g["params"]])
+
+    def _allocate(self, params):
+        params = [p for p in params if p not in self._slots]
+        if not params:
+            return
+        views = self._carve([k for p in params for k in (p.numel(), p.numel(), 1)], params[0].device)
+        for i, p in enumerate(params):
+            self._slots[p] = {"exp_avg": views[3 * i].view_as(p), "exp_avg_sq": views[3 * i + 1].view_as(p),
+                              "step": views[3 * i + 2].view(())}
+
+    def _adopt(self, p):
+        """Make state[p] the owned slots, taking over the values of tensors that live elsewhere (a checkpoint's, or
+        ones assigned by hand; torch's own `step` is a CPU tensor)."""
+        self._allocate([p])
+        st = self.state[p]
+        if "max_exp_avg_sq" in st:
+            raise ValueError("HipAdam: amsgrad state (max_exp_avg_sq) is not supported — use torch.optim.Adam")
+        for k, slot in self._slots[p].items():
+            have = st.get(k)
+            if have is None:
+                raise ValueError("HipAdam: state without %r" % k)
+            if not torch.is_tensor(have):
+                slot.fill_(float(have))
+            elif have.data_ptr() != slot.data_ptr():
+                slot.copy_(have.detach().to(device=slot.device, dtype=torch.float32).view_as(slot))
+            st[k] = slot
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._refuse_groups()
+        for g in self.param_groups:
+            for p in g["params"]:
+                if len(self.state.get(p, {})) != 0:
+                    self._adopt(p)
+        self._invalidate()
+
+    def _hyper_values(self):
+        return tuple((float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                      float(g["weight_decay"])) for g in self.param_groups)
+
+    def _sig_extra(self):
+        return ()
+
+    def _entries(self):
+        entries, fresh = [], []
+        self._refuse_groups()
+        for gi, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                grad = self._checked_grad(p)
+                if grad is None:
+                    continue  # absent: left untouched and without state, as torch does
+                if p not in self._slots:
+                    self._allocate([q for q in g["params"]])
+                s = self._slots[p]
+                if len(self.state.get(p, {})) == 0:
+                    fresh.append(p)
+                elif any(self.state[p].get(k) is not s[k] for k in s):
+                    self._adopt(p)
+                entries.append((p.data_ptr(), grad.data_ptr(), s["exp_avg"].data_ptr(), s["exp_avg_sq"].data_ptr(),
+                                s["step"].data_ptr(), p.numel(), gi))
+        return entries, fresh
+
+    def _after_fresh(self, fresh):
+        for p in fresh:
+            self.state[p].update(self._slots[p])
+
+
+def _split_bn_params(model, cfg):
+    """models/optimizer.py:26-51: BatchNorm parameters ("bn" in the name) get BN.WEIGHT_DECAY, the rest
+    SOLVER.WEIGHT_DECAY."""
     bn_params, non_bn_parameters = [], []
     for name, p in model.named_parameters():
         (bn_params if "bn" in name else non_bn_parameters).append(p)
@@ -326,10 +558,34 @@ def construct_hip_optimizer(model, cfg):
     assert len(list(model.parameters())) == len(non_bn_parameters) + len(bn_params), \
         "parameter size does not match: {} + {} != {}".format(len(non_bn_parameters), len(bn_params),
                                                               len(list(model.parameters())))
+    return optim_params
+
+
+def construct_hip_optimizer(model, cfg):
+    """models/optimizer.py:26-58 for SOLVER.OPTIMIZING_METHOD == "sgd" (a HipSGD).  "adam" keeps raising here, as it
+    always has — its branch of the reference (:59-65) is `construct_hip_adam`, and `construct_hip_solver` picks
+    between the two by name."""
+    optim_params = _split_bn_params(model, cfg)
     if cfg.SOLVER.OPTIMIZING_METHOD == "sgd":
         return HipSGD(optim_params, lr=cfg.SOLVER.BASE_LR, momentum=cfg.SOLVER.MOMENTUM,
                       weight_decay=cfg.SOLVER.WEIGHT_DECAY, dampening=cfg.SOLVER.DAMPENING,
                       nesterov=cfg.SOLVER.NESTEROV)
-    raise NotImplementedError("construct_hip_optimizer supports sgd only; for {!r} build torch's optimizer "
-                              "(torch.optim.Adam, the reference's models/optimizer.py)".format(
-                                  cfg.SOLVER.OPTIMIZING_METHOD))
+    if cfg.SOLVER.OPTIMIZING_METHOD == "adam":
+        raise NotImplementedError("construct_hip_optimizer builds sgd only; for 'adam' call construct_hip_adam(model, "
+                                  "cfg) or construct_hip_solver(model, cfg): a HipAdam, torch.optim.Adam's subclass "
+                                  "(the reference's models/optimizer.py:59-65)")
+    raise NotImplementedError("Does not support {} optimizer".format(cfg.SOLVER.OPTIMIZING_METHOD))
+
+
+def construct_hip_adam(model, cfg):
+    """models/optimizer.py:59-65: torch.optim.Adam(betas=(0.9, 0.999)) over the same parameter split, as a HipAdam."""
+    return HipAdam(_split_bn_params(model, cfg), lr=cfg.SOLVER.BASE_LR, betas=(0.9, 0.999),
+                   weight_decay=cfg.SOLVER.WEIGHT_DECAY)
+
+
+def construct_hip_solver(model, cfg):
+    """models/optimizer.py:26-69 whole: "sgd" -> HipSGD, "adam" -> HipAdam, anything else raises the reference's
+    NotImplementedError."""
+    if cfg.SOLVER.OPTIMIZING_METHOD == "adam":
+        return construct_hip_adam(model, cfg)
+    return construct_hip_optimizer(model, cfg)

@@ -202,11 +202,15 @@ class DeviceTrainMeter(object):
     NUM_GPUS > 1 (train_net.py:128-131), ONE device-to-host copy, then TrainMeter.update_stats' arithmetic row by row —
     the logged medians and averages are the reference's for the same values.  A drained row with the non-finite flag
     raises misc.check_nan_losses' RuntimeWarning (late by at most LOG_PERIOD steps; `HipSGD.step(guard=...)` keeps
-    such a step from touching the parameters), a bad-label count raises ValueError."""
+    such a step from touching the parameters), a bad-label count raises ValueError.  The BCE losses (`HipBCE`,
+    `HipBCEWithLogits`) write the same rows with field 6 = 1 and no top-k errors; with `cfg.DATA.MULTI_LABEL` the meter
+    folds the loss and the sample count only and logs what the reference's TrainMeter logs then (utils/meters.py:492,
+    523, 547): no top1_err / top5_err per iteration, and neither those nor the loss per epoch."""
 
     def __init__(self, epoch_iters, cfg, ring=None, device="cuda"):
         from slowfast.models.step_tail import StatsRing
         self._cfg = cfg
+        self._multi_label = bool(cfg.DATA.MULTI_LABEL)
         self.epoch_iters = epoch_iters
         self.MAX_EPOCH = cfg.SOLVER.MAX_EPOCH * epoch_iters
         self._tic, self._lap = time.perf_counter(), 0.0
@@ -241,6 +245,8 @@ class DeviceTrainMeter(object):
         self.loss.add_value(loss)
         self.loss_total += loss * mb_size
         self.num_samples += mb_size
+        if self._multi_label:
+            return
         self.mb_top1_err.add_value(top1_err)
         self.mb_top5_err.add_value(top5_err)
         self.num_top1_mis += top1_err * mb_size
@@ -262,10 +268,10 @@ class DeviceTrainMeter(object):
             raise RuntimeError("DeviceTrainMeter: {} steps since the last drain but the ring holds {} — drain at least "
                                "every LOG_PERIOD steps".format(fresh, ring.cap))
         for i in range(self._drained, self._drained + fresh):
-            loss, top1, top5, flag, n, bad = [float(v) for v in rows[i % ring.cap, :6]]
+            loss, top1, top5, flag, n, bad, kind = [float(v) for v in rows[i % ring.cap, :7]]
             if bad != 0:
-                raise ValueError("DeviceTrainMeter: step {} had label(s) outside [0, classes) ({:g} per rank on "
-                                 "average)".format(i, bad))
+                what = "label(s) outside [0, classes)" if kind == 0 else "target or probability outside [0, 1]"
+                raise ValueError("DeviceTrainMeter: step {} had {} ({:g} per rank on average)".format(i, what, bad))
             if flag != 0 or math.isnan(loss):
                 raise RuntimeWarning("ERROR: Got NaN losses {}".format(datetime.datetime.now()))
             self._fold(top1, top5, loss, int(round(n)) * world)
@@ -292,9 +298,10 @@ class DeviceTrainMeter(object):
             "loss": self.loss.get_win_median(),
             "lr": self.lr,
             "gpu_mem": "{:.2f} GB".format(self._gpu_mem()),
-            "top1_err": self.mb_top1_err.get_win_median(),
-            "top5_err": self.mb_top5_err.get_win_median(),
         }
+        if not self._multi_label:
+            stats["top1_err"] = self.mb_top1_err.get_win_median()
+            stats["top5_err"] = self.mb_top5_err.get_win_median()
         _LOG.info(format_json_stats(stats))
         return stats
 
@@ -314,8 +321,9 @@ class DeviceTrainMeter(object):
             stats["RAM"] = "{:.2f}/{:.2f} GB".format((vram.total - vram.available) / 1024 ** 3, vram.total / 1024 ** 3)
         except ImportError:  # the reference needs psutil for this one field
             pass
-        stats["top1_err"] = self.num_top1_mis / self.num_samples
-        stats["top5_err"] = self.num_top5_mis / self.num_samples
-        stats["loss"] = self.loss_total / self.num_samples
+        if not self._multi_label:
+            stats["top1_err"] = self.num_top1_mis / self.num_samples
+            stats["top5_err"] = self.num_top5_mis / self.num_samples
+            stats["loss"] = self.loss_total / self.num_samples
         _LOG.info(format_json_stats(stats))
         return stats

@@ -874,13 +874,45 @@ int sf_stripe_pool_bwd(const float* dz, int dz_cs, int dz_coff, const float* dme
  *   element, no atomics.
  *   SF_EINVAL, nothing enqueued: a null pointer (guard excepted), non-positive counts, zero_grad outside {0, 1}, a
  *   zero or 4-byte-misaligned address, numel <= 0, a group outside [0, n_groups), a first-step flag outside {0, 1}, a
- *   momentum address of 0 in a group whose momentum is not 0, chunks that do not tile the tensors exactly. */
+ *   momentum address of 0 in a group whose momentum is not 0, chunks that do not tile the tensors exactly.
+ * sf_bce: nn.BCELoss (from_logits = 0, x = probabilities: losses.py "bce") or nn.BCEWithLogitsLoss (from_logits = 1,
+ *   x = logits: "bce_logit") with mean reduction over all N * K elements, its gradient, a ring row and the flag in ONE
+ *   launch.  x, y (targets) fp32 [N][K] with row strides ldx, ldy >= K floats; dx [N][K] dense.
+ *   from_logits = 0, torch's binary_cross_entropy: loss = -(y max(log p, -100) + (1 - y) max(log(1 - p), -100)),
+ *   dx = (p - y) / max(p (1 - p), 1e-12) / (N K).  An element whose target or probability lies outside [0, 1] (torch
+ *   asserts on the device) adds no loss, gets dx = 0 and is counted in the row's bad-element field; the divisor stays
+ *   N K.  from_logits = 1: loss = max(x, 0) - x y + log1p(exp(-|x|)), dx = (sigmoid(x) - y) / (N K), both in the form
+ *   that neither overflows nor drops the small term at large |x|; targets are not range-checked (torch does not).
+ *   ring, counter, loss_out: as sf_ce_topk; the row is {loss, 0, 0, non-finite flag, N, bad-element count, 1, 0} —
+ *   field 6 names the loss that wrote the row (0: sf_ce_topk, 1: sf_bce).  A NaN or Inf in x or y sets the flag and
+ *   makes the loss NaN; the other elements' gradients are those of the clean input.  log, exp, log1p and the sums run
+ *   in fp64 in a fixed order (no atomics): two runs give equal bits.  One workgroup; any N and K.
+ *   SF_EINVAL, nothing enqueued: a null pointer, N <= 0, K <= 0, ldx < K, ldy < K, cap <= 0, from_logits not 0 / 1.
+ * sf_adam_step: torch.optim.Adam's update (torch/optim/adam.py::_single_tensor_adam, amsgrad = maximize = False) of
+ *   every parameter of every group in ONE call = two launches on `stream`: a one-workgroup kernel adds 1 to every
+ *   listed tensor's step count, then the update kernel reads it.  Per element, in fp32:  g += wd * p;
+ *   m += (g - m) (1 - beta1);  v = beta2 v + (1 - beta2) g g;  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps), with
+ *   bc_i = 1 - beta_i^step computed once per workgroup in fp64 (torch: Python floats).
+ *   table: int64 [n_tensors][7] = parameter, gradient, exp_avg, exp_avg_sq and step-count addresses (the step count
+ *   is ONE float in device memory per tensor, each at its own address: a replayed graph keeps advancing it), numel,
+ *   group.  chunks: as sf_sgd_step, tiled at sf_sgd_chunk_elems().  hyper: fp64 [n_groups][5] = lr, beta1, beta2, eps,
+ *   weight_decay, read from DEVICE memory (fp64 because 1 - beta2 of a float beta2 is off by 1e-5 of itself).
+ *   *_host, guard, zero_grad: as sf_sgd_step; a guarded-off call moves nothing, the step counts included.
+ *   A chunk whose four addresses are all 16-byte aligned moves 16 bytes per access, any other 4.
+ *   SF_EINVAL, nothing enqueued: a null pointer (guard excepted), non-positive counts, zero_grad outside {0, 1}, a
+ *   zero or 4-byte-misaligned address, numel <= 0, a group outside [0, n_groups), a hyper-parameter that is not
+ *   finite, a beta outside [0, 1), chunks that do not tile the tensors exactly. */
 int sf_ce_topk(const float* logits, int ld, const long* labels, int N, int K, int k_hi, float* dlogits, float* ring,
                int* counter, int cap, float* loss_out, void* stream);
 int sf_sgd_chunk_elems(void);
 int sf_sgd_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
                 int n_chunks, const float* hyper_host, const float* hyper, int n_groups, const float* guard,
                 int zero_grad, void* stream);
+int sf_bce(const float* x, int ldx, const float* y, int ldy, int N, int K, int from_logits, float* dx, float* ring,
+           int* counter, int cap, float* loss_out, void* stream);
+int sf_adam_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
+                 int n_chunks, const double* hyper_host, const double* hyper, int n_groups, const float* guard,
+                 int zero_grad, void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,10 @@ written, g read (+ g written with zero_grad) over that time.
 Method: every arm warmed up, then ROUNDS rounds in which the arms alternate; an arm's round is REPS calls; "issue" is
 the host clock until the last call returns, "total" until the device is idle (host clock between two device
 synchronisations), both per call; the figure is the median round, the spread its min .. max.  Clocks not pinned.
-usage: tools/microbench/step_tail_bench.py [out.txt] [workload ...]      (default: dual shufflenetv2)"""
+Adam mode (`--adam`): the update alone on the workload's parameter list — torch.optim.Adam(foreach=True), torch.optim.Adam(
+fused=True), HipAdam and HipAdam with zero_grad, a new learning rate in front of every call, same method; plus the
+raw `sf_adam_step` call (step-count launch + update launch) by HIP events: p, m, v read and written, g read.
+usage: tools/microbench/step_tail_bench.py [out.txt] [--adam] [workload ...]      (default: dual shufflenetv2; --adam: slowfast, the R50 parameter set)"""
 import contextlib
 import io
 import math
@@ -30,12 +33,13 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 import bench  # noqa: E402
 import sfhip  # noqa: E402
-from slowfast.models.step_tail import HipCrossEntropy, HipSGD, StatsRing, sgd_step  # noqa: E402
+from slowfast.models.step_tail import HipAdam, HipCrossEntropy, HipSGD, StatsRing, adam_step, sgd_step  # noqa: E402
 from slowfast.utils.distributed import FlatGradients  # noqa: E402
 from slowfast.utils.meters import topks_correct  # noqa: E402
 
 ROUNDS, REPS = 9, 5
 SGD = dict(lr=0.01, momentum=0.9, weight_decay=1e-4)
+ADAM = dict(lr=0.01, betas=(0.9, 0.999), weight_decay=1e-4)
 
 
 def alternate(arms):
@@ -70,8 +74,8 @@ def new_lr(opt):
         g["lr"] = lr
 
 
-def kernel_time(opt, zero_grad):
-    """Seconds per raw sf_sgd_step launch, one per round, by HIP events."""
+def kernel_time(opt, zero_grad, sgd_step=sgd_step):
+    """Seconds per raw sf_sgd_step launch (or sf_adam_step call), one per round, by HIP events."""
     args = (opt._table, opt._table_dev, opt._chunks, opt._chunks_dev, opt._hyper, opt._hyper_dev, None, zero_grad)
     for _ in range(3):
         sgd_step(*args)
@@ -189,14 +193,52 @@ def one_workload(workload, out):
             print(ln, flush=True)
 
 
+def adam_workload(workload, out):
+    dev = torch.device("cuda", 0)
+    with contextlib.redirect_stdout(io.StringIO()):
+        cfg, model, batch, desc = bench.build(workload, dev)
+    params = [p for p in model.parameters() if p.requires_grad]
+    flat = FlatGradients(params)
+    n = flat.flat.numel()
+    g = torch.Generator(device="cpu").manual_seed(1)
+    fill = torch.randn(n, generator=g).to(dev) * 1e-3
+    flat.flat.copy_(fill)
+    opts = {"foreach": torch.optim.Adam(params, foreach=True, **ADAM), "fused": torch.optim.Adam(params, fused=True, **ADAM),
+            "hip": HipAdam(params, **ADAM)}
+
+    def update(opt, **kw):
+        def fn():
+            new_lr(opt)
+            opt.step(**kw)
+        return fn
+
+    lines = ["== %s (Adam): %s; %d parameter tensors, %.2f M elements" % (workload, desc, len(params), n / 1e6)]
+    upd = [("torch foreach", update(opts["foreach"])), ("torch fused", update(opts["fused"])),
+           ("HipAdam", update(opts["hip"])), ("HipAdam zero_grad", update(opts["hip"], zero_grad=True))]
+    issue, total = alternate(upd)
+    lines.append("   update alone (call)        issue (host)                        total (device idle)")
+    for name, _ in upd:
+        lines.append("   %-22s %s   %s" % (name, fmt(issue[name]), fmt(total[name])))
+    lines.append("   sf_adam_step (HIP events, raw calls: step counts + update)     device time                  achieved")
+    for name, z in (("adam_tick_kernel + adam_step_kernel", False), ("adam_tick_kernel + adam_step_kernel zero_grad", True)):
+        flat.flat.copy_(fill)
+        t = kernel_time(opts["hip"], z, adam_step)
+        lines.append("   %-58s %s   %6.2f TB/s" % (name, fmt(t), n * 4 * (8 if z else 7) / statistics.median(t) / 1e12))
+    for ln in lines:
+        print(ln, file=out, flush=True)
+        if out is not sys.stdout:
+            print(ln, flush=True)
+
+
 def main():
-    args = [a for a in sys.argv[1:]]
+    args = [a for a in sys.argv[1:] if a != "--adam"]
+    adam = "--adam" in sys.argv[1:]
     out = open(args[0], "w") if args and args[0].endswith(".txt") else sys.stdout
-    workloads = [a for a in args if not a.endswith(".txt")] or ["dual", "shufflenetv2"]
+    workloads = [a for a in args if not a.endswith(".txt")] or (["slowfast"] if adam else ["dual", "shufflenetv2"])
     print("step_tail_bench: torch %s on %s; %d rounds x %d calls per arm, arms alternate, median (min .. max)" % (
         torch.__version__, torch.cuda.get_device_name(0), ROUNDS, REPS), file=out, flush=True)
     for w in workloads:
-        one_workload(w, out)
+        (adam_workload if adam else one_workload)(w, out)
 
 
 if __name__ == "__main__":
