@@ -5,6 +5,7 @@
 // per LOG_PERIOD, the hyper-parameters are read from device memory (the LR schedule is a 4-byte write a replayed graph
 // sees) and a non-finite loss switches the update off through a flag the loss kernel leaves.
 #include "common.h"
+#include "stats_row.h"
 
 #include <math.h>
 
@@ -17,26 +18,6 @@ namespace {
 // lane-strided sweeps (max + rank of the label, sum of exp, gradient).  exp / log / the sums run in fp64: at these sizes
 // that is free and every stored float is the rounded exact value.  Order of every sum is fixed (lane stride, xor
 // butterfly, rows in order per wavefront, wavefronts in order): equal bits run to run, no atomics.
-constexpr int CE_WAVES = 16;
-constexpr int CE_TPB = CE_WAVES * 64;
-constexpr int RING_ROW = 8;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 __global__ __launch_bounds__(CE_TPB) void ce_topk_kernel(const float* __restrict__ logits, int ld,
                                                          const long* __restrict__ labels, int N, int K, int k_hi,
                                                          float* __restrict__ dlogits, float* __restrict__ ring,
@@ -60,7 +41,7 @@ __global__ __launch_bounds__(CE_TPB) void ce_topk_kernel(const float* __restrict
       const float v = x[j];
       m = fmaxf(m, v);
       nf |= !isfinite(v);
-      rank += (v > xl || (v == xl && j < l)) ? 1 : 0;  // ties go to the lower index
+      rank += beats_label(v, xl, j, l);  // ties go to the lower index
     }
     m = wave_max(m);
     rank = wave_sum(rank);
@@ -107,8 +88,8 @@ __global__ __launch_bounds__(CE_TPB) void ce_topk_kernel(const float* __restrict
     float* row = ring + (long)slot * RING_ROW;
     const float n = (float)N;
     row[0] = mean;
-    row[1] = (1.0f - (float)c[0] / n) * 100.0f;  // train_net.py:123-125, in float32 as there
-    row[2] = (1.0f - (float)c[1] / n) * 100.0f;
+    row[1] = topk_error_pct(c[0], n);  // train_net.py:123-125, in float32 as there
+    row[2] = topk_error_pct(c[1], n);
     row[3] = flag;
     row[4] = n;
     row[5] = (float)c[3];
@@ -125,8 +106,6 @@ __global__ __launch_bounds__(CE_TPB) void ce_topk_kernel(const float* __restrict
 // sizes are boxes x 80 (AVA) or clips x 157 (Charades), ~1e4 elements.  Thread i owns elements i, i + 1024, ... of the
 // flattened [N][K]; log / exp / log1p and the sums in fp64, fixed order (thread stride, xor butterfly, wavefronts in
 // order): equal bits run to run, no atomics.
-constexpr float KIND_BCE = 1.f;  // row[6]: which loss wrote the row (0: cross-entropy)
-
 __global__ __launch_bounds__(CE_TPB) void bce_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ y,
                                                      int ldy, int N, int K, int from_logits, float* __restrict__ dx,
                                                      float* __restrict__ ring, int* __restrict__ counter, int cap,

@@ -70,6 +70,7 @@ _SIGNATURES = {
     "sf_clip_batch": (_ci, [_vp, _vp] + [_ci] * 5 + [_vp] * 4 + [_ci, _ci, _ci, _vp]),
     "sf_clip_batch_gray": (_ci, [_vp, _vp] + [_ci] * 4 + [_cf, _cf, _vp, _vp, _ci, _ci, _ci, _vp]),
     "sf_ensemble_update": (_ci, [_vp] * 4 + [_pi] * 3 + [_ci] * 4 + [_vp]),
+    "sf_ensemble_update_ml": (_ci, [_vp] * 3 + [_ci, _vp, _vp, _pi, _pi] + [_ci] * 4 + [_vp]),
     "sf_ncthw1_pack": (_ci, [_vp, _vp] + [_ci] * 7 + [_vp]),
     "sf_stem1_accepts": (_ci, [_ci] * 4),
     "sf_stem1_fwd": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _ci, _ci, _vp]),
@@ -201,6 +202,11 @@ _SIGNATURES = {
     # multi-label / detection loss, one-call Adam
     "sf_bce": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp, _vp]),
     "sf_adam_step": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _ci, _vp]),
+    # evaluation: top-k errors of a batch, the epoch's row store, mean average precision
+    "sf_topk_errors": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _pi, _ci, _vp]),
+    "sf_rows_append": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp]),
+    "sf_map_ws_bytes": (_cl, [_ci, _ci]),
+    "sf_map": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
 }
 EXPORTS = list(_SIGNATURES)
 
@@ -477,6 +483,72 @@ def ensemble_update(preds, video_idx, labels, video_preds, video_labels, clip_co
     assert video_labels.numel() == Nv and clip_count.numel() == Nv and bad_count.numel() == 1
     _call("sf_ensemble_update", _ptr(preds), _ptr(video_idx), _ptr(labels), _ptr(video_preds), _iptr(video_labels),
           _iptr(clip_count), _iptr(bad_count), B, K, Nv, int(mode))
+
+
+def _rows(t, what):
+    """A [N, K] fp32 GPU tensor as the kernels read it: unit column stride, row stride >= K.  Returns (tensor, stride)."""
+    _require_gpu(t, what)
+    N, K = t.shape
+    if t.stride(1) != 1 or (N > 1 and t.stride(0) < K):
+        t = t.contiguous()
+    return t, (t.stride(0) if N > 1 else K)
+
+
+def ensemble_update_ml(preds, video_idx, labels, video_preds, video_labels, clip_count, bad_count, mode):
+    """The multi-label TestMeter.update_stats on the device: preds / labels fp32 [B,K], video_idx int32 [B] folded into
+    video_preds / video_labels fp32 [Nv,K] and clip_count int32 [Nv]; mode 0 sum, 1 max.  bad_count: int32 [2], clips
+    whose video index was outside [0, Nv) and label rows that differed from the ones their video already held."""
+    _require_gpu(preds, "ensemble_update_ml")
+    _require_gpu(video_preds, "ensemble_update_ml")
+    _require_gpu(video_labels, "ensemble_update_ml")
+    assert all(t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() for t in (video_idx, clip_count, bad_count))
+    assert preds.dim() == 2 and preds.is_contiguous() and video_preds.dim() == 2 and video_preds.is_contiguous()
+    B, K = preds.shape
+    Nv = video_preds.shape[0]
+    assert video_preds.shape[1] == K and video_idx.numel() == B and tuple(labels.shape) == (B, K)
+    assert video_labels.is_contiguous() and tuple(video_labels.shape) == (Nv, K)
+    assert clip_count.numel() == Nv and bad_count.numel() == 2
+    labels, ldl = _rows(labels, "ensemble_update_ml")
+    _call("sf_ensemble_update_ml", _ptr(preds), _ptr(video_idx), _ptr(labels), int(ldl), _ptr(video_preds),
+          _ptr(video_labels), _iptr(clip_count), _iptr(bad_count), B, K, Nv, int(mode))
+
+
+def rows_append(preds, labels, store_preds, store_labels, cursor):
+    """ValMeter.update_predictions on the device: preds / labels fp32 [N,K] (row views) are copied to rows cursor[0]..
+    of store_preds / store_labels fp32 [cap,K]; cursor int32 [2] = {rows filled, rows refused for want of room}."""
+    if preds.dim() != 2 or tuple(labels.shape) != tuple(preds.shape):
+        raise ValueError("rows_append: preds [N, K] and labels [N, K], got %s and %s" % (tuple(preds.shape),
+                                                                                         tuple(labels.shape)))
+    N, K = preds.shape
+    preds, ldp = _rows(preds, "rows_append")
+    labels, ldl = _rows(labels, "rows_append")
+    for t in (store_preds, store_labels):
+        _require_gpu(t, "rows_append")
+        assert t.is_contiguous() and t.dim() == 2 and t.shape[1] == K and t.shape[0] == store_preds.shape[0]
+    assert cursor.is_cuda and cursor.dtype == torch.int32 and cursor.is_contiguous() and cursor.numel() == 2
+    _call("sf_rows_append", _ptr(preds), int(ldp), _ptr(labels), int(ldl), N, K, _ptr(store_preds), _ptr(store_labels),
+          _iptr(cursor), store_preds.shape[0], tag="rows_append")
+
+
+def mean_ap(scores, labels, out=None, per_class=False):
+    """One `sf_map` call (two launches, no host read): scores / labels fp32 [N,C] (row views) -> out fp64 [3] = {mAP,
+    classes with a positive, refused elements}, and the per-class AP fp64 [C] (-1: left out) when asked for."""
+    if scores.dim() != 2 or tuple(labels.shape) != tuple(scores.shape):
+        raise ValueError("mean_ap: scores [N, C] and labels [N, C], got %s and %s" % (tuple(scores.shape),
+                                                                                       tuple(labels.shape)))
+    N, C = scores.shape
+    scores, lds = _rows(scores, "mean_ap")
+    labels, ldl = _rows(labels, "mean_ap")
+    nbytes = lib().sf_map_ws_bytes(N, C)
+    if nbytes <= 0:
+        raise SfhipError("mean_ap: %d x %d is outside the kernel's range" % (N, C))
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=scores.device)
+    if out is None:
+        out = torch.empty((3,), dtype=torch.float64, device=scores.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == 3
+    ap = torch.empty((C,), dtype=torch.float64, device=scores.device) if per_class else None
+    _call("sf_map", _ptr(scores), int(lds), _ptr(labels), int(ldl), N, C, _ptr(ws), _ptr(out), _ptr(ap), tag="map")
+    return (out, ap) if per_class else out
 
 
 # ------------------------------------------------------------------------------------------------ one-channel stem

@@ -7,6 +7,8 @@
 * `HipBCE(ring)` / `HipBCEWithLogits(ring)` — `nn.BCELoss(reduction="mean")` on probabilities (detection, losses.py
   "bce") and `nn.BCEWithLogitsLoss(reduction="mean")` on logits (multi-label classification, "bce_logit") with the
   NaN check as ONE launch (`sf_bce`); `get_hip_loss_func(cfg, ring)` picks by `MODEL.LOSS_FUNC`.
+* `topk_errors(preds, labels, k_hi, ring)` — the evaluation batch's row (train_net.py:227-232): `sf_topk_errors`, the same
+  ring, no loss (`utils.meters.DeviceValMeter` drains it).
 * `HipSGD` — `torch.optim.SGD` whose `step()` is ONE launch over every parameter of every group (`sf_sgd_step`), with the
   hyper-parameters in device memory: `optim.set_lr` (:68-69) stays a host assignment, `step()` / `upload_hyper()` turn a
   change into one small copy, and a captured step follows the schedule.
@@ -26,7 +28,7 @@ TAB_ROW, HYP_ROW = 6, 5
 ADAM_TAB_ROW, ADAM_HYP_ROW = 7, 5
 STAGE_SLOTS = 16
 ROW_LOSS, ROW_TOP1, ROW_TOPK, ROW_FLAG, ROW_N, ROW_BAD, ROW_KIND = 0, 1, 2, 3, 4, 5, 6
-KIND_CE, KIND_BCE = 0, 1  # ROW_KIND: which loss kernel wrote the row
+KIND_CE, KIND_BCE, KIND_EVAL = 0, 1, 2  # ROW_KIND: which kernel wrote the row (2: sf_topk_errors, no loss)
 
 
 class StatsRing(object):
@@ -95,6 +97,23 @@ def bce(preds, targets, from_logits, ring, out, dgrad=None):
     sfhip._call("sf_bce", _vp(preds), int(ldx), _vp(targets), int(ldy), N, K, 1 if from_logits else 0, _vp(dgrad),
                 _vp(ring.rows), cnt, ring.cap, _vp(out), tag="bce")
     return dgrad
+
+
+def topk_errors(preds, labels, k_hi, ring):
+    """One `sf_topk_errors` launch: the top-1 / top-k_hi errors of an evaluation batch (train_net.py:227-232) as a ring
+    row of kind KIND_EVAL.  preds fp32 [N, K] (unit column stride, row stride >= K), labels int64 [N]."""
+    sfhip._require_gpu(preds, "topk_errors")
+    if preds.dim() != 2 or labels.dim() != 1 or labels.shape[0] != preds.shape[0]:
+        raise ValueError("topk_errors: preds [N, K] and labels [N], got %s and %s" % (tuple(preds.shape),
+                                                                                      tuple(labels.shape)))
+    if labels.dtype != torch.int64 or not labels.is_cuda:
+        raise ValueError("topk_errors: labels must be int64 on the GPU, got %s on %s" % (labels.dtype, labels.device))
+    N, K = preds.shape
+    preds, ld = _rows_view(preds, N, K)
+    labels = labels.contiguous()
+    cnt = ctypes.cast(ctypes.c_void_p(ring.counter.data_ptr()), sfhip._pi)
+    sfhip._call("sf_topk_errors", _vp(preds), int(ld), _vp(labels), N, K, int(k_hi), _vp(ring.rows), cnt, ring.cap,
+                tag="topk_errors")
 
 
 class _LossFunction(torch.autograd.Function):

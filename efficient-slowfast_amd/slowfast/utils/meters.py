@@ -2,7 +2,11 @@
 
 The reference copies every batch of predictions to the host and adds them to per-video rows one clip at a time in a
 Python loop.  Here the accumulators live on the model's device and one `index_add_` / `scatter_reduce_` per batch
-performs the ensemble, so the test loop never synchronises with the GPU until `finalize_metrics`."""
+performs the ensemble, so the test loop never synchronises with the GPU until `finalize_metrics`.
+
+The multi-label side (reference :623-632, :671-675, :690-714) is here too: `get_map` (numpy, no scikit-learn) for host
+tensors, `device_map` / `DeviceMultiLabelTestMeter` / `DeviceValMeter` on the `sf_map`, `sf_ensemble_update_ml`,
+`sf_topk_errors` and `sf_rows_append` kernels."""
 from slowfast._overlay import chain_module as _chain_module
 
 _chain_module(globals())  # the reference's namesake (when importable) supplies every name not defined below
@@ -25,6 +29,65 @@ def topks_correct(preds, labels, ks):
     _, inds = torch.topk(preds, max(ks), dim=1, largest=True, sorted=True)
     correct = inds.t().eq(labels.view(1, -1).expand(max(ks), -1))
     return [correct[:k, :].reshape(-1).float().sum() for k in ks]
+
+
+def _check_map_inputs(preds, labels):
+    preds, labels = np.asarray(preds), np.asarray(labels)
+    if preds.ndim != 2 or preds.shape != labels.shape:
+        raise ValueError("get_map: preds [N, C] and labels [N, C], got {} and {}".format(preds.shape, labels.shape))
+    bad = int((~np.isfinite(preds)).sum() + ((labels != 0) & (labels != 1)).sum())
+    if bad:
+        raise ValueError("get_map: {} element(s) with a NaN or infinite score or a label other than 0 or 1".format(bad))
+    return preds, labels == 1
+
+
+def average_precisions(preds, labels):
+    """Per-class average precision, float64 [C], -1 for a class without a positive: what
+    sklearn.metrics.average_precision_score(labels, preds, average=None) returns for the other classes, as
+
+        AP = (1/P) sum_{i : y_i = 1} TP(s_i) / CNT(s_i),  TP(t) = #{j : s_j >= t, y_j = 1},  CNT(t) = #{j : s_j >= t}
+
+    (scikit-learn walks the distinct thresholds of the sorted scores; tied scores form one threshold and every positive
+    of the tie group contributes the group's precision — the same sum).  Scores compare as floats: -0.0 ties +0.0."""
+    preds, pos = _check_map_inputs(preds, labels)
+    n, c = preds.shape
+    aps = np.full((c,), -1.0, dtype=np.float64)
+    for k in range(c):
+        s, y = preds[:, k], pos[:, k]
+        p = int(y.sum())
+        if p == 0:
+            continue
+        sp = s[y]
+        cnt = n - np.searchsorted(np.sort(s), sp, side="left")
+        tp = p - np.searchsorted(np.sort(sp), sp, side="left")
+        aps[k] = float(np.sum(tp.astype(np.float64) / cnt.astype(np.float64))) / p
+    return aps
+
+
+def get_map(preds, labels):
+    """utils/meters.py:690-714 for host arrays [N, C] without scikit-learn: the mean of `average_precisions` over the
+    classes with a positive, 0.0 when there is none (the reference prints scikit-learn's error and returns 0.0).  A NaN
+    or infinite score or a label other than 0 or 1 raises ValueError (the reference swallows scikit-learn's error and
+    reports 0.0 there)."""
+    _LOG.info("Getting mAP for {} examples".format(np.asarray(preds).shape[0]))
+    aps = average_precisions(preds, labels)
+    aps = aps[aps >= 0]
+    return float(np.mean(aps)) if aps.size else 0.0
+
+
+def _checked_map(out3, who):
+    """(mAP, classes, refused) as read from `sf_map`'s out -> the mAP, or ValueError for refused elements."""
+    if out3[2] != 0:
+        raise ValueError("{}: {} element(s) with a NaN or infinite score or a label other than 0 or 1".format(
+            who, int(out3[2])))
+    return float(out3[0])
+
+
+def device_map(preds, labels):
+    """`get_map` of GPU tensors [N, C]: one `sf_map` call and ONE device-to-host copy (its three-number result)."""
+    import sfhip
+    out = sfhip.mean_ap(preds.detach().float(), labels if labels.dtype == torch.float32 else labels.float())
+    return _checked_map(out.cpu().tolist(), "device_map")
 
 
 class TestMeter(object):
@@ -83,14 +146,20 @@ class TestMeter(object):
         return stats
 
     def finalize_metrics(self, ks=(1, 5)):
-        """Returns {"split": "test_final", "top{k}_acc": "xx.xx", ...} (multi-label mAP is not on this path)."""
-        if self.multi_label:
-            raise NotImplementedError("multi-label mAP (AVA/Charades) is outside the hot-path scope")
+        """Returns {"split": "test_final", "top{k}_acc": "xx.xx", ...}, or {..., "map": mAP} under multi_label
+        (utils/meters.py:353-358, through `get_map`)."""
         stats = {"split": "test_final", "complete": bool((self.clip_count == self.num_clips).all())}
+        if self.multi_label:
+            stats["map"] = get_map(self.video_preds.cpu().numpy(), self.video_labels.cpu().numpy())
+            return stats
         correct = topks_correct(self.video_preds, self.video_labels, ks)
         for k, c in zip(ks, correct):
             stats["top{}_acc".format(k)] = "{:.{prec}f}".format(float(c) / self.video_preds.size(0) * 100.0, prec=2)
         return stats
+
+
+_ML_REFUSAL = ("multi-label mAP (AVA/Charades) is outside the hot-path scope of DeviceTestMeter — use "
+               "DeviceMultiLabelTestMeter")
 
 
 class DeviceTestMeter(TestMeter):
@@ -126,7 +195,7 @@ class DeviceTestMeter(TestMeter):
     def update_stats(self, preds, labels, clip_ids):
         """preds [N, C], labels [N], clip_ids [N], all on the device: video = clip_id // num_clips."""
         if self.multi_label:
-            raise NotImplementedError("multi-label mAP (AVA/Charades) is outside the hot-path scope")
+            raise NotImplementedError(_ML_REFUSAL)
         import sfhip
         if self.video_preds is None:
             self._allocate()
@@ -138,7 +207,7 @@ class DeviceTestMeter(TestMeter):
     def finalize_metrics(self, ks=(1, 5)):
         """One copy of the accumulators to the host, then TestMeter's statistics (through `topks_correct`)."""
         if self.multi_label:
-            raise NotImplementedError("multi-label mAP (AVA/Charades) is outside the hot-path scope")
+            raise NotImplementedError(_ML_REFUSAL)
         if self.video_preds is None:
             self._allocate()
         n, k = self._shape
@@ -154,6 +223,69 @@ class DeviceTestMeter(TestMeter):
         for kk, c in zip(ks, correct):
             stats["top{}_acc".format(kk)] = "{:.{prec}f}".format(float(c) / video_preds.size(0) * 100.0, prec=2)
         return stats
+
+
+class DeviceMultiLabelTestMeter(TestMeter):
+    """The multi-label TestMeter (rows reset to -1e10, label rows, mAP) on the device: one `sf_ensemble_update_ml` launch
+    per batch, `sf_map` and ONE copy to the host in `finalize_metrics`.  A clip whose label row differs from the row its
+    video already holds (the reference's `assert torch.equal`, :292-296) is counted on the device and raises ValueError
+    at the end; a clip of a video outside [0, num_videos) raises IndexError."""
+
+    def __init__(self, num_videos, num_clips, num_cls, overall_iters, multi_label=True, ensemble_method="sum",
+                 device="cuda"):
+        if ensemble_method not in ("sum", "max"):
+            raise NotImplementedError("Ensemble Method {} is not supported".format(ensemble_method))
+        if not multi_label:
+            raise ValueError("DeviceMultiLabelTestMeter is the multi-label meter — use DeviceTestMeter")
+        self.num_clips = num_clips
+        self.overall_iters = overall_iters
+        self._tic, self._lap = time.perf_counter(), 0.0
+        self.multi_label = True
+        self.ensemble_method = ensemble_method
+        self.device = torch.device(device)
+        self._shape = (num_videos, num_cls)
+        self.video_preds = self.video_labels = self.clip_count = self.bad_count = None  # allocated on first use
+
+    def _allocate(self):
+        n, k = self._shape
+        self.video_preds = torch.full((n, k), -1e10, dtype=torch.float32, device=self.device)
+        self.video_labels = torch.zeros((n, k), dtype=torch.float32, device=self.device)
+        self.clip_count = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        self.bad_count = torch.zeros((2,), dtype=torch.int32, device=self.device)
+
+    def reset(self):
+        if self.video_preds is not None:
+            self.video_preds.fill_(-1e10)
+            for t in (self.video_labels, self.clip_count, self.bad_count):
+                t.zero_()
+
+    def update_stats(self, preds, labels, clip_ids):
+        """preds [N, C], labels [N, C] (any real dtype), clip_ids [N], all on the device."""
+        import sfhip
+        if self.video_preds is None:
+            self._allocate()
+        vid = torch.div(clip_ids, self.num_clips, rounding_mode="floor").to(torch.int32).contiguous()
+        labels = labels if labels.dtype == torch.float32 else labels.float()
+        sfhip.ensemble_update_ml(preds.detach().float().contiguous(), vid, labels, self.video_preds, self.video_labels,
+                                 self.clip_count, self.bad_count, 0 if self.ensemble_method == "sum" else 1)
+
+    def finalize_metrics(self, ks=(1, 5)):
+        """`sf_map` over the rows, then one copy: {"split": "test_final", "complete": ..., "map": ...}."""
+        import sfhip
+        if self.video_preds is None:
+            self._allocate()
+        n, _ = self._shape
+        out = sfhip.mean_ap(self.video_preds, self.video_labels)
+        packed = torch.cat([out, self.clip_count.double(), self.bad_count.double()]).cpu()  # the one copy
+        clip_count = packed[3:3 + n]
+        bad, mismatched = int(packed[3 + n]), int(packed[4 + n])
+        if bad:
+            raise IndexError("{} clip(s) named a video outside [0, {}) and were skipped".format(bad, n))
+        if mismatched:
+            raise ValueError("{} clip(s) carried a label row that differs from the one their video already "
+                             "held".format(mismatched))
+        return {"split": "test_final", "complete": bool((clip_count == self.num_clips).all()),
+                "map": _checked_map(packed[:3].tolist(), "DeviceMultiLabelTestMeter")}
 
 
 # ---------------------------------------------------------------------------------------------- training meter
@@ -192,6 +324,24 @@ def format_json_stats(stats):
         v = stats[k]
         items.append("%s: %s" % (json.dumps(k), "{:.6f}".format(v) if isinstance(v, float) else json.dumps(v)))
     return "json_stats: {" + ", ".join(items) + "}"
+
+
+def _drain_ring(ring, drained, world, who):
+    """The rows written to `ring` since step `drained`, oldest first, as lists of seven floats {loss, top-1 err, top-k
+    err, non-finite flag, N, bad count, kind}: one all-reduce (mean) of the block when world > 1 (train_net.py:128-131,
+    :233-234), ONE device-to-host copy."""
+    import slowfast.utils.distributed as du
+    # the counter rides in the block (exact in float32 far beyond any epoch: the difference below is what is used)
+    block = torch.cat([ring.rows.flatten(), ring.counter.to(torch.float64).sub_(drained).float()])
+    if world > 1:
+        du.all_reduce([block])
+    host = block.cpu()  # the one device-to-host copy (the only synchronisation of the logging period)
+    fresh = int(round(float(host[-1])))
+    rows = host[:-1].view(ring.cap, -1)
+    if fresh < 0 or fresh > ring.cap:
+        raise RuntimeError("{}: {} steps since the last drain but the ring holds {} — drain at least "
+                           "every LOG_PERIOD steps".format(who, fresh, ring.cap))
+    return [[float(v) for v in rows[i % ring.cap, :7]] for i in range(drained, drained + fresh)]
 
 
 class DeviceTrainMeter(object):
@@ -254,29 +404,17 @@ class DeviceTrainMeter(object):
 
     def drain(self):
         """Fold the rows written since the last drain; returns how many there were."""
-        import slowfast.utils.distributed as du
-        ring = self.ring
         world = max(int(self._cfg.NUM_GPUS), 1)
-        # the counter rides in the block (exact in float32 far beyond any epoch: the difference below is what is used)
-        block = torch.cat([ring.rows.flatten(), ring.counter.to(torch.float64).sub_(self._drained).float()])
-        if world > 1:
-            du.all_reduce([block])
-        host = block.cpu()  # the one device-to-host copy (the only synchronisation of the logging period)
-        fresh = int(round(float(host[-1])))
-        rows = host[:-1].view(ring.cap, -1)
-        if fresh < 0 or fresh > ring.cap:
-            raise RuntimeError("DeviceTrainMeter: {} steps since the last drain but the ring holds {} — drain at least "
-                               "every LOG_PERIOD steps".format(fresh, ring.cap))
-        for i in range(self._drained, self._drained + fresh):
-            loss, top1, top5, flag, n, bad, kind = [float(v) for v in rows[i % ring.cap, :7]]
+        rows = _drain_ring(self.ring, self._drained, world, "DeviceTrainMeter")
+        for i, (loss, top1, top5, flag, n, bad, kind) in enumerate(rows, self._drained):
             if bad != 0:
                 what = "label(s) outside [0, classes)" if kind == 0 else "target or probability outside [0, 1]"
                 raise ValueError("DeviceTrainMeter: step {} had {} ({:g} per rank on average)".format(i, what, bad))
             if flag != 0 or math.isnan(loss):
                 raise RuntimeWarning("ERROR: Got NaN losses {}".format(datetime.datetime.now()))
             self._fold(top1, top5, loss, int(round(n)) * world)
-        self._drained += fresh
-        return fresh
+        self._drained += len(rows)
+        return len(rows)
 
     def _eta(self, iters_left):
         return str(datetime.timedelta(seconds=int(self._lap * iters_left)))
@@ -315,15 +453,176 @@ class DeviceTrainMeter(object):
             "lr": self.lr,
             "gpu_mem": "{:.2f} GB".format(self._gpu_mem()),
         }
-        try:
-            import psutil
-            vram = psutil.virtual_memory()
-            stats["RAM"] = "{:.2f}/{:.2f} GB".format((vram.total - vram.available) / 1024 ** 3, vram.total / 1024 ** 3)
-        except ImportError:  # the reference needs psutil for this one field
-            pass
+        _ram_field(stats)
         if not self._multi_label:
             stats["top1_err"] = self.num_top1_mis / self.num_samples
             stats["top5_err"] = self.num_top5_mis / self.num_samples
             stats["loss"] = self.loss_total / self.num_samples
+        _LOG.info(format_json_stats(stats))
+        return stats
+
+
+# ---------------------------------------------------------------------------------------------- validation meter
+def _ram_field(stats):
+    try:
+        import psutil
+        vram = psutil.virtual_memory()
+        stats["RAM"] = "{:.2f}/{:.2f} GB".format((vram.total - vram.available) / 1024 ** 3, vram.total / 1024 ** 3)
+    except ImportError:  # the reference needs psutil for this one field
+        pass
+
+
+class DeviceValMeter(object):
+    """ValMeter (utils/meters.py:557-687) for an eval_epoch (train_net.py:166-251) that never reads a prediction on the
+    host.  Single-label: `update_stats(preds, labels)` is one `sf_topk_errors` launch that leaves the batch's top-1 /
+    top-k errors as a ring row; `log_iter_stats` (on a LOG_PERIOD boundary) and `log_epoch_stats` drain the ring as
+    DeviceTrainMeter does — one all-reduce when NUM_GPUS > 1, ONE copy — and fold the rows with ValMeter.update_stats'
+    arithmetic.  With `cfg.DATA.MULTI_LABEL`: `update_predictions(preds, labels)` is one `sf_rows_append` launch into a
+    device store of `max_iter` batches (sized on first use), and `log_epoch_stats` gathers every rank's filled rows
+    once, runs `sf_map` and makes ONE copy.  The logged records are the reference's."""
+
+    def __init__(self, max_iter, cfg, ring=None, device="cuda"):
+        from slowfast.models.step_tail import StatsRing
+        self._cfg = cfg
+        self._multi_label = bool(cfg.DATA.MULTI_LABEL)
+        self.max_iter = max_iter
+        self.device = torch.device(device)
+        self._tic, self._lap = time.perf_counter(), 0.0
+        self.ring = ring if ring is not None else StatsRing(cfg.LOG_PERIOD, device)
+        self._drained = 0  # ring.counter at the last drain
+        self.mb_top1_err = _ScalarWindow(cfg.LOG_PERIOD)
+        self.mb_top5_err = _ScalarWindow(cfg.LOG_PERIOD)
+        self.min_top1_err = 100.0
+        self.min_top5_err = 100.0
+        self.all_preds = self.all_labels = self._cursor = None  # [cap, K] stores and {rows filled, rows refused}
+        self.cap = 0
+        self.reset()
+
+    def reset(self):
+        self.mb_top1_err.reset()
+        self.mb_top5_err.reset()
+        self.num_top1_mis = 0
+        self.num_top5_mis = 0
+        self.num_samples = 0
+        self._appended = 0  # rows handed to update_predictions this epoch (the host's count of the cursor)
+        if self._cursor is not None:
+            self._cursor.zero_()
+
+    def iter_tic(self):
+        self._tic = time.perf_counter()
+
+    def iter_toc(self):
+        self._lap = time.perf_counter() - self._tic
+
+    def update_stats(self, preds, labels):
+        """Single-label: the batch's errors, one launch, no host read (train_net.py:227-243).  Multi-label: nothing, as
+        eval_epoch computes no errors then."""
+        if self._multi_label:
+            return
+        from slowfast.models.step_tail import topk_errors
+        topk_errors(preds.detach().float(), labels, self._cfg.TRAIN.TOPK, self.ring)
+
+    def update_predictions(self, preds, labels):
+        """Multi-label: append the batch to the device store (utils/meters.py:623-632).  Single-label: nothing — the
+        reference's list is never read then."""
+        if not self._multi_label:
+            return
+        import sfhip
+        preds = preds.detach().float()  # fp16 / bf16 predictions of an autocast forward are converted, as the labels are
+        if self._cursor is None:
+            self.cap = int(self.max_iter) * int(preds.shape[0])
+            self.all_preds = torch.empty((self.cap, preds.shape[1]), dtype=torch.float32, device=preds.device)
+            self.all_labels = torch.empty_like(self.all_preds)
+            self._cursor = torch.zeros((2,), dtype=torch.int32, device=preds.device)
+        sfhip.rows_append(preds, labels if labels.dtype == torch.float32 else labels.float(), self.all_preds,
+                          self.all_labels, self._cursor)
+        self._appended += int(preds.shape[0])
+
+    def _fold(self, top1_err, top5_err, mb_size):
+        """ValMeter.update_stats (utils/meters.py:609-621) for one batch's values."""
+        self.mb_top1_err.add_value(top1_err)
+        self.mb_top5_err.add_value(top5_err)
+        self.num_top1_mis += top1_err * mb_size
+        self.num_top5_mis += top5_err * mb_size
+        self.num_samples += mb_size
+
+    def drain(self):
+        """Fold the rows written since the last drain; returns how many there were."""
+        from slowfast.models.step_tail import KIND_EVAL
+        world = max(int(self._cfg.NUM_GPUS), 1)
+        rows = _drain_ring(self.ring, self._drained, world, "DeviceValMeter")
+        for i, (_, top1, top5, flag, n, bad, kind) in enumerate(rows, self._drained):
+            if kind != KIND_EVAL:
+                raise RuntimeError("DeviceValMeter: ring row {} was not written by sf_topk_errors (kind {:g}) — give the "
+                                   "validation meter a ring of its own".format(i, kind))
+            if bad != 0:
+                raise ValueError("DeviceValMeter: batch {} had label(s) outside [0, classes) ({:g} per rank on "
+                                 "average)".format(i, bad))
+            if flag != 0:
+                _LOG.warning("DeviceValMeter: batch {} had NaN or infinite predictions; those rows count as "
+                             "wrong".format(i))
+            self._fold(top1, top5, int(round(n)) * world)
+        self._drained += len(rows)
+        return len(rows)
+
+    def log_iter_stats(self, cur_epoch, cur_iter):
+        if (cur_iter + 1) % self._cfg.LOG_PERIOD != 0:
+            return None
+        stats = {
+            "_type": "val_iter",
+            "epoch": "{}/{}".format(cur_epoch + 1, self._cfg.SOLVER.MAX_EPOCH),
+            "iter": "{}/{}".format(cur_iter + 1, self.max_iter),
+            "time_diff": self._lap,
+            "eta": str(datetime.timedelta(seconds=int(self._lap * (self.max_iter - cur_iter - 1)))),
+            "gpu_mem": "{:.2f} GB".format(DeviceTrainMeter._gpu_mem()),
+        }
+        if not self._multi_label:
+            self.drain()
+            stats["top1_err"] = self.mb_top1_err.get_win_median()
+            stats["top5_err"] = self.mb_top5_err.get_win_median()
+        _LOG.info(format_json_stats(stats))
+        return stats
+
+    def _epoch_map(self):
+        """mAP of the epoch's rows: every rank's filled rows gathered once, `sf_map`, one copy."""
+        import sfhip
+        import slowfast.utils.distributed as du
+        if self._cursor is None or self._appended == 0:
+            raise RuntimeError("DeviceValMeter: no predictions were recorded this epoch")
+        n = min(self._appended, self.cap)
+        preds, labels, cursor = self.all_preds[:n], self.all_labels[:n], self._cursor
+        if int(self._cfg.NUM_GPUS) > 1:
+            preds, labels, cursor = du.all_gather([preds, labels, cursor])
+        out = sfhip.mean_ap(preds, labels)
+        host = torch.cat([out, cursor.double()]).cpu().tolist()  # the one device-to-host copy of the epoch
+        cursors = host[3:]
+        if any(v != 0 for v in cursors[1::2]):
+            raise RuntimeError("DeviceValMeter: {} row(s) did not fit the prediction store (cap = {} rows = max_iter {} "
+                               "x the first batch's rows)".format(int(sum(cursors[1::2])), self.cap, self.max_iter))
+        if any(v != n for v in cursors[0::2]):
+            raise RuntimeError("DeviceValMeter: the ranks stored {} rows, {} were expected on each".format(
+                [int(v) for v in cursors[0::2]], n))
+        return _checked_map(host[:3], "DeviceValMeter")
+
+    def log_epoch_stats(self, cur_epoch):
+        stats = {
+            "_type": "val_epoch",
+            "epoch": "{}/{}".format(cur_epoch + 1, self._cfg.SOLVER.MAX_EPOCH),
+            "time_diff": self._lap,
+            "gpu_mem": "{:.2f} GB".format(DeviceTrainMeter._gpu_mem()),
+        }
+        _ram_field(stats)
+        if self._multi_label:
+            stats["map"] = self._epoch_map()
+        else:
+            self.drain()
+            top1_err = self.num_top1_mis / self.num_samples
+            top5_err = self.num_top5_mis / self.num_samples
+            self.min_top1_err = min(self.min_top1_err, top1_err)
+            self.min_top5_err = min(self.min_top5_err, top5_err)
+            stats["top1_err"] = top1_err
+            stats["top5_err"] = top5_err
+            stats["min_top1_err"] = self.min_top1_err
+            stats["min_top5_err"] = self.min_top5_err
         _LOG.info(format_json_stats(stats))
         return stats

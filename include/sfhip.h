@@ -673,6 +673,16 @@ int sf_clip_batch_gray(const long* table_host, const long* table, int B, int n_f
 int sf_ensemble_update(const float* preds, const int* video_idx, const int* labels, float* video_preds,
                        int* video_labels, int* clip_count, int* bad_count, int B, int K, int Nv, int mode,
                        void* stream);
+/* sf_ensemble_update_ml (csrc/ensemble.hip): the multi-label TestMeter.update_stats (utils/meters.py:290-310) on the
+ *   same owner rule and fold.  labels fp32 [B,K] with row stride ldl >= K, video_labels fp32 [Nv,K].  The owner of a
+ *   video walks its clips in batch order as the host loop does: when the row the video holds (the stored one, then the
+ *   previous clip's) has a positive sum and differs from the clip's row — the reference's `assert torch.equal`,
+ *   :292-296 — one mismatch is added to bad_count[1]; the last clip's whole row is then stored.  bad_count is int32 [2]:
+ *   {clips with a video outside [0, Nv), label mismatches}.  Null pointers, non-positive sizes, ldl < K, another mode:
+ *   SF_EINVAL. */
+int sf_ensemble_update_ml(const float* preds, const int* video_idx, const float* labels, int ldl, float* video_preds,
+                          float* video_labels, int* clip_count, int* bad_count, int B, int K, int Nv, int mode,
+                          void* stream);
 
 /* ---- one-channel stem (csrc/conv_stem_gray.hip): nn.Conv3d(1, Cout, [kT,7,7], stride [1,2,2], padding [pT,3,3]) of
  * ResNetBasicStem (stem_helper.py:157-164) and its weight gradient (autograd's conv backward for `conv.weight`) on
@@ -913,6 +923,41 @@ int sf_bce(const float* x, int ldx, const float* y, int ldy, int N, int K, int f
 int sf_adam_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
                  int n_chunks, const double* hyper_host, const double* hyper, int n_groups, const float* guard,
                  int zero_grad, void* stream);
+
+/* ---- evaluation (csrc/eval_metrics.hip): tools/train_net.py:166-251 eval_epoch and utils/meters.py:557-714 (ValMeter,
+ * get_map) without the host.  No entry point synchronises or reads anything back.
+ * sf_topk_errors: metrics.topks_correct for k = 1 and k = k_hi and the two error percentages (train_net.py:227-232) of
+ *   one evaluation batch in ONE launch.  preds fp32 [N][K] with row stride ld >= K (the eval head's probabilities; no
+ *   exp, no log, no gradient), labels int64 [N].  ring / counter / cap: sf_ce_topk's memory and counter protocol; the
+ *   row is {0, top-1 error %, top-k_hi error %, non-finite flag, N, bad-label count, 2, 0}.  The hit rule, the
+ *   treatment of a row with a NaN or an Inf (wrong for every k, sets the flag) and of a label outside [0, K) (wrong,
+ *   counted, never read) are sf_ce_topk's — one device function serves both.  One workgroup; any N and K.
+ *   SF_EINVAL, nothing enqueued: a null pointer, N <= 0, K <= 0, ld < K, cap <= 0, k_hi < 1 or k_hi > K.
+ * sf_rows_append: ValMeter.update_predictions (utils/meters.py:623-632) as a copy.  preds and labels fp32 [N][K] with
+ *   row strides ldp, ldl >= K go to rows cursor[0] .. cursor[0] + N - 1 of the caller's stores store_preds /
+ *   store_labels, fp32 [cap][K] dense; cursor is device int32 [2] = {rows filled, rows refused}.  Rows that would pass
+ *   cap are not written and are added to cursor[1]; cursor[0] advances by the rows written.  The cursor is read from
+ *   device memory, so a captured call appends where the previous one stopped.  One workgroup.
+ *   SF_EINVAL, nothing enqueued: a null pointer, N <= 0, K <= 0, ldp < K, ldl < K, cap <= 0.
+ * sf_map: get_map (utils/meters.py:690-714) of scores fp32 [N][C] against labels fp32 [N][C] (row strides lds, ldl >= C)
+ *   in TWO launches whatever N and C are, without a sort.  For a class with P > 0 positives
+ *       AP = (1/P) sum_{i : y_i = 1} TP(s_i) / CNT(s_i),  TP(t) = #{j : s_j >= t, y_j = 1},  CNT(t) = #{j : s_j >= t}
+ *   — sklearn's average_precision_score: tied scores form one threshold there and every positive of the group adds the
+ *   group's precision.  Scores compare as floats (-0.0 ties +0.0).  The counts are integers, every term one fp64
+ *   division, every sum folded in a fixed order (no float atomics): the same inputs give the same bits.
+ *   out fp64 [3] = {mean AP over the classes with a positive (0 when there is none, as get_map returns then), the
+ *   number of those classes, the number of refused elements: a NaN or infinite score or a label other than 0 or 1 —
+ *   the caller must not use out[0] when that is not 0}.  ap: NULL, or fp64 [C] per-class AP, -1 for a class left out.
+ *   ws: sf_map_ws_bytes(N, C) bytes of caller-owned scratch (host-only query; 0 for sizes out of range), 8-byte
+ *   aligned as out and ap (SF_EALIGN otherwise).  O(N P) comparisons per class.
+ *   SF_EINVAL, nothing enqueued: a null pointer (ap excepted), N <= 0, C <= 0, lds < C, ldl < C, N above 16 776 960. */
+int sf_topk_errors(const float* preds, int ld, const long* labels, int N, int K, int k_hi, float* ring, int* counter,
+                   int cap, void* stream);
+int sf_rows_append(const float* preds, int ldp, const float* labels, int ldl, int N, int K, float* store_preds,
+                   float* store_labels, int* cursor, int cap, void* stream);
+long sf_map_ws_bytes(int N, int C);
+int sf_map(const float* scores, int lds, const float* labels, int ldl, int N, int C, void* ws, double* out,
+           double* ap, void* stream);
 
 #ifdef __cplusplus
 }
