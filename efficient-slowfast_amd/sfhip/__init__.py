@@ -207,6 +207,10 @@ _SIGNATURES = {
     "sf_rows_append": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp]),
     "sf_map_ws_bytes": (_cl, [_ci, _ci]),
     "sf_map": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
+    # per-class evaluation: confusion matrix and per-class hits of a batch, the class report
+    "sf_confusion_small_kmax": (_ci, []),
+    "sf_confusion_update": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
+    "sf_class_report": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp]),
 }
 EXPORTS = list(_SIGNATURES)
 
@@ -549,6 +553,51 @@ def mean_ap(scores, labels, out=None, per_class=False):
     ap = torch.empty((C,), dtype=torch.float64, device=scores.device) if per_class else None
     _call("sf_map", _ptr(scores), int(lds), _ptr(labels), int(ldl), N, C, _ptr(ws), _ptr(out), _ptr(ap), tag="map")
     return (out, ap) if per_class else out
+
+
+def _counters(t, shape, dtype, what):
+    if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise SfhipError("%s: expected a contiguous %s GPU tensor of shape %s, got %s %s on %s" % (
+            what, dtype, tuple(shape), t.dtype, tuple(t.shape), t.device))
+
+
+def confusion_update(preds, labels, k_hi, conf, hits, refused):
+    """One `sf_confusion_update` launch (no host read): preds fp32 [N,K] (a row view), labels int64 [N] are ADDED to conf
+    int64 [K,K] ([true, predicted]), hits int64 [K,2] (label within the top 1 / top k_hi, per true class) and refused
+    int64 [2] (rows with a label outside [0, K); rows holding a NaN or an infinity)."""
+    if preds.dim() != 2 or labels.dim() != 1 or labels.shape[0] != preds.shape[0]:
+        raise ValueError("confusion_update: preds [N, K] and labels [N], got %s and %s" % (tuple(preds.shape),
+                                                                                           tuple(labels.shape)))
+    N, K = preds.shape
+    preds, ld = _rows(preds, "confusion_update")
+    if labels.dtype != torch.int64 or not labels.is_cuda:
+        raise ValueError("confusion_update: labels must be int64 on the GPU, got %s on %s" % (labels.dtype,
+                                                                                              labels.device))
+    labels = labels.contiguous()
+    _counters(conf, (K, K), torch.int64, "confusion_update: conf")
+    _counters(hits, (K, 2), torch.int64, "confusion_update: hits")
+    _counters(refused, (2,), torch.int64, "confusion_update: refused")
+    _call("sf_confusion_update", _ptr(preds), int(ld), _ptr(labels), N, K, int(k_hi), _ptr(conf), _ptr(hits),
+          _ptr(refused), tag="confusion_update")
+
+
+def class_report(conf, hits, out=None, per_class=None):
+    """One `sf_class_report` launch (no host read): conf int64 [K,K], hits int64 [K,2] -> out fp64 [8] = {samples,
+    accuracy, mean-class accuracy, macro precision, macro recall, macro F1, classes with support, classes never
+    predicted} and per_class fp64 [K,6] = {support, precision, recall, F1, top-1 accuracy, top-k accuracy}."""
+    if conf.dim() != 2 or conf.shape[0] != conf.shape[1]:
+        raise ValueError("class_report: conf [K, K], got %s" % (tuple(conf.shape),))
+    K = conf.shape[0]
+    _counters(conf, (K, K), torch.int64, "class_report: conf")
+    _counters(hits, (K, 2), torch.int64, "class_report: hits")
+    if out is None:
+        out = torch.empty((8,), dtype=torch.float64, device=conf.device)
+    if per_class is None:
+        per_class = torch.empty((K, 6), dtype=torch.float64, device=conf.device)
+    _counters(out, (8,), torch.float64, "class_report: out")
+    _counters(per_class, (K, 6), torch.float64, "class_report: per_class")
+    _call("sf_class_report", _ptr(conf), _ptr(hits), K, _ptr(out), _ptr(per_class), tag="class_report")
+    return out, per_class
 
 
 # ------------------------------------------------------------------------------------------------ one-channel stem

@@ -6,7 +6,11 @@ performs the ensemble, so the test loop never synchronises with the GPU until `f
 
 The multi-label side (reference :623-632, :671-675, :690-714) is here too: `get_map` (numpy, no scikit-learn) for host
 tensors, `device_map` / `DeviceMultiLabelTestMeter` / `DeviceValMeter` on the `sf_map`, `sf_ensemble_update_ml`,
-`sf_topk_errors` and `sf_rows_append` kernels."""
+`sf_topk_errors` and `sf_rows_append` kernels.
+
+Class by class (no counterpart in the reference): `DevicePerClassMeter` keeps a confusion matrix and per-class top-k
+hits on the device (`sf_confusion_update`) and reads precision / recall / F1 per class once per epoch
+(`sf_class_report`); `DeviceValMeter` and `DeviceTestMeter` take one as `per_class=`."""
 from slowfast._overlay import chain_module as _chain_module
 
 _chain_module(globals())  # the reference's namesake (when importable) supplies every name not defined below
@@ -90,6 +94,125 @@ def device_map(preds, labels):
     return _checked_map(out.cpu().tolist(), "device_map")
 
 
+# ---------------------------------------------------------------------------------------------- per-class meter
+PER_CLASS_COLUMNS = ("support", "precision", "recall", "f1", "top1_acc", "topk_acc")
+SUMMARY_FIELDS = ("samples", "accuracy", "mean_class_accuracy", "macro_precision", "macro_recall", "macro_f1",
+                  "classes_with_support", "classes_never_predicted")
+_PER_CLASS_ML_REFUSAL = ("per-class reports are single-label (confusion matrix, precision / recall per class) — for "
+                         "multi-label evaluation sf_map already returns the per-class AP")
+_REPORT_KMAX = 1024  # sf_class_report: one workgroup
+
+
+def format_json_stats(stats):
+    """The line utils/logging.py:84-96 log_json_stats writes: floats with six decimals, keys sorted."""
+    items = []
+    for k in sorted(stats):
+        v = stats[k]
+        items.append("%s: %s" % (json.dumps(k), "{:.6f}".format(v) if isinstance(v, float) else json.dumps(v)))
+    return "json_stats: {" + ", ".join(items) + "}"
+
+
+class DevicePerClassMeter(object):
+    """Which class is taken for which, and every class's precision / recall / F1, without a prediction on the host.
+    The state is ONE int64 buffer on `device`: `conf` [K, K] ([true, predicted]), `hits` [K, 2] (label within the top 1 /
+    top `k_hi`, per true class) and `refused` [2] (rows with a label outside [0, K); rows holding a NaN or an infinity),
+    followed by the fp64 report `sf_class_report` writes.  `update(preds, labels)` is one `sf_confusion_update` launch —
+    no sync, capturable; `all_reduce()` is one collective on the int64 part; `finalize()` is one `sf_class_report`
+    launch and the ONE host read of the epoch.  The tie rule is `sf_topk_errors`' (include/sfhip.h): of equal scores
+    the lower class index is predicted."""
+
+    def __init__(self, num_classes, k_hi, device="cuda"):
+        K, k_hi = int(num_classes), int(k_hi)
+        if K < 1 or K > _REPORT_KMAX:
+            raise ValueError("DevicePerClassMeter: num_classes must be in [1, {}], got {}".format(_REPORT_KMAX, K))
+        if k_hi < 1 or k_hi > K:
+            raise ValueError("DevicePerClassMeter: k_hi must be in [1, num_classes = {}], got {}".format(K, k_hi))
+        self.num_classes, self.k_hi = K, k_hi
+        self.device = torch.device(device)
+        n_int = K * K + 2 * K + 2
+        self._buf = torch.zeros((n_int + len(SUMMARY_FIELDS) + len(PER_CLASS_COLUMNS) * K,), dtype=torch.int64,
+                                device=self.device)
+        self.state = self._buf[:n_int]  # what all_reduce sums
+        self.conf = self.state[:K * K].view(K, K)
+        self.hits = self.state[K * K:K * K + 2 * K].view(K, 2)
+        self.refused = self.state[K * K + 2 * K:]
+        report = self._buf[n_int:].view(torch.float64)
+        self.summary = report[:len(SUMMARY_FIELDS)]
+        self.per_class = report[len(SUMMARY_FIELDS):].view(K, len(PER_CLASS_COLUMNS))
+
+    def reset(self):
+        self._buf.zero_()
+
+    def update(self, preds, labels):
+        """preds [N, K] and labels [N] on the device: one launch, nothing read."""
+        import sfhip
+        if preds.dim() != 2 or preds.shape[1] != self.num_classes:
+            raise ValueError("DevicePerClassMeter: preds [N, {}], got {}".format(self.num_classes, tuple(preds.shape)))
+        preds = preds.detach()
+        sfhip.confusion_update(preds if preds.dtype == torch.float32 else preds.float(),
+                               labels if labels.dtype == torch.int64 else labels.long(), self.k_hi, self.conf,
+                               self.hits, self.refused)
+
+    def all_reduce(self):
+        """Sum the counters over the ranks: one collective on the flat int64 state; nothing at world size 1."""
+        import slowfast.utils.distributed as du
+        du.all_reduce([self.state], average=False)
+
+    def finalize(self, allow_refused=False):
+        """The report of everything added since reset(): one launch, then the one host read.  Returns {"confusion": int64
+        [K, K], "hits": int64 [K, 2], "per_class": fp64 [K, 6] (PER_CLASS_COLUMNS), "summary": {SUMMARY_FIELDS},
+        "refused": {"bad_label", "non_finite"}, "k_hi"} on the host.  Refused rows raise ValueError unless
+        `allow_refused`."""
+        import sfhip
+        K = self.num_classes
+        sfhip.class_report(self.conf, self.hits, self.summary, self.per_class)
+        host = self._buf.cpu()  # the one device-to-host copy
+        n_int = K * K + 2 * K + 2
+        bad_label, non_finite = int(host[n_int - 2]), int(host[n_int - 1])
+        if (bad_label or non_finite) and not allow_refused:
+            raise ValueError("DevicePerClassMeter: {} row(s) with a label outside [0, {}) and {} row(s) with a NaN or "
+                             "infinite prediction were left out".format(bad_label, K, non_finite))
+        report = host[n_int:].view(torch.float64)
+        summary = dict(zip(SUMMARY_FIELDS, report[:len(SUMMARY_FIELDS)].tolist()))
+        for name in ("samples", "classes_with_support", "classes_never_predicted"):
+            summary[name] = int(summary[name])
+        return {"confusion": host[:K * K].view(K, K).clone(), "hits": host[K * K:K * K + 2 * K].view(K, 2).clone(),
+                "per_class": report[len(SUMMARY_FIELDS):].view(K, len(PER_CLASS_COLUMNS)).clone(),
+                "summary": summary, "refused": {"bad_label": bad_label, "non_finite": non_finite}, "k_hi": self.k_hi}
+
+    def log_report(self, class_names=None, report=None, allow_refused=False):
+        """One `json_stats:` line for the summary and one per class (`class_names[c]`, or the index).  Formats `report`
+        (a finalize() result) when given, so that logging costs no second host read; returns the logged records."""
+        K = self.num_classes
+        if class_names is not None and len(class_names) != K:
+            raise ValueError("DevicePerClassMeter: {} class names for {} classes".format(len(class_names), K))
+        if report is None:
+            report = self.finalize(allow_refused=allow_refused)
+        records = [dict({"_type": "class_report", "k_hi": report["k_hi"],
+                         "refused_bad_label": report["refused"]["bad_label"],
+                         "refused_non_finite": report["refused"]["non_finite"]}, **report["summary"])]
+        table, conf = report["per_class"].tolist(), report["confusion"].tolist()
+        for c in range(K):
+            rec = {"_type": "class_report_class", "class": str(class_names[c]) if class_names is not None else c,
+                   "confused_as": conf[c]}
+            for name, v in zip(PER_CLASS_COLUMNS, table[c]):
+                rec[name] = int(v) if name == "support" else v
+            records.append(rec)
+        for rec in records:
+            _LOG.info(format_json_stats(rec))
+        return records
+
+
+def _checked_per_class(per_class, multi_label, who):
+    if per_class is None:
+        return None
+    if not isinstance(per_class, DevicePerClassMeter):
+        raise TypeError("{}: per_class must be a DevicePerClassMeter, got {}".format(who, type(per_class).__name__))
+    if multi_label:
+        raise ValueError("{}: {}".format(who, _PER_CLASS_ML_REFUSAL))
+    return per_class
+
+
 class TestMeter(object):
     """Sum / max ensemble of `num_clips` clip predictions per video and the final top-k accuracies."""
 
@@ -168,9 +291,13 @@ class DeviceTestMeter(TestMeter):
     is copied to the host before `finalize_metrics`."""
 
     def __init__(self, num_videos, num_clips, num_cls, overall_iters, multi_label=False, ensemble_method="sum",
-                 device="cuda"):
+                 device="cuda", per_class=None):
         if ensemble_method not in ("sum", "max"):
             raise NotImplementedError("Ensemble Method {} is not supported".format(ensemble_method))
+        self.per_class = _checked_per_class(per_class, multi_label, "DeviceTestMeter")
+        if self.per_class is not None and self.per_class.num_classes != num_cls:
+            raise ValueError("DeviceTestMeter: per_class counts {} classes, the meter {}".format(
+                self.per_class.num_classes, num_cls))
         self.num_clips = num_clips
         self.overall_iters = overall_iters
         self._tic, self._lap = time.perf_counter(), 0.0
@@ -211,6 +338,9 @@ class DeviceTestMeter(TestMeter):
         if self.video_preds is None:
             self._allocate()
         n, k = self._shape
+        if self.per_class is not None:  # the ensemble's rows, once: the report is the videos', whatever it held
+            self.per_class.reset()
+            self.per_class.update(self.video_preds, self.video_labels.long())
         packed = torch.cat([self.video_preds.flatten().view(torch.int32), self.video_labels, self.clip_count,
                             self.bad_count]).cpu()  # the one device-to-host copy
         video_preds = packed[:n * k].view(torch.float32).view(n, k)
@@ -232,9 +362,10 @@ class DeviceMultiLabelTestMeter(TestMeter):
     at the end; a clip of a video outside [0, num_videos) raises IndexError."""
 
     def __init__(self, num_videos, num_clips, num_cls, overall_iters, multi_label=True, ensemble_method="sum",
-                 device="cuda"):
+                 device="cuda", per_class=None):
         if ensemble_method not in ("sum", "max"):
             raise NotImplementedError("Ensemble Method {} is not supported".format(ensemble_method))
+        _checked_per_class(per_class, True, "DeviceMultiLabelTestMeter")
         if not multi_label:
             raise ValueError("DeviceMultiLabelTestMeter is the multi-label meter — use DeviceTestMeter")
         self.num_clips = num_clips
@@ -315,15 +446,6 @@ class _ScalarWindow(object):
 
     def get_global_avg(self):
         return self.total / self.count
-
-
-def format_json_stats(stats):
-    """The line utils/logging.py:84-96 log_json_stats writes: floats with six decimals, keys sorted."""
-    items = []
-    for k in sorted(stats):
-        v = stats[k]
-        items.append("%s: %s" % (json.dumps(k), "{:.6f}".format(v) if isinstance(v, float) else json.dumps(v)))
-    return "json_stats: {" + ", ".join(items) + "}"
 
 
 def _drain_ring(ring, drained, world, who):
@@ -481,10 +603,11 @@ class DeviceValMeter(object):
     device store of `max_iter` batches (sized on first use), and `log_epoch_stats` gathers every rank's filled rows
     once, runs `sf_map` and makes ONE copy.  The logged records are the reference's."""
 
-    def __init__(self, max_iter, cfg, ring=None, device="cuda"):
+    def __init__(self, max_iter, cfg, ring=None, device="cuda", per_class=None):
         from slowfast.models.step_tail import StatsRing
         self._cfg = cfg
         self._multi_label = bool(cfg.DATA.MULTI_LABEL)
+        self.per_class = _checked_per_class(per_class, self._multi_label, "DeviceValMeter")
         self.max_iter = max_iter
         self.device = torch.device(device)
         self._tic, self._lap = time.perf_counter(), 0.0
@@ -507,6 +630,8 @@ class DeviceValMeter(object):
         self._appended = 0  # rows handed to update_predictions this epoch (the host's count of the cursor)
         if self._cursor is not None:
             self._cursor.zero_()
+        if self.per_class is not None:
+            self.per_class.reset()
 
     def iter_tic(self):
         self._tic = time.perf_counter()
@@ -520,7 +645,10 @@ class DeviceValMeter(object):
         if self._multi_label:
             return
         from slowfast.models.step_tail import topk_errors
-        topk_errors(preds.detach().float(), labels, self._cfg.TRAIN.TOPK, self.ring)
+        preds = preds.detach().float()
+        topk_errors(preds, labels, self._cfg.TRAIN.TOPK, self.ring)
+        if self.per_class is not None:  # the same batch, one more launch, still nothing read
+            self.per_class.update(preds, labels)
 
     def update_predictions(self, preds, labels):
         """Multi-label: append the batch to the device store (utils/meters.py:623-632).  Single-label: nothing — the

@@ -959,6 +959,48 @@ long sf_map_ws_bytes(int N, int C);
 int sf_map(const float* scores, int lds, const float* labels, int ldl, int N, int C, void* ws, double* out,
            double* ap, void* stream);
 
+/* ---- per-class evaluation (csrc/class_report.hip): which class is taken for which, and every class's precision,
+ * recall and F1, from counters that stay on the device.  The reference has no code for this; the contract is this
+ * comment, restated by brute force in tests/_class_report_ref.py.  No entry point synchronises or reads anything back;
+ * every buffer is the caller's; both are capturable.
+ * The rule of a row is sf_topk_errors': class j stands IN FRONT OF class c iff x[j] > x[c], or x[j] == x[c] and j < c
+ *   (torch.topk's order).  Values compare as floats: -0.0 ties +0.0, and of equal values the lower index stands in
+ *   front.  The PREDICTED class is the one nothing stands in front of — the largest value, the lowest index among
+ *   equals; the label is within the top k iff fewer than k classes stand in front of it, so "predicted == label" and
+ *   "within the top 1" are one statement.  A NaN compares false with everything; a row that holds a NaN or an infinity
+ *   is refused whole (sf_topk_errors counts such a row as wrong for every k), as is a row whose label is outside [0, K).
+ * sf_confusion_update: ONE launch that ADDS a batch to the counters (the caller zero-fills them at the start of an epoch).
+ *   preds fp32 [N][K] with row stride ld >= K, labels int64 [N] (as sf_topk_errors takes them).
+ *   conf int64 [K][K], indexed [true class][predicted class].  hits int64 [K][2]: per true class, the rows whose label
+ *   is within the top 1 and within the top k_hi.  refused int64 [2] = {rows with a label outside [0, K) — their scores
+ *   are never read; rows with a valid label that hold a NaN or an infinity}.  A refused row adds to nothing else.
+ *   For every input: sum(conf) = N - refused[0] - refused[1]; trace(conf) = sum(hits[:, 0]) = the top-1 hits
+ *   sf_topk_errors counts for the batch (N - refused - the top-1 errors among the accepted rows); sum(hits[:, 1]) = its
+ *   top-k_hi hits; row sums of conf = support, column sums = predicted counts.
+ *   Only integer adds are used — the result does not depend on the order of execution — and no float atomics.
+ *   Two routes, split at K = sf_confusion_small_kmax() = 201, the largest K whose K*K + 2K + 2 uint32 counters fit the
+ *   160 KiB - 512 B of LDS one workgroup may hold on gfx950:
+ *     K <= 201: a thread per row; the counters of a workgroup's rows are kept in LDS and its non-zero ones go to
+ *       global memory once, one 64-bit integer atomic each.
+ *     K > 201: a wavefront per row; one global integer atomic per row into conf and at most two into hits.
+ *   A row is swept once (plus the one read of the label's score).  Rows that all start on 16 bytes (pointer aligned,
+ *   ld % 4 == 0) are read 16 bytes at a time, any other view 4 bytes at a time.
+ *   SF_EINVAL, nothing enqueued: a null pointer, N <= 0, K <= 0, ld < K, k_hi < 1 or k_hi > K.  SF_EALIGN, nothing
+ *   enqueued: preds not on 4 bytes, labels / conf / hits / refused not on 8.
+ * sf_class_report: ONE launch, one workgroup, K <= 1024.  per_class fp64 [K][6] = {support, precision, recall, F1,
+ *   top-1 accuracy, top-k_hi accuracy} with TP = conf[c][c], FP = column sum - TP, FN = support - TP:
+ *   precision = TP / (TP + FP), recall = TP / (TP + FN), F1 = 2 TP / (2 TP + FP + FN), accuracies = hits / support;
+ *   each is ONE fp64 division of exact integers, and 0 when the denominator is 0.
+ *   out fp64 [8] = {samples, accuracy = trace / samples, mean-class accuracy (mean recall over the classes with
+ *   support > 0), macro precision, macro recall, macro F1 (means over the same classes), the number of classes with
+ *   support, the number of classes never predicted}.  The sums run in class order in one thread: the same counters give
+ *   the same bits.  Means over no class, and the accuracy of no sample, are 0.
+ *   SF_EINVAL, nothing enqueued: a null pointer, K <= 0, K > 1024.  SF_EALIGN: a buffer not on 8 bytes. */
+int sf_confusion_small_kmax(void);
+int sf_confusion_update(const float* preds, int ld, const long* labels, int N, int K, int k_hi, long* conf, long* hits,
+                        long* refused, void* stream);
+int sf_class_report(const long* conf, const long* hits, int K, double* out, double* per_class, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,9 @@ HOT = ("conv_rows_kernel", "conv_bx_kernel", "conv_pw_bx_kernel", "conv_bx_wgrad
        "ctx_pool_bwd_kernel", "ctx_pool_bwd_finish_kernel", "sample_affine_fwd_kernel", "sample_affine_bwd_kernel",
        "sample_affine_finish_kernel", "stripe_pool_fwd_kernel", "stripe_bcast_kernel", "clip_views_kernel",
        "clip_views_gray_kernel", "ensemble_update_kernel", "clip_batch_kernel", "clip_batch_gray_kernel",
-       "ce_topk_kernel", "sgd_step_kernel", "bce_kernel", "adam_tick_kernel", "adam_step_kernel")
+       "ce_topk_kernel", "sgd_step_kernel", "bce_kernel", "adam_tick_kernel", "adam_step_kernel",
+       "topk_errors_kernel", "rows_append_kernel", "map_partial_kernel", "map_finish_kernel",
+       "confusion_small_kernel", "confusion_wave_kernel", "class_report_kernel")
 # kernels that are allowed scratch: the f32-MFMA forms, which run only for views the bf16-piece forms reject
 # (C % 4 != 0, unaligned strides or pointers, sf_attn_fwd without a workspace, the public two-kernel sf_attn_bwd)
 EXEMPT = ("attn_bwd_fused_kernelILi64",    # fused f32 sweep for 32 < d <= 64
