@@ -211,6 +211,10 @@ _SIGNATURES = {
     "sf_confusion_small_kmax": (_ci, []),
     "sf_confusion_update": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
     "sf_class_report": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp]),
+    # detection evaluation: AVA frame-mAP — true-positive matching, per-class average precision
+    "sf_ava_ws_bytes": (_cl, [_ci, _ci, _ci]),
+    "sf_ava_match": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _ci, _vp, _ci, _ci] + [_vp] * 5),
+    "sf_ava_ap": (_ci, [_vp, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _ci] + [_vp] * 4),
 }
 EXPORTS = list(_SIGNATURES)
 
@@ -598,6 +602,48 @@ def class_report(conf, hits, out=None, per_class=None):
     _counters(per_class, (K, 6), torch.float64, "class_report: per_class")
     _call("sf_class_report", _ptr(conf), _ptr(hits), K, _ptr(out), _ptr(per_class), tag="class_report")
     return out, per_class
+
+
+def ava_frame_map(preds, boxes, metadata, gt, flags=False):
+    """One `sf_ava_match` and one `sf_ava_ap` call (five launches, no host read): preds fp32 [K,C], boxes fp32 [K,5]
+    (batch index, x1, y1, x2, y2), metadata fp32 [K,2] (video index, second) against the device tables `gt` (an object
+    with gt_box fp64 [G,4], gt_cls / gt_off int32, lut int32 [V,S], whitelist uint8 [C], num_gt int32 [C]) -> out fp64
+    [4 + C] = {mAP, classes counted, refused scores, rows with a video index outside the table, AP per class (-1: left
+    out)}; with `flags` also tp uint8 [K,C] and valid uint8 [K]."""
+    if preds.dim() != 2 or boxes.dim() != 2 or metadata.dim() != 2 or boxes.shape[1] < 5 or metadata.shape[1] < 2 or \
+            not (preds.shape[0] == boxes.shape[0] == metadata.shape[0]):
+        raise ValueError("ava_frame_map: preds [K, C], boxes [K, 5] and metadata [K, 2], got %s, %s and %s" % (
+            tuple(preds.shape), tuple(boxes.shape), tuple(metadata.shape)))
+    K, C = preds.shape
+    if gt.whitelist.numel() != C or gt.num_gt.numel() != C:
+        raise ValueError("ava_frame_map: the ground-truth tables were built for %d classes, preds has %d" % (
+            gt.whitelist.numel(), C))
+    preds, ld = _rows(preds, "ava_frame_map")
+    boxes, ldb = _rows(boxes, "ava_frame_map")
+    metadata, ldm = _rows(metadata, "ava_frame_map")
+    G, I = gt.gt_cls.numel(), gt.gt_off.numel() - 1
+    V, S = gt.lut.shape
+    _counters(gt.gt_box, (G, 4), torch.float64, "ava_frame_map: gt_box")
+    _counters(gt.gt_cls, (G,), torch.int32, "ava_frame_map: gt_cls")
+    _counters(gt.gt_off, (I + 1,), torch.int32, "ava_frame_map: gt_off")
+    _counters(gt.lut, (V, S), torch.int32, "ava_frame_map: lut")
+    _counters(gt.whitelist, (C,), torch.uint8, "ava_frame_map: whitelist")
+    _counters(gt.num_gt, (C,), torch.int32, "ava_frame_map: num_gt")
+    nbytes = lib().sf_ava_ws_bytes(K, C, G)
+    if nbytes <= 0:
+        raise SfhipError("ava_frame_map: %d rows x %d classes is outside the kernels' range (K * C < 2^31, K <= "
+                         "16776960)" % (K, C))
+    dev = preds.device
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=dev)
+    tp = torch.empty((K, C), dtype=torch.uint8, device=dev)
+    valid = torch.empty((K,), dtype=torch.uint8, device=dev)
+    out = torch.empty((4 + C,), dtype=torch.float64, device=dev)
+    _call("sf_ava_match", _ptr(boxes), int(ldb), _ptr(metadata), int(ldm), K, C, _ptr(gt.gt_box) if G else None,
+          _ptr(gt.gt_cls) if G else None, _ptr(gt.gt_off), G, I, _ptr(gt.lut), V, S, _ptr(gt.whitelist), _ptr(ws),
+          _ptr(tp), _ptr(valid), tag="ava_match")
+    _call("sf_ava_ap", _ptr(preds), int(ld), _ptr(tp), _ptr(valid), K, C, _ptr(gt.whitelist), _ptr(gt.num_gt), G,
+          _ptr(ws), _ptr(out), ctypes.c_void_p(out.data_ptr() + 32), tag="ava_ap")
+    return (out, tp, valid) if flags else out
 
 
 # ------------------------------------------------------------------------------------------------ one-channel stem

@@ -10,7 +10,10 @@ tensors, `device_map` / `DeviceMultiLabelTestMeter` / `DeviceValMeter` on the `s
 
 Class by class (no counterpart in the reference): `DevicePerClassMeter` keeps a confusion matrix and per-class top-k
 hits on the device (`sf_confusion_update`) and reads precision / recall / F1 per class once per epoch
-(`sf_class_report`); `DeviceValMeter` and `DeviceTestMeter` take one as `per_class=`."""
+(`sf_class_report`); `DeviceValMeter` and `DeviceTestMeter` take one as `per_class=`.
+
+Detection (reference :28-213 get_ava_mini_groundtruth, AVAMeter): `DeviceAVAMeter` keeps predictions, boxes and metadata
+on the device and computes the AVA frame-mAP with `sf_ava_match` / `sf_ava_ap` (utils/ava_eval_helper.py)."""
 from slowfast._overlay import chain_module as _chain_module
 
 _chain_module(globals())  # the reference's namesake (when importable) supplies every name not defined below
@@ -752,5 +755,197 @@ class DeviceValMeter(object):
             stats["top5_err"] = top5_err
             stats["min_top1_err"] = self.min_top1_err
             stats["min_top5_err"] = self.min_top5_err
+        _LOG.info(format_json_stats(stats))
+        return stats
+
+
+# ---------------------------------------------------------------------------------------------- detection (AVA) meter
+def get_ava_mini_groundtruth(full_groundtruth):
+    """The ground truth of the "subset" of the AVA validation set, the frames with second % 4 == 0
+    (utils/meters.py:28-43): faster evaluation while training."""
+    ret = [collections.defaultdict(list), collections.defaultdict(list), collections.defaultdict(list)]
+    for i in range(3):
+        for key in full_groundtruth[i].keys():
+            if int(key.split(",")[1]) % 4 == 0:
+                ret[i][key] = full_groundtruth[i][key]
+    return ret
+
+
+class DeviceAVAMeter(object):
+    """AVAMeter (utils/meters.py:46-213) for a detection eval_epoch / test that never reads a prediction on the host.
+    `update_stats(preds, ori_boxes, metadata)` copies the batch into three device stores (row counts are host-known
+    shapes: plain copies into preallocated, doubling stores — no kernel, no sync); `finalize_metrics` runs
+    `sf_ava_match` + `sf_ava_ap` over the stored rows against ground-truth tables built on the host ONCE (in
+    `__init__`) and makes ONE device-to-host copy: the mAP, two refusal counters and the per-class AP.  The reference
+    keeps a Python list of batches, pickles every batch across ranks (train_net.py:209-213) and walks every (image,
+    class) pair in numpy; with several processes `all_gather()` here is one collective per store per epoch.
+
+    mode: "val" or "test" ("train" raises: the training side of AVAMeter is loss and lr only — DeviceTrainMeter).
+    The full ground truth is used in test mode or with AVA.FULL_TEST_ON_VAL, the mini one (second % 4 == 0) otherwise.
+    `full_map` is the mAP at IoU 0.5, `per_class_ap` maps category names to AP (the evaluator's
+    PascalBoxes_PerformanceByCategory/AP@0.5IOU/<name> entries)."""
+
+    def __init__(self, overall_iters, cfg, mode, video_idx_to_name=None):
+        import os
+        from slowfast.utils import ava_eval_helper as H
+        if mode == "train":
+            raise ValueError("DeviceAVAMeter evaluates detections (mode 'val' or 'test'); the training loop's loss / lr "
+                             "statistics are DeviceTrainMeter's")
+        if mode not in ("val", "test"):
+            raise ValueError("DeviceAVAMeter: unknown mode {!r} (expected 'val' or 'test')".format(mode))
+        self.cfg = cfg
+        self.mode = mode
+        self.lr = None
+        self.loss = _ScalarWindow(cfg.LOG_PERIOD)
+        self.full_ava_test = bool(cfg.AVA.FULL_TEST_ON_VAL)
+        self.overall_iters = overall_iters
+        self._tic, self._lap = time.perf_counter(), 0.0
+        self.excluded_keys = H.read_exclusions(os.path.join(cfg.AVA.ANNOTATION_DIR, cfg.AVA.EXCLUSION_FILE))
+        self.categories, self.class_whitelist = H.read_labelmap(
+            os.path.join(cfg.AVA.ANNOTATION_DIR, cfg.AVA.LABEL_MAP_FILE))
+        self.full_groundtruth = H.read_csv(os.path.join(cfg.AVA.ANNOTATION_DIR, cfg.AVA.GROUNDTRUTH_FILE),
+                                           self.class_whitelist)
+        self.mini_groundtruth = get_ava_mini_groundtruth(self.full_groundtruth)
+        self.video_idx_to_name = list(video_idx_to_name) if video_idx_to_name is not None else \
+            H.load_video_names(cfg, False)
+        self.uses_full_groundtruth = mode == "test" or self.full_ava_test
+        self._tables = None  # built on the first finalize_metrics: the number of classes is the predictions'
+        self.all_preds = self.all_ori_boxes = self.all_metadata = None  # device stores [cap, C], [cap, 5], [cap, 2]
+        self.rows = 0
+        self.full_map = None
+        self.per_class_ap = {}
+
+    # ------------------------------------------------------------------ the loop's side
+    def iter_tic(self):
+        self._tic = time.perf_counter()
+
+    def iter_toc(self):
+        self._lap = time.perf_counter() - self._tic
+
+    def reset(self):
+        self.loss.reset()
+        self.rows = 0  # the stores keep their memory
+
+    @property
+    def cap(self):
+        return 0 if self.all_preds is None else int(self.all_preds.shape[0])
+
+    def _reserve(self, n, preds):
+        """Room for n more rows: the first batch sizes the stores for overall_iters batches like it, later ones double."""
+        need = self.rows + n
+        if need <= self.cap:
+            return
+        cap = max(need, 2 * self.cap, int(self.overall_iters) * n)
+        stores = []
+        for old, width in ((self.all_preds, preds.shape[1]), (self.all_ori_boxes, 5), (self.all_metadata, 2)):
+            new = torch.empty((cap, width), dtype=torch.float32, device=preds.device)
+            if old is not None and self.rows:
+                new[:self.rows].copy_(old[:self.rows])
+            stores.append(new)
+        self.all_preds, self.all_ori_boxes, self.all_metadata = stores
+
+    def update_stats(self, preds, ori_boxes, metadata, loss=None, lr=None):
+        """AVAMeter.update_stats (utils/meters.py:151-168): preds [n, C], ori_boxes [n, 5], metadata [n, 2] of any
+        float / integer type, on the GPU."""
+        if not (preds.is_cuda and ori_boxes.is_cuda and metadata.is_cuda):
+            raise ValueError("DeviceAVAMeter.update_stats: preds, ori_boxes and metadata are GPU tensors (the "
+                             "evaluation runs on the device; there is no host route)")
+        n = int(preds.shape[0])
+        if preds.dim() != 2 or tuple(ori_boxes.shape) != (n, 5) or tuple(metadata.shape) != (n, 2):
+            raise ValueError("DeviceAVAMeter.update_stats: preds [n, C], ori_boxes [n, 5] and metadata [n, 2], got {}, "
+                             "{} and {}".format(tuple(preds.shape), tuple(ori_boxes.shape), tuple(metadata.shape)))
+        if self.all_preds is not None and preds.shape[1] != self.all_preds.shape[1]:
+            raise ValueError("DeviceAVAMeter.update_stats: {} classes, the earlier batches had {}".format(
+                preds.shape[1], self.all_preds.shape[1]))
+        if n:
+            self._reserve(n, preds)
+            lo, hi = self.rows, self.rows + n
+            self.all_preds[lo:hi].copy_(preds.detach())  # converts fp16 / bf16 / int64 on the way
+            self.all_ori_boxes[lo:hi].copy_(ori_boxes.detach())
+            self.all_metadata[lo:hi].copy_(metadata.detach())
+            self.rows = hi
+        if loss is not None:
+            self.loss.add_value(loss)
+        if lr is not None:
+            self.lr = lr
+
+    def log_iter_stats(self, cur_epoch, cur_iter):
+        """AVAMeter.log_iter_stats (utils/meters.py:83-127) for the val / test records."""
+        if (cur_iter + 1) % self.cfg.LOG_PERIOD != 0:
+            return None
+        eta = str(datetime.timedelta(seconds=int(self._lap * (self.overall_iters - cur_iter))))
+        stats = {"_type": "{}_iter".format(self.mode), "cur_iter": "{}".format(cur_iter + 1), "eta": eta,
+                 "time_diff": self._lap, "mode": self.mode}
+        if self.mode == "val":
+            stats["cur_epoch"] = "{}".format(cur_epoch + 1)
+        _LOG.info(format_json_stats(stats))
+        return stats
+
+    # ------------------------------------------------------------------ the epoch's end
+    def groundtruth_tables(self, num_classes, device):
+        """The device tables of the ground truth this meter evaluates against (built and uploaded once)."""
+        from slowfast.utils.ava_eval_helper import GroundTruthTables
+        if self._tables is None or self._tables.num_classes != num_classes:
+            gt = self.full_groundtruth if self.uses_full_groundtruth else self.mini_groundtruth
+            self._tables = GroundTruthTables(gt, self.excluded_keys, self.class_whitelist, self.video_idx_to_name,
+                                             num_classes, device=device)
+        return self._tables
+
+    def all_gather(self):
+        """Every rank's rows: (preds, ori_boxes, metadata), or None when no rank recorded a row.  One process: the
+        stores' filled part, nothing else.  Several (the size of the default process group): the ranks exchange their
+        row counts and class counts — read on the host once (16 bytes per rank), because the padded height is a shape
+        — then every store is padded to the largest count, gathered ONCE and compacted: three collectives per epoch in
+        place of the reference's pickled gather per batch (train_net.py:209-213).  A rank without rows (or without a
+        store: it never saw a batch) takes part with empty stores, so no rank waits in a collective for another."""
+        import slowfast.utils.distributed as du
+        world = du.get_world_size()
+        if world <= 1:
+            if self.all_preds is None or self.rows == 0:
+                return None
+            return tuple(t[:self.rows] for t in (self.all_preds, self.all_ori_boxes, self.all_metadata))
+        have = self.all_preds is not None
+        dev = self.all_preds.device if have else torch.device("cuda", torch.cuda.current_device())
+        mine = torch.tensor([[self.rows if have else 0, self.all_preds.shape[1] if have else 0]], dtype=torch.int64,
+                            device=dev)
+        sizes = du.all_gather([mine])[0].cpu().tolist()  # [world][2]
+        counts = [int(n) for n, _ in sizes]
+        widths = {int(c) for n, c in sizes if n}
+        if not widths:
+            return None
+        if len(widths) != 1:
+            raise ValueError("DeviceAVAMeter: the ranks recorded predictions of {} classes".format(sorted(widths)))
+        pad = max(counts)
+        out = []
+        for store, width in ((self.all_preds, widths.pop()), (self.all_ori_boxes, 5), (self.all_metadata, 2)):
+            padded = torch.zeros((pad, width), dtype=torch.float32, device=dev)
+            if have and self.rows:
+                padded[:self.rows].copy_(store[:self.rows])
+            whole = du.all_gather([padded])[0]
+            out.append(torch.cat([whole[r * pad:r * pad + n] for r, n in enumerate(counts)], dim=0))
+        return tuple(out)
+
+    def finalize_metrics(self, log=True):
+        """AVAMeter.finalize_metrics (utils/meters.py:170-195): five launches and ONE device-to-host copy (with
+        several ranks, also the row counts in `all_gather`)."""
+        from slowfast.utils import ava_eval_helper as H
+        gathered = self.all_gather()  # first: every rank enters the collectives, whatever it recorded
+        if gathered is None:
+            raise RuntimeError("DeviceAVAMeter: no predictions were recorded this epoch")
+        preds, boxes, meta = gathered
+        tables = self.groundtruth_tables(int(preds.shape[1]), preds.device)
+        self.full_map, ap = H.device_frame_map(preds, boxes, meta, tables, who="DeviceAVAMeter")
+        results = H.per_category_results(self.categories, self.full_map, ap)
+        self.per_class_ap = {k[len(H.CATEGORY_KEY):]: v for k, v in results.items() if k.startswith(H.CATEGORY_KEY)}
+        if log:
+            _LOG.info(format_json_stats({"mode": self.mode, "map": self.full_map}))
+        return self.full_map
+
+    def log_epoch_stats(self, cur_epoch):
+        """AVAMeter.log_epoch_stats (utils/meters.py:197-213)."""
+        self.finalize_metrics(log=False)
+        stats = {"_type": "{}_epoch".format(self.mode), "cur_epoch": "{}".format(cur_epoch + 1), "mode": self.mode,
+                 "map": self.full_map, "gpu_mem": "{:.2f} GB".format(DeviceTrainMeter._gpu_mem())}
+        _ram_field(stats)
         _LOG.info(format_json_stats(stats))
         return stats

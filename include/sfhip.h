@@ -1001,6 +1001,46 @@ int sf_confusion_update(const float* preds, int ld, const long* labels, int N, i
                         long* refused, void* stream);
 int sf_class_report(const long* conf, const long* hits, int K, double* out, double* per_class, void* stream);
 
+/* ---- detection evaluation (csrc/ava_eval.hip): the AVA frame-mAP at IoU 0.5 as utils/ava_eval_helper.py and the
+ * PascalDetectionEvaluator of utils/ava_evaluation/ define it, from device tensors.  No entry point synchronises or
+ * reads anything back; every buffer is the caller's.  tests/_ava_ref.py restates the rules below in numpy.
+ * Detections (ava_eval_helper.py:249-285): row i of preds fp32 [K][C] belongs to image (video, second) =
+ *   rint(metadata[i][0..1]) and is, for every class column j with whitelist[j] != 0, one detection with score
+ *   preds[i][j] and box boxes[i][1..4] = x1, y1, x2, y2 (boxes[i][0] is the batch index).  Rows of one image need not
+ *   be contiguous; the order of an image's detections is the row order.
+ * Ground truth, built on the host once: gt_box fp64 [G][4] (x1, y1, x2, y2), gt_cls int32 [G] (class COLUMN = id - 1),
+ *   gt_off int32 [I + 1] (rows of image m are gt_off[m] .. gt_off[m + 1] - 1, grouped by class, CSV order within a
+ *   class), lut int32 [V][S] ((video, second) -> image id, -1: not in the ground truth, -2: excluded; a second outside
+ *   [0, S) is -1), whitelist uint8 [C], num_gt int32 [C] (ground-truth rows per class over the non-excluded images,
+ *   whether or not they have detections).
+ * sf_ava_match: a fill of `first` and TWO launches.  valid uint8 [K] = 1 for a row that is evaluated, 0 for a dropped
+ *   one (excluded image; x1 >= x2 or y1 >= y2 or a NaN coordinate: _remove_invalid_boxes), 2 for a video index outside
+ *   [0, V) or non-finite metadata.  tp uint8 [K][C] = 1 iff (row, class) is a true positive
+ *   (per_image_evaluation.py:331-345): g* = the first maximum of the IoU over the image's ground-truth rows of the
+ *   class, IoU(g*) >= 0.5, and no earlier row of the image has the same g* with IoU >= 0.5.  Launch 1 takes the integer
+ *   minimum of the claiming rows per ground-truth box, launch 2 compares: the reference's sequential rule without an
+ *   assumption on row order, and the same bits run to run.  IoU is np_box_ops.iou in fp64, every operation rounded on
+ *   its own (no fused multiply-add).  An image without ground truth has false positives only.
+ * sf_ava_ap: THREE launches, no sort (metrics.py:60-125, object_detection_evaluation.py:777-815).  Per class with
+ *   num_gt > 0: AP = (1 / num_gt) sum over its true positives of the largest cumTP / position at or after it in
+ *   descending score order; equal scores are ordered by DESCENDING row index (numpy's argsort leaves that open).
+ *   Integer ranks, exact int64 fraction compares, one fp64 division per true positive, fixed-order fp64 sums.
+ *   out fp64 [4] = {mean AP over the classes with num_gt > 0 (NaN when there is none, as np.nanmean), the number of
+ *   those classes, the number of refused scores (NaN or infinite, of evaluated detections), the number of rows with
+ *   valid == 2 — the caller must not use out[0] unless both are 0}.  ap: NULL, or fp64 [C], -1 for a class left out.
+ *   O(K) comparisons per true positive.
+ * ws: sf_ava_ws_bytes(K, C, G) bytes, shared by both calls (host-only query; 0 for sizes out of range: K <= 0, C <= 0,
+ *   G < 0, K C >= 2^31, K above 16 776 960), on 8 bytes as gt_box, out and ap (SF_EALIGN otherwise).
+ *   SF_EINVAL, nothing enqueued: a null pointer (ap excepted; gt_box / gt_cls when G == 0), a size out of range,
+ *   ldb < 5, ldm < 2, ld < C, I < 0, V <= 0, S <= 0, V S >= 2^31. */
+long sf_ava_ws_bytes(int K, int C, int G);
+int sf_ava_match(const float* boxes, int ldb, const float* metadata, int ldm, int K, int C, const double* gt_box,
+                 const int* gt_cls, const int* gt_off, int G, int I, const int* lut, int V, int S,
+                 const unsigned char* whitelist, void* ws, unsigned char* tp, unsigned char* valid, void* stream);
+int sf_ava_ap(const float* preds, int ld, const unsigned char* tp, const unsigned char* valid, int K, int C,
+              const unsigned char* whitelist, const int* num_gt, int G, void* ws, double* out, double* ap,
+              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
