@@ -376,6 +376,118 @@ bool clip_batch_args_ok(const long* table_host, const long* table, int B, int n_
   if (*plane > 0x7fffffffL / 4) return false;
   return batch_table_ok(table_host, B, n_fast, n_slow, crop);
 }
+// ---- all B clips of one DETECTION batch (AVA, `AVA.IMG_PROC_BACKEND == "pytorch"`), both pathways, in ONE launch
+// (datasets/ava_dataset.py:233-338 per sample; datasets/loader.py:18-52 collates).  The grid, the table idea, the Slow
+// search and the one-owner stores are clip_batch_kernel's; the pixel arithmetic is NOT sample_rgb's, because the AVA
+// loader orders it differently: u / 255 per tap, resample the unnormalised image, crop and flip, add the PCA-lighting
+// offset (transform.py:636-663), then (. - mean) / std (:666-688), and only then BGR -> RGB.  The output window is
+// win_h x win_w (the `test` split takes no crop: the window is the whole scaled frame and need not be square).
+constexpr int DET_ROW = 12;  // clip address, T, H, W, new_h, new_w, y0, x0, flip, three lighting offsets (float32 bits)
+
+struct DetGeo {
+  const unsigned char* clip;
+  int T, H, W, new_h, new_w, y0, x0, flip, ok;
+  float off[3];
+};
+
+// One row's check, shared by the host entry and the kernel, as batch_row_ok with a rectangular window.
+__host__ __device__ __forceinline__ bool det_row_ok(const long* r, int win_h, int win_w) {
+  const long lim = 0x7fffffffL;
+  return r[0] != 0 && r[1] > 0 && r[1] <= lim && r[2] > 0 && r[2] <= lim && r[3] > 0 && r[3] <= lim && r[4] > 0 &&
+         r[4] <= lim && r[5] > 0 && r[5] <= lim && r[6] >= 0 && r[6] <= lim && r[7] >= 0 && r[7] <= lim &&
+         r[6] + win_h <= r[4] && r[7] + win_w <= r[5];
+}
+
+__device__ __forceinline__ DetGeo det_row(const long* __restrict__ tab, int b, int win_h, int win_w) {
+  const long* r = tab + (long)b * DET_ROW;
+  DetGeo g;
+  g.clip = (const unsigned char*)(const __attribute__((address_space(1))) unsigned char*)(unsigned long)r[0];
+  g.T = (int)r[1]; g.H = (int)r[2]; g.W = (int)r[3];
+  g.new_h = (int)r[4]; g.new_w = (int)r[5]; g.y0 = (int)r[6]; g.x0 = (int)r[7];
+  g.flip = r[8] != 0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) g.off[c] = __uint_as_float((unsigned)r[9 + c]);
+  g.ok = det_row_ok(r, win_h, win_w);
+  return g;
+}
+
+__device__ __forceinline__ float unit1(unsigned char u) { return __fdiv_rn((float)u, 255.f); }  // imgs / 255.0 (:247-248)
+
+// The value of the scaled, lit and normalised frame at (ys, xs), three channels in source (BGR) order; mean, std and
+// the offsets are indexed in that order too.
+__device__ __forceinline__ void sample_det(const unsigned char* __restrict__ fr, int H, int W, int new_h, int new_w,
+                                           int ys, int xs, const NormArgs& nm, const float off[3], float v[3]) {
+  float r[3];
+  if (new_h == H && new_w == W) {
+    const unsigned char* p = fr + ((long)ys * W + xs) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) r[c] = unit1(p[c]);
+  } else {
+    int ya, yb, xa, xb;
+    float ly0, ly1, lx0, lx1;
+    src_index((float)H / (float)new_h, ys, H, &ya, &yb, &ly0, &ly1);
+    src_index((float)W / (float)new_w, xs, W, &xa, &xb, &lx0, &lx1);
+    const unsigned char* p00 = fr + ((long)ya * W + xa) * 3;
+    const unsigned char* p01 = fr + ((long)ya * W + xb) * 3;
+    const unsigned char* p10 = fr + ((long)yb * W + xa) * 3;
+    const unsigned char* p11 = fr + ((long)yb * W + xb) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      r[c] = ly0 * (lx0 * unit1(p00[c]) + lx1 * unit1(p01[c])) + ly1 * (lx0 * unit1(p10[c]) + lx1 * unit1(p11[c]));
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = __fdiv_rn((r[c] + off[c]) - nm.m[c], nm.s[c]);
+}
+
+__global__ void clip_batch_det_kernel(const long* __restrict__ tab, const long* __restrict__ frame_idx,
+                                      const long* __restrict__ slow_idx, int n_fast, int n_slow, int win_h, int win_w,
+                                      int reverse, NormArgs nm, float* __restrict__ fast, float* __restrict__ slow, int ph,
+                                      int pw, int Wp, int plane) {
+  const int p = blockIdx.x * TPB + threadIdx.x;
+  if (p >= plane) return;
+  const int f = blockIdx.y, b = blockIdx.z;
+  const DetGeo g = det_row(tab, b, win_h, win_w);
+  const int yp = p / Wp, xp = p - yp * Wp;
+  f32x4 o = {0.f, 0.f, 0.f, 0.f};
+  const int yy = yp - ph, xx = xp - pw;
+  if (g.ok && yy >= 0 && yy < win_h && xx >= 0 && xx < win_w) {
+    const long ft = frame_idx[(long)b * n_fast + f];
+    const int t = ft < 0 ? 0 : (ft > g.T - 1 ? g.T - 1 : (int)ft);  // clamped into [0, T_i)
+    const int ys = g.y0 + yy;
+    const int xs = g.x0 + (g.flip ? win_w - 1 - xx : xx);  // flip is applied after the crop
+    float c[3];
+    sample_det(g.clip + (long)t * g.H * g.W * 3, g.H, g.W, g.new_h, g.new_w, ys, xs, nm, g.off, c);
+    if (reverse) {  // AVA.BGR False: imgs[:, [2, 1, 0]] (:329-332)
+      o[0] = c[2]; o[1] = c[1]; o[2] = c[0];
+    } else {
+      o[0] = c[0]; o[1] = c[1]; o[2] = c[2];
+    }
+  }
+  *reinterpret_cast<f32x4*>(fast + (((long)b * n_fast + f) * plane + p) * 4) = o;
+  for (int j = 0; j < n_slow; ++j)  // n_slow <= n_fast / alpha entries, wave-uniform
+    if (slow_idx[j] == f) *reinterpret_cast<f32x4*>(slow + (((long)b * n_slow + j) * plane + p) * 4) = o;
+}
+
+// Host-side check of the detection table's host copy: rows [B][12], then frame indices [B][n_fast], then n_slow Slow
+// positions.  A lighting offset must be a finite float32.
+bool det_table_ok(const long* tab, int B, int n_fast, int n_slow, int win_h, int win_w) {
+  for (int b = 0; b < B; ++b) {
+    const long* r = tab + (long)b * DET_ROW;
+    if (!det_row_ok(r, win_h, win_w)) return false;
+    for (int c = 0; c < 3; ++c)
+      if (r[9 + c] < 0 || r[9 + c] > 0xffffffffL || ((unsigned)r[9 + c] & 0x7f800000u) == 0x7f800000u) return false;
+  }
+  const long* fi = tab + (long)B * DET_ROW;
+  for (int b = 0; b < B; ++b) {
+    const long T = tab[(long)b * DET_ROW + 1];
+    for (int f = 0; f < n_fast; ++f)
+      if (fi[(long)b * n_fast + f] < 0 || fi[(long)b * n_fast + f] >= T) return false;
+  }
+  const long* si = fi + (long)B * n_fast;
+  for (int j = 0; j < n_slow; ++j)
+    if (si[j] < 0 || si[j] >= n_fast || (j > 0 && si[j] <= si[j - 1])) return false;  // distinct: one owner per Slow frame
+  return true;
+}
 }  // namespace
 
 extern "C" int sf_clip_prologue(const unsigned char* clip, int T, int H, int W, int new_h, int new_w, int y0, int x0,
@@ -494,6 +606,31 @@ extern "C" int sf_clip_batch_gray(const long* table_host, const long* table, int
                        (hipStream_t)stream, table, frame_idx, slow_idx, n_fast, n_slow, crop, mean, stdv, fast, slow, ph,
                        pw, Wp, (int)plane);
   }
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_clip_batch_det(const long* table_host, const long* table, int B, int n_fast, int n_slow, int win_h,
+                                 int win_w, int reverse, const float* mean3, const float* std3, float* fast,
+                                 float* slow, int ph, int pw, int Wp, void* stream) {
+  if (!table_host || !table || !fast || !mean3 || !std3 || B <= 0 || n_fast <= 0 || win_h <= 0 || win_w <= 0 || ph < 0 ||
+      pw < 0)
+    return SF_EINVAL;
+  if (n_slow < 0 || n_slow > n_fast || (slow == nullptr) != (n_slow == 0)) return SF_EINVAL;
+  if (B > 65535 || n_fast > 65535 || (long)Wp < (long)win_w + 2L * pw) return SF_EINVAL;
+  const long plane = ((long)win_h + 2L * ph) * Wp;
+  if (plane > 0x7fffffffL / 4) return SF_EINVAL;
+  if (!det_table_ok(table_host, B, n_fast, n_slow, win_h, win_w)) return SF_EINVAL;
+  if (!sf_aligned16(fast) || !sf_aligned16(slow)) return SF_EINVAL;
+  NormArgs nm;
+  for (int c = 0; c < 3; ++c) {
+    nm.m[c] = mean3[c];   // HOST pointers: three floats each, in source (BGR) order
+    nm.s[c] = std3[c];
+  }
+  const long* frame_idx = table + (long)B * DET_ROW;
+  hipLaunchKernelGGL(clip_batch_det_kernel, dim3(sf_cdiv(plane, TPB), n_fast, B), dim3(TPB), 0, (hipStream_t)stream,
+                     table, frame_idx, frame_idx + (long)B * n_fast, n_fast, n_slow, win_h, win_w, reverse, nm, fast, slow,
+                     ph, pw, Wp, (int)plane);
   SF_CHECK_LAUNCH();
   return SF_OK;
 }

@@ -69,6 +69,7 @@ _SIGNATURES = {
     "sf_clip_views_gray": (_ci, [_vp, _ci, _ci, _ci, _vp, _vp] + [_ci] * 4 + [_cf, _cf, _vp, _vp, _ci, _ci, _ci, _vp]),
     "sf_clip_batch": (_ci, [_vp, _vp] + [_ci] * 5 + [_vp] * 4 + [_ci, _ci, _ci, _vp]),
     "sf_clip_batch_gray": (_ci, [_vp, _vp] + [_ci] * 4 + [_cf, _cf, _vp, _vp, _ci, _ci, _ci, _vp]),
+    "sf_clip_batch_det": (_ci, [_vp, _vp] + [_ci] * 6 + [_vp] * 4 + [_ci, _ci, _ci, _vp]),
     "sf_ensemble_update": (_ci, [_vp] * 4 + [_pi] * 3 + [_ci] * 4 + [_vp]),
     "sf_ensemble_update_ml": (_ci, [_vp] * 3 + [_ci, _vp, _vp, _pi, _pi] + [_ci] * 4 + [_vp]),
     "sf_ncthw1_pack": (_ci, [_vp, _vp] + [_ci] * 7 + [_vp]),
@@ -469,6 +470,33 @@ def clip_batch(table_host, table, n_slow, crop, mean, std, fast, slow=None, gray
         m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
         s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
         _call("sf_clip_batch", *head, 1 if reverse else 0, ctypes.cast(m3, _vp), ctypes.cast(s3, _vp), *tail)
+    return fast, slow
+
+
+def clip_batch_det(table_host, table, n_slow, win_hw, mean, std, fast, slow=None, reverse=False, ph=0, pw=0):
+    """All B clips of one detection (AVA) batch — B separate uint8 BGR device spans, named by address in the table — in
+    one launch -> fast [B, n_fast, win_h+2ph, Wp, 4] and slow [B, n_slow, ...] (None with n_slow == 0: single pathway),
+    the PackedClip layout.  The arithmetic is the AVA loader's (resample u / 255, + lighting offset, normalise, then
+    BGR -> RGB with `reverse`), not clip_batch's.  table_host: the int64 CPU table (B rows address, T, H, W, new_h, new_w,
+    y0, x0, flip, three lighting offsets as float32 bits; B * n_fast frame indices; n_slow Slow positions; a tail the
+    kernel does not read may follow), table: its device copy.  win_hw: the output window (win_h, win_w), shared by the
+    batch.  mean / std: three values in source (BGR) order.  The caller keeps the spans alive until the launch has run."""
+    _require_gpu(fast, "clip_batch_det")
+    if not table.is_cuda or table_host.is_cuda:
+        raise SfhipError("clip_batch_det: the batch table's copy lives on the GPU, table_host on the host")
+    win_h, win_w = int(win_hw[0]), int(win_hw[1])
+    assert fast.is_contiguous() and fast.dim() == 5 and fast.shape[4] == 4 and fast.shape[2] == win_h + 2 * ph
+    B, n_fast = fast.shape[:2]
+    assert table_host.dtype == torch.int64 and table.dtype == torch.int64 and table_host.is_contiguous()
+    assert table.is_contiguous() and table_host.numel() == table.numel() >= B * (12 + n_fast) + n_slow
+    if slow is not None:
+        _require_gpu(slow, "clip_batch_det")
+        assert slow.is_contiguous() and tuple(slow.shape) == (B, n_slow) + tuple(fast.shape[2:])
+    assert len(mean) == 3 and len(std) == 3, "the AVA path is three-channel"
+    m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
+    _call("sf_clip_batch_det", _ptr(table_host), _ptr(table), B, n_fast, int(n_slow), win_h, win_w, 1 if reverse else 0,
+          ctypes.cast(m3, _vp), ctypes.cast(s3, _vp), _ptr(fast), _ptr(slow), ph, pw, fast.shape[3])
     return fast, slow
 
 

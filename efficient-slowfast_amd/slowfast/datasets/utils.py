@@ -7,7 +7,10 @@ normalise (`tensor_normalize`, :298-315), bilinear short-side scale, crop, flip,
 kernel per pathway (`sf_clip_prologue`) that writes the stems' input layout directly, so the decoded clip crosses
 PCIe as uint8 once instead of as two float NCTHW tensors.  Whole batches go in one launch for both pathways: the
 views of one test video (`test_view_params` -> `gpu_test_views` -> `sf_clip_views`) and the clips of one training
-batch, multigrid's short and long cycles included (`train_clip_params` -> `gpu_train_batch` -> `sf_clip_batch`)."""
+batch, multigrid's short and long cycles included (`train_clip_params` -> `gpu_train_batch` -> `sf_clip_batch`).
+The detection (AVA) loader's preprocessing (datasets/ava_dataset.py:233-338, the "pytorch" backend) orders the
+arithmetic differently and carries boxes: `det_clip_params` / `det_boxes` -> `gpu_detection_batch` ->
+`sf_clip_batch_det`, again one upload and one launch per batch."""
 from slowfast._overlay import chain_module as _chain_module
 
 _chain_module(globals())  # the reference's namesake (when importable) supplies every name not defined below
@@ -280,6 +283,175 @@ def gpu_train_batch(videos, samples, mean, std, alpha, reverse_input_channel=Fal
                      ph=ph, pw=pw)
     out = [sfhip.PackedClip(fast, C, crop, crop, ph, pw)]
     return out if slow is None else [sfhip.PackedClip(slow, C, crop, crop, ph, pw)] + out
+
+
+# ---- the detection (AVA) input step: datasets/ava_dataset.py:233-338 with AVA.IMG_PROC_BACKEND "pytorch", and the box
+# collation of datasets/loader.py:18-52.  The host keeps the draws and the boxes; pixels go through sf_clip_batch_det.
+DetParams = collections.namedtuple("DetParams", "new_h new_w y x flip win_h win_w crop offsets")
+DET_ROW = 12  # clip address, T, H, W, new_h, new_w, y0, x0, flip, three lighting offsets (float32 bit patterns)
+
+
+def det_sequence(center_idx, half_len, sample_rate, num_frames):
+    """datasets/utils.py:50-70 (get_sequence): the frames of the clip around `center_idx`, clamped into the video."""
+    return [min(max(i, 0), num_frames - 1) for i in range(center_idx - half_len, center_idx + half_len, sample_rate)]
+
+
+def det_clip_params(cfg, split, height, width):
+    """The decisions of `Ava._images_and_boxes_preprocessing` for one clip of height x width frames, without touching
+    pixels -> DetParams.  `offsets` are the PCA-lighting offsets (float32 values) in the order they are added to source
+    channels 0..2; (win_h, win_w) is the output window and `crop` the size the boxes are finally clipped to.
+    numpy's global RNG, the reference's order: train — scale, crop y, crop x (each only when the extent exceeds the
+    size), flip (always drawn; this backend ignores DATA.RANDOM_FLIP), then normal(0, 0.1, (1, 3)) with
+    AVA.TRAIN_USE_COLOR_AUGMENTATION; val / test — one scale draw and, with AVA.TEST_FORCE_FLIP, one flip draw."""
+    if cfg.AVA.IMG_PROC_BACKEND != "pytorch":
+        raise NotImplementedError(
+            "AVA.IMG_PROC_BACKEND %r resamples with OpenCV, which the device input step does not reproduce: select "
+            "AVA.IMG_PROC_BACKEND \"pytorch\"" % (cfg.AVA.IMG_PROC_BACKEND,))
+    if split not in ("train", "val", "test"):
+        raise NotImplementedError("{} split not supported yet!".format(split))
+    offsets = (0.0, 0.0, 0.0)
+    if split == "train":
+        lighting = cfg.AVA.TRAIN_USE_COLOR_AUGMENTATION
+        if lighting and not cfg.AVA.TRAIN_PCA_JITTER_ONLY:
+            raise NotImplementedError(
+                "AVA.TRAIN_PCA_JITTER_ONLY False: in the reference's pytorch backend transform.grayscale aliases its "
+                "input, so contrast and saturation jitter collapse the clip to one grey image; that is not reproduced "
+                "here — keep AVA.TRAIN_PCA_JITTER_ONLY True")
+        size = cfg.DATA.TRAIN_CROP_SIZE
+        nh, nw = _short_side(height, width, cfg.DATA.TRAIN_JITTER_SCALES[0], cfg.DATA.TRAIN_JITTER_SCALES[1], False)
+        if nh == size and nw == size:
+            raise ValueError("the scaled frame is already %d x %d: the reference's random_crop returns a bare tensor "
+                             "there and its caller fails to unpack it" % (size, size))
+        if nh < size or nw < size:
+            raise ValueError("the scaled frame %d x %d is smaller than the %d x %d crop" % (nh, nw, size, size))
+        y = int(np.random.randint(0, nh - size)) if nh > size else 0  # transform.py:376-383
+        x = int(np.random.randint(0, nw - size)) if nw > size else 0
+        flip = bool(np.random.uniform() < 0.5)                        # transform.py:415
+        if lighting:                                                  # transform.py:651-661
+            alpha = np.random.normal(0, 0.1, size=(1, 3))
+            eig_vec = np.array(cfg.AVA.TRAIN_PCA_EIGVEC).astype(np.float32)
+            eig_val = np.reshape(np.array(cfg.AVA.TRAIN_PCA_EIGVAL).astype(np.float32), (1, 3))
+            rgb = np.sum(eig_vec * np.repeat(alpha, 3, axis=0) * np.repeat(eig_val, 3, axis=0), axis=1)  # float64
+            offsets = tuple(float(np.float32(rgb[2 - c])) for c in range(3))  # a float32 tensor + a Python scalar
+        return DetParams(nh, nw, y, x, flip, size, size, size, offsets)
+    size = cfg.DATA.TEST_CROP_SIZE
+    nh, nw = _short_side(height, width, size, size, False)  # one draw, as the reference spends it
+    if split == "val":
+        y = int(math.ceil((nh - size) / 2))  # transform.py:447-448 (uniform_crop, spatial_idx 1)
+        x = int(math.ceil((nw - size) / 2))
+        win_h = win_w = size
+    else:
+        y, x, win_h, win_w = 0, 0, nh, nw  # no crop: the window is the whole scaled frame
+    flip = bool(np.random.uniform() < 1) if cfg.AVA.TEST_FORCE_FLIP else False
+    return DetParams(nh, nw, y, x, flip, win_h, win_w, size, offsets)
+
+
+def _clip_boxes(boxes, height, width):
+    """transform.py:471-490 (clip_boxes_to_image)."""
+    out = boxes.copy()
+    out[:, [0, 2]] = np.minimum(width - 1.0, np.maximum(0.0, boxes[:, [0, 2]]))
+    out[:, [1, 3]] = np.minimum(height - 1.0, np.maximum(0.0, boxes[:, [1, 3]]))
+    return out
+
+
+def det_boxes(boxes01, height, width, params):
+    """The box pipeline of `Ava._images_and_boxes_preprocessing` in numpy float64: [k, 4] boxes (x1, y1, x2, y2) in
+    [0, 1] of a height x width frame -> pixels of the output window, through the decisions `params` holds.
+    The final clip is to (crop, crop) in every split — in `test`, where the frame is wider, too: the reference's
+    behaviour."""
+    p = params
+    boxes = np.array(boxes01, dtype=np.float64, copy=True).reshape(-1, 4)
+    boxes[:, [0, 2]] *= width
+    boxes[:, [1, 3]] *= height
+    boxes = _clip_boxes(boxes, height, width)
+    if (p.new_h, p.new_w) != (height, width):  # transform.py:320-327: one factor for both axes
+        if width < height:
+            boxes = boxes * float(p.new_h) / height
+        else:
+            boxes = boxes * float(p.new_w) / width
+    boxes[:, [0, 2]] = boxes[:, [0, 2]] - p.x  # transform.py:352-354 (crop_boxes)
+    boxes[:, [1, 3]] = boxes[:, [1, 3]] - p.y
+    if p.flip:                                 # transform.py:418-420
+        boxes[:, [0, 2]] = p.win_w - boxes[:, [2, 0]] - 1
+    return _clip_boxes(boxes, p.crop, p.crop)
+
+
+def _f32_bits(v):
+    return int(np.array(v, dtype=np.float32).view(np.uint32))
+
+
+def det_table(videos, samples, n_slow_idx):
+    """The int64 host table sf_clip_batch_det reads: B rows (address of videos[b], T_b, H_b, W_b, new_h, new_w, y0, x0,
+    flip, three lighting offsets as float32 bit patterns), the B * n_fast frame indices (clip-major), then the Slow
+    pathway's positions among the Fast frames (`n_slow_idx`: a tensor, possibly empty)."""
+    rows = torch.tensor([[v.data_ptr(), v.shape[0], v.shape[1], v.shape[2], p.new_h, p.new_w, p.y, p.x, int(p.flip)] +
+                         [_f32_bits(o) for o in p.offsets] for v, (_, p) in zip(videos, samples)], dtype=torch.int64)
+    frames = torch.stack([torch.as_tensor(f) for f, _ in samples]).to(torch.int64)
+    return torch.cat([rows.flatten(), frames.flatten(), n_slow_idx.to(torch.int64).flatten()]).contiguous()
+
+
+def collate_boxes(boxes_list):
+    """`detection_collate` for "boxes" / "ori_boxes" (datasets/loader.py:35-44): [K, 5] float32 — the sample's index in
+    the batch, then the box — from B arrays [k_i, 4], on the host."""
+    rows = [np.concatenate([np.full((len(b), 1), float(i)), np.asarray(b, dtype=np.float64).reshape(-1, 4)], axis=1)
+            for i, b in enumerate(boxes_list)]
+    return torch.tensor(np.concatenate(rows, axis=0)).float()
+
+
+def collate_detection_extras(ori_boxes_list, metadata_list):
+    """(ori_boxes [K, 5] float32, metadata [K, 2] int64) as `detection_collate` gives them (datasets/loader.py:35-48),
+    on the host: what DeviceAVAMeter.update_stats takes beside the predictions, once moved to the GPU."""
+    metadata = torch.tensor([list(m) for md in metadata_list for m in md]).view(-1, 2)
+    return collate_boxes(ori_boxes_list), metadata
+
+
+def gpu_detection_batch(videos, samples, boxes_list, mean, std, alpha, reverse_input_channel=False, pad=(0, 0),
+                        wp=None):
+    """The whole input step of ONE detection batch in one kernel launch (sf_clip_batch_det), boxes included.
+
+    videos:     list of B frame spans, uint8 [T_i, H_i, W_i, 3] device tensors in BGR order, each its own allocation;
+                they stay alive until the launch has run
+    samples:    list of B (frame_indices, DetParams): indices into the span (`det_sequence`, or range(T) for a span that
+                holds exactly the clip) and `det_clip_params`' decisions; one window and one frame count for the batch
+    boxes_list: list of B [k_i, 4] arrays from `det_boxes`
+    mean, std:  DATA.MEAN / DATA.STD, applied in source (BGR) order as the reference does
+    reverse_input_channel: `not AVA.BGR`
+    the rest as `gpu_input_step`.  One table upload, one launch.  Returns ([slow, fast] PackedClips ([clip] with
+    alpha=None), bboxes): bboxes is the [K, 5] float32 device tensor `detection_collate` gives, computed on the host
+    and carried as float32 bit patterns in the tail of the table's upload — a view of the uploaded table."""
+    B = len(videos)
+    assert B == len(samples) == len(boxes_list) and B > 0
+    p0 = samples[0][1]
+    n_fast = len(samples[0][0])
+    for f, p in samples:
+        if (p.win_h, p.win_w) != (p0.win_h, p0.win_w):
+            raise ValueError("the clips of one batch share one output window: got %d x %d and %d x %d" % (
+                p0.win_h, p0.win_w, p.win_h, p.win_w))
+        assert len(f) == n_fast
+    win_h, win_w = p0.win_h, p0.win_w
+    ph, pw = pad
+    wp = win_w + 2 * pw if wp is None else wp
+    dev = videos[0].device
+    for v in videos:
+        if not v.is_cuda or v.device != dev:
+            raise sfhip.SfhipError("gpu_detection_batch: every frame span lives on one GPU, got %s" % v.device)
+        assert v.dtype == torch.uint8 and v.dim() == 4 and v.shape[3] == 3 and v.is_contiguous()
+    slow_idx = slow_frame_indices(n_fast, alpha) if alpha is not None else torch.zeros(0, dtype=torch.long)
+    n_slow = slow_idx.numel()
+    head = det_table(videos, samples, slow_idx)
+    bboxes = collate_boxes(boxes_list)  # float32 [K, 5]
+    K = bboxes.shape[0]
+    tail = torch.zeros((5 * K + 1) // 2 * 2, dtype=torch.float32)
+    tail[:5 * K] = bboxes.flatten()
+    table_host = torch.cat([head, tail.view(torch.int64)]).contiguous()
+    table = table_host.to(dev)  # the one upload: rows, frame indices, Slow positions and the boxes together
+    fast = torch.empty((B, n_fast, win_h + 2 * ph, wp, 4), dtype=torch.float32, device=dev)
+    slow = torch.empty((B, n_slow, win_h + 2 * ph, wp, 4), dtype=torch.float32, device=dev) if n_slow else None
+    sfhip.clip_batch_det(table_host, table, n_slow, (win_h, win_w), mean, std, fast, slow,
+                         reverse=reverse_input_channel, ph=ph, pw=pw)
+    out = [sfhip.PackedClip(fast, 3, win_h, win_w, ph, pw)]
+    out = out if slow is None else [sfhip.PackedClip(slow, 3, win_h, win_w, ph, pw)] + out
+    return out, table[head.numel():].view(torch.float32)[:5 * K].view(K, 5)
 
 
 def stem_input_geometry(model, crop):

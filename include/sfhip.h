@@ -663,6 +663,36 @@ int sf_clip_batch(const long* table_host, const long* table, int B, int n_fast, 
 int sf_clip_batch_gray(const long* table_host, const long* table, int B, int n_fast, int n_slow, int crop, float mean,
                        float stdv, float* fast, float* slow, int ph, int pw, int Wp, void* stream);
 
+/* ---- detection input step, one launch per batch (AVA with AVA.IMG_PROC_BACKEND "pytorch":
+ * datasets/ava_dataset.py:233-338 _images_and_boxes_preprocessing and the transform.py functions it calls — :283-337
+ * random_short_side_scale_jitter, :359-392 random_crop, :395-422 horizontal_flip, :425-468 uniform_crop, :636-663
+ * lighting_jitter, :666-688 color_normalization; datasets/utils.py:73-112 pack_pathway_output).
+ * sf_clip_batch_det: ALL B clips of ONE detection batch, for both pathways in one launch.  The B frame spans are
+ *   separate device allocations, uint8 [T_i,H_i,W_i,3] in BGR order.  The batch table is B rows (clip device address,
+ *   T_i, H_i, W_i, new_h, new_w, y0, x0, flip, and the three PCA-lighting offsets as float32 bit patterns in the order
+ *   they are added to source channels 0..2), then B * n_fast frame indices (clip-major), then the n_slow Fast-frame
+ *   positions the Slow pathway takes (strictly increasing), all int64; anything behind that is not read.  `table` is
+ *   the device copy and `table_host` the host array it was uploaded from: the host copy is checked before anything is
+ *   launched, the kernel reads the device copy and re-checks its row — a device row that fails writes zeros for that
+ *   clip, and a device frame index is clamped into [0, T_i).
+ *   The arithmetic is the AVA loader's, in its order, in fp32: u / 255 per tap, torch's bilinear resample
+ *   (align_corners=False; none when (new_h, new_w) == (H_i, W_i)), crop at (y0, x0) and flip inside the window,
+ *   + offset[c], (. - mean3[c]) / std3[c] with true divides (mean3 / std3 in source, BGR, order), and with `reverse`
+ *   (AVA.BGR False) the channels are stored 2, 1, 0.  This is not sf_clip_batch's arithmetic, which normalises first.
+ *   The output window is win_h x win_w, shared by the batch; the `test` split takes no crop, so it need not be square.
+ *   fast [B][n_fast][win_h+2ph][Wp][4] and slow [B][n_slow][win_h+2ph][Wp][4]: the stems' layout, borders and the pad
+ *   channel zero.  A frame that goes to both pathways is computed once and stored twice.  slow == NULL with
+ *   n_slow == 0: a single-pathway model.  One owner per output element, 16-byte stores, 64-bit element offsets, no
+ *   atomics.
+ *   SF_EINVAL, nothing launched: sf_clip_batch's list (null pointers, B <= 0, non-positive sizes, a zero clip address,
+ *   a frame index outside [0, T_i), n_slow > n_fast, Slow positions outside [0, n_fast) or not increasing, slow given
+ *   without n_slow or the reverse, B or n_fast above 65535, buffers not 16-byte aligned), the window outside the
+ *   scaled frame in either dimension, Wp < win_w + 2 pw, and a lighting offset in the host table that is not a finite
+ *   float32.  mean3 / std3: HOST. */
+int sf_clip_batch_det(const long* table_host, const long* table, int B, int n_fast, int n_slow, int win_h, int win_w,
+                      int reverse, const float* mean3, const float* std3, float* fast, float* slow, int ph, int pw,
+                      int Wp, void* stream);
+
 /* sf_ensemble_update (csrc/ensemble.hip): TestMeter.update_stats (utils/meters.py:283-317) on the device.  preds [B,K],
  *   video_idx int32 [B] (clip id / clips per video), labels int32 [B] or NULL; video_preds [Nv,K], video_labels int32
  *   [Nv], clip_count int32 [Nv] are the meter's accumulators.  mode 0: video_preds[video_idx[b]] += preds[b]; mode 1:
