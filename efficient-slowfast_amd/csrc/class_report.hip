@@ -13,6 +13,8 @@
 //     sum(conf) = N - refused[0] - refused[1],  trace(conf) = sum(hits[:, 0]) = sf_topk_errors' top-1 hits,
 //     sum(hits[:, 1]) = its top-k_hi hits,  row sums of conf = support,  column sums = predicted counts.
 // Only integer adds: the result does not depend on the order of execution.  No float atomics.
+// sf_class_weights turns the same counters into fp32 class weights for the weighted losses of step_tail.hip (balanced or
+// effective-number), in one launch and without a host read.
 #include "common.h"
 #include "stats_row.h"
 
@@ -241,6 +243,53 @@ __global__ __launch_bounds__(REP_TPB) void class_report_kernel(const long* __res
   }
 }
 
+// ---------------------------------------------------------------------------------------------- class weights
+// ONE workgroup.  Support = row sums of conf (a wavefront per row, as above); thread 0 counts the samples S and the
+// classes with support K+ in class order; thread c then makes class c's weight, 0 for a class without support.
+//   balanced:  S / (K+ * support[c]) — ONE fp64 division of exact integers, rounded once to fp32.
+//   effective: e[c] = (1 - beta) / (1 - beta^support[c]) in fp64, times K+ / sum(e) (the sum in class order).
+__global__ __launch_bounds__(REP_TPB) void class_weights_kernel(const long* __restrict__ conf, int K, int scheme,
+                                                                double beta, float* __restrict__ w) {
+  __shared__ long s_sup[REP_KMAX];
+  __shared__ double s_e[REP_KMAX];
+  __shared__ long s_tot[2];  // S, K+
+  __shared__ double s_scale;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int r = wave; r < K; r += REP_WAVES) {
+    const long* row = conf + (long)r * K;
+    long s = 0;
+    for (int j = lane; j < K; j += 64) s += row[j];
+    s = wave_sum_i64(s);
+    if (lane == 0) s_sup[r] = s;
+  }
+  __syncthreads();
+  const int c = threadIdx.x;
+  const long sup = c < K ? s_sup[c] : 0;
+  if (scheme == SF_WEIGHTS_EFFECTIVE && c < K) s_e[c] = sup > 0 ? (1.0 - beta) / (1.0 - pow(beta, (double)sup)) : 0.0;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    long samples = 0, with_support = 0;
+    double se = 0.0;
+    for (int k = 0; k < K; ++k) {
+      samples += s_sup[k] > 0 ? s_sup[k] : 0;
+      with_support += s_sup[k] > 0 ? 1 : 0;
+      if (scheme == SF_WEIGHTS_EFFECTIVE) se += s_e[k];
+    }
+    s_tot[0] = samples;
+    s_tot[1] = with_support;
+    s_scale = se > 0.0 ? (double)with_support / se : 0.0;
+  }
+  __syncthreads();
+  if (c < K) {
+    float v = 0.f;
+    if (sup > 0) {
+      v = scheme == SF_WEIGHTS_EFFECTIVE ? (float)(s_e[c] * s_scale)
+                                         : (float)((double)s_tot[0] / (double)(s_tot[1] * sup));
+    }
+    w[c] = v;
+  }
+}
+
 template <bool VEC>
 int launch_confusion(const float* preds, int ld, const long* labels, int N, int K, int k_hi, u64* conf, u64* hits,
                      u64* refused, hipStream_t s) {
@@ -288,6 +337,21 @@ extern "C" int sf_class_report(const long* conf, const long* hits, int K, double
        reinterpret_cast<uintptr_t>(per_class)) & 7)
     return SF_EALIGN;
   hipLaunchKernelGGL(class_report_kernel, dim3(1), dim3(REP_TPB), 0, (hipStream_t)stream, conf, hits, K, out, per_class);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_class_weights(const long* conf, int K, int scheme, const double* beta, float* w, void* stream) {
+  if (!conf || !w) return SF_EINVAL;
+  if (K <= 0 || K > REP_KMAX) return SF_EINVAL;
+  if (scheme != SF_WEIGHTS_BALANCED && scheme != SF_WEIGHTS_EFFECTIVE) return SF_EINVAL;
+  double b = 0.0;
+  if (scheme == SF_WEIGHTS_EFFECTIVE) {  // beta is read here, on the host, before the launch
+    if (!beta || !(*beta > 0.0 && *beta < 1.0)) return SF_EINVAL;
+    b = *beta;
+  }
+  if ((reinterpret_cast<uintptr_t>(conf) & 7) || (reinterpret_cast<uintptr_t>(w) & 3)) return SF_EALIGN;
+  hipLaunchKernelGGL(class_weights_kernel, dim3(1), dim3(REP_TPB), 0, (hipStream_t)stream, conf, K, scheme, b, w);
   SF_CHECK_LAUNCH();
   return SF_OK;
 }

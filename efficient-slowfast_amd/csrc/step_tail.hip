@@ -1,5 +1,6 @@
 // step_tail.hip — what follows the backward pass in tools/train_net.py:67-157: the loss with its gradient and the
-// meter's top-k counts in one launch (sf_ce_topk; sf_bce for the multi-label and detection losses), torch.optim.SGD over
+// meter's top-k counts in one launch (sf_ce_topk; sf_bce for the multi-label and detection losses; sf_ce_topk_w and
+// sf_bce_w are the same launches with class weights read from device memory), torch.optim.SGD over
 // every parameter of every group in one launch (sf_sgd_step), torch.optim.Adam in two (sf_adam_step: the step counts,
 // then the update).  Nothing here needs the host: the statistics go to a ring in device memory that the meter drains once
 // per LOG_PERIOD, the hyper-parameters are read from device memory (the LR schedule is a 4-byte write a replayed graph
@@ -18,15 +19,40 @@ namespace {
 // lane-strided sweeps (max + rank of the label, sum of exp, gradient).  exp / log / the sums run in fp64: at these sizes
 // that is free and every stored float is the rounded exact value.  Order of every sum is fixed (lane stride, xor
 // butterfly, rows in order per wavefront, wavefronts in order): equal bits run to run, no atomics.
-__global__ __launch_bounds__(CE_TPB) void ce_topk_kernel(const float* __restrict__ logits, int ld,
-                                                         const long* __restrict__ labels, int N, int K, int k_hi,
-                                                         float* __restrict__ dlogits, float* __restrict__ ring,
-                                                         int* __restrict__ counter, int cap,
-                                                         float* __restrict__ loss_out) {
+// WEIGHTED (sf_ce_topk_w): F.cross_entropy(weight = wgt): row r counts wgt[labels[r]] times and the divisor is W, the sum
+// of those weights over the rows with a valid label, instead of N.  W comes first, in the same launch: thread t adds
+// the weights of rows t, t + 1024, ..., xor butterfly, wavefronts in order, one barrier — every thread then holds the
+// same W.  The row's factor is w * (1 / W) and the mean tot * (1 / W): with every weight 1.0f and every label valid
+// these are the unweighted 1 / N and tot * (1 / N) bit for bit.  W == 0 (every present class has weight 0; torch
+// returns NaN), or a W that is not finite: the loss is NaN, the flag 1 and dlogits all zeros.
+__device__ __forceinline__ double ce_weight_total(const long* __restrict__ labels, const float* __restrict__ wgt, int N,
+                                                  int K) {
+  __shared__ double s_w[CE_WAVES];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double ws = 0.0;
+  for (int r = threadIdx.x; r < N; r += CE_TPB) {
+    const long l = labels[r];
+    if (l >= 0 && l < K) ws += (double)wgt[l];
+  }
+  ws = wave_sum(ws);
+  if (lane == 0) s_w[wave] = ws;
+  __syncthreads();
+  double wtot = 0.0;
+  for (int w = 0; w < CE_WAVES; ++w) wtot += s_w[w];
+  return wtot;
+}
+
+template <bool WEIGHTED>
+__device__ __forceinline__ void ce_topk_body(const float* __restrict__ logits, int ld, const long* __restrict__ labels,
+                                             const float* __restrict__ wgt, int N, int K, int k_hi,
+                                             float* __restrict__ dlogits, float* __restrict__ ring,
+                                             int* __restrict__ counter, int cap, float* __restrict__ loss_out) {
   __shared__ double s_loss[CE_WAVES];
   __shared__ int s_cnt[CE_WAVES][4];  // top-1 hits, top-k_hi hits, rows with a non-finite logit, bad labels
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double inv_n = 1.0 / (double)N;
+  const double wtot = WEIGHTED ? ce_weight_total(labels, wgt, N, K) : (double)N;
+  const bool w_ok = !WEIGHTED || (wtot > 0.0 && isfinite(wtot));
+  const double inv_n = 1.0 / wtot;  // WEIGHTED: 1 / W
   double loss = 0.0;
   int hit1 = 0, hitk = 0, nonfinite = 0, bad = 0;
   for (int r = wave; r < N; r += CE_WAVES) {
@@ -35,6 +61,9 @@ __global__ __launch_bounds__(CE_TPB) void ce_topk_kernel(const float* __restrict
     const long l = labels[r];
     const bool ok = l >= 0 && l < K;  // a label outside [0, K): no loss, no gradient, never a read
     const float xl = ok ? x[l] : 0.f;
+    const double wr = (WEIGHTED && ok) ? (double)wgt[l] : 1.0;
+    const double fac = WEIGHTED ? wr * inv_n : inv_n;
+    const bool grad = WEIGHTED ? (ok && w_ok) : ok;
     float m = -INFINITY;
     int rank = 0, nf = 0;
     for (int j = lane; j < K; j += 64) {
@@ -52,10 +81,13 @@ __global__ __launch_bounds__(CE_TPB) void ce_topk_kernel(const float* __restrict
     const double inv_s = 1.0 / s;
     for (int j = lane; j < K; j += 64) {
       const double p = exp((double)x[j] - (double)m) * inv_s;
-      dx[j] = ok ? (float)((p - (j == l ? 1.0 : 0.0)) * inv_n) : 0.f;
+      dx[j] = grad ? (float)((p - (j == l ? 1.0 : 0.0)) * fac) : 0.f;
     }
     if (ok) {
-      loss += log(s) + (double)m - (double)xl;
+      if (WEIGHTED)
+        loss += wr * (log(s) + (double)m - (double)xl);
+      else
+        loss += log(s) + (double)m - (double)xl;
       if (!nf) {  // a row with a NaN or an Inf is wrong for every k
         hit1 += rank < 1;
         hitk += rank < k_hi;
@@ -63,7 +95,8 @@ __global__ __launch_bounds__(CE_TPB) void ce_topk_kernel(const float* __restrict
     } else {
       bad += 1;
     }
-    nonfinite += nf;
+    // WEIGHTED: a row that is left out (torch's ignore_index) is left out whole — what it holds does not reach the flag
+    nonfinite += (WEIGHTED && !ok) ? 0 : nf;
   }
   if (lane == 0) {
     s_loss[wave] = loss;
@@ -81,7 +114,7 @@ __global__ __launch_bounds__(CE_TPB) void ce_topk_kernel(const float* __restrict
 #pragma unroll
       for (int i = 0; i < 4; ++i) c[i] += s_cnt[w][i];
     }
-    const float mean = (float)(tot * inv_n);
+    const float mean = (!WEIGHTED || w_ok) ? (float)(tot * inv_n) : NAN;
     const float flag = (c[2] != 0 || !isfinite(mean)) ? 1.f : 0.f;
     const int step = counter[0];
     const int slot = ((step % cap) + cap) % cap;
@@ -101,15 +134,38 @@ __global__ __launch_bounds__(CE_TPB) void ce_topk_kernel(const float* __restrict
   }
 }
 
+__global__ __launch_bounds__(CE_TPB) void ce_topk_kernel(const float* __restrict__ logits, int ld,
+                                                         const long* __restrict__ labels, int N, int K, int k_hi,
+                                                         float* __restrict__ dlogits, float* __restrict__ ring,
+                                                         int* __restrict__ counter, int cap,
+                                                         float* __restrict__ loss_out) {
+  ce_topk_body<false>(logits, ld, labels, nullptr, N, K, k_hi, dlogits, ring, counter, cap, loss_out);
+}
+
+__global__ __launch_bounds__(CE_TPB) void ce_topk_w_kernel(const float* __restrict__ logits, int ld,
+                                                           const long* __restrict__ labels,
+                                                           const float* __restrict__ wgt, int N, int K, int k_hi,
+                                                           float* __restrict__ dlogits, float* __restrict__ ring,
+                                                           int* __restrict__ counter, int cap,
+                                                           float* __restrict__ loss_out) {
+  ce_topk_body<true>(logits, ld, labels, wgt, N, K, k_hi, dlogits, ring, counter, cap, loss_out);
+}
+
 // ---------------------------------------------------------------------------------------------- BCE
 // nn.BCELoss / nn.BCEWithLogitsLoss (mean) with the gradient, a ring row and the flag.  ONE workgroup as above: the real
 // sizes are boxes x 80 (AVA) or clips x 157 (Charades), ~1e4 elements.  Thread i owns elements i, i + 1024, ... of the
 // flattened [N][K]; log / exp / log1p and the sums in fp64, fixed order (thread stride, xor butterfly, wavefronts in
 // order): equal bits run to run, no atomics.
-__global__ __launch_bounds__(CE_TPB) void bce_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ y,
-                                                     int ldy, int N, int K, int from_logits, float* __restrict__ dx,
-                                                     float* __restrict__ ring, int* __restrict__ counter, int cap,
-                                                     float* __restrict__ loss_out) {
+// WEIGHTED (sf_bce_w): nn.BCELoss(weight = wgt[K]) / nn.BCEWithLogitsLoss(weight = wgt[K], pos_weight = pos[K]); either
+// vector may be null (= all ones).  Element (r, j) counts wgt[j] times and the divisor stays N * K, as in torch.  With
+// logits and p = pos[j]:  loss = (1 - y) x + (1 + (p - 1) y) softplus(-x), written as the unweighted loss plus
+// (p - 1) y softplus(-x), and the gradient as (sigmoid - y) + (p - 1) y (sigmoid - 1): at p = 1 the added terms are
+// exact zeros, and a weight of 1 is a multiply by one — all-ones vectors give sf_bce's bits.
+template <bool WEIGHTED>
+__device__ __forceinline__ void bce_body(const float* __restrict__ x, int ldx, const float* __restrict__ y, int ldy,
+                                         const float* __restrict__ wgt, const float* __restrict__ pos, int N, int K,
+                                         int from_logits, float* __restrict__ dx, float* __restrict__ ring,
+                                         int* __restrict__ counter, int cap, float* __restrict__ loss_out) {
   __shared__ double s_loss[CE_WAVES];
   __shared__ int s_cnt[CE_WAVES][2];  // elements with a NaN / Inf input, elements outside [0, 1]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -123,17 +179,30 @@ __global__ __launch_bounds__(CE_TPB) void bce_kernel(const float* __restrict__ x
     const float xf = x[r * ldx + j], yf = y[r * ldy + j];
     const double xv = (double)xf, yv = (double)yf;
     const bool nf = !isfinite(xf) || !isfinite(yf);
+    const double wj = (WEIGHTED && wgt != nullptr) ? (double)wgt[j] : 1.0;
+    const double winv = WEIGHTED ? wj * inv : inv;
     double l, d;
     if (from_logits) {
       const double t = exp(-fabs(xv));  // in (0, 1]: no overflow at any x; log1p keeps it where 1 + t == 1
       l = fmax(xv, 0.0) - xv * yv + log1p(t);
-      d = ((xv >= 0.0 ? 1.0 / (1.0 + t) : t / (1.0 + t)) - yv) * inv;
+      if (!WEIGHTED) {
+        d = ((xv >= 0.0 ? 1.0 / (1.0 + t) : t / (1.0 + t)) - yv) * inv;
+      } else {
+        const double sig = xv >= 0.0 ? 1.0 / (1.0 + t) : t / (1.0 + t);
+        d = sig - yv;
+        if (pos != nullptr) {
+          const double py = ((double)pos[j] - 1.0) * yv;
+          l += py * (fmax(-xv, 0.0) + log1p(t));
+          d += py * (sig - 1.0);
+        }
+        d *= winv;
+      }
     } else if (nf || (xf >= 0.f && xf <= 1.f && yf >= 0.f && yf <= 1.f)) {
       // torch's binary_cross_entropy: both logs clamped at -100, the gradient's denominator at 1e-12
       l = -(yv * fmax(log(xv), -100.0) + (1.0 - yv) * fmax(log(1.0 - xv), -100.0));
       double den = xv * (1.0 - xv);
       den = den < 1e-12 ? 1e-12 : den;  // (a NaN stays one)
-      d = (xv - yv) / den * inv;
+      d = (xv - yv) / den * winv;
     } else {  // where torch asserts on the device: no loss, no gradient; the divisor stays N * K
       l = 0.0;
       d = 0.0;
@@ -143,7 +212,10 @@ __global__ __launch_bounds__(CE_TPB) void bce_kernel(const float* __restrict__ x
       l = (double)NAN;
       nonfinite += 1;
     }
-    loss += l;
+    if (WEIGHTED)
+      loss += wj * l;
+    else
+      loss += l;
     dx[e] = (float)d;
   }
   loss = wave_sum(loss);
@@ -180,6 +252,22 @@ __global__ __launch_bounds__(CE_TPB) void bce_kernel(const float* __restrict__ x
     loss_out[1] = flag;
     counter[0] = step + 1;  // the only writer: a plain store
   }
+}
+
+__global__ __launch_bounds__(CE_TPB) void bce_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ y,
+                                                     int ldy, int N, int K, int from_logits, float* __restrict__ dx,
+                                                     float* __restrict__ ring, int* __restrict__ counter, int cap,
+                                                     float* __restrict__ loss_out) {
+  bce_body<false>(x, ldx, y, ldy, nullptr, nullptr, N, K, from_logits, dx, ring, counter, cap, loss_out);
+}
+
+__global__ __launch_bounds__(CE_TPB) void bce_w_kernel(const float* __restrict__ x, int ldx,
+                                                       const float* __restrict__ y, int ldy,
+                                                       const float* __restrict__ wgt, const float* __restrict__ pos,
+                                                       int N, int K, int from_logits, float* __restrict__ dx,
+                                                       float* __restrict__ ring, int* __restrict__ counter, int cap,
+                                                       float* __restrict__ loss_out) {
+  bce_body<true>(x, ldx, y, ldy, wgt, pos, N, K, from_logits, dx, ring, counter, cap, loss_out);
 }
 
 // ---------------------------------------------------------------------------------------------- SGD
@@ -432,6 +520,16 @@ extern "C" int sf_ce_topk(const float* logits, int ld, const long* labels, int N
   return SF_OK;
 }
 
+extern "C" int sf_ce_topk_w(const float* logits, int ld, const long* labels, const float* weight, int N, int K, int k_hi,
+                            float* dlogits, float* ring, int* counter, int cap, float* loss_out, void* stream) {
+  if (!logits || !labels || !weight || !dlogits || !ring || !counter || !loss_out) return SF_EINVAL;
+  if (N <= 0 || K <= 0 || ld < K || cap <= 0 || k_hi < 1 || k_hi > K) return SF_EINVAL;
+  hipLaunchKernelGGL(ce_topk_w_kernel, dim3(1), dim3(CE_TPB), 0, (hipStream_t)stream, logits, ld, labels, weight, N, K,
+                     k_hi, dlogits, ring, counter, cap, loss_out);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
 extern "C" int sf_sgd_chunk_elems(void) { return SGD_CHUNK; }
 
 extern "C" int sf_sgd_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host,
@@ -452,6 +550,18 @@ extern "C" int sf_bce(const float* x, int ldx, const float* y, int ldy, int N, i
   if (N <= 0 || K <= 0 || ldx < K || ldy < K || cap <= 0 || (from_logits != 0 && from_logits != 1)) return SF_EINVAL;
   hipLaunchKernelGGL(bce_kernel, dim3(1), dim3(CE_TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, N, K, from_logits, dx,
                      ring, counter, cap, loss_out);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_bce_w(const float* x, int ldx, const float* y, int ldy, const float* weight, const float* pos_weight,
+                        int N, int K, int from_logits, float* dx, float* ring, int* counter, int cap, float* loss_out,
+                        void* stream) {
+  if (!x || !y || !dx || !ring || !counter || !loss_out) return SF_EINVAL;
+  if (N <= 0 || K <= 0 || ldx < K || ldy < K || cap <= 0 || (from_logits != 0 && from_logits != 1)) return SF_EINVAL;
+  if (pos_weight && !from_logits) return SF_EINVAL;  // torch's BCELoss has no pos_weight
+  hipLaunchKernelGGL(bce_w_kernel, dim3(1), dim3(CE_TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, weight, pos_weight, N,
+                     K, from_logits, dx, ring, counter, cap, loss_out);
   SF_CHECK_LAUNCH();
   return SF_OK;
 }

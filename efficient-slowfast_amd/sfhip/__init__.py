@@ -203,6 +203,9 @@ _SIGNATURES = {
     # multi-label / detection loss, one-call Adam
     "sf_bce": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp, _vp]),
     "sf_adam_step": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _ci, _vp]),
+    # class-weighted losses
+    "sf_ce_topk_w": (_ci, [_vp, _ci, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp, _vp]),
+    "sf_bce_w": (_ci, [_vp, _ci, _vp, _ci, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp, _vp]),
     # evaluation: top-k errors of a batch, the epoch's row store, mean average precision
     "sf_topk_errors": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _pi, _ci, _vp]),
     "sf_rows_append": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp]),
@@ -212,6 +215,7 @@ _SIGNATURES = {
     "sf_confusion_small_kmax": (_ci, []),
     "sf_confusion_update": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]),
     "sf_class_report": (_ci, [_vp, _vp, _ci, _vp, _vp, _vp]),
+    "sf_class_weights": (_ci, [_vp, _ci, _ci, _vp, _vp, _vp]),
     # detection evaluation: AVA frame-mAP — true-positive matching, per-class average precision
     "sf_ava_ws_bytes": (_cl, [_ci, _ci, _ci]),
     "sf_ava_match": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _ci, _vp, _ci, _ci] + [_vp] * 5),
@@ -630,6 +634,33 @@ def class_report(conf, hits, out=None, per_class=None):
     _counters(per_class, (K, 6), torch.float64, "class_report: per_class")
     _call("sf_class_report", _ptr(conf), _ptr(hits), K, _ptr(out), _ptr(per_class), tag="class_report")
     return out, per_class
+
+
+WEIGHT_SCHEMES = {"balanced": 0, "effective": 1}  # SF_WEIGHTS_BALANCED, SF_WEIGHTS_EFFECTIVE
+
+
+def class_weights(conf, scheme="balanced", beta=None, out=None):
+    """One `sf_class_weights` launch (no host read): conf int64 [K,K] -> fp32 [K] class weights for the weighted losses.
+    "balanced": samples / (classes with support * support[c]); "effective": (1 - beta) / (1 - beta^support[c]) rescaled to
+    sum to the number of classes with support, `beta` a float in (0, 1).  A class without support gets 0."""
+    if scheme not in WEIGHT_SCHEMES:
+        raise ValueError("class_weights: scheme must be one of %s, got %r" % (sorted(WEIGHT_SCHEMES), scheme))
+    if scheme == "effective":
+        if beta is None or not 0.0 < float(beta) < 1.0:
+            raise ValueError("class_weights: scheme 'effective' needs beta in (0, 1), got %r" % (beta,))
+    elif beta is not None:
+        raise ValueError("class_weights: beta belongs to scheme 'effective', got %r with %r" % (beta, scheme))
+    if conf.dim() != 2 or conf.shape[0] != conf.shape[1]:
+        raise ValueError("class_weights: conf [K, K], got %s" % (tuple(conf.shape),))
+    K = conf.shape[0]
+    _counters(conf, (K, K), torch.int64, "class_weights: conf")
+    if out is None:
+        out = torch.empty((K,), dtype=torch.float32, device=conf.device)
+    _counters(out, (K,), torch.float32, "class_weights: out")
+    b = ctypes.c_double(float(beta)) if beta is not None else None
+    _call("sf_class_weights", _ptr(conf), K, WEIGHT_SCHEMES[scheme], ctypes.byref(b) if b is not None else None,
+          _ptr(out), tag="class_weights")
+    return out
 
 
 def ava_frame_map(preds, boxes, metadata, gt, flags=False):

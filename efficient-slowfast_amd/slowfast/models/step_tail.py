@@ -7,6 +7,10 @@
 * `HipBCE(ring)` / `HipBCEWithLogits(ring)` — `nn.BCELoss(reduction="mean")` on probabilities (detection, losses.py
   "bce") and `nn.BCEWithLogitsLoss(reduction="mean")` on logits (multi-label classification, "bce_logit") with the
   NaN check as ONE launch (`sf_bce`); `get_hip_loss_func(cfg, ring)` picks by `MODEL.LOSS_FUNC`.
+* Class weights — `HipCrossEntropy(..., weight=)`, `HipBCE(..., weight=)`, `HipBCEWithLogits(..., weight=, pos_weight=)`:
+  `nn.CrossEntropyLoss(weight=)`, `nn.BCELoss(weight=)`, `nn.BCEWithLogitsLoss(weight=, pos_weight=)` as the same one
+  launch (`sf_ce_topk_w`, `sf_bce_w`), the weights read from device memory at every step
+  (`utils.meters.DevicePerClassMeter.class_weights(out=)` refreshes them in place, also under a captured step).
 * `topk_errors(preds, labels, k_hi, ring)` — the evaluation batch's row (train_net.py:227-232): `sf_topk_errors`, the same
   ring, no loss (`utils.meters.DeviceValMeter` drains it).
 * `HipSGD` — `torch.optim.SGD` whose `step()` is ONE launch over every parameter of every group (`sf_sgd_step`), with the
@@ -99,6 +103,70 @@ def bce(preds, targets, from_logits, ring, out, dgrad=None):
     return dgrad
 
 
+def _weight_vector(t, K, device, who, name):
+    """fp32 [K], contiguous, on `device` — what the weighted kernels read; anything else is a ValueError."""
+    if not torch.is_tensor(t):
+        raise ValueError("%s: %s must be a tensor, got %s" % (who, name, type(t).__name__))
+    if t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != K or not t.is_contiguous():
+        raise ValueError("%s: %s must be a contiguous float32 tensor of shape (%d,), got %s %s" % (
+            who, name, K, t.dtype, tuple(t.shape)))
+    if t.device != device:
+        raise ValueError("%s: %s is on %s, the predictions on %s" % (who, name, t.device, device))
+    return t
+
+
+def ce_topk_w(preds, labels, weight, k_hi, ring, out, dlogits=None):
+    """One `sf_ce_topk_w` launch: `ce_topk` with class weights, F.cross_entropy(weight=) — the divisor is the sum of
+    the rows' weights.  weight fp32 [K], contiguous, on the predictions' GPU."""
+    if preds.dim() != 2 or labels.dim() != 1 or labels.shape[0] != preds.shape[0]:
+        raise ValueError("ce_topk_w: preds [N, K] and labels [N], got %s and %s" % (tuple(preds.shape),
+                                                                                    tuple(labels.shape)))
+    N, K = preds.shape
+    weight = _weight_vector(weight, K, preds.device, "ce_topk_w", "weight")  # refused before anything needs the GPU
+    sfhip._require_gpu(preds, "ce_topk_w")
+    if labels.dtype != torch.int64 or not labels.is_cuda:
+        raise ValueError("ce_topk_w: labels must be int64 on the GPU, got %s on %s" % (labels.dtype, labels.device))
+    preds, ld = _rows_view(preds, N, K)
+    labels = labels.contiguous()
+    if dlogits is None:
+        dlogits = torch.empty((N, K), dtype=torch.float32, device=preds.device)
+    assert dlogits.is_contiguous() and tuple(dlogits.shape) == (N, K) and out.numel() >= 2
+    cnt = ctypes.cast(ctypes.c_void_p(ring.counter.data_ptr()), sfhip._pi)
+    sfhip._call("sf_ce_topk_w", _vp(preds), int(ld), _vp(labels), _vp(weight), N, K, int(k_hi), _vp(dlogits),
+                _vp(ring.rows), cnt, ring.cap, _vp(out), tag="ce_topk_w")
+    return dlogits
+
+
+def bce_w(preds, targets, from_logits, ring, out, weight=None, pos_weight=None, dgrad=None):
+    """One `sf_bce_w` launch: `bce` with nn.BCELoss(weight=) / nn.BCEWithLogitsLoss(weight=, pos_weight=).  weight and
+    pos_weight fp32 [K], contiguous, on the predictions' GPU, or None (all ones); pos_weight needs from_logits."""
+    if preds.dim() != 2 or tuple(targets.shape) != tuple(preds.shape):
+        raise ValueError("bce_w: preds [N, K] and targets [N, K], got %s and %s" % (tuple(preds.shape),
+                                                                                   tuple(targets.shape)))
+    if pos_weight is not None and not from_logits:
+        raise ValueError("bce_w: pos_weight belongs to the loss on logits (nn.BCEWithLogitsLoss); nn.BCELoss has none")
+    N, K = preds.shape
+    if weight is not None:  # refused before anything needs the GPU
+        weight = _weight_vector(weight, K, preds.device, "bce_w", "weight")
+    if pos_weight is not None:
+        pos_weight = _weight_vector(pos_weight, K, preds.device, "bce_w", "pos_weight")
+    sfhip._require_gpu(preds, "bce_w")
+    if not targets.is_cuda:
+        raise sfhip.SfhipError("bce_w: targets are on %s — the loss kernel runs on the GPU only" % targets.device)
+    if targets.dtype != torch.float32:
+        targets = targets.float()
+    sfhip._require_gpu(targets, "bce_w")
+    preds, ldx = _rows_view(preds, N, K)
+    targets, ldy = _rows_view(targets, N, K)
+    if dgrad is None:
+        dgrad = torch.empty((N, K), dtype=torch.float32, device=preds.device)
+    assert dgrad.is_contiguous() and tuple(dgrad.shape) == (N, K) and out.numel() >= 2
+    cnt = ctypes.cast(ctypes.c_void_p(ring.counter.data_ptr()), sfhip._pi)
+    sfhip._call("sf_bce_w", _vp(preds), int(ldx), _vp(targets), int(ldy), _vp(weight), _vp(pos_weight), N, K,
+                1 if from_logits else 0, _vp(dgrad), _vp(ring.rows), cnt, ring.cap, _vp(out), tag="bce_w")
+    return dgrad
+
+
 def topk_errors(preds, labels, k_hi, ring):
     """One `sf_topk_errors` launch: the top-1 / top-k_hi errors of an evaluation batch (train_net.py:227-232) as a ring
     row of kind KIND_EVAL.  preds fp32 [N, K] (unit column stride, row stride >= K), labels int64 [N]."""
@@ -155,45 +223,121 @@ class _HipLoss(object):
         preds.backward(gradient=self.dlogits)
 
 
-class HipCrossEntropy(_HipLoss):
-    """`HipCrossEntropy(cfg.TRAIN.TOPK, ring)`: softmax cross-entropy with the meter's top-1 / top-k errors."""
+def _as_weight(w, device, who, name):
+    """A weight argument of a loss object -> the tensor the kernel reads.  A tensor is kept as it is — a REFERENCE, so a
+    captured step sees values refreshed in place; a host list / numpy array is checked once (one dimension, finite,
+    non-negative) and uploaded.  The length is checked against K at the first call."""
+    if w is None:
+        return None
+    if torch.is_tensor(w):
+        if w.dtype != torch.float32 or w.dim() != 1 or not w.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous one-dimensional float32 tensor, got %s %s" % (
+                who, name, w.dtype, tuple(w.shape)))
+        if w.device != torch.device(device):
+            raise ValueError("%s: %s is on %s, the ring on %s" % (who, name, w.device, device))
+        return w
+    import numpy as np
+    try:
+        host = np.asarray(w, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s: %s must be a float32 tensor or a sequence of numbers, got %r" % (who, name, w))
+    if host.ndim != 1 or host.size == 0:
+        raise ValueError("%s: %s must have one dimension [K], got shape %s" % (who, name, host.shape))
+    if not np.isfinite(host).all() or (host < 0).any():
+        raise ValueError("%s: %s must be finite and non-negative, got %s" % (who, name, host.tolist()))
+    return torch.tensor(host, dtype=torch.float32).to(device)
 
-    def __init__(self, topk, ring, keep_loss=False):
+
+def _set_weight(cur, new, who, name):
+    if cur is None:
+        raise ValueError("%s.set_%s: the loss was made without %s" % (who, name, name))
+    new = torch.as_tensor(new)
+    if tuple(new.shape) != tuple(cur.shape):
+        raise ValueError("%s.set_%s: shape %s, the loss holds %s" % (who, name, tuple(new.shape), tuple(cur.shape)))
+    cur.copy_(new)
+
+
+class HipCrossEntropy(_HipLoss):
+    """`HipCrossEntropy(cfg.TRAIN.TOPK, ring)`: softmax cross-entropy with the meter's top-1 / top-k errors.
+
+    `weight` (fp32 [K] on the ring's device, or a host list / numpy array uploaded once): nn.CrossEntropyLoss(weight=)
+    as the same one launch (`sf_ce_topk_w`).  A tensor is kept by reference — `class_weights(out=weight)` once per epoch
+    or `set_weight(t)` (a `copy_`) change what the next step, captured or not, reads.  With several GPUs every rank
+    divides by the weight sum of ITS rows and DDP averages the gradients, exactly what nn.CrossEntropyLoss(weight=) does
+    under DDP: that is not the weighted mean over the global batch."""
+
+    def __init__(self, topk, ring, keep_loss=False, weight=None):
         if int(topk) < 1:
             raise ValueError("HipCrossEntropy: topk must be at least 1, got %r" % (topk,))
         super().__init__(ring, keep_loss)
         self.topk = int(topk)
+        self.weight = _as_weight(weight, ring.rows.device, "HipCrossEntropy", "weight")
+
+    def set_weight(self, t):
+        _set_weight(self.weight, t, "HipCrossEntropy", "weight")
 
     def _launch(self, preds, labels):
-        return ce_topk(preds, labels, self.topk, self.ring, self.out)
+        if self.weight is None:
+            return ce_topk(preds, labels, self.topk, self.ring, self.out)
+        return ce_topk_w(preds, labels, self.weight, self.topk, self.ring, self.out)
 
 
 class HipBCE(_HipLoss):
     """`nn.BCELoss(reduction="mean")` on probabilities [N, K] (the detection head's output).  A batch without boxes
-    ([0, K]) raises ValueError: the reference computes NaN there and stops on check_nan_losses."""
+    ([0, K]) raises ValueError: the reference computes NaN there and stops on check_nan_losses.  `weight` (fp32 [K], as
+    HipCrossEntropy takes it): nn.BCELoss(weight=), the mean over N K of weight[j] * loss (`sf_bce_w`)."""
     from_logits = False
+
+    def __init__(self, ring, keep_loss=False, weight=None, pos_weight=None):
+        who = type(self).__name__
+        if pos_weight is not None and not self.from_logits:
+            raise ValueError("%s: pos_weight belongs to the loss on logits (HipBCEWithLogits); nn.BCELoss has none" % who)
+        super().__init__(ring, keep_loss)
+        self.weight = _as_weight(weight, ring.rows.device, who, "weight")
+        self.pos_weight = _as_weight(pos_weight, ring.rows.device, who, "pos_weight")
+
+    def set_weight(self, t):
+        _set_weight(self.weight, t, type(self).__name__, "weight")
+
+    def set_pos_weight(self, t):
+        _set_weight(self.pos_weight, t, type(self).__name__, "pos_weight")
 
     def _launch(self, preds, labels):
         if preds.dim() == 2 and preds.shape[0] * preds.shape[1] == 0:
             raise ValueError("%s: empty batch %s (a detection batch without boxes?) — the mean over no elements is "
                              "NaN" % (type(self).__name__, tuple(preds.shape)))
-        return bce(preds, labels, self.from_logits, self.ring, self.out)
+        if self.weight is None and self.pos_weight is None:
+            return bce(preds, labels, self.from_logits, self.ring, self.out)
+        return bce_w(preds, labels, self.from_logits, self.ring, self.out, weight=self.weight,
+                     pos_weight=self.pos_weight)
 
 
 class HipBCEWithLogits(HipBCE):
-    """`nn.BCEWithLogitsLoss(reduction="mean")` on raw logits [N, K] (multi-label classification in training mode)."""
+    """`nn.BCEWithLogitsLoss(reduction="mean")` on raw logits [N, K] (multi-label classification in training mode);
+    `weight` / `pos_weight` (fp32 [K]) as nn.BCEWithLogitsLoss takes them."""
     from_logits = True
 
 
-def get_hip_loss_func(cfg, ring):
-    """models/losses.py:20-28 by `cfg.MODEL.LOSS_FUNC`, on the kernels above."""
+def get_hip_loss_func(cfg, ring, class_weights=None, pos_weight=None):
+    """models/losses.py:20-28 by `cfg.MODEL.LOSS_FUNC`, on the kernels above.  `class_weights` / `pos_weight` (a tensor
+    or a host sequence, [K]) give the weighted objects; "cross_entropy_weighted" — the name the reference keeps
+    commented out in losses.py — is cross-entropy that requires `class_weights`.  There is no config key for the
+    weights: config/defaults.py mirrors the reference's key set."""
     name = cfg.MODEL.LOSS_FUNC
-    if name == "cross_entropy":
-        return HipCrossEntropy(cfg.TRAIN.TOPK, ring)
+    for what, w in (("class_weights", class_weights), ("pos_weight", pos_weight)):
+        if w is not None and len(w) != cfg.MODEL.NUM_CLASSES:
+            raise ValueError("Loss {}: {} of length {} for MODEL.NUM_CLASSES = {}".format(
+                name, what, len(w), cfg.MODEL.NUM_CLASSES))
+    if name in ("cross_entropy", "cross_entropy_weighted"):
+        if name == "cross_entropy_weighted" and class_weights is None:
+            raise ValueError("Loss cross_entropy_weighted needs class_weights")
+        if pos_weight is not None:
+            raise ValueError("Loss {}: pos_weight belongs to bce_logit".format(name))
+        return HipCrossEntropy(cfg.TRAIN.TOPK, ring, weight=class_weights)
     if name == "bce":
-        return HipBCE(ring)
+        return HipBCE(ring, weight=class_weights, pos_weight=pos_weight)
     if name == "bce_logit":
-        return HipBCEWithLogits(ring)
+        return HipBCEWithLogits(ring, weight=class_weights, pos_weight=pos_weight)
     raise NotImplementedError("Loss {} is not supported".format(name))
 
 

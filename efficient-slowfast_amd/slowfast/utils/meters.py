@@ -161,6 +161,17 @@ class DevicePerClassMeter(object):
         import slowfast.utils.distributed as du
         du.all_reduce([self.state], average=False)
 
+    def class_weights(self, scheme="balanced", beta=None, out=None):
+        """fp32 [K] class weights from the counters added since reset(), for `HipCrossEntropy(weight=)` / `HipBCE(weight=)`:
+        one `sf_class_weights` launch, nothing read — capturable; `out` (fp32 [K] on the meter's device) is written in
+        place, so a loss that holds it sees the new weights.  "balanced": scikit-learn's compute_class_weight("balanced")
+        over the classes with support, samples / (classes with support * support[c]); "effective": the class-balanced
+        (1 - beta) / (1 - beta^support[c]), rescaled to sum to the number of classes with support, `beta` in (0, 1).  A
+        class without support gets 0.  Across ranks call it AFTER `all_reduce()` has summed the counters: there is no
+        collective in here, and weights made from one rank's counters differ from rank to rank."""
+        import sfhip
+        return sfhip.class_weights(self.conf, scheme=scheme, beta=beta, out=out)
+
     def finalize(self, allow_refused=False):
         """The report of everything added since reset(): one launch, then the one host read.  Returns {"confusion": int64
         [K, K], "hits": int64 [K, 2], "per_class": fp64 [K, 6] (PER_CLASS_COLUMNS), "summary": {SUMMARY_FIELDS},

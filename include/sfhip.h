@@ -941,7 +941,34 @@ int sf_stripe_pool_bwd(const float* dz, int dz_cs, int dz_coff, const float* dme
  *   A chunk whose four addresses are all 16-byte aligned moves 16 bytes per access, any other 4.
  *   SF_EINVAL, nothing enqueued: a null pointer (guard excepted), non-positive counts, zero_grad outside {0, 1}, a
  *   zero or 4-byte-misaligned address, numel <= 0, a group outside [0, n_groups), a hyper-parameter that is not
- *   finite, a beta outside [0, 1), chunks that do not tile the tensors exactly. */
+ *   finite, a beta outside [0, 1), chunks that do not tile the tensors exactly.
+ * sf_ce_topk_w: sf_ce_topk with class weights — F.cross_entropy(x, y, weight = w, reduction = "mean") — still ONE launch
+ *   of one workgroup.  weight fp32 [K] in device memory (read by the kernel: a replayed graph sees new values).  With
+ *   W = the sum of w[y_r] over the rows with a valid label:  loss = sum w[y_r] (logsumexp(x_r) - x_r[y_r]) / W  and
+ *   dlogits[r] = (w[y_r] / W) (softmax(x_r) - onehot(y_r)).  W is summed first inside the launch (one pass over the
+ *   labels, fixed order, one barrier; no atomics, no second launch).  The row's factor is formed as w[y_r] * (1 / W)
+ *   and the mean as total * (1 / W): with every weight 1.0f and every label valid, loss, flag, dlogits and the ring row
+ *   equal sf_ce_topk's bit for bit.  (With labels outside [0, K) the divisor differs: N there, W here — as in torch,
+ *   where ignored rows leave the weighted mean.)
+ *   Everything else is sf_ce_topk's: a label outside [0, K) adds no loss, no weight to W, gets a zero gradient row, is
+ *   counted in the bad-label field, and neither x nor weight is read at that index; the top-1 / top-k_hi errors are
+ *   unweighted; the ring row has the same layout and kind 0 with the weighted mean in field 0; the flag is set by a
+ *   NaN or an Inf in a row with a valid label or by a non-finite loss.  ONE difference: a row with a label outside
+ *   [0, K) is left out whole, as torch leaves an ignored row out — a NaN among its logits reaches neither the loss nor
+ *   the gradient (its row is zeros) nor the flag (sf_ce_topk sets the flag for it).  A row whose class has weight 0
+ *   adds nothing and is not "bad".
+ *   W == 0 (every present class has weight 0 — torch returns NaN) or a W that is not finite: the loss is NaN, the flag
+ *   1 (a guarded optimizer skips the update) and dlogits is ALL ZEROS — no NaN reaches a gradient.
+ *   SF_EINVAL, nothing enqueued: as sf_ce_topk, or a null weight.
+ * sf_bce_w: sf_bce with element weights, ONE launch of one workgroup.  weight and pos_weight are fp32 [K] in device
+ *   memory; either may be NULL (= all ones).  from_logits = 0: nn.BCELoss(weight = w), mean over N K of w[j] l;
+ *   pos_weight must be NULL (torch has none).  from_logits = 1: nn.BCEWithLogitsLoss(weight = w, pos_weight = p),
+ *   l = (1 - y) x + (1 + (p[j] - 1) y) softplus(-x) in the overflow-free form (exp(-|x|), log1p),
+ *   dx = w[j] ((1 + (p[j] - 1) y) sigmoid(x) - p[j] y) / (N K).  The divisor is N K whatever the weights, as in torch.
+ *   The arithmetic is arranged so that a weight of 1.0f multiplies by one and p = 1.0f adds exact zeros: with both
+ *   vectors NULL or all ones every output equals sf_bce's bit for bit.  Clamps, the bad-element rule, the row (kind 1)
+ *   and the flag are sf_bce's; the weighted form scales the clamped loss.
+ *   SF_EINVAL, nothing enqueued: as sf_bce, or pos_weight with from_logits = 0. */
 int sf_ce_topk(const float* logits, int ld, const long* labels, int N, int K, int k_hi, float* dlogits, float* ring,
                int* counter, int cap, float* loss_out, void* stream);
 int sf_sgd_chunk_elems(void);
@@ -953,6 +980,10 @@ int sf_bce(const float* x, int ldx, const float* y, int ldy, int N, int K, int f
 int sf_adam_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
                  int n_chunks, const double* hyper_host, const double* hyper, int n_groups, const float* guard,
                  int zero_grad, void* stream);
+int sf_ce_topk_w(const float* logits, int ld, const long* labels, const float* weight, int N, int K, int k_hi,
+                 float* dlogits, float* ring, int* counter, int cap, float* loss_out, void* stream);
+int sf_bce_w(const float* x, int ldx, const float* y, int ldy, const float* weight, const float* pos_weight, int N,
+             int K, int from_logits, float* dx, float* ring, int* counter, int cap, float* loss_out, void* stream);
 
 /* ---- evaluation (csrc/eval_metrics.hip): tools/train_net.py:166-251 eval_epoch and utils/meters.py:557-714 (ValMeter,
  * get_map) without the host.  No entry point synchronises or reads anything back.
@@ -1025,7 +1056,22 @@ int sf_map(const float* scores, int lds, const float* labels, int ldl, int N, in
  *   support > 0), macro precision, macro recall, macro F1 (means over the same classes), the number of classes with
  *   support, the number of classes never predicted}.  The sums run in class order in one thread: the same counters give
  *   the same bits.  Means over no class, and the accuracy of no sample, are 0.
- *   SF_EINVAL, nothing enqueued: a null pointer, K <= 0, K > 1024.  SF_EALIGN: a buffer not on 8 bytes. */
+ *   SF_EINVAL, nothing enqueued: a null pointer, K <= 0, K > 1024.  SF_EALIGN: a buffer not on 8 bytes.
+ * sf_class_weights: class weights for sf_ce_topk_w / sf_bce_w from the same counters, ONE launch, one workgroup,
+ *   K <= 1024, no host read.  support[c] = row sum c of conf, S = the samples counted, K+ = the classes with
+ *   support > 0; w fp32 [K]; a class without support gets 0 (all-zero counters give all zeros).
+ *   SF_WEIGHTS_BALANCED: scikit-learn's compute_class_weight("balanced") over the classes with support,
+ *     w[c] = S / (K+ support[c]) — ONE fp64 division of exact integers, rounded once to fp32.
+ *   SF_WEIGHTS_EFFECTIVE: the class-balanced weight of the effective number of samples,
+ *     e[c] = (1 - beta) / (1 - beta^support[c]), w[c] = e[c] K+ / sum(e) — in fp64, the sum in class order, rounded once
+ *     to fp32; the weights over the classes with support sum to K+.  beta points to ONE fp64 in HOST memory, read
+ *     during the call, in (0, 1); it is not read for SF_WEIGHTS_BALANCED and may be NULL there.
+ *   Across ranks the counters must have been summed first (the caller's collective); there is none here.
+ *   SF_EINVAL, nothing enqueued: a null conf or w, K <= 0, K > 1024, an unknown scheme, SF_WEIGHTS_EFFECTIVE with a
+ *   null beta or one outside (0, 1).  SF_EALIGN: conf not on 8 bytes, w not on 4. */
+#define SF_WEIGHTS_BALANCED 0
+#define SF_WEIGHTS_EFFECTIVE 1
+int sf_class_weights(const long* conf, int K, int scheme, const double* beta, float* w, void* stream);
 int sf_confusion_small_kmax(void);
 int sf_confusion_update(const float* preds, int ld, const long* labels, int N, int K, int k_hi, long* conf, long* hits,
                         long* refused, void* stream);
