@@ -206,6 +206,10 @@ _SIGNATURES = {
     # class-weighted losses
     "sf_ce_topk_w": (_ci, [_vp, _ci, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp, _vp]),
     "sf_bce_w": (_ci, [_vp, _ci, _vp, _ci, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp, _vp]),
+    # gradient clipping: global norm (two launches), scale, value clamp
+    "sf_grad_norm": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _pi, _ci, _vp]),
+    "sf_grad_scale": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp]),
+    "sf_grad_clamp": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp]),
     # evaluation: top-k errors of a batch, the epoch's row store, mean average precision
     "sf_topk_errors": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _pi, _ci, _vp]),
     "sf_rows_append": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp]),

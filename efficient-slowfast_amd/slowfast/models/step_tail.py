@@ -20,6 +20,10 @@
   launch of their own in front of the update, so a replayed step keeps counting).
 * `construct_hip_solver(model, cfg)` — models/optimizer.py:26-69: `construct_hip_optimizer` for `sgd`,
   `construct_hip_adam` for `adam`.
+* `HipGradClip` — `torch.nn.utils.clip_grad_norm_` / `clip_grad_value_` between the backward pass and `step()`: a
+  fixed-order fp64 global norm (`sf_grad_norm`), a scale launch that touches nothing when nothing needs clipping
+  (`sf_grad_scale`), the value clamp (`sf_grad_clamp`); a non-finite gradient raises `.guard`, which `step(guard=)` takes.
+  `construct_hip_grad_clip(model, cfg)` reads upstream's SOLVER.CLIP_GRAD_L2NORM / SOLVER.CLIP_GRAD_VAL.
 There is no fallback: tensors that are not fp32 on the current GPU are refused."""
 import ctypes
 
@@ -708,6 +712,260 @@ class HipAdam(_TableOptimizer, torch.optim.Adam):
     def _after_fresh(self, fresh):
         for p in fresh:
             self.state[p].update(self._slots[p])
+
+
+# ------------------------------------------------------------------------------------------------ gradient clipping
+CLIP_TAB_ROW = 2                                              # gradient address, numel
+CLIP_STATE = 8                                                # floats of the state block sf_grad_norm writes
+ST_NORM32, ST_COEF, ST_FLAG, ST_GUARD = 2, 3, 4, 5            # its fields ([0..1]: the norm as one fp64)
+NORM_INF, NORM_L2 = 0, 2                                      # SF_NORM_INF, SF_NORM_L2
+ROW_GRAD_NORM = 7                                             # the ring column sf_grad_norm fills
+
+
+def build_clip_tables(entries, chunk):
+    """entries: (gradient address, numel) per tensor -> (table int64 [n, 2], chunks int64 [n_chunks, 2]), tiled as
+    build_sgd_tables does."""
+    return _build_tables(entries, chunk, CLIP_TAB_ROW, 1)
+
+
+def _clip_tables_args(tag, table_host, table, chunks_host, chunks):
+    for h, d in ((table_host, table), (chunks_host, chunks)):
+        assert h.dtype == d.dtype == torch.int64 and h.is_contiguous() and d.is_contiguous() and not h.is_cuda
+        assert h.shape == d.shape
+    if not (table.is_cuda and chunks.is_cuda):
+        raise sfhip.SfhipError("%s: table and chunks live on the GPU — there is no CPU fallback" % tag)
+    return (_vp(table_host), _vp(table), table_host.shape[0], _vp(chunks_host), _vp(chunks), chunks_host.shape[0])
+
+
+def grad_norm(table_host, table, chunks_host, chunks, norm_type, partials, state, max_norm=None, guard=None, ring=None):
+    """One `sf_grad_norm` call (two launches): the total norm of the gradients in the table into `state` (fp32 [8]: the
+    norm as fp64 in [0:2], then norm, coefficient, non-finite flag, guard_out).  partials fp64 [n_chunks]; max_norm a
+    device fp32 [1] or None; guard the loss's guard or None; ring a StatsRing or None."""
+    args = _clip_tables_args("grad_norm", table_host, table, chunks_host, chunks)
+    if not (partials.is_cuda and state.is_cuda):
+        raise sfhip.SfhipError("grad_norm: partials and state live on the GPU — there is no CPU fallback")
+    assert partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= chunks_host.shape[0]
+    assert state.dtype == torch.float32 and state.is_contiguous() and state.numel() >= CLIP_STATE
+    cnt = ctypes.cast(ctypes.c_void_p(ring.counter.data_ptr()), sfhip._pi) if ring is not None else None
+    sfhip._call("sf_grad_norm", *args, int(norm_type), _vp(max_norm), _vp(guard), _vp(partials), _vp(state),
+                _vp(ring.rows) if ring is not None else None, cnt, ring.cap if ring is not None else 0, tag="grad_norm")
+
+
+def grad_scale(table_host, table, chunks_host, chunks, state):
+    """One `sf_grad_scale` launch: g *= state[3], nothing touched when state[5] (the guard) is raised or state[3] is 1."""
+    args = _clip_tables_args("grad_scale", table_host, table, chunks_host, chunks)
+    if not state.is_cuda:
+        raise sfhip.SfhipError("grad_scale: state lives on the GPU — there is no CPU fallback")
+    sfhip._call("sf_grad_scale", *args, _vp(state), tag="grad_scale")
+
+
+def grad_clamp(table_host, table, chunks_host, chunks, value):
+    """One `sf_grad_clamp` launch: g = clamp(g, -value, value), value a device fp32 [1]."""
+    args = _clip_tables_args("grad_clamp", table_host, table, chunks_host, chunks)
+    if not value.is_cuda:
+        raise sfhip.SfhipError("grad_clamp: value lives on the GPU — there is no CPU fallback")
+    sfhip._call("sf_grad_clamp", *args, _vp(value), tag="grad_clamp")
+
+
+def _positive_or_none(v, name):
+    if v is None:
+        return None
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise ValueError("HipGradClip: %s must be a positive finite number, got %r" % (name, v))
+    if not (f > 0.0) or f == float("inf"):
+        raise ValueError("HipGradClip: %s must be a positive finite number, got %r" % (name, v))
+    return f
+
+
+class HipGradClip(object):
+    """`torch.nn.utils.clip_grad_norm_` / `clip_grad_value_` between `loss.backward()` and `optimizer.step()`, on
+    libsfhip kernels over an address table of every gradient (`sf_grad_clamp`, `sf_grad_norm`, `sf_grad_scale`):
+
+        clip = HipGradClip(optimizer.param_groups, max_norm=1.0, ring=meter.ring)
+        loss.backward(); clip.clip(guard=loss_fun.guard); optimizer.step(guard=clip.guard)
+
+    `parameters` is an iterable of parameters or an optimizer's `param_groups`; parameters whose `.grad` is None are
+    skipped, as torch does.  `clip(guard=None)` clamps to [-clip_value, clip_value] (if `clip_value`), then computes the
+    total norm (`norm_type` 2 or inf) and scales by min(1, max_norm / (norm + 1e-6)) (if `max_norm`) — the order
+    upstream SlowFast applies when both SOLVER.CLIP_GRAD_VAL and SOLVER.CLIP_GRAD_L2NORM are set.  The norm is summed
+    in fp64 in a fixed order (equal gradients give equal bits); the scale launch touches no memory when the
+    coefficient is exactly 1.  Nothing is read on the host: `max_norm` / `clip_value` live in device memory (assign the
+    attributes; `clip()` / `upload_hyper()` turn a change into one small copy), `.total_norm` is a device fp32 view,
+    `.guard` a fixed-address float32 [1] that is non-zero when the `guard` handed to `clip()` was raised or a gradient
+    is not finite — hand it to `optimizer.step(guard=clip.guard)`.  With `ring` (the meter's StatsRing) the norm goes
+    to column 7 of the row the step's loss kernel wrote (`DeviceTrainMeter(grad_norm=True)` logs it).
+
+    One deviation from torch: when the norm is not finite the gradients are left EXACTLY as they are and the guard is
+    raised; torch multiplies every gradient by NaN.  Either way the step is lost — here the parameters survive (the
+    guarded optimizer skips the update) and the meter reports it.
+
+    With `clip_value` alone no norm pass runs, so there is nothing to put behind `.guard` / `.total_norm`: they raise
+    then — hand the loss's guard to the optimizer.  Under stream capture `clip()` refuses to build a new address table:
+    warm up eagerly first.  An empty parameter list, or one without gradients, is a no-op without a launch.  There is no
+    fallback: gradients that are not contiguous fp32 tensors on the current GPU are refused."""
+
+    def __init__(self, parameters, max_norm=None, norm_type=2.0, clip_value=None, ring=None):
+        params = []
+        for p in parameters:
+            params += list(p["params"]) if isinstance(p, dict) else [p]
+        for p in params:
+            if not torch.is_tensor(p):
+                raise ValueError("HipGradClip: parameters are tensors or param_groups, got %s" % type(p).__name__)
+        try:
+            nt = float(norm_type)
+        except (TypeError, ValueError):
+            nt = None
+        if nt not in (2.0, float("inf")):
+            raise ValueError("HipGradClip: norm_type must be 2 or inf, got %r" % (norm_type,))
+        self.norm_type = nt
+        self.max_norm = _positive_or_none(max_norm, "max_norm")
+        self.clip_value = _positive_or_none(clip_value, "clip_value")
+        if self.max_norm is None and self.clip_value is None:
+            raise ValueError("HipGradClip: give max_norm, clip_value or both")
+        self._modes = (self.max_norm is not None, self.clip_value is not None)
+        self.ring = ring
+        self._params = params
+        self._sig = None
+        self._table = self._chunks = self._table_dev = self._chunks_dev = self._partials = None
+        self._state = self._hyper_dev = self._hyper_vals = self._stage = None
+
+    # ---- device memory this object owns
+    def _device(self):
+        for p in self._params:
+            if p.is_cuda:
+                return p.device
+        raise sfhip.SfhipError("HipGradClip: no parameter is on a GPU — the clipping kernels run on the GPU only "
+                               "(no CPU fallback)")
+
+    def _ensure_state(self):
+        if self._state is None:
+            self._state = torch.zeros((CLIP_STATE,), dtype=torch.float32, device=self._device())
+            self._state[ST_COEF] = 1.0
+        return self._state
+
+    def _norm_field(self, name, i):
+        if self.max_norm is None:
+            raise RuntimeError("HipGradClip.%s: no norm pass runs with clip_value alone — hand the loss's guard to the "
+                               "optimizer" % name)
+        return self._ensure_state()[i:i + 1]
+
+    guard = property(lambda self: self._norm_field("guard", ST_GUARD))
+    total_norm = property(lambda self: self._norm_field("total_norm", ST_NORM32))
+    coef = property(lambda self: self._norm_field("coef", ST_COEF))
+    nonfinite = property(lambda self: self._norm_field("nonfinite", ST_FLAG))
+
+    @property
+    def total_norm64(self):
+        """The norm as the kernel summed it: a device fp64 [1] view."""
+        self._norm_field("total_norm64", 0)
+        return self._state[0:2].view(torch.float64)
+
+    def upload_hyper(self):
+        """Copy max_norm / clip_value to the device if they changed since the last upload (HipSGD.upload_hyper's way:
+        a pinned staging row, one small copy on the current stream).  Call it before replaying a captured `clip()`
+        after assigning either attribute.  Returns whether anything was copied."""
+        self.max_norm = _positive_or_none(self.max_norm, "max_norm")
+        self.clip_value = _positive_or_none(self.clip_value, "clip_value")
+        vals = (self.max_norm, self.clip_value)
+        if vals == self._hyper_vals:
+            return False
+        if tuple(v is not None for v in vals) != self._modes:
+            raise ValueError("HipGradClip: max_norm / clip_value cannot be switched on or off after construction")
+        row = torch.tensor([v if v is not None else 0.0 for v in vals], dtype=torch.float32)
+        if self._hyper_dev is None:
+            self._hyper_dev = torch.empty((2,), dtype=torch.float32, device=self._device())
+            self._stage = torch.empty((STAGE_SLOTS, 2), dtype=torch.float32).pin_memory()
+            self._stage_events, self._stage_next = [None] * STAGE_SLOTS, 0
+        i = self._stage_next
+        self._stage_next = (i + 1) % STAGE_SLOTS
+        if self._stage_events[i] is not None:
+            self._stage_events[i].synchronize()
+        self._stage[i].copy_(row)
+        self._hyper_dev.copy_(self._stage[i], non_blocking=True)
+        self._stage_events[i] = torch.cuda.Event()
+        self._stage_events[i].record()
+        self._hyper_vals = vals
+        return True
+
+    # ---- the address table
+    @staticmethod
+    def _checked_grad(p):
+        g = p.grad
+        if g is None:
+            return None
+        if g.dtype != torch.float32:  # (sparse ones: refused by _signature)
+            raise ValueError("HipGradClip: gradient of dtype %s — float32 only" % g.dtype)
+        if not g.is_contiguous():
+            raise ValueError("HipGradClip: gradients must be contiguous")
+        sfhip._require_gpu(g, "HipGradClip")
+        return g if g.numel() > 0 else None
+
+    def _signature(self):
+        grads = [p.grad for p in self._params]
+        if any(g is not None and g.is_sparse for g in grads):  # (a sparse tensor has no address to sign with)
+            raise ValueError("HipGradClip: sparse gradients are not supported — use torch.nn.utils.clip_grad_norm_")
+        return [0 if g is None else g.data_ptr() for g in grads]
+
+    def _rebuild(self):
+        entries = []
+        for p in self._params:
+            g = self._checked_grad(p)
+            if g is not None:
+                entries.append((g.data_ptr(), g.numel()))
+        if not entries:
+            self._table = None
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("HipGradClip.clip under stream capture needs a new address table, which takes "
+                               "host-to-device copies — warm up eagerly first (run the same step outside the capture)")
+        dev = self._device()
+        self._table, self._chunks = build_clip_tables(entries, sfhip.lib().sf_sgd_chunk_elems())
+        self._table_dev, self._chunks_dev = self._table.to(dev), self._chunks.to(dev)
+        if self._partials is None or self._partials.numel() < self._chunks.shape[0]:
+            self._partials = torch.zeros((self._chunks.shape[0],), dtype=torch.float64, device=dev)
+
+    @torch.no_grad()
+    def clip(self, guard=None):
+        """Clamp, then norm + scale, as configured; `guard` is the loss's guard (a float32 tensor on the GPU) or None.
+        Returns `.total_norm` (a device view, not a host number) when a norm pass ran, else None."""
+        if not self._params:
+            return None
+        sig = self._signature()
+        if sig != self._sig:
+            self._rebuild()
+            self._sig = sig
+        if self._table is None:
+            return None
+        if not torch.cuda.is_current_stream_capturing():
+            self.upload_hyper()
+        elif self._hyper_dev is None:
+            raise RuntimeError("HipGradClip.clip under stream capture: warm up eagerly first")
+        if guard is not None and (not guard.is_cuda or guard.dtype != torch.float32):
+            raise ValueError("HipGradClip.clip: guard is a float32 tensor on the GPU")
+        tabs = (self._table, self._table_dev, self._chunks, self._chunks_dev)
+        if self.clip_value is not None:
+            grad_clamp(*tabs, self._hyper_dev[1:2])
+        if self.max_norm is None:
+            return None
+        state = self._ensure_state()
+        grad_norm(*tabs, NORM_L2 if self.norm_type == 2.0 else NORM_INF, self._partials, state,
+                  max_norm=self._hyper_dev[0:1], guard=guard, ring=self.ring)
+        grad_scale(*tabs, state)
+        return state[ST_NORM32:ST_NORM32 + 1]
+
+
+def construct_hip_grad_clip(model, cfg, ring=None):
+    """Upstream SlowFast's SOLVER.CLIP_GRAD_L2NORM / SOLVER.CLIP_GRAD_VAL as a HipGradClip over the model's parameters,
+    or None when the config has neither key or both are None (config/defaults.py mirrors the reference's key set, which
+    has neither: set them with `cfg.SOLVER.CLIP_GRAD_L2NORM = 1.0` on a config that allows new keys, or build the
+    HipGradClip directly)."""
+    max_norm = cfg.SOLVER.get("CLIP_GRAD_L2NORM", None)
+    clip_value = cfg.SOLVER.get("CLIP_GRAD_VAL", None)
+    if max_norm is None and clip_value is None:
+        return None
+    return HipGradClip(model.parameters(), max_norm=max_norm, norm_type=2.0, clip_value=clip_value, ring=ring)
 
 
 def _split_bn_params(model, cfg):

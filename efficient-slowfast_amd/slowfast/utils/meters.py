@@ -462,10 +462,10 @@ class _ScalarWindow(object):
         return self.total / self.count
 
 
-def _drain_ring(ring, drained, world, who):
+def _drain_ring(ring, drained, world, who, cols=7):
     """The rows written to `ring` since step `drained`, oldest first, as lists of seven floats {loss, top-1 err, top-k
-    err, non-finite flag, N, bad count, kind}: one all-reduce (mean) of the block when world > 1 (train_net.py:128-131,
-    :233-234), ONE device-to-host copy."""
+    err, non-finite flag, N, bad count, kind} (cols=8: and the gradient norm `HipGradClip` left in column 7): one
+    all-reduce (mean) of the block when world > 1 (train_net.py:128-131, :233-234), ONE device-to-host copy."""
     import slowfast.utils.distributed as du
     # the counter rides in the block (exact in float32 far beyond any epoch: the difference below is what is used)
     block = torch.cat([ring.rows.flatten(), ring.counter.to(torch.float64).sub_(drained).float()])
@@ -477,7 +477,7 @@ def _drain_ring(ring, drained, world, who):
     if fresh < 0 or fresh > ring.cap:
         raise RuntimeError("{}: {} steps since the last drain but the ring holds {} — drain at least "
                            "every LOG_PERIOD steps".format(who, fresh, ring.cap))
-    return [[float(v) for v in rows[i % ring.cap, :7]] for i in range(drained, drained + fresh)]
+    return [[float(v) for v in rows[i % ring.cap, :cols]] for i in range(drained, drained + fresh)]
 
 
 class DeviceTrainMeter(object):
@@ -491,12 +491,17 @@ class DeviceTrainMeter(object):
     such a step from touching the parameters), a bad-label count raises ValueError.  The BCE losses (`HipBCE`,
     `HipBCEWithLogits`) write the same rows with field 6 = 1 and no top-k errors; with `cfg.DATA.MULTI_LABEL` the meter
     folds the loss and the sample count only and logs what the reference's TrainMeter logs then (utils/meters.py:492,
-    523, 547): no top1_err / top5_err per iteration, and neither those nor the loss per epoch."""
+    523, 547): no top1_err / top5_err per iteration, and neither those nor the loss per epoch.
+    `grad_norm=True` (opt-in; the default changes nothing): the drain also folds column 7 of every row — the step's
+    total gradient norm, left there by `models.step_tail.HipGradClip(..., ring=meter.ring)` — into a window, and
+    `log_iter_stats` adds its median as "grad_norm"; a row whose norm is not finite raises the same RuntimeWarning."""
 
-    def __init__(self, epoch_iters, cfg, ring=None, device="cuda"):
+    def __init__(self, epoch_iters, cfg, ring=None, device="cuda", grad_norm=False):
         from slowfast.models.step_tail import StatsRing
         self._cfg = cfg
         self._multi_label = bool(cfg.DATA.MULTI_LABEL)
+        self._grad_norm = bool(grad_norm)
+        self.grad_norm = _ScalarWindow(cfg.LOG_PERIOD)
         self.epoch_iters = epoch_iters
         self.MAX_EPOCH = cfg.SOLVER.MAX_EPOCH * epoch_iters
         self._tic, self._lap = time.perf_counter(), 0.0
@@ -513,6 +518,7 @@ class DeviceTrainMeter(object):
         self.lr = None
         self.mb_top1_err.reset()
         self.mb_top5_err.reset()
+        self.grad_norm.reset()
         self.num_top1_mis = 0
         self.num_top5_mis = 0
         self.num_samples = 0
@@ -541,14 +547,16 @@ class DeviceTrainMeter(object):
     def drain(self):
         """Fold the rows written since the last drain; returns how many there were."""
         world = max(int(self._cfg.NUM_GPUS), 1)
-        rows = _drain_ring(self.ring, self._drained, world, "DeviceTrainMeter")
-        for i, (loss, top1, top5, flag, n, bad, kind) in enumerate(rows, self._drained):
+        rows = _drain_ring(self.ring, self._drained, world, "DeviceTrainMeter", cols=8 if self._grad_norm else 7)
+        for i, (loss, top1, top5, flag, n, bad, kind, *norm) in enumerate(rows, self._drained):
             if bad != 0:
                 what = "label(s) outside [0, classes)" if kind == 0 else "target or probability outside [0, 1]"
                 raise ValueError("DeviceTrainMeter: step {} had {} ({:g} per rank on average)".format(i, what, bad))
-            if flag != 0 or math.isnan(loss):
+            if flag != 0 or math.isnan(loss) or (norm and not math.isfinite(norm[0])):
                 raise RuntimeWarning("ERROR: Got NaN losses {}".format(datetime.datetime.now()))
             self._fold(top1, top5, loss, int(round(n)) * world)
+            if norm:
+                self.grad_norm.add_value(norm[0])
         self._drained += len(rows)
         return len(rows)
 
@@ -576,6 +584,8 @@ class DeviceTrainMeter(object):
         if not self._multi_label:
             stats["top1_err"] = self.mb_top1_err.get_win_median()
             stats["top5_err"] = self.mb_top5_err.get_win_median()
+        if self._grad_norm:
+            stats["grad_norm"] = self.grad_norm.get_win_median()
         _LOG.info(format_json_stats(stats))
         return stats
 

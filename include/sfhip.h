@@ -985,6 +985,50 @@ int sf_ce_topk_w(const float* logits, int ld, const long* labels, const float* w
 int sf_bce_w(const float* x, int ldx, const float* y, int ldy, const float* weight, const float* pos_weight, int N,
              int K, int from_logits, float* dx, float* ring, int* counter, int cap, float* loss_out, void* stream);
 
+/* ---- gradient clipping (csrc/grad_clip.hip): torch/nn/utils/clip_grad.py (clip_grad_norm_, clip_grad_value_) between
+ * the backward pass and sf_sgd_step / sf_adam_step, without the host.  No entry point synchronises or reads back.
+ * All three are addressed like sf_sgd_step.  table: int64 [n_tensors][2] = gradient address, numel.  chunks: int64
+ *   [n_chunks][2] = tensor index, first element, tiled at sf_sgd_chunk_elems() exactly as sf_sgd_step's.  The *_host
+ *   arguments are the host arrays the two were uploaded from: they are checked before anything is launched, and every
+ *   kernel re-checks the device row it reads (a row that fails does nothing, never a wild access).  One workgroup per
+ *   chunk; a chunk whose address is 16-byte aligned moves 16 bytes per access, any other 4.
+ * sf_grad_norm: the total norm of all listed gradients, norm_type = SF_NORM_L2 or SF_NORM_INF, in TWO launches.
+ *   Launch 1, one workgroup per chunk: thread t squares (fp64) and adds the elements of the groups of four t, t + 256,
+ *   ... in order, xor butterfly over the wavefront, the four wavefronts in order through LDS; ONE fp64 partial per chunk
+ *   goes to partials (caller-owned, fp64 [n_chunks]).  Both access widths read the same elements in the same order:
+ *   the partial does not depend on the alignment.  SF_NORM_INF: the partial is max |g|, a NaN propagating (torch.max).
+ *   Launch 2, ONE workgroup: thread t folds partials t, t + 256, ... in order, then the same two steps.  No atomics, no
+ *   "last workgroup" finish: equal inputs give equal bits.  It writes state (caller-owned, 8 floats, 8-byte aligned):
+ *     [0..1] the norm as one fp64 (sqrt of the sum, or the maximum);  [2] the norm rounded once to fp32;
+ *     [3] the coefficient min(1, max_norm / (norm + 1e-6)) — torch's formula — evaluated in fp64, rounded once to fp32;
+ *         1 when max_norm is NULL or not positive, or when the norm is not finite;
+ *     [4] 1 when the norm is not finite (a NaN or an Inf among the gradients), else 0;
+ *     [5] guard_out = (guard_in != NULL && *guard_in != 0) || [4] ? 1 : 0 — what sf_grad_scale reads and what
+ *         sf_sgd_step / sf_adam_step take as `guard`;  [6..7] unused.
+ *   max_norm: NULL, or ONE fp32 in DEVICE memory (a replayed graph sees a new value).  guard_in: NULL, or the loss's
+ *   guard (sf_ce_topk's loss_out + 1).  ring / counter / cap: NULL, NULL, anything — or sf_ce_topk's ring: when
+ *   *counter > 0 the fp32 norm goes to column 7 of row (*counter - 1) % cap, the row the step's loss kernel wrote and
+ *   whose column 7 every loss kernel leaves 0; no other column is touched and *counter == 0 writes nothing.
+ *   SF_EINVAL, nothing enqueued: a null table / chunks / partials / state, non-positive counts, an unknown norm_type, a
+ *   zero or 4-byte-misaligned address, numel <= 0, chunks that do not tile the tensors exactly, ring without counter or
+ *   the reverse, a ring with cap <= 0.  SF_EALIGN: partials or state not on 8 bytes.
+ * sf_grad_scale: g *= state[3] in fp32, ONE launch.  Every workgroup returns without touching memory when state[5] is
+ *   not 0 or state[3] is not in [0, 1): g * 1.0f is g, so a step that needs no clipping costs no gradient traffic here,
+ *   and a step whose norm is not finite leaves the gradients as they are (torch multiplies them by NaN).
+ *   SF_EINVAL as above (or a null state); SF_EALIGN: state not on 8 bytes.
+ * sf_grad_clamp: clip_grad_value_, g = min(max(g, -v), v) with torch.clamp's bits (a NaN passes, -0.0 keeps its sign,
+ *   +-Inf become +-v), ONE launch.  value: ONE fp32 in DEVICE memory; not positive or NaN: nothing moves.  Elements
+ *   inside the range are not written again.  SF_EINVAL as above (or a null value). */
+#define SF_NORM_INF 0
+#define SF_NORM_L2 2
+int sf_grad_norm(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
+                 int n_chunks, int norm_type, const float* max_norm, const float* guard_in, double* partials,
+                 float* state, float* ring, int* counter, int cap, void* stream);
+int sf_grad_scale(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
+                  int n_chunks, const float* state, void* stream);
+int sf_grad_clamp(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
+                  int n_chunks, const float* value, void* stream);
+
 /* ---- evaluation (csrc/eval_metrics.hip): tools/train_net.py:166-251 eval_epoch and utils/meters.py:557-714 (ValMeter,
  * get_map) without the host.  No entry point synchronises or reads anything back.
  * sf_topk_errors: metrics.topks_correct for k = 1 and k = k_hi and the two error percentages (train_net.py:227-232) of
