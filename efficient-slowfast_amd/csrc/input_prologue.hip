@@ -8,6 +8,7 @@
 // its (up to 4) source taps, normalises them and writes one aligned 16-byte store.  HBM-bound: 3 B read per tap,
 // 16 B written per pixel.
 #include "common.h"
+#include "mix_row.h"
 
 namespace {
 constexpr int TPB = 256;
@@ -350,6 +351,148 @@ __global__ void clip_batch_gray_kernel(const long* __restrict__ tab, const long*
   }
 }
 
+// ---- the same batch with mixup / CutMix inside the launch (upstream datasets/mixup.py, MixUp._mix_batch on the collated
+// float batch): the table carries B mix rows (mix_row.h) behind the Slow positions.  A mixed pixel is the pixel of
+// clip b, of its partner p (CutMix inside the box: still one resample), or both combined (mixup: two resamples, both
+// uint8 reads) — clip p through its own row and its own frame index.  Grid, ownership and stores are clip_batch_kernel's.
+struct MixGeo {
+  int partner, mode, y0, x0, y1, x1, ok;
+  float lam;
+};
+
+__device__ __forceinline__ MixGeo mix_row(const long* __restrict__ mix, int b, int B, int crop) {
+  const long* r = mix + (long)b * MIX_ROW;
+  MixGeo m;
+  // the host entry checked its copy of the rows; a row that differs on the device yields zeros, never a wild read
+  m.ok = mix_row_ok(r, B) && mix_box_ok(r, crop);
+  m.partner = m.ok ? (int)r[0] : b;
+  m.mode = (int)r[1];
+  m.lam = mix_lambda(r[2]);
+  m.y0 = (int)r[3]; m.x0 = (int)r[4]; m.y1 = (int)r[5]; m.x1 = (int)r[6];
+  return m;
+}
+
+// lam * own + (1 - lam) * other as torch computes it on float32 tensors: two rounded products and one rounded sum.
+// HIP's __fmul_rn / __fadd_rn are plain operators, which the build's -ffp-contract=fast fuses into an fma whatever a
+// contract pragma says: the products pass through an empty asm, so the sum only ever sees the rounded values.
+__device__ __forceinline__ float mix2(float lam, float rest, float own, float other) {
+  float a = __fmul_rn(lam, own), b = __fmul_rn(rest, other);
+  asm("" : "+v"(a), "+v"(b));
+  return __fadd_rn(a, b);
+}
+
+// the frame of clip `b` that Fast position f takes, clamped into [0, T_b)
+__device__ __forceinline__ const unsigned char* batch_frame(const ClipGeo& g, const long* __restrict__ frame_idx, int b,
+                                                            int n_fast, int f, int channels) {
+  const long ft = frame_idx[(long)b * n_fast + f];
+  const int t = ft < 0 ? 0 : (ft > g.T - 1 ? g.T - 1 : (int)ft);
+  return g.clip + (long)t * g.H * g.W * channels;
+}
+
+__global__ void clip_batch_mix_kernel(const long* __restrict__ tab, const long* __restrict__ frame_idx,
+                                      const long* __restrict__ slow_idx, const long* __restrict__ mix, int B, int n_fast,
+                                      int n_slow, int crop, int reverse, NormArgs nm, float* __restrict__ fast,
+                                      float* __restrict__ slow, int ph, int pw, int Wp, int plane) {
+  const int p = blockIdx.x * TPB + threadIdx.x;
+  if (p >= plane) return;
+  const int f = blockIdx.y, b = blockIdx.z;
+  const MixGeo mg = mix_row(mix, b, B, crop);
+  const ClipGeo g = batch_row(tab, b, crop);
+  const ClipGeo gp = batch_row(tab, mg.partner, crop);
+  const int yp = p / Wp, xp = p - yp * Wp;
+  f32x4 o = {0.f, 0.f, 0.f, 0.f};
+  const int yy = yp - ph, xx = xp - pw;
+  if (mg.ok && g.ok && gp.ok && yy >= 0 && yy < crop && xx >= 0 && xx < crop) {
+    const unsigned char* own = batch_frame(g, frame_idx, b, n_fast, f, 3);
+    const unsigned char* oth = batch_frame(gp, frame_idx, mg.partner, n_fast, f, 3);
+    const bool boxed = mg.mode == MIX_CUTMIX && yy >= mg.y0 && yy < mg.y1 && xx >= mg.x0 && xx < mg.x1;
+    float c[3];
+    if (boxed)
+      sample_rgb(oth, gp.H, gp.W, gp.new_h, gp.new_w, gp.y0 + yy, gp.x0 + (gp.flip ? crop - 1 - xx : xx), nm, c);
+    else
+      sample_rgb(own, g.H, g.W, g.new_h, g.new_w, g.y0 + yy, g.x0 + (g.flip ? crop - 1 - xx : xx), nm, c);
+    if (mg.mode == MIX_MIXUP) {  // two roundings of a product and one of the sum, never an fma: torch's x * lam + y * (1 - lam)
+      float d[3];
+      sample_rgb(oth, gp.H, gp.W, gp.new_h, gp.new_w, gp.y0 + yy, gp.x0 + (gp.flip ? crop - 1 - xx : xx), nm, d);
+      const float rest = __fsub_rn(1.0f, mg.lam);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) c[k] = mix2(mg.lam, rest, c[k], d[k]);
+    }
+    if (reverse) {
+      o[0] = c[2]; o[1] = c[1]; o[2] = c[0];
+    } else {
+      o[0] = c[0]; o[1] = c[1]; o[2] = c[2];
+    }
+  }
+  *reinterpret_cast<f32x4*>(fast + (((long)b * n_fast + f) * plane + p) * 4) = o;
+  for (int j = 0; j < n_slow; ++j)  // n_slow <= n_fast / alpha entries, wave-uniform
+    if (slow_idx[j] == f) *reinterpret_cast<f32x4*>(slow + (((long)b * n_slow + j) * plane + p) * 4) = o;
+}
+
+// One-channel clips: VEC as in clip_batch_gray_kernel.
+template <int VEC>
+__global__ void clip_batch_mix_gray_kernel(const long* __restrict__ tab, const long* __restrict__ frame_idx,
+                                           const long* __restrict__ slow_idx, const long* __restrict__ mix, int B,
+                                           int n_fast, int n_slow, int crop, float mean, float stdv,
+                                           float* __restrict__ fast, float* __restrict__ slow, int ph, int pw, int Wp,
+                                           int plane) {
+  const int p = blockIdx.x * TPB + threadIdx.x;
+  if (p >= plane) return;
+  const int f = blockIdx.y, b = blockIdx.z;
+  const MixGeo mg = mix_row(mix, b, B, crop);
+  const ClipGeo g = batch_row(tab, b, crop);
+  const ClipGeo gp = batch_row(tab, mg.partner, crop);
+  const int wq = Wp / VEC;
+  const int yp = p / wq, xp0 = (p - yp * wq) * VEC;
+  const int yy = yp - ph;
+  float o[VEC];
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) o[i] = 0.f;
+  if (mg.ok && g.ok && gp.ok && yy >= 0 && yy < crop) {
+    const unsigned char* own = batch_frame(g, frame_idx, b, n_fast, f, 1);
+    const unsigned char* oth = batch_frame(gp, frame_idx, mg.partner, n_fast, f, 1);
+    const bool rows = mg.mode == MIX_CUTMIX && yy >= mg.y0 && yy < mg.y1;
+    const float rest = __fsub_rn(1.0f, mg.lam);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) {
+      const int xx = xp0 + i - pw;
+      if (xx >= 0 && xx < crop) {
+        float v;
+        if (rows && xx >= mg.x0 && xx < mg.x1)
+          v = sample_gray(oth, gp.H, gp.W, gp.new_h, gp.new_w, gp.y0 + yy, gp.x0 + (gp.flip ? crop - 1 - xx : xx), mean,
+                          stdv);
+        else
+          v = sample_gray(own, g.H, g.W, g.new_h, g.new_w, g.y0 + yy, g.x0 + (g.flip ? crop - 1 - xx : xx), mean, stdv);
+        if (mg.mode == MIX_MIXUP) {
+          const float d = sample_gray(oth, gp.H, gp.W, gp.new_h, gp.new_w, gp.y0 + yy,
+                                      gp.x0 + (gp.flip ? crop - 1 - xx : xx), mean, stdv);
+          v = mix2(mg.lam, rest, v, d);
+        }
+        o[i] = v;
+      }
+    }
+  }
+  const long fo = (((long)b * n_fast + f) * plane + p) * VEC;
+  if constexpr (VEC == 4) {
+    const f32x4 q = {o[0], o[1], o[2], o[3]};
+    *reinterpret_cast<f32x4*>(fast + fo) = q;
+    for (int j = 0; j < n_slow; ++j)
+      if (slow_idx[j] == f) *reinterpret_cast<f32x4*>(slow + (((long)b * n_slow + j) * plane + p) * VEC) = q;
+  } else {
+    fast[fo] = o[0];
+    for (int j = 0; j < n_slow; ++j)
+      if (slow_idx[j] == f) slow[((long)b * n_slow + j) * plane + p] = o[0];
+  }
+}
+
+// Host-side check of the mix rows behind a batch table: [B][SF_MIX_ROW] after the Slow positions.
+bool mix_table_ok(const long* tab, int B, int n_fast, int n_slow, int crop) {
+  const long* mix = tab + (long)B * (BATCH_ROW + n_fast) + n_slow;
+  for (int b = 0; b < B; ++b)
+    if (!mix_row_ok(mix + (long)b * MIX_ROW, B) || !mix_box_ok(mix + (long)b * MIX_ROW, crop)) return false;
+  return true;
+}
+
 // Host-side check of the batch table's host copy: rows [B][9], then frame indices [B][n_fast], then n_slow Slow positions.
 bool batch_table_ok(const long* tab, int B, int n_fast, int n_slow, int crop) {
   for (int b = 0; b < B; ++b)
@@ -605,6 +748,52 @@ extern "C" int sf_clip_batch_gray(const long* table_host, const long* table, int
     hipLaunchKernelGGL(clip_batch_gray_kernel<1>, dim3(sf_cdiv(plane, TPB), n_fast, B), dim3(TPB), 0,
                        (hipStream_t)stream, table, frame_idx, slow_idx, n_fast, n_slow, crop, mean, stdv, fast, slow, ph,
                        pw, Wp, (int)plane);
+  }
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_clip_batch_mix(const long* table_host, const long* table, int B, int n_fast, int n_slow, int crop,
+                                 int reverse, const float* mean3, const float* std3, float* fast, float* slow, int ph,
+                                 int pw, int Wp, void* stream) {
+  long plane = 0;
+  if (!mean3 || !std3 ||
+      !clip_batch_args_ok(table_host, table, B, n_fast, n_slow, crop, fast, slow, ph, pw, Wp, &plane))
+    return SF_EINVAL;
+  if (!mix_table_ok(table_host, B, n_fast, n_slow, crop)) return SF_EINVAL;
+  if (!sf_aligned16(fast) || !sf_aligned16(slow)) return SF_EINVAL;
+  NormArgs nm;
+  for (int c = 0; c < 3; ++c) {
+    nm.m[c] = mean3[c];   // HOST pointers: three floats each
+    nm.s[c] = std3[c];
+  }
+  const long* frame_idx = table + (long)B * BATCH_ROW;
+  const long* slow_idx = frame_idx + (long)B * n_fast;
+  hipLaunchKernelGGL(clip_batch_mix_kernel, dim3(sf_cdiv(plane, TPB), n_fast, B), dim3(TPB), 0, (hipStream_t)stream,
+                     table, frame_idx, slow_idx, slow_idx + n_slow, B, n_fast, n_slow, crop, reverse, nm, fast, slow, ph,
+                     pw, Wp, (int)plane);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_clip_batch_mix_gray(const long* table_host, const long* table, int B, int n_fast, int n_slow, int crop,
+                                      float mean, float stdv, float* fast, float* slow, int ph, int pw, int Wp,
+                                      void* stream) {
+  long plane = 0;
+  if (!clip_batch_args_ok(table_host, table, B, n_fast, n_slow, crop, fast, slow, ph, pw, Wp, &plane)) return SF_EINVAL;
+  if (!mix_table_ok(table_host, B, n_fast, n_slow, crop)) return SF_EINVAL;
+  if (((uintptr_t)fast | (uintptr_t)slow) % sizeof(float)) return SF_EINVAL;  // not even a float's alignment
+  const long* frame_idx = table + (long)B * BATCH_ROW;
+  const long* slow_idx = frame_idx + (long)B * n_fast;
+  const long* mix = slow_idx + n_slow;
+  if (Wp % 4 == 0 && sf_aligned16(fast) && sf_aligned16(slow)) {
+    hipLaunchKernelGGL(clip_batch_mix_gray_kernel<4>, dim3(sf_cdiv(plane / 4, TPB), n_fast, B), dim3(TPB), 0,
+                       (hipStream_t)stream, table, frame_idx, slow_idx, mix, B, n_fast, n_slow, crop, mean, stdv, fast,
+                       slow, ph, pw, Wp, (int)(plane / 4));
+  } else {
+    hipLaunchKernelGGL(clip_batch_mix_gray_kernel<1>, dim3(sf_cdiv(plane, TPB), n_fast, B), dim3(TPB), 0,
+                       (hipStream_t)stream, table, frame_idx, slow_idx, mix, B, n_fast, n_slow, crop, mean, stdv, fast,
+                       slow, ph, pw, Wp, (int)plane);
   }
   SF_CHECK_LAUNCH();
   return SF_OK;

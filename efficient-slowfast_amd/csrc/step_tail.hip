@@ -6,6 +6,7 @@
 // per LOG_PERIOD, the hyper-parameters are read from device memory (the LR schedule is a 4-byte write a replayed graph
 // sees) and a non-finite loss switches the update off through a flag the loss kernel leaves.
 #include "common.h"
+#include "mix_row.h"
 #include "stats_row.h"
 
 #include <math.h>
@@ -25,6 +26,11 @@ namespace {
 // same W.  The row's factor is w * (1 / W) and the mean tot * (1 / W): with every weight 1.0f and every label valid
 // these are the unweighted 1 / N and tot * (1 / N) bit for bit.  W == 0 (every present class has weight 0; torch
 // returns NaN), or a W that is not finite: the loss is NaN, the flag 1 and dlogits all zeros.
+// MIX (sf_ce_mix): the target of row r is t = (1 - eps) (lam onehot(a) + (1 - lam) onehot(b)) + eps / K with a the row's
+// label, b its partner's and lam from the row's mix row — two labels, one weight and one scalar instead of an N x K
+// tensor.  The loss needs sum_j t_j x_j = (1 - eps) (lam x_a + (1 - lam) x_b) + (eps / K) sum_j x_j: the sum of the row
+// rides in the exp sweep.  The hits are counted against the dominant label (a when lam >= 0.5, else b).  At eps = 0
+// and lam = 1 the products are by one and the added terms exact zeros (finite logits): sf_ce_topk's bits.
 __device__ __forceinline__ double ce_weight_total(const long* __restrict__ labels, const float* __restrict__ wgt, int N,
                                                   int K) {
   __shared__ double s_w[CE_WAVES];
@@ -42,24 +48,49 @@ __device__ __forceinline__ double ce_weight_total(const long* __restrict__ label
   return wtot;
 }
 
-template <bool WEIGHTED>
+template <bool WEIGHTED, bool MIX = false>
 __device__ __forceinline__ void ce_topk_body(const float* __restrict__ logits, int ld, const long* __restrict__ labels,
                                              const float* __restrict__ wgt, int N, int K, int k_hi,
                                              float* __restrict__ dlogits, float* __restrict__ ring,
-                                             int* __restrict__ counter, int cap, float* __restrict__ loss_out) {
+                                             int* __restrict__ counter, int cap, float* __restrict__ loss_out,
+                                             const long* __restrict__ mix = nullptr, float smoothing = 0.f) {
+  static_assert(!(WEIGHTED && MIX), "class weights and soft targets divide differently: not offered together");
   __shared__ double s_loss[CE_WAVES];
   __shared__ int s_cnt[CE_WAVES][4];  // top-1 hits, top-k_hi hits, rows with a non-finite logit, bad labels
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const double wtot = WEIGHTED ? ce_weight_total(labels, wgt, N, K) : (double)N;
   const bool w_ok = !WEIGHTED || (wtot > 0.0 && isfinite(wtot));
   const double inv_n = 1.0 / wtot;  // WEIGHTED: 1 / W
+  const double keep = MIX ? 1.0 - (double)smoothing : 1.0;         // 1 - eps
+  const double uni = MIX ? (double)smoothing / (double)K : 0.0;    // eps / K
   double loss = 0.0;
   int hit1 = 0, hitk = 0, nonfinite = 0, bad = 0;
   for (int r = wave; r < N; r += CE_WAVES) {
     const float* x = logits + (long)r * ld;
     float* dx = dlogits + (long)r * K;
-    const long l = labels[r];
-    const bool ok = l >= 0 && l < K;  // a label outside [0, K): no loss, no gradient, never a read
+    long l = labels[r];
+    bool ok = l >= 0 && l < K;  // a label outside [0, K): no loss, no gradient, never a read
+    long la = l, lb = l;        // MIX: the row's own label and its partner's
+    double lam = 1.0, xa = 0.0, xb = 0.0;
+    if (MIX) {
+      long p = r;
+      if (mix != nullptr) {  // the host entry checked its copy; a device row that differs is a bad row, never a read
+        const long* mr = mix + (long)r * MIX_ROW;
+        const bool pair = mix_pair_ok(mr, N);
+        ok = ok && pair;
+        if (pair) {
+          p = mr[0];
+          lam = (double)mix_lambda(mr[2]);
+        }
+      }
+      lb = labels[p];
+      ok = ok && lb >= 0 && lb < K;
+      l = lam >= 0.5 ? la : lb;  // the dominant label: what the hits are counted against
+      if (ok) {
+        xa = (double)x[la];
+        xb = (double)x[lb];
+      }
+    }
     const float xl = ok ? x[l] : 0.f;
     const double wr = (WEIGHTED && ok) ? (double)wgt[l] : 1.0;
     const double fac = WEIGHTED ? wr * inv_n : inv_n;
@@ -75,17 +106,36 @@ __device__ __forceinline__ void ce_topk_body(const float* __restrict__ logits, i
     m = wave_max(m);
     rank = wave_sum(rank);
     nf = wave_sum(nf) != 0;
-    double s = 0.0;
-    for (int j = lane; j < K; j += 64) s += exp((double)x[j] - (double)m);  // NaN / Inf propagate from here
+    double s = 0.0, sx = 0.0;
+    if (MIX) {
+      for (int j = lane; j < K; j += 64) {
+        s += exp((double)x[j] - (double)m);
+        sx += (double)x[j];
+      }
+    } else {
+      for (int j = lane; j < K; j += 64) s += exp((double)x[j] - (double)m);  // NaN / Inf propagate from here
+    }
     s = wave_sum(s);
+    if (MIX) sx = wave_sum(sx);
     const double inv_s = 1.0 / s;
-    for (int j = lane; j < K; j += 64) {
-      const double p = exp((double)x[j] - (double)m) * inv_s;
-      dx[j] = grad ? (float)((p - (j == l ? 1.0 : 0.0)) * fac) : 0.f;
+    if (MIX) {
+      const double lam_b = 1.0 - lam;
+      for (int j = lane; j < K; j += 64) {
+        const double p = exp((double)x[j] - (double)m) * inv_s;
+        const double t = keep * (lam * (j == la ? 1.0 : 0.0) + lam_b * (j == lb ? 1.0 : 0.0)) + uni;
+        dx[j] = grad ? (float)((p - t) * fac) : 0.f;
+      }
+    } else {
+      for (int j = lane; j < K; j += 64) {
+        const double p = exp((double)x[j] - (double)m) * inv_s;
+        dx[j] = grad ? (float)((p - (j == l ? 1.0 : 0.0)) * fac) : 0.f;
+      }
     }
     if (ok) {
       if (WEIGHTED)
         loss += wr * (log(s) + (double)m - (double)xl);
+      else if (MIX)
+        loss += log(s) + (double)m - (keep * (lam * xa + (1.0 - lam) * xb) + uni * sx);
       else
         loss += log(s) + (double)m - (double)xl;
       if (!nf) {  // a row with a NaN or an Inf is wrong for every k
@@ -149,6 +199,16 @@ __global__ __launch_bounds__(CE_TPB) void ce_topk_w_kernel(const float* __restri
                                                            int* __restrict__ counter, int cap,
                                                            float* __restrict__ loss_out) {
   ce_topk_body<true>(logits, ld, labels, wgt, N, K, k_hi, dlogits, ring, counter, cap, loss_out);
+}
+
+__global__ __launch_bounds__(CE_TPB) void ce_mix_kernel(const float* __restrict__ logits, int ld,
+                                                        const long* __restrict__ labels, const long* __restrict__ mix,
+                                                        int N, int K, int k_hi, float smoothing,
+                                                        float* __restrict__ dlogits, float* __restrict__ ring,
+                                                        int* __restrict__ counter, int cap,
+                                                        float* __restrict__ loss_out) {
+  ce_topk_body<false, true>(logits, ld, labels, nullptr, N, K, k_hi, dlogits, ring, counter, cap, loss_out, mix,
+                            smoothing);
 }
 
 // ---------------------------------------------------------------------------------------------- BCE
@@ -526,6 +586,22 @@ extern "C" int sf_ce_topk_w(const float* logits, int ld, const long* labels, con
   if (N <= 0 || K <= 0 || ld < K || cap <= 0 || k_hi < 1 || k_hi > K) return SF_EINVAL;
   hipLaunchKernelGGL(ce_topk_w_kernel, dim3(1), dim3(CE_TPB), 0, (hipStream_t)stream, logits, ld, labels, weight, N, K,
                      k_hi, dlogits, ring, counter, cap, loss_out);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_ce_mix(const float* logits, int ld, const long* labels, const long* mix_host, const long* mix, int N,
+                         int K, int k_hi, float smoothing, float* dlogits, float* ring, int* counter, int cap,
+                         float* loss_out, void* stream) {
+  if (!logits || !labels || !dlogits || !ring || !counter || !loss_out) return SF_EINVAL;
+  if (N <= 0 || K <= 0 || ld < K || cap <= 0 || k_hi < 1 || k_hi > K) return SF_EINVAL;
+  if (!(smoothing >= 0.f && smoothing < 1.f)) return SF_EINVAL;  // (a NaN fails both)
+  if ((mix == nullptr) != (mix_host == nullptr)) return SF_EINVAL;
+  if (mix_host != nullptr)
+    for (int r = 0; r < N; ++r)
+      if (!mix_row_ok(mix_host + (long)r * MIX_ROW, N)) return SF_EINVAL;
+  hipLaunchKernelGGL(ce_mix_kernel, dim3(1), dim3(CE_TPB), 0, (hipStream_t)stream, logits, ld, labels, mix, N, K, k_hi,
+                     smoothing, dlogits, ring, counter, cap, loss_out);
   SF_CHECK_LAUNCH();
   return SF_OK;
 }

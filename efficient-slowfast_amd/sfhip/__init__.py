@@ -70,6 +70,8 @@ _SIGNATURES = {
     "sf_clip_batch": (_ci, [_vp, _vp] + [_ci] * 5 + [_vp] * 4 + [_ci, _ci, _ci, _vp]),
     "sf_clip_batch_gray": (_ci, [_vp, _vp] + [_ci] * 4 + [_cf, _cf, _vp, _vp, _ci, _ci, _ci, _vp]),
     "sf_clip_batch_det": (_ci, [_vp, _vp] + [_ci] * 6 + [_vp] * 4 + [_ci, _ci, _ci, _vp]),
+    "sf_clip_batch_mix": (_ci, [_vp, _vp] + [_ci] * 5 + [_vp] * 4 + [_ci, _ci, _ci, _vp]),
+    "sf_clip_batch_mix_gray": (_ci, [_vp, _vp] + [_ci] * 4 + [_cf, _cf, _vp, _vp, _ci, _ci, _ci, _vp]),
     "sf_ensemble_update": (_ci, [_vp] * 4 + [_pi] * 3 + [_ci] * 4 + [_vp]),
     "sf_ensemble_update_ml": (_ci, [_vp] * 3 + [_ci, _vp, _vp, _pi, _pi] + [_ci] * 4 + [_vp]),
     "sf_ncthw1_pack": (_ci, [_vp, _vp] + [_ci] * 7 + [_vp]),
@@ -206,6 +208,8 @@ _SIGNATURES = {
     # class-weighted losses
     "sf_ce_topk_w": (_ci, [_vp, _ci, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp, _vp]),
     "sf_bce_w": (_ci, [_vp, _ci, _vp, _ci, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp, _vp]),
+    # soft targets: label smoothing, mixup and CutMix
+    "sf_ce_mix": (_ci, [_vp, _ci, _vp, _vp, _vp, _ci, _ci, _ci, _cf, _vp, _vp, _pi, _ci, _vp, _vp]),
     # gradient clipping: global norm (two launches), scale, value clamp
     "sf_grad_norm": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _pi, _ci, _vp]),
     "sf_grad_scale": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp]),
@@ -478,6 +482,37 @@ def clip_batch(table_host, table, n_slow, crop, mean, std, fast, slow=None, gray
         m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
         s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
         _call("sf_clip_batch", *head, 1 if reverse else 0, ctypes.cast(m3, _vp), ctypes.cast(s3, _vp), *tail)
+    return fast, slow
+
+
+SF_MIX_ROW = 7  # include/sfhip.h: partner row, mode, lam as float32 bits, y0, x0, y1, x1 (int64 each)
+
+
+def clip_batch_mix(table_host, table, n_slow, crop, mean, std, fast, slow=None, gray=False, reverse=False, ph=0, pw=0):
+    """`clip_batch` with mixup / CutMix inside the launch (`sf_clip_batch_mix` / `sf_clip_batch_mix_gray`): the table is
+    clip_batch's followed by B mix rows (partner row, mode 0 none / 1 mixup / 2 CutMix, lam as float32 bits, the box y0,
+    x0, y1, x1 in output crop coordinates).  Everything else — buffers, layouts, the caller keeping the spans alive — is
+    clip_batch's."""
+    _require_gpu(fast, "clip_batch_mix")
+    if not table.is_cuda or table_host.is_cuda:
+        raise SfhipError("clip_batch_mix: the batch table's copy lives on the GPU, table_host on the host")
+    assert fast.is_contiguous() and fast.dim() == 5 and fast.shape[4] == (1 if gray else 4)
+    B, n_fast = fast.shape[:2]
+    assert table_host.dtype == torch.int64 and table.dtype == torch.int64 and table_host.is_contiguous()
+    assert table.is_contiguous() and table_host.numel() == table.numel() == B * (9 + n_fast + SF_MIX_ROW) + n_slow
+    if slow is not None:
+        _require_gpu(slow, "clip_batch_mix")
+        assert slow.is_contiguous() and tuple(slow.shape) == (B, n_slow) + tuple(fast.shape[2:])
+    head = (_ptr(table_host), _ptr(table), B, n_fast, int(n_slow), int(crop))
+    tail = (_ptr(fast), _ptr(slow), ph, pw, fast.shape[3])
+    if gray:
+        assert len(mean) == 1 and len(std) == 1, "one-channel clips take a one-element mean / std"
+        assert not reverse, "DATA.REVERSE_INPUT_CHANNEL has no meaning for one-channel clips"
+        _call("sf_clip_batch_mix_gray", *head, float(mean[0]), float(std[0]), *tail)
+    else:
+        m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
+        s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
+        _call("sf_clip_batch_mix", *head, 1 if reverse else 0, ctypes.cast(m3, _vp), ctypes.cast(s3, _vp), *tail)
     return fast, slow
 
 

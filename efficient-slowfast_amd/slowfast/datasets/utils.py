@@ -285,6 +285,131 @@ def gpu_train_batch(videos, samples, mean, std, alpha, reverse_input_channel=Fal
     return out if slow is None else [sfhip.PackedClip(slow, C, crop, crop, ph, pw)] + out
 
 
+# ---- mixup / CutMix (upstream SlowFast datasets/mixup.py, after timm): the host keeps the draws, the pixels are mixed
+# inside the one-launch input step (sf_clip_batch_mix) and the labels inside the loss (sf_ce_mix) from the same rows.
+MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2
+MixParams = collections.namedtuple("MixParams", "partner mode lam box")
+MixParams.__doc__ = """The mix decision of one batch of B clips.  partner: B row indices; mode (MIX_NONE / MIX_MIXUP /
+MIX_CUTMIX), lam (a Python float in [0, 1]) and box ((y0, x0, y1, x1) in output crop coordinates): one value for the
+batch, or a sequence of B values (one per row)."""
+
+
+def rand_bbox(crop, lam):
+    """mixup.py rand_bbox (margin 0) for a crop x crop output: a box of side ratio sqrt(1 - lam) around a centre drawn
+    uniformly (numpy's global RNG: cy, then cx), clipped to the crop.  Returns (y0, x0, y1, x1)."""
+    ratio = np.sqrt(1.0 - lam)
+    cut_h, cut_w = int(crop * ratio), int(crop * ratio)
+    cy = int(np.random.randint(0, crop))
+    cx = int(np.random.randint(0, crop))
+    y0, y1 = int(np.clip(cy - cut_h // 2, 0, crop)), int(np.clip(cy + cut_h // 2, 0, crop))
+    x0, x1 = int(np.clip(cx - cut_w // 2, 0, crop)), int(np.clip(cx + cut_w // 2, 0, crop))
+    return y0, x0, y1, x1
+
+
+def sample_mix_params(B, crop, mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5):
+    """The decision of MixUp._params_per_batch / _mix_batch (mixup.py, mode "batch") for one batch, without touching
+    pixels: ONE decision per batch, the partner of row b is B - 1 - b (x.flip(0)).
+    RNG order, upstream's, all from numpy's global RNG: rand() against `prob`; with both alphas positive rand() against
+    `switch_prob` (CutMix when below); lam ~ beta(alpha, alpha) of the chosen form; for CutMix the box centre cy, then
+    cx (`rand_bbox`), after which lam is corrected to 1 - box area / crop^2 (correct_lam).  Nothing beyond the first
+    rand() is drawn when it is not below `prob`; lam == 1 after the draw means no mixing, as upstream.
+    Returns MixParams; without mixing: mode MIX_NONE, lam 1.0 and an empty box."""
+    if B <= 0 or crop <= 0:
+        raise ValueError("sample_mix_params: B and crop must be positive, got %r and %r" % (B, crop))
+    if mixup_alpha < 0 or cutmix_alpha < 0 or not 0.0 <= prob <= 1.0 or not 0.0 <= switch_prob <= 1.0:
+        raise ValueError("sample_mix_params: alphas must not be negative and the probabilities lie in [0, 1]")
+    partner = tuple(B - 1 - b for b in range(B))
+    none = MixParams(partner, MIX_NONE, 1.0, (0, 0, 0, 0))
+    if mixup_alpha <= 0 and cutmix_alpha <= 0:
+        return none
+    if not np.random.rand() < prob:
+        return none
+    if mixup_alpha > 0 and cutmix_alpha > 0:
+        cutmix = bool(np.random.rand() < switch_prob)
+    else:
+        cutmix = cutmix_alpha > 0
+    alpha = cutmix_alpha if cutmix else mixup_alpha
+    lam = float(np.random.beta(alpha, alpha))
+    if lam == 1.0:
+        return none
+    if not cutmix:
+        return MixParams(partner, MIX_MIXUP, lam, (0, 0, 0, 0))
+    y0, x0, y1, x1 = rand_bbox(crop, lam)
+    lam = 1.0 - (y1 - y0) * (x1 - x0) / float(crop * crop)
+    return MixParams(partner, MIX_CUTMIX, lam, (y0, x0, y1, x1))
+
+
+def _per_row(v, B, what):
+    if isinstance(v, (int, float, np.integer, np.floating)):
+        return [v] * B
+    v = list(v)
+    if len(v) != B:
+        raise ValueError("mix_rows: %s has %d entries for %d rows" % (what, len(v), B))
+    return v
+
+
+def mix_rows(mix):
+    """The int64 host rows [B, 7] sf_clip_batch_mix and sf_ce_mix read: partner, mode, lam as the bit pattern of its
+    float32 value (low 32 bits), y0, x0, y1, x1.  Both kernels use that float32 lam — pixels and labels are mixed by
+    the same number."""
+    B = len(mix.partner)
+    if B == 0:
+        raise ValueError("mix_rows: no rows")
+    modes, lams = _per_row(mix.mode, B, "mode"), _per_row(mix.lam, B, "lam")
+    box = mix.box
+    boxes = [tuple(box)] * B if len(box) == 4 and not isinstance(box[0], (tuple, list)) else _per_row(box, B, "box")
+    rows = torch.empty((B, sfhip.SF_MIX_ROW), dtype=torch.int64)
+    for b in range(B):
+        lam = float(lams[b])
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError("mix_rows: lam must lie in [0, 1], got %r" % (lams[b],))
+        if int(modes[b]) not in (MIX_NONE, MIX_MIXUP, MIX_CUTMIX):
+            raise ValueError("mix_rows: mode must be 0 (none), 1 (mixup) or 2 (CutMix), got %r" % (modes[b],))
+        if len(boxes[b]) != 4:
+            raise ValueError("mix_rows: a box is (y0, x0, y1, x1), got %r" % (boxes[b],))
+        bits = int(np.float32(lam).view(np.uint32))
+        rows[b] = torch.tensor([int(mix.partner[b]), int(modes[b]), bits] + [int(v) for v in boxes[b]], dtype=torch.int64)
+    return rows
+
+
+def gpu_train_batch_mix(videos, samples, mix, mean, std, alpha, reverse_input_channel=False, pad=(0, 0), wp=None):
+    """`gpu_train_batch` with mixup / CutMix inside the launch (sf_clip_batch_mix): `mix` is a MixParams for the B
+    clips (`sample_mix_params`).  Still one table upload — the mix rows ride behind the batch table — and one launch.
+    Returns (packed, rows): the PackedClips as gpu_train_batch returns them, and the [B, 7] int64 DEVICE view of the mix
+    rows inside the uploaded table, which the loss takes (`HipCrossEntropy(...)(preds, labels, mix=rows)`); its
+    `mix_host` attribute is the host copy the loss entry checks."""
+    B = len(videos)
+    assert B == len(samples) and B > 0
+    if len(mix.partner) != B:
+        raise ValueError("gpu_train_batch_mix: mix rows for %d clips, the batch has %d" % (len(mix.partner), B))
+    crop = samples[0][1].crop
+    n_fast = len(samples[0][0])
+    assert all(p.crop == crop and len(f) == n_fast for f, p in samples)
+    ph, pw = pad
+    wp = crop + 2 * pw if wp is None else wp
+    dev = videos[0].device
+    gray = videos[0].dim() == 3 or videos[0].shape[3] == 1
+    for v in videos:
+        if not v.is_cuda or v.device != dev:
+            raise sfhip.SfhipError("gpu_train_batch_mix: every decoded span lives on one GPU, got %s" % v.device)
+        assert v.dtype == torch.uint8 and v.dim() in (3, 4) and v.is_contiguous()
+        assert (v.dim() == 3 or v.shape[3] == 1) == gray and (gray or v.shape[3] == 3)
+    C, cpad = (1, 1) if gray else (3, 4)
+    slow_idx = slow_frame_indices(n_fast, alpha) if alpha is not None else torch.zeros(0, dtype=torch.long)
+    n_slow = slow_idx.numel()
+    rows_host = mix_rows(mix)
+    table_host = torch.cat([batch_table(videos, samples, slow_idx), rows_host.flatten()]).contiguous()
+    table = table_host.to(dev)  # the one upload: rows, frame indices, Slow positions and mix rows together
+    fast = torch.empty((B, n_fast, crop + 2 * ph, wp, cpad), dtype=torch.float32, device=dev)
+    slow = torch.empty((B, n_slow, crop + 2 * ph, wp, cpad), dtype=torch.float32, device=dev) if n_slow else None
+    sfhip.clip_batch_mix(table_host, table, n_slow, crop, mean, std, fast, slow, gray=gray,
+                         reverse=reverse_input_channel, ph=ph, pw=pw)
+    out = [sfhip.PackedClip(fast, C, crop, crop, ph, pw)]
+    rows = table[table.numel() - B * sfhip.SF_MIX_ROW:].view(B, sfhip.SF_MIX_ROW)
+    rows.mix_host = rows_host
+    return (out if slow is None else [sfhip.PackedClip(slow, C, crop, crop, ph, pw)] + out), rows
+
+
 # ---- the detection (AVA) input step: datasets/ava_dataset.py:233-338 with AVA.IMG_PROC_BACKEND "pytorch", and the box
 # collation of datasets/loader.py:18-52.  The host keeps the draws and the boxes; pixels go through sf_clip_batch_det.
 DetParams = collections.namedtuple("DetParams", "new_h new_w y x flip win_h win_w crop offsets")

@@ -11,6 +11,9 @@
   `nn.CrossEntropyLoss(weight=)`, `nn.BCELoss(weight=)`, `nn.BCEWithLogitsLoss(weight=, pos_weight=)` as the same one
   launch (`sf_ce_topk_w`, `sf_bce_w`), the weights read from device memory at every step
   (`utils.meters.DevicePerClassMeter.class_weights(out=)` refreshes them in place, also under a captured step).
+* Soft targets — `HipCrossEntropy(..., label_smoothing=)` and `loss_fun(preds, labels, mix=rows)`: label smoothing,
+  mixup and CutMix (upstream's MIXUP.* and datasets/mixup.py) as the same one launch (`sf_ce_mix`) from the mix rows the
+  input step already used (`datasets.utils.gpu_train_batch_mix`); `construct_hip_mixup(cfg)` draws the batch's mix.
 * `topk_errors(preds, labels, k_hi, ring)` — the evaluation batch's row (train_net.py:227-232): `sf_topk_errors`, the same
   ring, no loss (`utils.meters.DeviceValMeter` drains it).
 * `HipSGD` — `torch.optim.SGD` whose `step()` is ONE launch over every parameter of every group (`sf_sgd_step`), with the
@@ -141,6 +144,61 @@ def ce_topk_w(preds, labels, weight, k_hi, ring, out, dlogits=None):
     return dlogits
 
 
+def _smoothing(v, who):
+    """label smoothing as the kernel takes it: a number in [0, 1)."""
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        raise ValueError("%s: label smoothing must be a number in [0, 1), got %r" % (who, v))
+    if not 0.0 <= f < 1.0:  # (a NaN fails both)
+        raise ValueError("%s: label smoothing must lie in [0, 1), got %r" % (who, v))
+    return f
+
+
+def _mix_pair(mix_host, mix, N, who):
+    """The mix rows of `N` predictions as the loss entry takes them: int64 [N, 7], contiguous — `mix` on the GPU, `mix_host`
+    the host copy it was uploaded from.  Both None: no mixing."""
+    if mix is None and mix_host is None:
+        return None, None
+    if mix is None or mix_host is None:
+        raise ValueError("%s: mix rows come as a pair — the device rows and the host copy they were uploaded from" % who)
+    for name, t in (("mix_host", mix_host), ("mix", mix)):
+        if not torch.is_tensor(t) or t.dtype != torch.int64 or tuple(t.shape) != (N, sfhip.SF_MIX_ROW) or \
+                not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous int64 tensor of shape (%d, %d), got %s %s" % (
+                who, name, N, sfhip.SF_MIX_ROW, getattr(t, "dtype", type(t).__name__),
+                tuple(getattr(t, "shape", ()))))
+    if mix_host.device.type != "cpu":
+        raise ValueError("%s: mix_host is the HOST copy of the rows, got a tensor on %s" % (who, mix_host.device))
+    return mix_host, mix
+
+
+def ce_mix(preds, labels, k_hi, ring, out, mix_host=None, mix=None, smoothing=0.0, dlogits=None):
+    """One `sf_ce_mix` launch: `ce_topk` on the soft targets of label smoothing (`smoothing` in [0, 1)), mixup and
+    CutMix — F.cross_entropy(preds, t) with t = (1 - eps) (lam onehot(a) + (1 - lam) onehot(b)) + eps / K, a the row's
+    label, b its partner's.  mix: the device rows int64 [N, 7] `gpu_train_batch_mix` returns (partner, mode, lam as
+    float32 bits, box), mix_host their host copy; both None: no mixing."""
+    if preds.dim() != 2 or labels.dim() != 1 or labels.shape[0] != preds.shape[0]:
+        raise ValueError("ce_mix: preds [N, K] and labels [N], got %s and %s" % (tuple(preds.shape), tuple(labels.shape)))
+    N, K = preds.shape
+    eps = _smoothing(smoothing, "ce_mix")  # refused before anything needs the GPU
+    mix_host, mix = _mix_pair(mix_host, mix, N, "ce_mix")
+    sfhip._require_gpu(preds, "ce_mix")
+    if labels.dtype != torch.int64 or not labels.is_cuda:
+        raise ValueError("ce_mix: labels must be int64 on the GPU, got %s on %s" % (labels.dtype, labels.device))
+    if mix is not None and not mix.is_cuda:
+        raise sfhip.SfhipError("ce_mix: the mix rows are on %s — the loss kernel runs on the GPU only" % mix.device)
+    preds, ld = _rows_view(preds, N, K)
+    labels = labels.contiguous()
+    if dlogits is None:
+        dlogits = torch.empty((N, K), dtype=torch.float32, device=preds.device)
+    assert dlogits.is_contiguous() and tuple(dlogits.shape) == (N, K) and out.numel() >= 2
+    cnt = ctypes.cast(ctypes.c_void_p(ring.counter.data_ptr()), sfhip._pi)
+    sfhip._call("sf_ce_mix", _vp(preds), int(ld), _vp(labels), _vp(mix_host), _vp(mix), N, K, int(k_hi), eps,
+                _vp(dlogits), _vp(ring.rows), cnt, ring.cap, _vp(out), tag="ce_mix")
+    return dlogits
+
+
 def bce_w(preds, targets, from_logits, ring, out, weight=None, pos_weight=None, dgrad=None):
     """One `sf_bce_w` launch: `bce` with nn.BCELoss(weight=) / nn.BCEWithLogitsLoss(weight=, pos_weight=).  weight and
     pos_weight fp32 [K], contiguous, on the predictions' GPU, or None (all ones); pos_weight needs from_logits."""
@@ -268,19 +326,71 @@ class HipCrossEntropy(_HipLoss):
     as the same one launch (`sf_ce_topk_w`).  A tensor is kept by reference — `class_weights(out=weight)` once per epoch
     or `set_weight(t)` (a `copy_`) change what the next step, captured or not, reads.  With several GPUs every rank
     divides by the weight sum of ITS rows and DDP averages the gradients, exactly what nn.CrossEntropyLoss(weight=) does
-    under DDP: that is not the weighted mean over the global batch."""
+    under DDP: that is not the weighted mean over the global batch.
 
-    def __init__(self, topk, ring, keep_loss=False, weight=None):
+    `label_smoothing` (a number in [0, 1)) and `loss_fun(preds, labels, mix=rows)`: soft targets — label smoothing,
+    mixup and CutMix (upstream's MIXUP.LABEL_SMOOTH_VALUE and datasets/mixup.py) — as the same one launch (`sf_ce_mix`);
+    the errors are counted against each row's dominant label.  `mix` is the [N, 7] int64 device tensor
+    `datasets.utils.gpu_train_batch_mix` returns (its `mix_host` attribute is the host copy the entry checks), or a
+    `(host rows, device rows)` pair.  The device rows are taken by REFERENCE: a captured step reads whatever they hold
+    when it is replayed, so copy each batch's rows into one fixed tensor (`fixed.copy_(rows)`); a tensor without a
+    host copy is checked by the kernel alone (a row that fails there is a bad row: no loss, no gradient, counted).
+    Class weights together with soft targets are refused: torch itself divides the two differently (by N for
+    probability targets, by the weight sum for index targets).  With `label_smoothing == 0` and no `mix` the object
+    launches `sf_ce_topk` / `sf_ce_topk_w` exactly as before."""
+
+    def __init__(self, topk, ring, keep_loss=False, weight=None, label_smoothing=0.0):
         if int(topk) < 1:
             raise ValueError("HipCrossEntropy: topk must be at least 1, got %r" % (topk,))
+        eps = _smoothing(label_smoothing, "HipCrossEntropy")
+        if weight is not None and eps != 0.0:
+            raise ValueError("HipCrossEntropy: weight together with label_smoothing is not supported — torch divides by "
+                             "N for probability targets and by the weight sum for index targets")
         super().__init__(ring, keep_loss)
         self.topk = int(topk)
         self.weight = _as_weight(weight, ring.rows.device, "HipCrossEntropy", "weight")
+        self.label_smoothing = eps
+        self._mix = None        # the mix rows of the call in flight: (host rows, device rows)
+        self._identity = None   # host rows that mix nothing, for device rows that come without a host copy
 
     def set_weight(self, t):
         _set_weight(self.weight, t, "HipCrossEntropy", "weight")
 
+    def _host_rows(self, mix):
+        """(host rows, device rows) of a `mix` argument."""
+        if isinstance(mix, (tuple, list)):
+            if len(mix) != 2:
+                raise ValueError("HipCrossEntropy: mix is the device rows or a (host rows, device rows) pair")
+            return mix[0], mix[1]
+        if not torch.is_tensor(mix):
+            raise ValueError("HipCrossEntropy: mix must be an int64 tensor [N, %d] or a (host, device) pair, got %s" % (
+                sfhip.SF_MIX_ROW, type(mix).__name__))
+        host = getattr(mix, "mix_host", None)
+        if host is None and mix.dim() == 2:  # a fixed tensor refilled by the caller: the kernel's own check stands alone
+            n = mix.shape[0]
+            if self._identity is None or self._identity.shape[0] != n:
+                ident = torch.zeros((n, sfhip.SF_MIX_ROW), dtype=torch.int64)
+                ident[:, 0] = torch.arange(n)
+                ident[:, 2] = 0x3f800000  # lam = 1.0f
+                self._identity = ident
+            host = self._identity
+        return host, mix
+
+    def __call__(self, preds, labels, mix=None):
+        if mix is not None and self.weight is not None:
+            raise ValueError("HipCrossEntropy: weight together with mix rows is not supported — torch divides by N for "
+                             "probability targets and by the weight sum for index targets")
+        self._mix = None if mix is None else self._host_rows(mix)
+        try:
+            return _LossFunction.apply(preds, labels, self)
+        finally:
+            self._mix = None
+
     def _launch(self, preds, labels):
+        if self.label_smoothing != 0.0 or self._mix is not None:
+            host, dev = self._mix if self._mix is not None else (None, None)
+            return ce_mix(preds, labels, self.topk, self.ring, self.out, mix_host=host, mix=dev,
+                          smoothing=self.label_smoothing)
         if self.weight is None:
             return ce_topk(preds, labels, self.topk, self.ring, self.out)
         return ce_topk_w(preds, labels, self.weight, self.topk, self.ring, self.out)
@@ -322,11 +432,52 @@ class HipBCEWithLogits(HipBCE):
     from_logits = True
 
 
+def _mixup_keys(cfg):
+    """Upstream SlowFast's MIXUP node read with `.get` (config/defaults.py mirrors the reference's key set, which has no
+    such node: add one to a config that allows new keys) -> (enable, alpha, cutmix_alpha, prob, switch_prob,
+    label smoothing), upstream's defaults where a key is missing.  The smoothing counts only with MIXUP.ENABLE, as
+    upstream, where the MixUp object is what smooths the labels."""
+    node = getattr(cfg, "MIXUP", None)
+    if node is None or not node.get("ENABLE", False):
+        return False, 0.0, 0.0, 0.0, 0.0, 0.0
+    return (True, float(node.get("ALPHA", 0.8)), float(node.get("CUTMIX_ALPHA", 1.0)), float(node.get("PROB", 1.0)),
+            float(node.get("SWITCH_PROB", 0.5)), float(node.get("LABEL_SMOOTH_VALUE", 0.1)))
+
+
+class HipMixUp(object):
+    """The batch's mix decision with upstream's MIXUP.* settings: `mix = mixup.sample(B, crop)` (a
+    `datasets.utils.MixParams`, drawn from numpy's global RNG in upstream's order) goes to
+    `datasets.utils.gpu_train_batch_mix`, whose rows go to the loss; `label_smoothing` is what `get_hip_loss_func`
+    hands to HipCrossEntropy."""
+
+    def __init__(self, mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, label_smoothing=0.1):
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.prob, self.switch_prob = float(prob), float(switch_prob)
+        self.label_smoothing = _smoothing(label_smoothing, "HipMixUp")
+        if self.mixup_alpha < 0 or self.cutmix_alpha < 0 or not 0.0 <= self.prob <= 1.0 or \
+                not 0.0 <= self.switch_prob <= 1.0:
+            raise ValueError("HipMixUp: alphas must not be negative and the probabilities lie in [0, 1]")
+
+    def sample(self, B, crop):
+        from slowfast.datasets.utils import sample_mix_params
+        return sample_mix_params(B, crop, self.mixup_alpha, self.cutmix_alpha, self.prob, self.switch_prob)
+
+
+def construct_hip_mixup(cfg):
+    """Upstream SlowFast's MIXUP.ENABLE / ALPHA / CUTMIX_ALPHA / PROB / SWITCH_PROB / LABEL_SMOOTH_VALUE as a HipMixUp, or
+    None when the config has no MIXUP node or MIXUP.ENABLE is false."""
+    enable, alpha, cutmix_alpha, prob, switch_prob, eps = _mixup_keys(cfg)
+    if not enable:
+        return None
+    return HipMixUp(alpha, cutmix_alpha, prob, switch_prob, eps)
+
+
 def get_hip_loss_func(cfg, ring, class_weights=None, pos_weight=None):
     """models/losses.py:20-28 by `cfg.MODEL.LOSS_FUNC`, on the kernels above.  `class_weights` / `pos_weight` (a tensor
     or a host sequence, [K]) give the weighted objects; "cross_entropy_weighted" — the name the reference keeps
     commented out in losses.py — is cross-entropy that requires `class_weights`.  There is no config key for the
-    weights: config/defaults.py mirrors the reference's key set."""
+    weights: config/defaults.py mirrors the reference's key set.  With upstream's MIXUP.ENABLE the cross-entropy takes
+    MIXUP.LABEL_SMOOTH_VALUE (`construct_hip_mixup` draws the batch's mix)."""
     name = cfg.MODEL.LOSS_FUNC
     for what, w in (("class_weights", class_weights), ("pos_weight", pos_weight)):
         if w is not None and len(w) != cfg.MODEL.NUM_CLASSES:
@@ -337,7 +488,7 @@ def get_hip_loss_func(cfg, ring, class_weights=None, pos_weight=None):
             raise ValueError("Loss cross_entropy_weighted needs class_weights")
         if pos_weight is not None:
             raise ValueError("Loss {}: pos_weight belongs to bce_logit".format(name))
-        return HipCrossEntropy(cfg.TRAIN.TOPK, ring, weight=class_weights)
+        return HipCrossEntropy(cfg.TRAIN.TOPK, ring, weight=class_weights, label_smoothing=_mixup_keys(cfg)[5])
     if name == "bce":
         return HipBCE(ring, weight=class_weights, pos_weight=pos_weight)
     if name == "bce_logit":

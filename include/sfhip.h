@@ -663,6 +663,33 @@ int sf_clip_batch(const long* table_host, const long* table, int B, int n_fast, 
 int sf_clip_batch_gray(const long* table_host, const long* table, int B, int n_fast, int n_slow, int crop, float mean,
                        float stdv, float* fast, float* slow, int ph, int pw, int Wp, void* stream);
 
+/* ---- mixup / CutMix inside the training input step (upstream SlowFast datasets/mixup.py: MixUp._mix_batch mixes the
+ * collated float batch with its flip along the batch axis — x * lam + x.flip(0) * (1 - lam), or the flipped batch's
+ * pixels inside one box).  Here a mixed pixel is one or two resamples of uint8 spans: no float batch is read back.
+ * A MIX ROW is SF_MIX_ROW = 7 int64: partner row, mode (0 none, 1 mixup, 2 CutMix), lam as a float32 bit pattern in
+ *   the low 32 bits (the high 32 zero), then the box y0, x0, y1, x1 in output (post-flip) crop coordinates.  A row is
+ *   valid when the partner lies in [0, B), the mode in {0, 1, 2} and lam in [0, 1]; its box when 0 <= y0 <= y1 <= crop
+ *   and 0 <= x0 <= x1 <= crop.  sf_ce_mix (below) reads the same rows.
+ * sf_clip_batch_mix: sf_clip_batch whose table carries a tail: after the B rows, the frame indices and the Slow
+ *   positions come B mix rows.  For output pixel (yy, xx) of frame f of clip b with partner p:
+ *   mode 0: the pixel of clip b — sf_clip_batch's bits.
+ *   mode 1: fl(fl(lam * own) + fl(fl(1.0f - lam) * other)) per channel — two rounded products and a rounded sum, never
+ *           contracted into an fma: the bits of mixing the two sf_clip_batch outputs with separate float32 multiplies
+ *           and an add.  `other` is clip p through ITS row (scale, crop offset, flip) and ITS frame index f.
+ *   mode 2: clip p's pixel where y0 <= yy < y1 and x0 <= xx < x1, clip b's elsewhere, in every frame of both pathways:
+ *           one resample per pixel, as without mixing.
+ *   Borders stay zero, a frame that goes to both pathways is mixed once and stored twice, one owner per output
+ *   element, 16-byte stores, no atomics.  The kernel re-checks the device rows it reads: clip b is written as zeros
+ *   when its own or its partner's batch row fails sf_clip_batch's check, or its mix row or box is not valid.
+ *   SF_EINVAL, nothing launched: sf_clip_batch's list, or a mix row or a box of the host table that is not valid.
+ * sf_clip_batch_mix_gray: the same for one-channel spans, with both store widths of sf_clip_batch_gray. */
+#define SF_MIX_ROW 7
+int sf_clip_batch_mix(const long* table_host, const long* table, int B, int n_fast, int n_slow, int crop, int reverse,
+                      const float* mean3, const float* std3, float* fast, float* slow, int ph, int pw, int Wp,
+                      void* stream);
+int sf_clip_batch_mix_gray(const long* table_host, const long* table, int B, int n_fast, int n_slow, int crop,
+                           float mean, float stdv, float* fast, float* slow, int ph, int pw, int Wp, void* stream);
+
 /* ---- detection input step, one launch per batch (AVA with AVA.IMG_PROC_BACKEND "pytorch":
  * datasets/ava_dataset.py:233-338 _images_and_boxes_preprocessing and the transform.py functions it calls — :283-337
  * random_short_side_scale_jitter, :359-392 random_crop, :395-422 horizontal_flip, :425-468 uniform_crop, :636-663
@@ -968,7 +995,29 @@ int sf_stripe_pool_bwd(const float* dz, int dz_cs, int dz_coff, const float* dme
  *   The arithmetic is arranged so that a weight of 1.0f multiplies by one and p = 1.0f adds exact zeros: with both
  *   vectors NULL or all ones every output equals sf_bce's bit for bit.  Clamps, the bad-element rule, the row (kind 1)
  *   and the flag are sf_bce's; the weighted form scales the clamped loss.
- *   SF_EINVAL, nothing enqueued: as sf_bce, or pos_weight with from_logits = 0. */
+ *   SF_EINVAL, nothing enqueued: as sf_bce, or pos_weight with from_logits = 0.
+ * sf_ce_mix: sf_ce_topk on the soft targets of label smoothing, mixup and CutMix — F.cross_entropy(x, t) with probability
+ *   targets, equal to upstream SlowFast's lam * CE(a) + (1 - lam) * CE(b) with label_smoothing = eps (datasets/mixup.py
+ *   mixup_target, losses.py SoftTargetCrossEntropy) — still ONE launch of one workgroup and no N x K target tensor.
+ *   mix: device int64 [N][SF_MIX_ROW], the rows sf_clip_batch_mix read (the loss reads the partner and lam only);
+ *   mix_host: the host array it was uploaded from, checked before the launch.  Both NULL: no mixing, lam = 1.
+ *   With a = labels[r], b = labels[partner_r], lam = lam_r, eps = smoothing:
+ *     t_r = (1 - eps) (lam onehot(a) + (1 - lam) onehot(b)) + eps / K,
+ *     loss = (1 / N) sum_r (logsumexp(x_r) - sum_j t_rj x_rj),   dlogits[r] = (softmax(x_r) - t_r) / N.
+ *   The top-1 / top-k_hi errors use sf_ce_topk's hit rule against the row's dominant label: a when lam >= 0.5, else b.
+ *   The ring row (kind 0, column 7 left 0), the flag and loss_out are sf_ce_topk's; exp, log and all sums in fp64 in a
+ *   fixed order, no atomics: two runs give equal bits.  With smoothing == 0, no mix table and finite logits every
+ *   output equals sf_ce_topk's bit for bit (eps = 0 and lam = 1 multiply by one and add exact zeros).
+ *   A BAD ROW — a or b outside [0, K), a device mix row whose partner is outside [0, N) or whose lam is not in
+ *   [0, 1] — adds no loss, gets a zero gradient row, counts as wrong and is counted in field 5; the divisor stays N and
+ *   nothing is read out of bounds.
+ *   SF_EINVAL, nothing enqueued: everything sf_ce_topk refuses, smoothing outside [0, 1) or NaN, exactly one of mix /
+ *   mix_host, a host row with its partner outside [0, N), its mode outside {0, 1, 2} or lam outside [0, 1].
+ *   Class weights together with soft targets are not offered: torch divides by N for probability targets and by the
+ *   weight sum for index targets. */
+int sf_ce_mix(const float* logits, int ld, const long* labels, const long* mix_host, const long* mix, int N, int K,
+              int k_hi, float smoothing, float* dlogits, float* ring, int* counter, int cap, float* loss_out,
+              void* stream);
 int sf_ce_topk(const float* logits, int ld, const long* labels, int N, int K, int k_hi, float* dlogits, float* ring,
                int* counter, int cap, float* loss_out, void* stream);
 int sf_sgd_chunk_elems(void);
