@@ -519,6 +519,234 @@ bool clip_batch_args_ok(const long* table_host, const long* table, int B, int n_
   if (*plane > 0x7fffffffL / 4) return false;
   return batch_table_ok(table_host, B, n_fast, n_slow, crop);
 }
+
+// ---- the same batch with Jester's colour jitter inside the launch (decoder.py:456-469 -> transform.py:692-717,
+// RandomColorJitter: PIL's ImageEnhance.Brightness, then Contrast, then Color, on every sampled uint8 frame before
+// tensor_normalize).  The table carries B jitter rows behind the Slow positions: three float32 factors per CLIP.  The
+// contrast stage blends against the frame's grey mean, a reduction over the whole decoded frame, so a first launch
+// (frame_grey_means_kernel) leaves one int per (clip, Fast frame) and the clip launch reads it.  Checked against
+// Pillow 12.2.0: PIL casts the factor to a C float and blends in float32, one rounded product and one rounded sum.
+constexpr int JITTER_ROW = SF_JITTER_ROW;  // brightness, contrast, colour: float32 bits in the low half of an int64
+
+struct JitGeo {
+  float fb, fc, fs;
+  int m, ok;  // m: the frame's grey mean (the contrast stage's other image)
+};
+
+// a factor word: the high half zero and the float finite (checked on the host copy and again on the device copy)
+__host__ __device__ __forceinline__ bool jitter_row_ok(const long* r) {
+  for (int i = 0; i < JITTER_ROW; ++i)
+    if (r[i] < 0 || r[i] > 0xffffffffL || ((unsigned)r[i] & 0x7f800000u) == 0x7f800000u) return false;
+  return true;
+}
+
+__device__ __forceinline__ JitGeo jitter_row(const long* __restrict__ jit, int b) {
+  const long* r = jit + (long)b * JITTER_ROW;
+  JitGeo j;
+  j.ok = jitter_row_ok(r);
+  j.fb = __uint_as_float((unsigned)r[0]);
+  j.fc = __uint_as_float((unsigned)r[1]);
+  j.fs = __uint_as_float((unsigned)r[2]);
+  j.m = 0;
+  return j;
+}
+
+// Image.blend(x0, x1, f) on uint8 values: fl(x0 + fl(f * (x1 - x0))), the product kept from fusing into the sum as in
+// mix2.  For 0 <= f <= 1 PIL truncates, otherwise it clips to [0, 255] and truncates: one expression serves both,
+// because inside [0, 1] the rounded sum cannot leave [min(x0, x1), max(x0, x1)].
+__device__ __forceinline__ int blend8(float f, int x0, int x1) {
+  float p = __fmul_rn(f, (float)(x1 - x0));
+  asm("" : "+v"(p));
+  const float t = __fadd_rn((float)x0, p);
+  return (int)fminf(fmaxf(t, 0.f), 255.f);
+}
+
+// ImageEnhance.Brightness: blend against black
+__device__ __forceinline__ void bright3(float fb, int c[3]) {
+  if (fb > 0.f) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = blend8(fb, 0, c[k]);
+  }
+}
+
+// convert("L"): ITU-R 601-2 luma in 16-bit fixed point
+__device__ __forceinline__ int grey3(const int c[3]) { return (19595 * c[0] + 38470 * c[1] + 7471 * c[2] + 32768) >> 16; }
+
+// The jitter of ONE source pixel, uint8 in and uint8 out: what every tap of the resampling reads.  A stage whose
+// factor is <= 0 is skipped (transform.py:706-717).
+__device__ __forceinline__ void jitter_px(const unsigned char* __restrict__ p, const JitGeo& j, unsigned char u[3]) {
+  int c[3] = {p[0], p[1], p[2]};
+  bright3(j.fb, c);
+  if (j.fc > 0.f) {  // ImageEnhance.Contrast: blend against the frame's grey mean
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = blend8(j.fc, j.m, c[k]);
+  }
+  if (j.fs > 0.f) {  // ImageEnhance.Color: blend against the pixel's own grey
+    const int l = grey3(c);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = blend8(j.fs, l, c[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) u[k] = (unsigned char)c[k];
+}
+
+// The weighted sum of four normalised taps with the roundings sample_rgb's `ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * d +
+// lx1 * e)` has in the plain kernels.  There the build's -ffp-contract=fast and the vectoriser settle them: each row is
+// fma(lx0, left, fl(lx1 * right)), and the two rows meet as fl(ly0 * top) + fl(ly1 * bottom), a packed multiply and
+// an add, no fma.  Around the jitter's integer arithmetic the compiler pairs the operations differently, so this
+// path states that form outright (empty asm keeps the products from fusing, as in mix2); the GPU tests hold the two
+// to equal bits.
+__device__ __forceinline__ float bilerp_as_plain(float ly0, float ly1, float lx0, float lx1, float a, float b, float d,
+                                                 float e) {
+  float tb = __fmul_rn(lx1, b), te = __fmul_rn(lx1, e);
+  asm("" : "+v"(tb), "+v"(te));
+  float top = __fmul_rn(ly0, __fmaf_rn(lx0, a, tb)), bot = __fmul_rn(ly1, __fmaf_rn(lx0, d, te));
+  asm("" : "+v"(top), "+v"(bot));
+  return __fadd_rn(top, bot);
+}
+
+// sample_rgb with every tap passed through jitter_px, so a clip whose three factors are all <= 0 holds sample_rgb's
+// bits.
+__device__ __forceinline__ void sample_rgb_jitter(const unsigned char* __restrict__ fr, int H, int W, int new_h,
+                                                  int new_w, int ys, int xs, const NormArgs& nm, const JitGeo& j,
+                                                  float v[3]) {
+  if (new_h == H && new_w == W) {
+    unsigned char p[3];
+    jitter_px(fr + ((long)ys * W + xs) * 3, j, p);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = norm1(p[c], nm.m[c], nm.s[c]);
+  } else {
+    int ya, yb, xa, xb;
+    float ly0, ly1, lx0, lx1;
+    src_index((float)H / (float)new_h, ys, H, &ya, &yb, &ly0, &ly1);
+    src_index((float)W / (float)new_w, xs, W, &xa, &xb, &lx0, &lx1);
+    unsigned char p00[3], p01[3], p10[3], p11[3];
+    jitter_px(fr + ((long)ya * W + xa) * 3, j, p00);
+    jitter_px(fr + ((long)ya * W + xb) * 3, j, p01);
+    jitter_px(fr + ((long)yb * W + xa) * 3, j, p10);
+    jitter_px(fr + ((long)yb * W + xb) * 3, j, p11);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float a = norm1(p00[c], nm.m[c], nm.s[c]), b = norm1(p01[c], nm.m[c], nm.s[c]);
+      const float d = norm1(p10[c], nm.m[c], nm.s[c]), e = norm1(p11[c], nm.m[c], nm.s[c]);
+      v[c] = bilerp_as_plain(ly0, ly1, lx0, lx1, a, b, d, e);
+    }
+  }
+}
+
+// The grey mean of every (clip, Fast frame) after the clip's brightness stage: int(ImageStat.Stat(L).mean[0] + 0.5) =
+// (2 S + n) / (2 n) for the sum S of the n = H * W grey values.  One workgroup per frame (grid n_fast x B: 256 for a
+// batch of 8 x 32, one per CU), each thread sums pixels in an integer register, the wavefronts meet in LDS and thread 0
+// owns the output element: no atomics.  The frame starts at any byte, so the first (address % 4) pixels and the last
+// (< 4) go one by one and the rest as aligned 12-byte groups of four pixels.
+struct Px4 {
+  unsigned w[3];
+};
+
+__device__ __forceinline__ unsigned grey_bright(float fb, int r, int g, int b) {
+  int c[3] = {r, g, b};
+  bright3(fb, c);
+  return (unsigned)grey3(c);
+}
+
+// four pixels in three words: r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+__device__ __forceinline__ unsigned grey_bright4(float fb, const Px4& w) {
+  const unsigned a = w.w[0], m = w.w[1], z = w.w[2];
+  return grey_bright(fb, a & 255, (a >> 8) & 255, (a >> 16) & 255) + grey_bright(fb, a >> 24, m & 255, (m >> 8) & 255) +
+         grey_bright(fb, (m >> 16) & 255, m >> 24, z & 255) + grey_bright(fb, (z >> 8) & 255, (z >> 16) & 255, z >> 24);
+}
+
+__global__ void __launch_bounds__(TPB) frame_grey_means_kernel(const long* __restrict__ tab,
+                                                               const long* __restrict__ frame_idx,
+                                                               const long* __restrict__ jit, int n_fast, int crop,
+                                                               int* __restrict__ means) {
+  const int f = blockIdx.x, b = blockIdx.y;
+  const ClipGeo g = batch_row(tab, b, crop);
+  const JitGeo j = jitter_row(jit, b);
+  int* out = means + (long)b * n_fast + f;
+  if (!g.ok || !j.ok || !(j.fc > 0.f)) {  // no contrast stage (or no valid row): nothing is read
+    if (threadIdx.x == 0) *out = 0;
+    return;
+  }
+  const unsigned char* fr = batch_frame(g, frame_idx, b, n_fast, f, 3);
+  const long n = (long)g.H * g.W;
+  long head = (long)((unsigned long)fr & 3);  // base + 3 * head is 4-byte aligned: 3 h = -a (mod 4) <=> h = a
+  if (head > n) head = n;
+  const long groups = (n - head) / 4;
+  const long rest = head + groups * 4;  // first pixel of the tail
+  unsigned long acc = 0;
+  for (long i = threadIdx.x; i < head + (n - rest); i += TPB) {
+    const unsigned char* p = fr + (i < head ? i : rest + (i - head)) * 3;
+    acc += grey_bright(j.fb, p[0], p[1], p[2]);
+  }
+  const auto* q = (const __attribute__((address_space(1))) unsigned*)(unsigned long)(fr + head * 3);
+  const auto load4 = [q](long i) { return Px4{{q[3 * i], q[3 * i + 1], q[3 * i + 2]}}; };
+  long i = threadIdx.x;
+  for (; i + 3 * TPB < groups; i += 4 * TPB) {  // four loads in flight per thread
+    const Px4 w0 = load4(i), w1 = load4(i + TPB), w2 = load4(i + 2 * TPB), w3 = load4(i + 3 * TPB);
+    acc += grey_bright4(j.fb, w0) + grey_bright4(j.fb, w1) + grey_bright4(j.fb, w2) + grey_bright4(j.fb, w3);
+  }
+  for (; i < groups; i += TPB) acc += grey_bright4(j.fb, load4(i));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
+  __shared__ unsigned long part[TPB / 64];
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long S = 0;
+#pragma unroll
+    for (int w = 0; w < TPB / 64; ++w) S += part[w];
+    const unsigned long un = (unsigned long)n;
+    *out = (int)(S / un + (2 * (S % un) >= un ? 1 : 0));  // (2 S + n) / (2 n) without the doubled sum
+  }
+}
+
+// clip_batch_kernel with the jitter in every tap: grid, ownership, borders and stores are its own.
+__global__ void clip_batch_jitter_kernel(const long* __restrict__ tab, const long* __restrict__ frame_idx,
+                                         const long* __restrict__ slow_idx, const long* __restrict__ jit,
+                                         const int* __restrict__ means, int n_fast, int n_slow, int crop, int reverse,
+                                         NormArgs nm, float* __restrict__ fast, float* __restrict__ slow, int ph, int pw,
+                                         int Wp, int plane) {
+  const int p = blockIdx.x * TPB + threadIdx.x;
+  if (p >= plane) return;
+  const int f = blockIdx.y, b = blockIdx.z;
+  const ClipGeo g = batch_row(tab, b, crop);
+  JitGeo j = jitter_row(jit, b);
+  const int yp = p / Wp, xp = p - yp * Wp;
+  f32x4 o = {0.f, 0.f, 0.f, 0.f};
+  const int yy = yp - ph, xx = xp - pw;
+  if (g.ok && j.ok && yy >= 0 && yy < crop && xx >= 0 && xx < crop) {
+    j.m = means[(long)b * n_fast + f];
+    const int ys = g.y0 + yy;
+    const int xs = g.x0 + (g.flip ? crop - 1 - xx : xx);
+    float c[3];
+    sample_rgb_jitter(batch_frame(g, frame_idx, b, n_fast, f, 3), g.H, g.W, g.new_h, g.new_w, ys, xs, nm, j, c);
+    if (reverse) {
+      o[0] = c[2]; o[1] = c[1]; o[2] = c[0];
+    } else {
+      o[0] = c[0]; o[1] = c[1]; o[2] = c[2];
+    }
+  }
+  *reinterpret_cast<f32x4*>(fast + (((long)b * n_fast + f) * plane + p) * 4) = o;
+  for (int k = 0; k < n_slow; ++k)  // n_slow <= n_fast / alpha entries, wave-uniform
+    if (slow_idx[k] == f) *reinterpret_cast<f32x4*>(slow + (((long)b * n_slow + k) * plane + p) * 4) = o;
+}
+
+// Host-side check of the jitter rows behind a batch table: [B][SF_JITTER_ROW] after the Slow positions.
+bool jitter_table_ok(const long* tab, int B, int n_fast, int n_slow) {
+  const long* jit = tab + (long)B * (BATCH_ROW + n_fast) + n_slow;
+  for (int b = 0; b < B; ++b)
+    if (!jitter_row_ok(jit + (long)b * JITTER_ROW)) return false;
+  return true;
+}
+
+bool means_ok(const int* means) { return means && (uintptr_t)means % sizeof(int) == 0; }
+
+void launch_grey_means(const long* table, int B, int n_fast, int n_slow, int crop, int* means, hipStream_t stream) {
+  const long* frame_idx = table + (long)B * BATCH_ROW;
+  hipLaunchKernelGGL(frame_grey_means_kernel, dim3(n_fast, B), dim3(TPB), 0, stream, table, frame_idx,
+                     frame_idx + (long)B * n_fast + n_slow, n_fast, crop, means);
+}
 // ---- all B clips of one DETECTION batch (AVA, `AVA.IMG_PROC_BACKEND == "pytorch"`), both pathways, in ONE launch
 // (datasets/ava_dataset.py:233-338 per sample; datasets/loader.py:18-52 collates).  The grid, the table idea, the Slow
 // search and the one-owner stores are clip_batch_kernel's; the pixel arithmetic is NOT sample_rgb's, because the AVA
@@ -795,6 +1023,44 @@ extern "C" int sf_clip_batch_mix_gray(const long* table_host, const long* table,
                        (hipStream_t)stream, table, frame_idx, slow_idx, mix, B, n_fast, n_slow, crop, mean, stdv, fast,
                        slow, ph, pw, Wp, (int)plane);
   }
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_frame_grey_means(const long* table_host, const long* table, int B, int n_fast, int n_slow, int* means,
+                                   void* stream) {
+  if (!table_host || !table || !means_ok(means) || B <= 0 || n_fast <= 0 || n_slow < 0 || n_slow > n_fast || B > 65535 ||
+      n_fast > 65535)
+    return SF_EINVAL;
+  // crop 0: the means read whole frames, there is no window to place
+  if (!batch_table_ok(table_host, B, n_fast, n_slow, 0) || !jitter_table_ok(table_host, B, n_fast, n_slow))
+    return SF_EINVAL;
+  launch_grey_means(table, B, n_fast, n_slow, 0, means, (hipStream_t)stream);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_clip_batch_jitter(const long* table_host, const long* table, int B, int n_fast, int n_slow, int crop,
+                                    int reverse, const float* mean3, const float* std3, int* means, float* fast,
+                                    float* slow, int ph, int pw, int Wp, void* stream) {
+  long plane = 0;
+  if (!mean3 || !std3 ||
+      !clip_batch_args_ok(table_host, table, B, n_fast, n_slow, crop, fast, slow, ph, pw, Wp, &plane))
+    return SF_EINVAL;
+  if (!means_ok(means) || !jitter_table_ok(table_host, B, n_fast, n_slow)) return SF_EINVAL;
+  if (!sf_aligned16(fast) || !sf_aligned16(slow)) return SF_EINVAL;
+  NormArgs nm;
+  for (int c = 0; c < 3; ++c) {
+    nm.m[c] = mean3[c];   // HOST pointers: three floats each
+    nm.s[c] = std3[c];
+  }
+  launch_grey_means(table, B, n_fast, n_slow, crop, means, (hipStream_t)stream);
+  SF_CHECK_LAUNCH();
+  const long* frame_idx = table + (long)B * BATCH_ROW;
+  const long* slow_idx = frame_idx + (long)B * n_fast;
+  hipLaunchKernelGGL(clip_batch_jitter_kernel, dim3(sf_cdiv(plane, TPB), n_fast, B), dim3(TPB), 0, (hipStream_t)stream,
+                     table, frame_idx, slow_idx, slow_idx + n_slow, means, n_fast, n_slow, crop, reverse, nm, fast, slow,
+                     ph, pw, Wp, (int)plane);
   SF_CHECK_LAUNCH();
   return SF_OK;
 }

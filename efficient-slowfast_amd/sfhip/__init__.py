@@ -72,6 +72,8 @@ _SIGNATURES = {
     "sf_clip_batch_det": (_ci, [_vp, _vp] + [_ci] * 6 + [_vp] * 4 + [_ci, _ci, _ci, _vp]),
     "sf_clip_batch_mix": (_ci, [_vp, _vp] + [_ci] * 5 + [_vp] * 4 + [_ci, _ci, _ci, _vp]),
     "sf_clip_batch_mix_gray": (_ci, [_vp, _vp] + [_ci] * 4 + [_cf, _cf, _vp, _vp, _ci, _ci, _ci, _vp]),
+    "sf_frame_grey_means": (_ci, [_vp, _vp, _ci, _ci, _ci, _pi, _vp]),
+    "sf_clip_batch_jitter": (_ci, [_vp, _vp] + [_ci] * 5 + [_vp, _vp, _pi, _vp, _vp, _ci, _ci, _ci, _vp]),
     "sf_ensemble_update": (_ci, [_vp] * 4 + [_pi] * 3 + [_ci] * 4 + [_vp]),
     "sf_ensemble_update_ml": (_ci, [_vp] * 3 + [_ci, _vp, _vp, _pi, _pi] + [_ci] * 4 + [_vp]),
     "sf_ncthw1_pack": (_ci, [_vp, _vp] + [_ci] * 7 + [_vp]),
@@ -513,6 +515,51 @@ def clip_batch_mix(table_host, table, n_slow, crop, mean, std, fast, slow=None, 
         m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
         s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
         _call("sf_clip_batch_mix", *head, 1 if reverse else 0, ctypes.cast(m3, _vp), ctypes.cast(s3, _vp), *tail)
+    return fast, slow
+
+
+SF_JITTER_ROW = 3  # include/sfhip.h: brightness, contrast and colour factors as float32 bits (int64 each)
+
+
+def _jitter_table(table_host, table, B, n_fast, n_slow, means, what):
+    """The checks the two jitter entries share: the table pair, its length, and `means` int32 [B, n_fast] on the GPU."""
+    if not means.is_cuda:
+        raise SfhipError("%s: means is on %s — the SlowFast hot path only runs on an MI355X GPU (no CPU fallback)" % (
+            what, means.device))
+    if not table.is_cuda or table_host.is_cuda:
+        raise SfhipError("%s: the batch table's copy lives on the GPU, table_host on the host" % what)
+    assert means.dtype == torch.int32 and means.is_contiguous() and tuple(means.shape) == (B, n_fast)
+    assert table_host.dtype == torch.int64 and table.dtype == torch.int64 and table_host.is_contiguous()
+    assert table.is_contiguous() and table_host.numel() == table.numel() == B * (9 + n_fast + SF_JITTER_ROW) + n_slow
+
+
+def frame_grey_means(table_host, table, n_slow, means):
+    """The grey mean of every (clip, Fast frame) of a batch after the clip's brightness stage (`sf_frame_grey_means`):
+    what ImageEnhance.Contrast blends against.  The table is clip_batch's followed by B jitter rows (brightness,
+    contrast, colour as float32 bits); means: int32 [B, n_fast] on the GPU, every element written."""
+    B, n_fast = means.shape
+    _jitter_table(table_host, table, B, n_fast, n_slow, means, "frame_grey_means")
+    _call("sf_frame_grey_means", _ptr(table_host), _ptr(table), B, n_fast, int(n_slow), _iptr(means))
+    return means
+
+
+def clip_batch_jitter(table_host, table, n_slow, crop, mean, std, means, fast, slow=None, reverse=False, ph=0, pw=0):
+    """`clip_batch` with Jester's colour jitter (PIL's ImageEnhance.Brightness, Contrast, Color) inside the launch
+    (`sf_clip_batch_jitter`): the table is clip_batch's followed by B jitter rows, `means` an int32 [B, n_fast] device
+    scratch the call fills first (one launch) and the clip launch reads.  RGB spans only.  Everything else — buffers,
+    layouts, the caller keeping the spans alive — is clip_batch's."""
+    _require_gpu(fast, "clip_batch_jitter")
+    assert fast.is_contiguous() and fast.dim() == 5 and fast.shape[4] == 4
+    B, n_fast = fast.shape[:2]
+    _jitter_table(table_host, table, B, n_fast, n_slow, means, "clip_batch_jitter")
+    if slow is not None:
+        _require_gpu(slow, "clip_batch_jitter")
+        assert slow.is_contiguous() and tuple(slow.shape) == (B, n_slow) + tuple(fast.shape[2:])
+    assert len(mean) == 3 and len(std) == 3, "the colour jitter is three-channel"
+    m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
+    _call("sf_clip_batch_jitter", _ptr(table_host), _ptr(table), B, n_fast, int(n_slow), int(crop), 1 if reverse else 0,
+          ctypes.cast(m3, _vp), ctypes.cast(s3, _vp), _iptr(means), _ptr(fast), _ptr(slow), ph, pw, fast.shape[3])
     return fast, slow
 
 

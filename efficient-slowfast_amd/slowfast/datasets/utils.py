@@ -10,7 +10,9 @@ views of one test video (`test_view_params` -> `gpu_test_views` -> `sf_clip_view
 batch, multigrid's short and long cycles included (`train_clip_params` -> `gpu_train_batch` -> `sf_clip_batch`).
 The detection (AVA) loader's preprocessing (datasets/ava_dataset.py:233-338, the "pytorch" backend) orders the
 arithmetic differently and carries boxes: `det_clip_params` / `det_boxes` -> `gpu_detection_batch` ->
-`sf_clip_batch_det`, again one upload and one launch per batch."""
+`sf_clip_batch_det`, again one upload and one launch per batch.  The Jester loader colour-jitters every train / val
+clip with PIL before normalising (decoder.py:456-469): `jester_clip_params` -> `gpu_train_batch_jitter` ->
+`sf_clip_batch_jitter` does that to the uint8 pixels the resampling taps read, bit for bit."""
 from slowfast._overlay import chain_module as _chain_module
 
 _chain_module(globals())  # the reference's namesake (when importable) supplies every name not defined below
@@ -408,6 +410,89 @@ def gpu_train_batch_mix(videos, samples, mix, mean, std, alpha, reverse_input_ch
     rows = table[table.numel() - B * sfhip.SF_MIX_ROW:].view(B, sfhip.SF_MIX_ROW)
     rows.mix_host = rows_host
     return (out if slow is None else [sfhip.PackedClip(slow, C, crop, crop, ph, pw)] + out), rows
+
+
+# ---- Jester's colour jitter (datasets/decoder.py:456-469 -> transform.RandomColorJitter, transform.py:692-717): the host
+# keeps the three draws per clip, the pixels are jittered inside the one-launch input step (sf_clip_batch_jitter).
+ColorJitter = collections.namedtuple("ColorJitter", "bright contrast color")
+ColorJitter.__doc__ = """The factors ImageEnhance.Brightness, .Contrast and .Color take for every frame of ONE clip
+(Python floats; the kernels use their float32 values, as PIL does).  A factor <= 0 skips its stage."""
+
+
+def sample_color_jitter(lo=0.4, hi=1.4):
+    """decoder.py:458-460: bright, contrast, color ~ uniform(lo, hi) from Python's `random`, in that order."""
+    bright = random.uniform(lo, hi)
+    contrast = random.uniform(lo, hi)
+    color = random.uniform(lo, hi)
+    return ColorJitter(bright, contrast, color)
+
+
+def jester_clip_params(cfg, mode, num_frames_total, height, width, short_cycle_idx=None, fps=None):
+    """The decisions of ONE sample of the Jester loader (datasets/jester.py:142-165, :186-189, :212-247) in `mode`
+    "train" or "val" — both are sampled and jittered like training clips there — for a decoded span of
+    num_frames_total frames of height x width: `train_clip_params`' decisions and the colour jitter of
+    decode(..., jester=True).  Returns (frame_indices, SpatialParams, ColorJitter).
+    RNG order, the reference's: Python `random` for the sampling rate (only with MULTIGRID.LONG_CYCLE_SAMPLING_RATE > 0),
+    the window start, then bright, contrast, color; numpy's global RNG for scale, crop y, crop x and flip (drawn after
+    decode returns; the two generators do not meet).  The reference does not jitter test views: mode "test" raises."""
+    if mode == "test":
+        raise NotImplementedError("the Jester loader neither jitters nor randomly samples its test views "
+                                  "(decode(..., jester_test=True)): take them from test_view_params")
+    if mode not in ("train", "val"):
+        raise NotImplementedError("Does not support {} mode".format(mode))
+    # the numpy draws of train_clip_params use the other generator, so taking the jitter after them keeps both streams
+    frames, params = train_clip_params(cfg, num_frames_total, height, width, short_cycle_idx=short_cycle_idx, fps=fps)
+    return frames, params, sample_color_jitter()
+
+
+def jitter_rows(jitters):
+    """The int64 host rows [B, 3] sf_clip_batch_jitter reads behind the batch table: per clip the brightness, contrast
+    and colour factors as the bit patterns of their float32 values (low 32 bits).  None: a clip that is not jittered
+    (three zeros: every stage skipped)."""
+    rows = torch.empty((len(jitters), sfhip.SF_JITTER_ROW), dtype=torch.int64)
+    for b, j in enumerate(jitters):
+        vals = (0.0, 0.0, 0.0) if j is None else tuple(float(v) for v in j)
+        if len(vals) != 3 or not all(abs(v) <= float(np.finfo(np.float32).max) for v in vals):  # NaN fails too
+            raise ValueError("jitter_rows: a clip takes three finite factors (bright, contrast, color), got %r" % (j,))
+        rows[b] = torch.tensor([_f32_bits(v) for v in vals], dtype=torch.int64)
+    return rows
+
+
+def gpu_train_batch_jitter(videos, samples, jitters, mean, std, alpha, reverse_input_channel=False, pad=(0, 0),
+                           wp=None):
+    """`gpu_train_batch` with Jester's colour jitter inside the call (sf_clip_batch_jitter): `jitters` holds one
+    ColorJitter (or None) per clip, as `jester_clip_params` returns them.  Still one table upload — the jitter rows ride
+    behind the batch table — and one ABI call, which is two launches: the grey mean of every sampled frame (the
+    contrast stage's reference), then the clip launch.  RGB spans only.  Returns [slow, fast] ([clip] with alpha=None)
+    PackedClips holding the bits `gpu_train_batch` gives for spans jittered frame by frame with PIL."""
+    B = len(videos)
+    assert B == len(samples) and B > 0
+    if len(jitters) != B:
+        raise ValueError("gpu_train_batch_jitter: jitter factors for %d clips, the batch has %d" % (len(jitters), B))
+    crop = samples[0][1].crop
+    n_fast = len(samples[0][0])
+    assert all(p.crop == crop and len(f) == n_fast for f, p in samples)
+    ph, pw = pad
+    wp = crop + 2 * pw if wp is None else wp
+    dev = videos[0].device
+    for v in videos:
+        if v.dim() == 3 or v.shape[3] == 1:
+            raise ValueError("gpu_train_batch_jitter: the colour jitter is defined for RGB spans [T, H, W, 3], got %s" %
+                             (tuple(v.shape),))
+        if not v.is_cuda or v.device != dev:
+            raise sfhip.SfhipError("gpu_train_batch_jitter: every decoded span lives on one GPU, got %s" % v.device)
+        assert v.dtype == torch.uint8 and v.dim() == 4 and v.shape[3] == 3 and v.is_contiguous()
+    slow_idx = slow_frame_indices(n_fast, alpha) if alpha is not None else torch.zeros(0, dtype=torch.long)
+    n_slow = slow_idx.numel()
+    table_host = torch.cat([batch_table(videos, samples, slow_idx), jitter_rows(jitters).flatten()]).contiguous()
+    table = table_host.to(dev)  # the one upload: rows, frame indices, Slow positions and jitter rows together
+    means = torch.empty((B, n_fast), dtype=torch.int32, device=dev)  # the first launch writes every element
+    fast = torch.empty((B, n_fast, crop + 2 * ph, wp, 4), dtype=torch.float32, device=dev)
+    slow = torch.empty((B, n_slow, crop + 2 * ph, wp, 4), dtype=torch.float32, device=dev) if n_slow else None
+    sfhip.clip_batch_jitter(table_host, table, n_slow, crop, mean, std, means, fast, slow,
+                            reverse=reverse_input_channel, ph=ph, pw=pw)
+    out = [sfhip.PackedClip(fast, 3, crop, crop, ph, pw)]
+    return out if slow is None else [sfhip.PackedClip(slow, 3, crop, crop, ph, pw)] + out
 
 
 # ---- the detection (AVA) input step: datasets/ava_dataset.py:233-338 with AVA.IMG_PROC_BACKEND "pytorch", and the box

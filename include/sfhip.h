@@ -690,6 +690,42 @@ int sf_clip_batch_mix(const long* table_host, const long* table, int B, int n_fa
 int sf_clip_batch_mix_gray(const long* table_host, const long* table, int B, int n_fast, int n_slow, int crop,
                            float mean, float stdv, float* fast, float* slow, int ph, int pw, int Wp, void* stream);
 
+/* ---- Jester's colour jitter inside the training input step (datasets/decoder.py:456-469: decode(..., jester=True)
+ * draws brightness, contrast and colour factors per clip and passes every sampled frame through
+ * transform.RandomColorJitter, datasets/transform.py:692-717 — PIL's ImageEnhance.Brightness, then Contrast, then
+ * Color — before tensor_normalize).  Here the jitter acts on each uint8 source pixel a resampling tap reads: no frame
+ * goes back to the host.  The arithmetic is PIL's (checked against Pillow 12.2.0), bit for bit:
+ *   blend(f, x0, x1) = fl(x0 + fl(f * (x1 - x0))) in float32 — f is the factor as a C float, one rounded product and
+ *     one rounded sum, never an fma — truncated toward zero for 0 <= f <= 1, else clipped to [0, 255] and truncated;
+ *   grey(c) = (19595 c0 + 38470 c1 + 7471 c2 + 32768) >> 16 (channel 0 is R);
+ *   brightness: c_i <- blend(fb, 0, c_i); contrast: c_i <- blend(fc, m, c_i) with m the frame's grey mean; colour:
+ *     c_i <- blend(fs, grey(c), c_i); in that order, a stage with a factor <= 0 skipped;
+ *   m = (2 S + n) / (2 n) in integers, S the sum of grey(.) of the brightness-jittered pixels over the WHOLE decoded
+ *     H x W frame (n = H * W), which is int(ImageStat.Stat(L).mean[0] + 0.5).  m belongs to a frame, the factors to a clip.
+ * A JITTER ROW is SF_JITTER_ROW = 3 int64: the brightness, contrast and colour factors, each a float32 bit pattern in
+ *   the low 32 bits (the high 32 zero); valid when all three are finite.  The table is sf_clip_batch's (B rows,
+ *   B * n_fast frame indices, n_slow Slow positions) followed by B jitter rows.
+ * sf_frame_grey_means: means[b * n_fast + f] (device int32) = the grey mean of clip b's source frame frame_idx[b][f]
+ *   after clip b's brightness stage.  One workgroup per (clip, Fast frame), an integer reduction in registers and LDS
+ *   with a 64-bit sum, one owner per element, no atomics; aligned 12-byte loads between a byte-wise head and tail.  A
+ *   clip whose contrast factor is <= 0 gets 0 for its frames without a read; so does a device row that fails
+ *   sf_clip_batch's row check (with no crop window) or whose factors are not finite.
+ *   SF_EINVAL, nothing launched: what sf_clip_batch asks of the table (the crop window aside), a factor word of the
+ *   host table that is not a finite float32 with a zero high half, `means` null or not 4-byte aligned.
+ * sf_clip_batch_jitter: the means launch into `means` (int32 [B][n_fast], device, need not be initialised), then ONE
+ *   clip launch of sf_clip_batch's shape — same grid, 16-byte stores, zero borders, a frame that goes to both pathways
+ *   computed once and stored twice — whose every tap goes through the jitter before u / 255.  A clip whose three
+ *   factors are all <= 0 holds sf_clip_batch's bits.  Clip b is written as zeros when its device batch row or its
+ *   device jitter row fails the check.  RGB only: ImageEnhance.Color leaves a one-channel image as it is, and Jester is RGB.
+ *   SF_EINVAL, nothing launched: sf_clip_batch's list, a factor word of the host table that is not valid, `means` null
+ *   or not 4-byte aligned.  mean3 / std3: HOST. */
+#define SF_JITTER_ROW 3
+int sf_frame_grey_means(const long* table_host, const long* table, int B, int n_fast, int n_slow, int* means,
+                        void* stream);
+int sf_clip_batch_jitter(const long* table_host, const long* table, int B, int n_fast, int n_slow, int crop,
+                         int reverse, const float* mean3, const float* std3, int* means, float* fast, float* slow,
+                         int ph, int pw, int Wp, void* stream);
+
 /* ---- detection input step, one launch per batch (AVA with AVA.IMG_PROC_BACKEND "pytorch":
  * datasets/ava_dataset.py:233-338 _images_and_boxes_preprocessing and the transform.py functions it calls — :283-337
  * random_short_side_scale_jitter, :359-392 random_crop, :395-422 horizontal_flip, :425-468 uniform_crop, :636-663
