@@ -2,7 +2,9 @@
 // meter's top-k counts in one launch (sf_ce_topk; sf_bce for the multi-label and detection losses; sf_ce_topk_w and
 // sf_bce_w are the same launches with class weights read from device memory), torch.optim.SGD over
 // every parameter of every group in one launch (sf_sgd_step), torch.optim.Adam in two (sf_adam_step: the step counts,
-// then the update).  Nothing here needs the host: the statistics go to a ring in device memory that the meter drains once
+// then the update), torch.optim.AdamW the same way (sf_adamw_step: the same kernel body with the decay decoupled) and SGD
+// behind a per-tensor trust ratio (sf_lars_sgd_step: sf_sgd_step's body reading {r, wd_t} per tensor from the array
+// lars.hip::sf_lars_ratios leaves in device memory).  Nothing here needs the host: the statistics go to a ring in device memory that the meter drains once
 // per LOG_PERIOD, the hyper-parameters are read from device memory (the LR schedule is a 4-byte write a replayed graph
 // sees) and a non-finite loss switches the update off through a flag the loss kernel leaves.
 #include "common.h"
@@ -342,8 +344,12 @@ struct Hyper {
 };
 
 // torch/optim/sgd.py::_single_tensor_sgd for one element; returns the new parameter, *b the new momentum buffer.
-__device__ __forceinline__ float sgd1(float p, float g, float* b, const Hyper& h, bool has_buf, bool first) {
+// LARS (sf_lars_sgd_step): h.wd is the TENSOR's weight decay and the decayed gradient is scaled by the tensor's trust
+// ratio r, one fp32 multiply; r == 1 is a multiply by one: sf_sgd_step's bits.
+template <bool LARS>
+__device__ __forceinline__ float sgd1(float p, float g, float* b, const Hyper& h, bool has_buf, bool first, float r) {
   if (h.wd != 0.f) g = fmaf(h.wd, p, g);
+  if (LARS) g *= r;
   if (has_buf) {
     const float nb = first ? g : fmaf(h.mom, *b, h.keep * g);
     *b = nb;
@@ -357,11 +363,11 @@ __device__ __forceinline__ float* as_global(long addr) {
   return (float*)(__attribute__((address_space(1))) float*)(unsigned long)addr;
 }
 
-__global__ __launch_bounds__(SGD_TPB) void sgd_step_kernel(const long* __restrict__ table,
-                                                           const long* __restrict__ chunks,
-                                                           const float* __restrict__ hyper,
-                                                           const float* __restrict__ guard, int n_tensors, int n_groups,
-                                                           int zero_grad) {
+template <bool LARS>
+__device__ __forceinline__ void sgd_step_body(const long* __restrict__ table, const long* __restrict__ chunks,
+                                              const float* __restrict__ hyper, const float* __restrict__ ratios,
+                                              const float* __restrict__ guard, int n_tensors, int n_groups,
+                                              int zero_grad) {
   if (guard != nullptr && guard[0] != 0.f) return;  // the step's loss was not finite (or NaN itself): no update
   const long* c = chunks + (long)blockIdx.x * 2;
   const long ti = c[0], start = c[1];
@@ -377,6 +383,11 @@ __global__ __launch_bounds__(SGD_TPB) void sgd_step_kernel(const long* __restric
   h.mom = hy[2];
   h.keep = 1.f - hy[3];
   h.nesterov = hy[4] != 0.f;
+  float r = 1.f;
+  if (LARS) {  // {r, wd_t} of this TENSOR, as sf_lars_ratios left them; the group's weight decay is not applied again
+    r = ratios[2 * ti];
+    h.wd = ratios[2 * ti + 1];
+  }
   const bool has_buf = row[2] != 0 && h.mom != 0.f;
   const bool first = row[5] != 0;
   float* p = as_global(row[0]) + start;
@@ -394,7 +405,7 @@ __global__ __launch_bounds__(SGD_TPB) void sgd_step_kernel(const long* __restric
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float be = bv[e];
-        pv[e] = sgd1(pv[e], gv[e], &be, h, has_buf, first);
+        pv[e] = sgd1<LARS>(pv[e], gv[e], &be, h, has_buf, first, r);
         bv[e] = be;
       }
       reinterpret_cast<f32x4*>(p)[i] = pv;
@@ -404,18 +415,35 @@ __global__ __launch_bounds__(SGD_TPB) void sgd_step_kernel(const long* __restric
     const int i = (n4 << 2) + threadIdx.x;  // up to three elements left
     if (i < len) {
       float be = (has_buf && !first) ? b[i] : 0.f;
-      p[i] = sgd1(p[i], g[i], &be, h, has_buf, first);
+      p[i] = sgd1<LARS>(p[i], g[i], &be, h, has_buf, first, r);
       if (has_buf) b[i] = be;
       if (zero_grad) g[i] = 0.f;
     }
   } else {
     for (int i = threadIdx.x; i < len; i += SGD_TPB) {
       float be = (has_buf && !first) ? b[i] : 0.f;
-      p[i] = sgd1(p[i], g[i], &be, h, has_buf, first);
+      p[i] = sgd1<LARS>(p[i], g[i], &be, h, has_buf, first, r);
       if (has_buf) b[i] = be;
       if (zero_grad) g[i] = 0.f;
     }
   }
+}
+
+__global__ __launch_bounds__(SGD_TPB) void sgd_step_kernel(const long* __restrict__ table,
+                                                           const long* __restrict__ chunks,
+                                                           const float* __restrict__ hyper,
+                                                           const float* __restrict__ guard, int n_tensors, int n_groups,
+                                                           int zero_grad) {
+  sgd_step_body<false>(table, chunks, hyper, nullptr, guard, n_tensors, n_groups, zero_grad);
+}
+
+__global__ __launch_bounds__(SGD_TPB) void lars_sgd_step_kernel(const long* __restrict__ table,
+                                                                const long* __restrict__ chunks,
+                                                                const float* __restrict__ hyper,
+                                                                const float* __restrict__ ratios,
+                                                                const float* __restrict__ guard, int n_tensors,
+                                                                int n_groups, int zero_grad) {
+  sgd_step_body<true>(table, chunks, hyper, ratios, guard, n_tensors, n_groups, zero_grad);
 }
 
 // the chunks tile the tensors exactly, in table order: (0, 0), (0, C), ..., (1, 0), ... (numel: column `col` of a row)
@@ -459,13 +487,18 @@ __global__ __launch_bounds__(SGD_TPB) void adam_tick_kernel(const long* __restri
 }
 
 struct AdamScalars {
-  float w1, b2, w2, step_size, inv_bc2_sqrt, eps, wd;  // w_i = 1 - beta_i
+  float w1, b2, w2, step_size, inv_bc2_sqrt, eps, wd;  // w_i = 1 - beta_i; DECOUPLED: wd holds 1 - lr * weight_decay
   int ok;
 };
 
 // torch/optim/adam.py::_single_tensor_adam (amsgrad = maximize = False) for one element; returns the new parameter.
+// DECOUPLED (sf_adamw_step, torch.optim.AdamW): p *= 1 - lr * wd in front, nothing added to g.
+template <bool DECOUPLED>
 __device__ __forceinline__ float adam1(float p, float g, float* m, float* v, const AdamScalars& a) {
-  if (a.wd != 0.f) g = fmaf(a.wd, p, g);
+  if (DECOUPLED)
+    p *= a.wd;
+  else if (a.wd != 0.f)
+    g = fmaf(a.wd, p, g);
   const float dm = g - *m;
   const float nm = a.w1 < 0.5f ? fmaf(a.w1, dm, *m) : g - dm * (1.f - a.w1);  // exp_avg.lerp_(grad, 1 - beta1)
   const float nv = fmaf(a.w2 * g, g, a.b2 * *v);
@@ -475,11 +508,10 @@ __device__ __forceinline__ float adam1(float p, float g, float* m, float* v, con
   return fmaf(-a.step_size, nm / denom, p);
 }
 
-__global__ __launch_bounds__(SGD_TPB) void adam_step_kernel(const long* __restrict__ table,
-                                                            const long* __restrict__ chunks,
-                                                            const double* __restrict__ hyper,
-                                                            const float* __restrict__ guard, int n_tensors,
-                                                            int n_groups, int zero_grad) {
+template <bool DECOUPLED>
+__device__ __forceinline__ void adam_step_body(const long* __restrict__ table, const long* __restrict__ chunks,
+                                               const double* __restrict__ hyper, const float* __restrict__ guard,
+                                               int n_tensors, int n_groups, int zero_grad) {
   __shared__ AdamScalars s_a;
   if (guard != nullptr && guard[0] != 0.f) return;  // as in sgd_step_kernel: nothing moves
   const long* c = chunks + (long)blockIdx.x * 2;
@@ -501,7 +533,7 @@ __global__ __launch_bounds__(SGD_TPB) void adam_step_kernel(const long* __restri
     a.step_size = (float)(lr / bc1);
     a.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
     a.eps = (float)hy[3];
-    a.wd = (float)hy[4];
+    a.wd = DECOUPLED ? (float)(1.0 - lr * hy[4]) : (float)hy[4];  // torch multiplies by the Python float 1 - lr * wd
     a.ok = t >= 1.0 && bc1 > 0.0 && bc2 > 0.0;  // a step count nobody advanced: leave the chunk alone
     s_a = a;
   }
@@ -524,7 +556,7 @@ __global__ __launch_bounds__(SGD_TPB) void adam_step_kernel(const long* __restri
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float me = mv[e], ve = vv[e];
-        pv[e] = adam1(pv[e], gv[e], &me, &ve, a);
+        pv[e] = adam1<DECOUPLED>(pv[e], gv[e], &me, &ve, a);
         mv[e] = me;
         vv[e] = ve;
       }
@@ -536,7 +568,7 @@ __global__ __launch_bounds__(SGD_TPB) void adam_step_kernel(const long* __restri
     const int i = (n4 << 2) + threadIdx.x;  // up to three elements left
     if (i < len) {
       float me = m[i], ve = v[i];
-      p[i] = adam1(p[i], g[i], &me, &ve, a);
+      p[i] = adam1<DECOUPLED>(p[i], g[i], &me, &ve, a);
       m[i] = me;
       v[i] = ve;
       if (zero_grad) g[i] = 0.f;
@@ -544,12 +576,28 @@ __global__ __launch_bounds__(SGD_TPB) void adam_step_kernel(const long* __restri
   } else {
     for (int i = threadIdx.x; i < len; i += SGD_TPB) {
       float me = m[i], ve = v[i];
-      p[i] = adam1(p[i], g[i], &me, &ve, a);
+      p[i] = adam1<DECOUPLED>(p[i], g[i], &me, &ve, a);
       m[i] = me;
       v[i] = ve;
       if (zero_grad) g[i] = 0.f;
     }
   }
+}
+
+__global__ __launch_bounds__(SGD_TPB) void adam_step_kernel(const long* __restrict__ table,
+                                                            const long* __restrict__ chunks,
+                                                            const double* __restrict__ hyper,
+                                                            const float* __restrict__ guard, int n_tensors,
+                                                            int n_groups, int zero_grad) {
+  adam_step_body<false>(table, chunks, hyper, guard, n_tensors, n_groups, zero_grad);
+}
+
+__global__ __launch_bounds__(SGD_TPB) void adamw_step_kernel(const long* __restrict__ table,
+                                                             const long* __restrict__ chunks,
+                                                             const double* __restrict__ hyper,
+                                                             const float* __restrict__ guard, int n_tensors,
+                                                             int n_groups, int zero_grad) {
+  adam_step_body<true>(table, chunks, hyper, guard, n_tensors, n_groups, zero_grad);
 }
 
 bool adam_tables_ok(const long* tab, int n_tensors, const long* chunks, int n_chunks, const double* hyper,
@@ -620,6 +668,18 @@ extern "C" int sf_sgd_step(const long* table_host, const long* table, int n_tens
   return SF_OK;
 }
 
+extern "C" int sf_lars_sgd_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host,
+                                const long* chunks, int n_chunks, const float* hyper_host, const float* hyper,
+                                int n_groups, const float* ratios, const float* guard, int zero_grad, void* stream) {
+  if (!table_host || !table || !chunks_host || !chunks || !hyper_host || !hyper || !ratios) return SF_EINVAL;
+  if (n_tensors <= 0 || n_chunks <= 0 || n_groups <= 0 || (zero_grad != 0 && zero_grad != 1)) return SF_EINVAL;
+  if (!sgd_tables_ok(table_host, n_tensors, chunks_host, n_chunks, hyper_host, n_groups)) return SF_EINVAL;
+  hipLaunchKernelGGL(lars_sgd_step_kernel, dim3(n_chunks), dim3(SGD_TPB), 0, (hipStream_t)stream, table, chunks, hyper,
+                     ratios, guard, n_tensors, n_groups, zero_grad);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
 extern "C" int sf_bce(const float* x, int ldx, const float* y, int ldy, int N, int K, int from_logits, float* dx,
                       float* ring, int* counter, int cap, float* loss_out, void* stream) {
   if (!x || !y || !dx || !ring || !counter || !loss_out) return SF_EINVAL;
@@ -651,6 +711,20 @@ extern "C" int sf_adam_step(const long* table_host, const long* table, int n_ten
   hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(SGD_TPB), 0, (hipStream_t)stream, table, guard, n_tensors);
   SF_CHECK_LAUNCH();
   hipLaunchKernelGGL(adam_step_kernel, dim3(n_chunks), dim3(SGD_TPB), 0, (hipStream_t)stream, table, chunks, hyper,
+                     guard, n_tensors, n_groups, zero_grad);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+extern "C" int sf_adamw_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host,
+                             const long* chunks, int n_chunks, const double* hyper_host, const double* hyper,
+                             int n_groups, const float* guard, int zero_grad, void* stream) {
+  if (!table_host || !table || !chunks_host || !chunks || !hyper_host || !hyper) return SF_EINVAL;
+  if (n_tensors <= 0 || n_chunks <= 0 || n_groups <= 0 || (zero_grad != 0 && zero_grad != 1)) return SF_EINVAL;
+  if (!adam_tables_ok(table_host, n_tensors, chunks_host, n_chunks, hyper_host, n_groups)) return SF_EINVAL;
+  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(SGD_TPB), 0, (hipStream_t)stream, table, guard, n_tensors);
+  SF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(adamw_step_kernel, dim3(n_chunks), dim3(SGD_TPB), 0, (hipStream_t)stream, table, chunks, hyper,
                      guard, n_tensors, n_groups, zero_grad);
   SF_CHECK_LAUNCH();
   return SF_OK;

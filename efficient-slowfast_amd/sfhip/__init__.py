@@ -216,6 +216,10 @@ _SIGNATURES = {
     "sf_grad_norm": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _pi, _ci, _vp]),
     "sf_grad_scale": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp]),
     "sf_grad_clamp": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp]),
+    # large-batch optimizers: one-call AdamW, per-tensor LARS trust ratios (two launches) and the SGD step behind them
+    "sf_adamw_step": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _ci, _vp]),
+    "sf_lars_sgd_step": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp]),
+    "sf_lars_ratios": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
     # evaluation: top-k errors of a batch, the epoch's row store, mean average precision
     "sf_topk_errors": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _pi, _ci, _vp]),
     "sf_rows_append": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp]),

@@ -21,8 +21,12 @@
   change into one small copy, and a captured step follows the schedule.
 * `HipAdam` — `torch.optim.Adam` the same way (`sf_adam_step`: the step counts live in device memory and advance in a
   launch of their own in front of the update, so a replayed step keeps counting).
-* `construct_hip_solver(model, cfg)` — models/optimizer.py:26-69: `construct_hip_optimizer` for `sgd`,
-  `construct_hip_adam` for `adam`.
+* `HipAdamW` — `torch.optim.AdamW`, HipAdam's kernel body with the decay decoupled (`sf_adamw_step`).
+* `HipLARS` — HipSGD behind a layer-wise trust ratio (LARS / LARC): both norms of every tensor in two launches
+  (`sf_lars_ratios`), then the SGD launch reading {r, wd_t} per tensor (`sf_lars_sgd_step`).
+* `construct_hip_solver(model, cfg)` — models/optimizer.py:26-69: `construct_hip_optimizer` for `sgd`
+  (`construct_hip_lars` with upstream's SOLVER.LARS_ON), `construct_hip_adam` for `adam`, `construct_hip_adamw` for
+  upstream's `adamw`.
 * `HipGradClip` — `torch.nn.utils.clip_grad_norm_` / `clip_grad_value_` between the backward pass and `step()`: a
   fixed-order fp64 global norm (`sf_grad_norm`), a scale launch that touches nothing when nothing needs clipping
   (`sf_grad_scale`), the value clamp (`sf_grad_clamp`); a non-finite gradient raises `.guard`, which `step(guard=)` takes.
@@ -37,6 +41,7 @@ import sfhip
 RING_ROW = 8
 TAB_ROW, HYP_ROW = 6, 5
 ADAM_TAB_ROW, ADAM_HYP_ROW = 7, 5
+LARS_TAB_ROW, LARS_HYP_ROW = 6, 3
 STAGE_SLOTS = 16
 ROW_LOSS, ROW_TOP1, ROW_TOPK, ROW_FLAG, ROW_N, ROW_BAD, ROW_KIND = 0, 1, 2, 3, 4, 5, 6
 KIND_CE, KIND_BCE, KIND_EVAL = 0, 1, 2  # ROW_KIND: which kernel wrote the row (2: sf_topk_errors, no loss)
@@ -543,6 +548,59 @@ def adam_step(table_host, table, chunks_host, chunks, hyper_host, hyper, guard=N
                 zero_grad)
 
 
+def build_lars_tables(entries, chunk):
+    """entries: (parameter address, gradient address, numel, group, ignored) per tensor -> (table int64 [n, 6] with the
+    index of the tensor's first chunk in column 4, chunks int64 [n_chunks, 2]), tiled as build_sgd_tables does."""
+    rows, first = [], 0
+    for p, g, numel, group, ignored in entries:
+        rows.append((int(p), int(g), int(numel), int(group), first, 1 if ignored else 0))
+        first += (int(numel) + chunk - 1) // chunk
+    return _build_tables(rows, chunk, LARS_TAB_ROW, 2)
+
+
+def lars_ratios(table_host, table, chunks_host, chunks, hyper_host, hyper, partials, ratios, state, guard=None):
+    """One `sf_lars_ratios` call (two launches): {r, wd_t} of every tensor of the table into ratios (fp32 [n, 2]) and
+    the guard into state (fp32 [8]: [4] non-finite flag, [5] guard_out).  hyper fp32 [n_groups + 1, 3] = lr,
+    weight_decay, apply per group, then trust_coefficient, eps, clip; partials fp64 [n_chunks, 2]; guard the loss's
+    (or the clipper's) guard or None."""
+    for h, d in ((table_host, table), (chunks_host, chunks)):
+        assert h.dtype == d.dtype == torch.int64 and h.is_contiguous() and d.is_contiguous() and not h.is_cuda
+        assert h.shape == d.shape
+    assert hyper_host.dtype == hyper.dtype == torch.float32 and hyper_host.shape == hyper.shape
+    assert hyper.is_contiguous() and hyper_host.is_contiguous() and hyper_host.shape[0] >= 2
+    if not (table.is_cuda and chunks.is_cuda and hyper.is_cuda and partials.is_cuda and ratios.is_cuda and state.is_cuda):
+        raise sfhip.SfhipError("lars_ratios: tables, hyper, partials, ratios and state live on the GPU — there is no CPU "
+                               "fallback")
+    assert partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= 2 * chunks_host.shape[0]
+    assert ratios.dtype == torch.float32 and ratios.is_contiguous() and ratios.numel() >= 2 * table_host.shape[0]
+    assert state.dtype == torch.float32 and state.is_contiguous() and state.numel() >= CLIP_STATE
+    sfhip._call("sf_lars_ratios", _vp(table_host), _vp(table), table_host.shape[0], _vp(chunks_host), _vp(chunks),
+                chunks_host.shape[0], _vp(hyper_host), _vp(hyper), hyper_host.shape[0] - 1, _vp(guard), _vp(partials),
+                _vp(ratios), _vp(state), tag="lars_ratios")
+
+
+def lars_sgd_step(table_host, table, chunks_host, chunks, hyper_host, hyper, ratios, guard=None, zero_grad=False):
+    """One `sf_lars_sgd_step` launch: `sgd_step` with {r, wd_t} per tensor from `ratios` (fp32 [n, 2] on the GPU)."""
+    for h, d in ((table_host, table), (chunks_host, chunks)):
+        assert h.dtype == d.dtype == torch.int64 and h.is_contiguous() and d.is_contiguous() and not h.is_cuda
+        assert h.shape == d.shape
+    assert hyper_host.dtype == hyper.dtype == torch.float32 and hyper_host.shape == hyper.shape
+    assert hyper.is_contiguous() and hyper_host.is_contiguous()
+    if not (table.is_cuda and chunks.is_cuda and hyper.is_cuda and ratios.is_cuda):
+        raise sfhip.SfhipError("lars_sgd_step: table, chunks, hyper and ratios live on the GPU — there is no CPU "
+                               "fallback")
+    assert ratios.dtype == torch.float32 and ratios.is_contiguous() and ratios.numel() >= 2 * table_host.shape[0]
+    sfhip._call("sf_lars_sgd_step", _vp(table_host), _vp(table), table_host.shape[0], _vp(chunks_host), _vp(chunks),
+                chunks_host.shape[0], _vp(hyper_host), _vp(hyper), hyper_host.shape[0], _vp(ratios), _vp(guard),
+                1 if zero_grad else 0, tag="lars_sgd_step")
+
+
+def adamw_step(table_host, table, chunks_host, chunks, hyper_host, hyper, guard=None, zero_grad=False):
+    """One `sf_adamw_step` call (two launches); tables and hyper as `adam_step` takes them."""
+    _table_step("sf_adamw_step", torch.float64, table_host, table, chunks_host, chunks, hyper_host, hyper, guard,
+                zero_grad)
+
+
 class _TableOptimizer(object):
     """What HipSGD and HipAdam share, mixed in in front of torch's optimizer: the parameter checks, 16-byte aligned
     state slots carved from allocations the optimizer owns, the address table cached by a cheap signature, the pinned
@@ -778,21 +836,113 @@ class HipSGD(_TableOptimizer, torch.optim.SGD):
         self._table_dev = self._table.to(self._table_dev.device)
 
 
-# ---------------------------------------------------------------------------------------------------------- Adam
-class HipAdam(_TableOptimizer, torch.optim.Adam):
-    """torch.optim.Adam (same constructor, param_groups and state_dict keys) whose `step()` is ONE native call over every
-    parameter of every group (`sf_adam_step`).
+# ---------------------------------------------------------------------------------------------------------- LARS
+class HipLARS(HipSGD):
+    """HipSGD behind a layer-wise trust ratio — LARS / LARC (upstream SlowFast's SOLVER.LARS_ON, NVIDIA apex's LARC):
 
-    `exp_avg`, `exp_avg_sq` and `step` are 16-byte aligned views of one allocation owned by the optimizer; `step` is a
-    float32 scalar in DEVICE memory per parameter (torch keeps it on the host), advanced by the call itself, so a
-    captured step keeps counting when it is replayed.  They appear in `state[p]` from the parameter's first step on;
-    a parameter whose `.grad` is None is left untouched and gets no state.  `step(guard=, zero_grad=)` as in HipSGD: a
-    guarded-off step moves nothing — parameters, moments, step counts, gradients."""
-    _NAME, _TORCH = "HipAdam", "torch.optim.Adam"
-    _REFUSED = ("amsgrad", "maximize", "differentiable", "decoupled_weight_decay")
+        opt = HipLARS(groups, lr=..., momentum=0.9, weight_decay=1e-4, trust_coefficient=0.02, clip=True)
+        loss.backward(); opt.step(guard=loss_fun.guard, zero_grad=True)
+
+    Per tensor, with pn = ||p||, gn = ||g|| and the group's lr and weight decay wd:
+    r = trust_coefficient * pn / (gn + pn * wd + eps), with `clip` r = min(r / lr, 1) (LARC's clipping mode: the
+    step never exceeds plain SGD's); then g = (g + wd * p) * r goes through SGD's momentum and p -= lr * g.  A tensor
+    with a zero norm gets r = 1 and no decay.  Groups with `apply_LARS` False (a group key, default True) and, with
+    `ignore_1d_param`, one-dimensional parameters (BN scales, biases) get plain SGD with weight decay.
+
+    `step()` is two native calls: `sf_lars_ratios` (two launches: both norms of every tensor in fp64 in a fixed order —
+    equal gradients give equal bits, whatever their alignment) and `sf_lars_sgd_step` (HipSGD's launch reading {r, wd_t}
+    per tensor).  Nothing is read on the host: lr, weight decay, trust_coefficient, eps and the switches live in device
+    memory (`upload_hyper()` as for HipSGD, so a captured step follows the schedule), `.ratios` is a device fp32
+    [n_tensors, 2] view (table order: the parameters with a gradient, group by group) and `.guard` a fixed-address
+    float32 [1] that is non-zero when the `guard` handed to `step()` was raised or a parameter or gradient is not
+    finite — the update launch takes it, so such a step moves nothing.  Partials, ratios and that state are views of ONE
+    allocation the optimizer owns.  `state_dict()` is torch.optim.SGD's (the ratios are not state; `apply_LARS` rides
+    in the param_groups, and groups loaded without it keep the value they had)."""
+    _NAME = "HipLARS"
+
+    def __init__(self, params, *args, trust_coefficient=0.02, clip=True, eps=1e-8, ignore_1d_param=False, **kwargs):
+        for name, v in (("trust_coefficient", trust_coefficient), ("eps", eps)):
+            f = float(v)
+            if not (f >= 0.0) or f == float("inf"):
+                raise ValueError("HipLARS: %s must be a finite number that is not negative, got %r" % (name, v))
+        self.trust_coefficient, self.eps = float(trust_coefficient), float(eps)
+        self.clip, self.ignore_1d_param = bool(clip), bool(ignore_1d_param)
+        self._lars_table = self._lars_table_dev = self._lars_block = None
+        self._partials = self._ratios = self._lars_state = None
+        super().__init__(params, *args, **kwargs)
+        self.defaults["apply_LARS"] = True
+        for g in self.param_groups:
+            g.setdefault("apply_LARS", True)
+
+    def load_state_dict(self, state_dict):
+        keep = [g.get("apply_LARS", True) for g in self.param_groups]
+        super().load_state_dict(state_dict)
+        for g, a in zip(self.param_groups, keep):
+            g.setdefault("apply_LARS", a)
+
+    # ---- device memory this object owns
+    def _lars_field(self, name):
+        if self._lars_state is None:
+            raise RuntimeError("HipLARS.%s: nothing has been computed yet — it exists from the first step() on" % name)
+        return self._lars_state
+
+    @property
+    def guard(self):
+        """float32 [1] on the GPU: the guard of the last step (the one handed in, or a non-finite parameter / gradient)."""
+        return self._lars_field("guard")[ST_GUARD:ST_GUARD + 1]
+
+    @property
+    def nonfinite(self):
+        return self._lars_field("nonfinite")[ST_FLAG:ST_FLAG + 1]
+
+    @property
+    def ratios(self):
+        """fp32 [n_tensors, 2] on the GPU: {r, wd_t} of the last step, in table order."""
+        self._lars_field("ratios")
+        return self._ratios
+
+    def _hyper_values(self):
+        # ONE row: sf_lars_sgd_step's [n_groups][5], then sf_lars_ratios' [n_groups + 1][3] — one upload serves both
+        flat = [v for row in super()._hyper_values() for v in row]
+        for g in self.param_groups:
+            flat += [float(g["lr"]), float(g["weight_decay"]), 1.0 if g.get("apply_LARS", True) else 0.0]
+        flat += [float(self.trust_coefficient), float(self.eps), 1.0 if self.clip else 0.0]
+        return (tuple(flat),)
+
+    def _build(self, entries, chunk):
+        table, chunks = build_sgd_tables(entries, chunk)
+        plist = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        assert len(plist) == len(entries)
+        lars = [(e[0], e[1], e[3], e[4], self.ignore_1d_param and p.dim() <= 1) for e, p in zip(entries, plist)]
+        self._lars_table, lars_chunks = build_lars_tables(lars, chunk)
+        assert torch.equal(lars_chunks, chunks)
+        dev = plist[0].device
+        self._lars_table_dev = self._lars_table.to(dev)
+        n, nc = len(entries), chunks.shape[0]
+        if self._partials is None or self._partials.numel() != 2 * nc or self._ratios.shape[0] != n:
+            if self._lars_block is not None:
+                self._blocks = [b for b in self._blocks if b is not self._lars_block]
+            part, ratios, state = self._carve([4 * nc, 2 * n, CLIP_STATE], dev)
+            self._lars_block = self._blocks[-1]
+            self._partials, self._ratios, self._lars_state = part.view(torch.float64), ratios.view(n, 2), state
+        return table, chunks
+
+    def _launch(self, table_host, table, chunks_host, chunks, hyper_host, hyper, guard, zero_grad):
+        G = len(self.param_groups)
+        k = G * HYP_ROW
+        lars_ratios(self._lars_table, self._lars_table_dev, chunks_host, chunks,
+                    hyper_host[0, k:].view(G + 1, LARS_HYP_ROW), hyper[0, k:].view(G + 1, LARS_HYP_ROW), self._partials,
+                    self._ratios, self._lars_state, guard=guard)
+        lars_sgd_step(table_host, table, chunks_host, chunks, hyper_host[0, :k].view(G, HYP_ROW),
+                      hyper[0, :k].view(G, HYP_ROW), self._ratios, guard=self._lars_state[ST_GUARD:ST_GUARD + 1],
+                      zero_grad=zero_grad)
+
+
+# ---------------------------------------------------------------------------------------------------------- Adam
+class _AdamTables(_TableOptimizer):
+    """What HipAdam and HipAdamW share: the state slots, their adoption from a checkpoint and the address table."""
     _HYP_DTYPE, _KEY_COLS = torch.float64, 7
     _build = staticmethod(build_adam_tables)
-    _launch = staticmethod(adam_step)
 
     def __init__(self, params, *args, **kwargs):
         super().__init__(params, *args, **kwargs)
@@ -814,11 +964,11 @@ class HipAdam(_TableOptimizer, torch.optim.Adam):
         self._allocate([p])
         st = self.state[p]
         if "max_exp_avg_sq" in st:
-            raise ValueError("HipAdam: amsgrad state (max_exp_avg_sq) is not supported — use torch.optim.Adam")
+            raise ValueError("%s: amsgrad state (max_exp_avg_sq) is not supported — use %s" % (self._NAME, self._TORCH))
         for k, slot in self._slots[p].items():
             have = st.get(k)
             if have is None:
-                raise ValueError("HipAdam: state without %r" % k)
+                raise ValueError("%s: state without %r" % (self._NAME, k))
             if not torch.is_tensor(have):
                 slot.fill_(float(have))
             elif have.data_ptr() != slot.data_ptr():
@@ -863,6 +1013,37 @@ class HipAdam(_TableOptimizer, torch.optim.Adam):
     def _after_fresh(self, fresh):
         for p in fresh:
             self.state[p].update(self._slots[p])
+
+
+class HipAdam(_AdamTables, torch.optim.Adam):
+    """torch.optim.Adam (same constructor, param_groups and state_dict keys) whose `step()` is ONE native call over every
+    parameter of every group (`sf_adam_step`).
+
+    `exp_avg`, `exp_avg_sq` and `step` are 16-byte aligned views of one allocation owned by the optimizer; `step` is a
+    float32 scalar in DEVICE memory per parameter (torch keeps it on the host), advanced by the call itself, so a
+    captured step keeps counting when it is replayed.  They appear in `state[p]` from the parameter's first step on;
+    a parameter whose `.grad` is None is left untouched and gets no state.  `step(guard=, zero_grad=)` as in HipSGD: a
+    guarded-off step moves nothing — parameters, moments, step counts, gradients."""
+    _NAME, _TORCH = "HipAdam", "torch.optim.Adam"
+    _REFUSED = ("amsgrad", "maximize", "differentiable", "decoupled_weight_decay")
+    _launch = staticmethod(adam_step)
+
+
+class HipAdamW(_AdamTables, torch.optim.AdamW):
+    """torch.optim.AdamW (same constructor, param_groups and state_dict keys) the way HipAdam is torch.optim.Adam: ONE
+    native call (`sf_adamw_step`, HipAdam's kernel body with the decay decoupled — p *= 1 - lr * weight_decay in front of
+    the update, nothing added to the gradient).  State layout, guard, zero_grad, checkpoints and stream capture are
+    HipAdam's; a state dict saved by torch.optim.AdamW loads, and the reverse.  Groups with `decoupled_weight_decay`
+    switched off are refused: that is HipAdam."""
+    _NAME, _TORCH = "HipAdamW", "torch.optim.AdamW"
+    _REFUSED = ("amsgrad", "maximize", "differentiable")
+    _launch = staticmethod(adamw_step)
+
+    def _refuse_groups(self):
+        super()._refuse_groups()
+        for g in self.param_groups:
+            if not g.get("decoupled_weight_decay", True):
+                raise ValueError("HipAdamW: decoupled_weight_decay = False is torch.optim.Adam's update — use HipAdam")
 
 
 # ------------------------------------------------------------------------------------------------ gradient clipping
@@ -1155,9 +1336,40 @@ def construct_hip_adam(model, cfg):
                    weight_decay=cfg.SOLVER.WEIGHT_DECAY)
 
 
+def construct_hip_adamw(model, cfg):
+    """Upstream SlowFast's SOLVER.OPTIMIZING_METHOD == "adamw": torch.optim.AdamW(betas=(0.9, 0.999)) over the same
+    parameter split, as a HipAdamW."""
+    return HipAdamW(_split_bn_params(model, cfg), lr=cfg.SOLVER.BASE_LR, betas=(0.9, 0.999),
+                    weight_decay=cfg.SOLVER.WEIGHT_DECAY)
+
+
+def _lars_keys(cfg):
+    """Upstream SlowFast's SOLVER.LARS_ON read with `.get` (config/defaults.py mirrors the reference's key set, which
+    has no such key: set it on a config that allows new keys) -> (on, trust_coefficient, clip).  Upstream wraps its SGD
+    as LARS(optimizer, trust_coefficient=0.001, clip=False); SOLVER.LARS_TRUST_COEFFICIENT / SOLVER.LARS_CLIP, where a
+    config has them, replace those two."""
+    node = cfg.SOLVER
+    return (bool(node.get("LARS_ON", False)), float(node.get("LARS_TRUST_COEFFICIENT", 0.001)),
+            bool(node.get("LARS_CLIP", False)))
+
+
+def construct_hip_lars(model, cfg):
+    """SOLVER.OPTIMIZING_METHOD == "sgd" with upstream's SOLVER.LARS_ON: construct_hip_optimizer's SGD as a HipLARS.  The
+    BatchNorm group does not apply LARS (plain SGD with BN.WEIGHT_DECAY), the rest does."""
+    _, trust, clip = _lars_keys(cfg)
+    groups = _split_bn_params(model, cfg)
+    groups[0]["apply_LARS"] = False
+    return HipLARS(groups, lr=cfg.SOLVER.BASE_LR, momentum=cfg.SOLVER.MOMENTUM, weight_decay=cfg.SOLVER.WEIGHT_DECAY,
+                   dampening=cfg.SOLVER.DAMPENING, nesterov=cfg.SOLVER.NESTEROV, trust_coefficient=trust, clip=clip)
+
+
 def construct_hip_solver(model, cfg):
-    """models/optimizer.py:26-69 whole: "sgd" -> HipSGD, "adam" -> HipAdam, anything else raises the reference's
-    NotImplementedError."""
+    """models/optimizer.py:26-69 whole: "sgd" -> HipSGD (with upstream's SOLVER.LARS_ON: HipLARS), "adam" -> HipAdam,
+    upstream's "adamw" -> HipAdamW, anything else raises the reference's NotImplementedError."""
     if cfg.SOLVER.OPTIMIZING_METHOD == "adam":
         return construct_hip_adam(model, cfg)
+    if cfg.SOLVER.OPTIMIZING_METHOD == "adamw":
+        return construct_hip_adamw(model, cfg)
+    if cfg.SOLVER.OPTIMIZING_METHOD == "sgd" and _lars_keys(cfg)[0]:
+        return construct_hip_lars(model, cfg)
     return construct_hip_optimizer(model, cfg)

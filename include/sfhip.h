@@ -1050,7 +1050,26 @@ int sf_stripe_pool_bwd(const float* dz, int dz_cs, int dz_coff, const float* dme
  *   SF_EINVAL, nothing enqueued: everything sf_ce_topk refuses, smoothing outside [0, 1) or NaN, exactly one of mix /
  *   mix_host, a host row with its partner outside [0, N), its mode outside {0, 1, 2} or lam outside [0, 1].
  *   Class weights together with soft targets are not offered: torch divides by N for probability targets and by the
- *   weight sum for index targets. */
+ *   weight sum for index targets.
+ * sf_adamw_step: torch.optim.AdamW's update (_single_tensor_adam with decoupled_weight_decay = True, amsgrad = maximize
+ *   = False) — sf_adam_step with ONE change per element:  p *= f  in front, with f = (float)(1 - lr * weight_decay)
+ *   computed once per workgroup in fp64 beside the bias corrections (torch multiplies by that Python float), and no
+ *   wd * p added to g.  Table, chunks, hyper rows, *_host checks, guard, zero_grad and the step-count launch are
+ *   sf_adam_step's, and both are one kernel body behind a template flag.  With weight_decay == 0 in every group f is
+ *   1.0f and every output equals sf_adam_step's bit for bit.  SF_EINVAL: sf_adam_step's list.
+ * sf_lars_sgd_step: sf_sgd_step behind a per-tensor trust ratio (LARS / LARC).  ratios: fp32 [n_tensors][2] = {r, wd_t}
+ *   in DEVICE memory, row i for row i of the table — what sf_lars_ratios writes.  Per element
+ *   g = (g + wd_t * p) * r  — sf_sgd_step's fused form of the decay, then one fp32 multiply — and then sf_sgd_step's
+ *   momentum, dampening, nesterov, first-step flag and  p -= lr * g,  unchanged; the group's weight_decay (hyper column
+ *   1) is NOT applied again.  One kernel body behind a template flag: when every tensor has r == 1 and wd_t == its
+ *   group's weight decay every output equals sf_sgd_step's bit for bit.  guard (hand it sf_lars_ratios' state + 5),
+ *   zero_grad and the *_host checks are sf_sgd_step's.  SF_EINVAL: sf_sgd_step's list, or a null ratios. */
+int sf_adamw_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
+                  int n_chunks, const double* hyper_host, const double* hyper, int n_groups, const float* guard,
+                  int zero_grad, void* stream);
+int sf_lars_sgd_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host,
+                     const long* chunks, int n_chunks, const float* hyper_host, const float* hyper, int n_groups,
+                     const float* ratios, const float* guard, int zero_grad, void* stream);
 int sf_ce_mix(const float* logits, int ld, const long* labels, const long* mix_host, const long* mix, int N, int K,
               int k_hi, float smoothing, float* dlogits, float* ring, int* counter, int cap, float* loss_out,
               void* stream);
@@ -1113,6 +1132,42 @@ int sf_grad_scale(const long* table_host, const long* table, int n_tensors, cons
                   int n_chunks, const float* state, void* stream);
 int sf_grad_clamp(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
                   int n_chunks, const float* value, void* stream);
+
+/* ---- layer-wise trust ratios (csrc/lars.hip): LARS / LARC (upstream SlowFast's SOLVER.LARS_ON, NVIDIA apex's LARC)
+ * between the backward pass and sf_lars_sgd_step, without the host.  Nothing synchronises or reads back.
+ * sf_lars_ratios: ||p|| and ||g|| of every listed tensor and the ratio they give, in TWO launches.
+ *   table: int64 [n_tensors][6] = parameter address, gradient address, numel, group, index of the tensor's first
+ *   chunk, ignored flag (0 / 1: the tensor gets plain SGD — 1-D parameters under ignore_1d_param).  chunks: int64
+ *   [n_chunks][2] as sf_sgd_step's, tiled at sf_sgd_chunk_elems() in table order, so a tensor's chunks are contiguous.
+ *   hyper: fp32 [n_groups + 1][3] in DEVICE memory = per group lr, weight_decay, apply (0 / 1); then ONE row
+ *   trust_coefficient, eps, clip (0 / 1).  A new lr is a 4-byte device write that a replayed graph sees.  The *_host
+ *   arguments are the host arrays the three were uploaded from: checked before anything is launched, and every kernel
+ *   re-checks the device row it reads (a row that fails reads nothing: zero partials, r = 1, wd_t = 0).
+ *   Launch 1, one workgroup per chunk, reads the chunk of p and of g once: thread t squares (fp64) and adds the
+ *   elements of the groups of four t, t + 256, ... in order, xor butterfly over the wavefront, the four wavefronts in
+ *   order through LDS — sf_grad_norm's order; TWO fp64 partials per chunk go to partials (caller-owned, fp64
+ *   [n_chunks][2] = sum p^2, sum g^2).  Both access widths (16 bytes where the array's address allows, else 4) read
+ *   the same elements in the same order: a partial does not depend on the alignment.
+ *   Launch 2, n_tensors + 1 workgroups.  Workgroup t folds tensor t's partials in chunk order (thread i takes i,
+ *   i + 256, ..., then the same two steps), takes pn = sqrt(sum p^2), gn = sqrt(sum g^2) and writes ratios[t] (caller-
+ *   owned, fp32 [n_tensors][2]) = {r, wd_t}, evaluated in fp64 and rounded once, wd = the group's weight_decay:
+ *     apply == 0 or the tensor is ignored:   r = 1, wd_t = wd  (plain SGD with weight decay);
+ *     a norm that is not finite:             r = 1, wd_t = wd, and the guard is raised;
+ *     pn != 0 and gn != 0:                   r = trust * pn / (gn + pn * wd + eps);  with clip: r = min(r / lr, 1);
+ *                                            wd_t = wd;
+ *     a zero norm:                           r = 1, wd_t = 0.
+ *   The last workgroup looks at every partial and writes state (caller-owned, 8 floats, 8-byte aligned, sf_grad_norm's
+ *   layout):  [4] 1 when a partial is not finite (a NaN or an Inf in a parameter or a gradient, ignored tensors
+ *   included), else 0;  [5] guard_out = (guard_in != NULL && *guard_in != 0) || [4] ? 1 : 0 — what sf_lars_sgd_step
+ *   takes as `guard`; the other six floats are not touched.  Every word has ONE writer, a plain store: no atomics, no
+ *   "last workgroup" finish — equal inputs give equal bits.
+ *   SF_EINVAL, nothing enqueued: a null pointer (guard_in excepted), non-positive counts, a zero or 4-byte-misaligned
+ *   address, numel <= 0, a group outside [0, n_groups), a first-chunk column that is not the running chunk count, an
+ *   ignored flag, apply or clip outside {0, 1}, chunks that do not tile the tensors exactly.  SF_EALIGN: partials or
+ *   state not on 8 bytes. */
+int sf_lars_ratios(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
+                   int n_chunks, const float* hyper_host, const float* hyper, int n_groups, const float* guard_in,
+                   double* partials, float* ratios, float* state, void* stream);
 
 /* ---- evaluation (csrc/eval_metrics.hip): tools/train_net.py:166-251 eval_epoch and utils/meters.py:557-714 (ValMeter,
  * get_map) without the host.  No entry point synchronises or reads anything back.
