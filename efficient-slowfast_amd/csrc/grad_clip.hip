@@ -8,36 +8,25 @@
 //   sf_grad_clamp  g = min(max(g, -v), v), torch.clamp's bits.
 // Nothing here needs the host: max_norm / the clamp value are read from device memory, and every scalar the next
 // kernel needs stays there, so clip + step replay inside a captured graph.
+#include "chunk_table.h"
 #include "common.h"
 #include "stats_row.h"
 
 #include <math.h>
 
 namespace {
-constexpr int GC_TPB = 256;
-constexpr int GC_WAVES = GC_TPB / 64;
-constexpr int GC_CHUNK = 4096;  // == sf_sgd_chunk_elems() (checked at every entry): the optimizers' chunk list serves
-constexpr int GC_TAB_ROW = 2;   // gradient address, numel
-// the state block, in floats: [0..1] the norm as ONE fp64, then norm (fp32), coefficient, non-finite flag, guard_out
-constexpr int ST_NORM32 = 2, ST_COEF = 3, ST_FLAG = 4, ST_GUARD = 5;
+constexpr int GC_TAB_ROW = 2;  // gradient address, numel
 
-__device__ __forceinline__ float* as_global(long addr) {
-  // the address names global memory (a hipMalloc'ed span): say so, or every access becomes a flat one
-  return (float*)(__attribute__((address_space(1))) float*)(unsigned long)addr;
-}
-
-// the chunk of this workgroup: its first element and length, or nullptr for a row that fails the checks the host entry
-// made on its copy of both tables (a device row that differs does nothing, never a wild access)
+// the chunk of this workgroup: its first element and length, or nullptr for a chunk chunk_resolve refuses or a gradient
+// address that is null or off 4 bytes
 __device__ __forceinline__ float* chunk_of(const long* __restrict__ table, const long* __restrict__ chunks, int n_tensors,
                                            int* len) {
-  const long* c = chunks + (long)blockIdx.x * 2;
-  const long ti = c[0], start = c[1];
-  if (ti < 0 || ti >= n_tensors) return nullptr;
-  const long* row = table + ti * GC_TAB_ROW;
-  const long addr = row[0], numel = row[1];
-  if (addr == 0 || (addr & 3) != 0 || start < 0 || start >= numel) return nullptr;
-  *len = (int)(numel - start < GC_CHUNK ? numel - start : GC_CHUNK);
-  return as_global(addr) + start;
+  Chunk c;
+  if (!chunk_resolve(table, chunks, n_tensors, GC_TAB_ROW, 1, &c)) return nullptr;
+  const long addr = c.row[0];
+  if (addr == 0 || (addr & 3) != 0) return nullptr;
+  *len = c.len;
+  return as_global(addr) + c.start;
 }
 
 // max with NaN propagating (torch.max): fmaxf drops a NaN
@@ -45,31 +34,19 @@ __device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b
 __device__ __forceinline__ double max_nan(double a, double b) {
   return (a != a || b != b) ? (double)NAN : (a > b ? a : b);
 }
-__device__ __forceinline__ double wave_max_nan(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max_nan(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-// thread-sequential value -> xor butterfly -> wavefronts in order through LDS; thread 0 holds the result
+// how two partial results of the norm combine: the greater (inf norm) or the sum (L2), in span_reduce's order and
+// block_fold's
 template <bool INF>
-__device__ __forceinline__ double block_fold(double v) {
-  __shared__ double s_part[GC_WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = INF ? wave_max_nan(v) : wave_sum(v);
-  if (lane == 0) s_part[wave] = v;
-  __syncthreads();
-  double r = s_part[0];
-#pragma unroll
-  for (int w = 1; w < GC_WAVES; ++w) r = INF ? max_nan(r, s_part[w]) : r + s_part[w];
-  return r;
-}
+struct NormFold {
+  __device__ __forceinline__ double operator()(double a, double b) const { return INF ? max_nan(a, b) : a + b; }
+};
+struct AbsMax {  // span_reduce: the inf norm's element step
+  __device__ __forceinline__ float operator()(float top, float v) const { return max_nan(top, fabsf(v)); }
+};
 
-// Pass 1.  Thread t owns the groups of four elements t, t + 256, ... of its chunk, element by element in order, then the
-// element behind the last whole group (up to three are left).  The 16-byte path and the 4-byte path read the same
-// elements in the same order in the same thread: the partial does not depend on the gradient's alignment.
+// Pass 1: span_reduce over the chunk (the partial does not depend on the gradient's alignment), then block_fold.
 template <bool INF>
-__global__ __launch_bounds__(GC_TPB) void grad_norm_partial_kernel(const long* __restrict__ table,
+__global__ __launch_bounds__(CHUNK_TPB) void grad_norm_partial_kernel(const long* __restrict__ table,
                                                                    const long* __restrict__ chunks, int n_tensors,
                                                                    double* __restrict__ partials) {
   int len = 0;
@@ -78,55 +55,28 @@ __global__ __launch_bounds__(GC_TPB) void grad_norm_partial_kernel(const long* _
     if (threadIdx.x == 0) partials[blockIdx.x] = 0.0;
     return;
   }
-  double acc = 0.0;
-  float top = 0.f;
-  const int n4 = len >> 2;
-  if (((unsigned long)g & 15) == 0) {
-    for (int i = threadIdx.x; i < n4; i += GC_TPB) {
-      const f32x4 v = reinterpret_cast<const f32x4*>(g)[i];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (INF)
-          top = max_nan(top, fabsf(v[e]));
-        else
-          acc += (double)v[e] * (double)v[e];
-      }
-    }
-  } else {
-    for (int i = threadIdx.x; i < n4; i += GC_TPB) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float v = g[4 * i + e];
-        if (INF)
-          top = max_nan(top, fabsf(v));
-        else
-          acc += (double)v * (double)v;
-      }
-    }
-  }
-  const int i = (n4 << 2) + threadIdx.x;
-  if (i < len) {
-    const float v = g[i];
-    if (INF)
-      top = max_nan(top, fabsf(v));
-    else
-      acc += (double)v * (double)v;
-  }
-  const double r = block_fold<INF>(INF ? (double)top : acc);
-  if (threadIdx.x == 0) partials[blockIdx.x] = r;
+  double r[1];
+  if (INF)
+    r[0] = (double)span_reduce(g, len, 0.f, AbsMax());
+  else
+    r[0] = span_reduce(g, len, 0.0, SumSq());
+  block_fold(r, NormFold<INF>());
+  if (threadIdx.x == 0) partials[blockIdx.x] = r[0];
 }
 
 // Pass 2, ONE workgroup: thread t folds partials t, t + 256, ... in order, then block_fold.  Thread 0 writes the state.
 template <bool INF>
-__global__ __launch_bounds__(GC_TPB) void grad_norm_finish_kernel(const double* __restrict__ partials, int n_chunks,
+__global__ __launch_bounds__(CHUNK_TPB) void grad_norm_finish_kernel(const double* __restrict__ partials, int n_chunks,
                                                                   const float* __restrict__ max_norm,
                                                                   const float* __restrict__ guard_in,
                                                                   float* __restrict__ state, float* __restrict__ ring,
                                                                   const int* __restrict__ counter, int cap) {
-  double v = 0.0;
-  for (int i = threadIdx.x; i < n_chunks; i += GC_TPB) v = INF ? max_nan(v, partials[i]) : v + partials[i];
-  const double tot = block_fold<INF>(v);
+  const NormFold<INF> comb;
+  double v[1] = {0.0};
+  for (int i = threadIdx.x; i < n_chunks; i += CHUNK_TPB) v[0] = comb(v[0], partials[i]);
+  block_fold(v, comb);
   if (threadIdx.x != 0) return;
+  const double tot = v[0];
   const double norm = INF ? tot : sqrt(tot);
   const float norm32 = (float)norm;
   const bool bad = !isfinite(norm);
@@ -155,7 +105,7 @@ __global__ __launch_bounds__(GC_TPB) void grad_norm_finish_kernel(const double* 
   }
 }
 
-__global__ __launch_bounds__(GC_TPB) void grad_scale_kernel(const long* __restrict__ table,
+__global__ __launch_bounds__(CHUNK_TPB) void grad_scale_kernel(const long* __restrict__ table,
                                                             const long* __restrict__ chunks, int n_tensors,
                                                             const float* __restrict__ state) {
   const float coef = state[ST_COEF];
@@ -167,7 +117,7 @@ __global__ __launch_bounds__(GC_TPB) void grad_scale_kernel(const long* __restri
   if (g == nullptr) return;
   if (((unsigned long)g & 15) == 0) {
     const int n4 = len >> 2;
-    for (int i = threadIdx.x; i < n4; i += GC_TPB) {
+    for (int i = threadIdx.x; i < n4; i += CHUNK_TPB) {
       f32x4 v = reinterpret_cast<f32x4*>(g)[i];
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] *= coef;
@@ -176,14 +126,14 @@ __global__ __launch_bounds__(GC_TPB) void grad_scale_kernel(const long* __restri
     const int i = (n4 << 2) + threadIdx.x;  // up to three elements left
     if (i < len) g[i] *= coef;
   } else {
-    for (int i = threadIdx.x; i < len; i += GC_TPB) g[i] *= coef;
+    for (int i = threadIdx.x; i < len; i += CHUNK_TPB) g[i] *= coef;
   }
 }
 
 // torch.clamp(g, -v, v): a NaN fails both comparisons and passes, -0.0 is inside and keeps its sign
 __device__ __forceinline__ float clamp1(float g, float v) { return g < -v ? -v : (g > v ? v : g); }
 
-__global__ __launch_bounds__(GC_TPB) void grad_clamp_kernel(const long* __restrict__ table,
+__global__ __launch_bounds__(CHUNK_TPB) void grad_clamp_kernel(const long* __restrict__ table,
                                                             const long* __restrict__ chunks, int n_tensors,
                                                             const float* __restrict__ value) {
   const float v = value[0];
@@ -193,7 +143,7 @@ __global__ __launch_bounds__(GC_TPB) void grad_clamp_kernel(const long* __restri
   if (g == nullptr) return;
   if (((unsigned long)g & 15) == 0) {
     const int n4 = len >> 2;
-    for (int i = threadIdx.x; i < n4; i += GC_TPB) {
+    for (int i = threadIdx.x; i < n4; i += CHUNK_TPB) {
       const f32x4 x = reinterpret_cast<f32x4*>(g)[i];
       f32x4 y;
       bool moved = false;
@@ -207,35 +157,23 @@ __global__ __launch_bounds__(GC_TPB) void grad_clamp_kernel(const long* __restri
     const int i = (n4 << 2) + threadIdx.x;  // up to three elements left
     if (i < len && (g[i] < -v || g[i] > v)) g[i] = clamp1(g[i], v);
   } else {
-    for (int i = threadIdx.x; i < len; i += GC_TPB)
+    for (int i = threadIdx.x; i < len; i += CHUNK_TPB)
       if (g[i] < -v || g[i] > v) g[i] = clamp1(g[i], v);
   }
 }
 
-// sf_sgd_step's rule for the chunk list (step_tail.hip::chunks_tile): the chunks tile the tensors exactly, in table
-// order — (0, 0), (0, C), ..., (1, 0), ...
 bool clip_tables_ok(const long* tab, int n_tensors, const long* chunks, int n_chunks) {
-  if (sf_sgd_chunk_elems() != GC_CHUNK) return false;
   for (int t = 0; t < n_tensors; ++t) {
     const long* r = tab + (long)t * GC_TAB_ROW;
     if (r[0] == 0 || (r[0] & 3) != 0 || r[1] <= 0) return false;
   }
-  long t = 0, s = 0;
-  for (int i = 0; i < n_chunks; ++i) {
-    if (t >= n_tensors || chunks[2 * i] != t || chunks[2 * i + 1] != s) return false;
-    s += GC_CHUNK;
-    if (s >= tab[t * GC_TAB_ROW + 1]) {
-      ++t;
-      s = 0;
-    }
-  }
-  return t == n_tensors && s == 0;
+  return chunks_tile(tab, GC_TAB_ROW, 1, n_tensors, chunks, n_chunks);
 }
 
 bool clip_args_ok(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
                   int n_chunks) {
-  if (!table_host || !table || !chunks_host || !chunks || n_tensors <= 0 || n_chunks <= 0) return false;
-  return clip_tables_ok(table_host, n_tensors, chunks_host, n_chunks);
+  return tables_args_ok(table_host, table, n_tensors, chunks_host, chunks, n_chunks) &&
+         clip_tables_ok(table_host, n_tensors, chunks_host, n_chunks);
 }
 }  // namespace
 
@@ -250,16 +188,16 @@ extern "C" int sf_grad_norm(const long* table_host, const long* table, int n_ten
     return SF_EALIGN;
   hipStream_t s = (hipStream_t)stream;
   if (norm_type == SF_NORM_INF) {
-    hipLaunchKernelGGL(grad_norm_partial_kernel<true>, dim3(n_chunks), dim3(GC_TPB), 0, s, table, chunks, n_tensors,
+    hipLaunchKernelGGL(grad_norm_partial_kernel<true>, dim3(n_chunks), dim3(CHUNK_TPB), 0, s, table, chunks, n_tensors,
                        partials);
     SF_CHECK_LAUNCH();
-    hipLaunchKernelGGL(grad_norm_finish_kernel<true>, dim3(1), dim3(GC_TPB), 0, s, partials, n_chunks, max_norm,
+    hipLaunchKernelGGL(grad_norm_finish_kernel<true>, dim3(1), dim3(CHUNK_TPB), 0, s, partials, n_chunks, max_norm,
                        guard_in, state, ring, counter, cap);
   } else {
-    hipLaunchKernelGGL(grad_norm_partial_kernel<false>, dim3(n_chunks), dim3(GC_TPB), 0, s, table, chunks, n_tensors,
+    hipLaunchKernelGGL(grad_norm_partial_kernel<false>, dim3(n_chunks), dim3(CHUNK_TPB), 0, s, table, chunks, n_tensors,
                        partials);
     SF_CHECK_LAUNCH();
-    hipLaunchKernelGGL(grad_norm_finish_kernel<false>, dim3(1), dim3(GC_TPB), 0, s, partials, n_chunks, max_norm,
+    hipLaunchKernelGGL(grad_norm_finish_kernel<false>, dim3(1), dim3(CHUNK_TPB), 0, s, partials, n_chunks, max_norm,
                        guard_in, state, ring, counter, cap);
   }
   SF_CHECK_LAUNCH();
@@ -270,7 +208,7 @@ extern "C" int sf_grad_scale(const long* table_host, const long* table, int n_te
                              const long* chunks, int n_chunks, const float* state, void* stream) {
   if (!clip_args_ok(table_host, table, n_tensors, chunks_host, chunks, n_chunks) || !state) return SF_EINVAL;
   if ((reinterpret_cast<uintptr_t>(state) & 7) != 0) return SF_EALIGN;
-  hipLaunchKernelGGL(grad_scale_kernel, dim3(n_chunks), dim3(GC_TPB), 0, (hipStream_t)stream, table, chunks, n_tensors,
+  hipLaunchKernelGGL(grad_scale_kernel, dim3(n_chunks), dim3(CHUNK_TPB), 0, (hipStream_t)stream, table, chunks, n_tensors,
                      state);
   SF_CHECK_LAUNCH();
   return SF_OK;
@@ -279,7 +217,7 @@ extern "C" int sf_grad_scale(const long* table_host, const long* table, int n_te
 extern "C" int sf_grad_clamp(const long* table_host, const long* table, int n_tensors, const long* chunks_host,
                              const long* chunks, int n_chunks, const float* value, void* stream) {
   if (!clip_args_ok(table_host, table, n_tensors, chunks_host, chunks, n_chunks) || !value) return SF_EINVAL;
-  hipLaunchKernelGGL(grad_clamp_kernel, dim3(n_chunks), dim3(GC_TPB), 0, (hipStream_t)stream, table, chunks, n_tensors,
+  hipLaunchKernelGGL(grad_clamp_kernel, dim3(n_chunks), dim3(CHUNK_TPB), 0, (hipStream_t)stream, table, chunks, n_tensors,
                      value);
   SF_CHECK_LAUNCH();
   return SF_OK;

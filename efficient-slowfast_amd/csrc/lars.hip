@@ -2,12 +2,13 @@
 // the backward pass and sf_lars_sgd_step: ||p|| and ||g|| of EVERY tensor of the model in two launches, addressed like
 // the optimizers (an int64 table of tensors, the chunk list tiled at sf_sgd_chunk_elems(), so one tensor's chunks are
 // contiguous).
-//   launch 1   one workgroup per chunk reads its span of p and of g once and leaves sum p^2 and sum g^2 (fp64, the
-//              fixed order of grad_clip.hip's norm pass) as two partials.
+//   launch 1   one workgroup per chunk reads its span of p and of g once and leaves sum p^2 and sum g^2 (fp64, in
+//              chunk_table.h's fixed order: span_reduce, then block_fold — what sf_grad_norm uses) as two partials.
 //   launch 2   one workgroup per tensor folds that tensor's partials in chunk order and writes {r, wd_t}; one more
 //              workgroup of the same launch looks at every partial and writes the guard.  Each word has one writer:
 //              no atomics, no "last workgroup" finish, equal inputs give equal bits.
 // Nothing here needs the host: lr, weight decay, the trust coefficient, eps and the switches are read from device memory.
+#include "chunk_table.h"
 #include "common.h"
 #include "stats_row.h"
 
@@ -16,114 +17,48 @@
 #include <cmath>
 
 namespace {
-constexpr int LR_TPB = 256;
-constexpr int LR_WAVES = LR_TPB / 64;
-constexpr int LR_CHUNK = 4096;   // == sf_sgd_chunk_elems() (checked at the entry): the optimizers' chunk list serves
-constexpr int LR_TAB_ROW = 6;    // parameter, gradient, numel, group, first chunk, ignored (0 / 1)
-constexpr int LR_HYP_ROW = 3;    // per group: lr, weight_decay, apply; the row behind them: trust_coefficient, eps, clip
-constexpr int ST_FLAG = 4, ST_GUARD = 5;  // sf_grad_norm's state block: [4] non-finite, [5] guard_out
-
-__device__ __forceinline__ const float* as_global(long addr) {
-  // the address names global memory (a hipMalloc'ed span): say so, or every access becomes a flat one
-  return (const float*)(__attribute__((address_space(1))) const float*)(unsigned long)addr;
-}
-
-// two thread-sequential values -> xor butterfly -> wavefronts in order through LDS; thread 0 holds the results
-__device__ __forceinline__ void block_fold2(double* a, double* b) {
-  __shared__ double s_part[LR_WAVES][2];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const double va = wave_sum(*a), vb = wave_sum(*b);
-  if (lane == 0) {
-    s_part[wave][0] = va;
-    s_part[wave][1] = vb;
-  }
-  __syncthreads();
-  double ra = s_part[0][0], rb = s_part[0][1];
-#pragma unroll
-  for (int w = 1; w < LR_WAVES; ++w) {
-    ra += s_part[w][0];
-    rb += s_part[w][1];
-  }
-  *a = ra;
-  *b = rb;
-}
-
-// thread t owns the groups of four elements t, t + 256, ... of the span, element by element in order, then the element
-// behind the last whole group (up to three are left).  The 16-byte path and the 4-byte path read the same elements in
-// the same order in the same thread: the sum does not depend on the alignment.
-__device__ __forceinline__ double span_sumsq(const float* __restrict__ x, int len) {
-  double acc = 0.0;
-  const int n4 = len >> 2;
-  if (((unsigned long)x & 15) == 0) {
-    for (int i = threadIdx.x; i < n4; i += LR_TPB) {
-      const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc += (double)v[e] * (double)v[e];
-    }
-  } else {
-    for (int i = threadIdx.x; i < n4; i += LR_TPB) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float v = x[4 * i + e];
-        acc += (double)v * (double)v;
-      }
-    }
-  }
-  const int i = (n4 << 2) + threadIdx.x;
-  if (i < len) {
-    const float v = x[i];
-    acc += (double)v * (double)v;
-  }
-  return acc;
-}
+constexpr int LR_TAB_ROW = 6;  // parameter, gradient, numel, group, first chunk, ignored (0 / 1)
+constexpr int LR_HYP_ROW = 3;  // per group: lr, weight_decay, apply; the row behind them: trust_coefficient, eps, clip
 
 // Launch 1.  partials[2 c] = sum p^2, partials[2 c + 1] = sum g^2 of chunk c; a chunk whose device row fails the checks
 // the host entry made on its copy writes two zeros, never a wild access.
-__global__ __launch_bounds__(LR_TPB) void lars_partial_kernel(const long* __restrict__ table,
+__global__ __launch_bounds__(CHUNK_TPB) void lars_partial_kernel(const long* __restrict__ table,
                                                               const long* __restrict__ chunks, int n_tensors,
                                                               double* __restrict__ partials) {
-  const long* c = chunks + (long)blockIdx.x * 2;
-  const long ti = c[0], start = c[1];
-  bool ok = ti >= 0 && ti < n_tensors;  // block-uniform
-  long pa = 0, ga = 0, numel = 0;
-  if (ok) {
-    const long* row = table + ti * LR_TAB_ROW;
-    pa = row[0];
-    ga = row[1];
-    numel = row[2];
-    ok = pa != 0 && ga != 0 && ((pa | ga) & 3) == 0 && start >= 0 && start < numel;
+  Chunk c;
+  double s[2] = {0.0, 0.0};  // sum p^2, sum g^2
+  if (chunk_resolve(table, chunks, n_tensors, LR_TAB_ROW, 2, &c)) {  // block-uniform
+    const long pa = c.row[0], ga = c.row[1];
+    if (pa != 0 && ga != 0 && ((pa | ga) & 3) == 0) {
+      s[0] = span_reduce(as_global(pa) + c.start, c.len, 0.0, SumSq());
+      s[1] = span_reduce(as_global(ga) + c.start, c.len, 0.0, SumSq());
+    }
   }
-  double sp = 0.0, sg = 0.0;
-  if (ok) {
-    const int len = (int)(numel - start < LR_CHUNK ? numel - start : LR_CHUNK);
-    sp = span_sumsq(as_global(pa) + start, len);
-    sg = span_sumsq(as_global(ga) + start, len);
-  }
-  block_fold2(&sp, &sg);
+  block_fold(s, Sum());
   if (threadIdx.x == 0) {
-    partials[2 * (long)blockIdx.x] = sp;
-    partials[2 * (long)blockIdx.x + 1] = sg;
+    partials[2 * (long)blockIdx.x] = s[0];
+    partials[2 * (long)blockIdx.x + 1] = s[1];
   }
 }
 
-// Launch 2.  Workgroup t < n_tensors: thread i folds the tensor's partials i, i + 256, ... in chunk order, then the two
-// steps above; thread 0 writes ratios[t] = {r, wd_t}, evaluated in fp64 and rounded once.  Workgroup n_tensors: any
+// Launch 2.  Workgroup t < n_tensors: thread i folds the tensor's partials i, i + 256, ... in chunk order, then
+// block_fold; thread 0 writes ratios[t] = {r, wd_t}, evaluated in fp64 and rounded once.  Workgroup n_tensors: any
 // partial that is not finite (a sum of squares in fp64 is finite unless an element is not) raises the guard.
-__global__ __launch_bounds__(LR_TPB) void lars_ratio_kernel(const long* __restrict__ table, int n_tensors,
+__global__ __launch_bounds__(CHUNK_TPB) void lars_ratio_kernel(const long* __restrict__ table, int n_tensors,
                                                             const float* __restrict__ hyper, int n_groups,
                                                             const double* __restrict__ partials, int n_chunks,
                                                             const float* __restrict__ guard_in,
                                                             float* __restrict__ ratios, float* __restrict__ state) {
   if ((int)blockIdx.x == n_tensors) {
-    __shared__ int s_bad[LR_WAVES];
+    __shared__ int s_bad[CHUNK_WAVES];
     int bad = 0;
-    for (long i = threadIdx.x; i < 2 * (long)n_chunks; i += LR_TPB) bad |= !isfinite(partials[i]);
+    for (long i = threadIdx.x; i < 2 * (long)n_chunks; i += CHUNK_TPB) bad |= !isfinite(partials[i]);
     bad = wave_sum(bad);
     if ((threadIdx.x & 63) == 0) s_bad[threadIdx.x >> 6] = bad;
     __syncthreads();
     if (threadIdx.x == 0) {
       int any = 0;
-      for (int w = 0; w < LR_WAVES; ++w) any |= s_bad[w];
+      for (int w = 0; w < CHUNK_WAVES; ++w) any |= s_bad[w];
       const bool raised = guard_in != nullptr && guard_in[0] != 0.f;  // NaN != 0: raised
       state[ST_FLAG] = any ? 1.f : 0.f;
       state[ST_GUARD] = (raised || any) ? 1.f : 0.f;
@@ -133,19 +68,20 @@ __global__ __launch_bounds__(LR_TPB) void lars_ratio_kernel(const long* __restri
   const long t = blockIdx.x;
   const long* row = table + t * LR_TAB_ROW;
   const long numel = row[2], grp = row[3], first = row[4];
-  const long nch = numel > 0 ? (numel + LR_CHUNK - 1) / LR_CHUNK : 0;
+  const long nch = numel > 0 ? (numel + CHUNK_ELEMS - 1) / CHUNK_ELEMS : 0;
   // block-uniform: a device row that differs from the checked host copy reads no partial and leaves plain SGD behind
   const bool ok = numel > 0 && grp >= 0 && grp < n_groups && first >= 0 && first <= n_chunks - nch;
-  double sp = 0.0, sg = 0.0;
+  double s[2] = {0.0, 0.0};
   if (ok) {
     const double* part = partials + 2 * first;
-    for (long i = threadIdx.x; i < nch; i += LR_TPB) {
-      sp += part[2 * i];
-      sg += part[2 * i + 1];
+    for (long i = threadIdx.x; i < nch; i += CHUNK_TPB) {
+      s[0] += part[2 * i];
+      s[1] += part[2 * i + 1];
     }
   }
-  block_fold2(&sp, &sg);
+  block_fold(s, Sum());
   if (threadIdx.x != 0) return;
+  const double sp = s[0], sg = s[1];
   float r = 1.f, wd_t = 0.f;
   if (ok) {
     const float* hy = hyper + grp * LR_HYP_ROW;
@@ -172,7 +108,6 @@ __global__ __launch_bounds__(LR_TPB) void lars_ratio_kernel(const long* __restri
 }
 
 bool lars_tables_ok(const long* tab, int n_tensors, const long* chunks, int n_chunks, const float* hyper, int n_groups) {
-  if (sf_sgd_chunk_elems() != LR_CHUNK) return false;
   for (int g = 0; g < n_groups; ++g) {
     const float a = hyper[g * LR_HYP_ROW + 2];
     if (a != 0.f && a != 1.f) return false;
@@ -184,19 +119,9 @@ bool lars_tables_ok(const long* tab, int n_tensors, const long* chunks, int n_ch
     const long* r = tab + (long)t * LR_TAB_ROW;
     if (r[0] == 0 || r[1] == 0 || ((r[0] | r[1]) & 3) != 0 || r[2] <= 0) return false;
     if (r[3] < 0 || r[3] >= n_groups || r[4] != first || (r[5] != 0 && r[5] != 1)) return false;
-    first += (r[2] + LR_CHUNK - 1) / LR_CHUNK;
+    first += (r[2] + CHUNK_ELEMS - 1) / CHUNK_ELEMS;
   }
-  if (first != n_chunks) return false;
-  long t = 0, s = 0;  // step_tail.hip::chunks_tile: (0, 0), (0, C), ..., (1, 0), ...
-  for (int i = 0; i < n_chunks; ++i) {
-    if (t >= n_tensors || chunks[2 * i] != t || chunks[2 * i + 1] != s) return false;
-    s += LR_CHUNK;
-    if (s >= tab[t * LR_TAB_ROW + 2]) {
-      ++t;
-      s = 0;
-    }
-  }
-  return t == n_tensors && s == 0;
+  return first == n_chunks && chunks_tile(tab, LR_TAB_ROW, 2, n_tensors, chunks, n_chunks);
 }
 }  // namespace
 
@@ -204,16 +129,16 @@ extern "C" int sf_lars_ratios(const long* table_host, const long* table, int n_t
                               const long* chunks, int n_chunks, const float* hyper_host, const float* hyper,
                               int n_groups, const float* guard_in, double* partials, float* ratios, float* state,
                               void* stream) {
-  if (!table_host || !table || !chunks_host || !chunks || !hyper_host || !hyper) return SF_EINVAL;
-  if (!partials || !ratios || !state || n_tensors <= 0 || n_chunks <= 0 || n_groups <= 0) return SF_EINVAL;
+  if (!tables_args_ok(table_host, table, n_tensors, chunks_host, chunks, n_chunks)) return SF_EINVAL;
+  if (!hyper_host || !hyper || !partials || !ratios || !state || n_groups <= 0) return SF_EINVAL;
   if (!lars_tables_ok(table_host, n_tensors, chunks_host, n_chunks, hyper_host, n_groups)) return SF_EINVAL;
   if ((reinterpret_cast<uintptr_t>(ratios) & 3) != 0) return SF_EINVAL;
   if ((reinterpret_cast<uintptr_t>(partials) & 7) != 0 || (reinterpret_cast<uintptr_t>(state) & 7) != 0)
     return SF_EALIGN;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(lars_partial_kernel, dim3(n_chunks), dim3(LR_TPB), 0, s, table, chunks, n_tensors, partials);
+  hipLaunchKernelGGL(lars_partial_kernel, dim3(n_chunks), dim3(CHUNK_TPB), 0, s, table, chunks, n_tensors, partials);
   SF_CHECK_LAUNCH();
-  hipLaunchKernelGGL(lars_ratio_kernel, dim3(n_tensors + 1), dim3(LR_TPB), 0, s, table, n_tensors, hyper, n_groups,
+  hipLaunchKernelGGL(lars_ratio_kernel, dim3(n_tensors + 1), dim3(CHUNK_TPB), 0, s, table, n_tensors, hyper, n_groups,
                      partials, n_chunks, guard_in, ratios, state);
   SF_CHECK_LAUNCH();
   return SF_OK;

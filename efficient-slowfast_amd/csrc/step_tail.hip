@@ -7,6 +7,7 @@
 // lars.hip::sf_lars_ratios leaves in device memory).  Nothing here needs the host: the statistics go to a ring in device memory that the meter drains once
 // per LOG_PERIOD, the hyper-parameters are read from device memory (the LR schedule is a 4-byte write a replayed graph
 // sees) and a non-finite loss switches the update off through a flag the loss kernel leaves.
+#include "chunk_table.h"
 #include "common.h"
 #include "mix_row.h"
 #include "stats_row.h"
@@ -333,10 +334,8 @@ __global__ __launch_bounds__(CE_TPB) void bce_w_kernel(const float* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------- SGD
-constexpr int SGD_TPB = 256;
-constexpr int SGD_CHUNK = 4096;  // elements per workgroup: four 16-byte accesses per thread and array
-constexpr int TAB_ROW = 6;       // parameter, gradient, momentum buffer (0: none), numel, group, first step
-constexpr int HYP_ROW = 5;       // lr, weight_decay, momentum, dampening, nesterov
+constexpr int TAB_ROW = 6;  // parameter, gradient, momentum buffer (0: none), numel, group, first step
+constexpr int HYP_ROW = 5;  // lr, weight_decay, momentum, dampening, nesterov
 
 struct Hyper {
   float lr, wd, mom, keep;  // keep = 1 - dampening
@@ -358,24 +357,17 @@ __device__ __forceinline__ float sgd1(float p, float g, float* b, const Hyper& h
   return fmaf(-h.lr, g, p);
 }
 
-__device__ __forceinline__ float* as_global(long addr) {
-  // the address names global memory (a hipMalloc'ed span): say so, or every access becomes a flat one
-  return (float*)(__attribute__((address_space(1))) float*)(unsigned long)addr;
-}
-
 template <bool LARS>
 __device__ __forceinline__ void sgd_step_body(const long* __restrict__ table, const long* __restrict__ chunks,
                                               const float* __restrict__ hyper, const float* __restrict__ ratios,
                                               const float* __restrict__ guard, int n_tensors, int n_groups,
                                               int zero_grad) {
   if (guard != nullptr && guard[0] != 0.f) return;  // the step's loss was not finite (or NaN itself): no update
-  const long* c = chunks + (long)blockIdx.x * 2;
-  const long ti = c[0], start = c[1];
-  // the host entry checked its copy of both tables; a device row that differs does nothing, never a wild access
-  if (ti < 0 || ti >= n_tensors) return;
-  const long* row = table + ti * TAB_ROW;
-  const long numel = row[3], grp = row[4];
-  if (row[0] == 0 || row[1] == 0 || start < 0 || start >= numel || grp < 0 || grp >= n_groups) return;
+  Chunk c;
+  if (!chunk_resolve(table, chunks, n_tensors, TAB_ROW, 3, &c)) return;
+  const long* row = c.row;
+  const long ti = c.ti, start = c.start, grp = row[4];
+  if (row[0] == 0 || row[1] == 0 || grp < 0 || grp >= n_groups) return;
   const float* hy = hyper + grp * HYP_ROW;
   Hyper h;
   h.lr = hy[0];
@@ -393,11 +385,11 @@ __device__ __forceinline__ void sgd_step_body(const long* __restrict__ table, co
   float* p = as_global(row[0]) + start;
   float* g = as_global(row[1]) + start;
   float* b = as_global(has_buf ? row[2] : row[0]) + start;  // never dereferenced without has_buf
-  const int len = (int)(numel - start < SGD_CHUNK ? numel - start : SGD_CHUNK);
+  const int len = c.len;
   const unsigned long bits = (unsigned long)p | (unsigned long)g | (unsigned long)b;
   if ((bits & 15) == 0) {
     const int n4 = len >> 2;
-    for (int i = threadIdx.x; i < n4; i += SGD_TPB) {
+    for (int i = threadIdx.x; i < n4; i += CHUNK_TPB) {
       f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
       const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
       f32x4 bv = {0.f, 0.f, 0.f, 0.f};
@@ -420,7 +412,7 @@ __device__ __forceinline__ void sgd_step_body(const long* __restrict__ table, co
       if (zero_grad) g[i] = 0.f;
     }
   } else {
-    for (int i = threadIdx.x; i < len; i += SGD_TPB) {
+    for (int i = threadIdx.x; i < len; i += CHUNK_TPB) {
       float be = (has_buf && !first) ? b[i] : 0.f;
       p[i] = sgd1<LARS>(p[i], g[i], &be, h, has_buf, first, r);
       if (has_buf) b[i] = be;
@@ -429,7 +421,7 @@ __device__ __forceinline__ void sgd_step_body(const long* __restrict__ table, co
   }
 }
 
-__global__ __launch_bounds__(SGD_TPB) void sgd_step_kernel(const long* __restrict__ table,
+__global__ __launch_bounds__(CHUNK_TPB) void sgd_step_kernel(const long* __restrict__ table,
                                                            const long* __restrict__ chunks,
                                                            const float* __restrict__ hyper,
                                                            const float* __restrict__ guard, int n_tensors, int n_groups,
@@ -437,27 +429,13 @@ __global__ __launch_bounds__(SGD_TPB) void sgd_step_kernel(const long* __restric
   sgd_step_body<false>(table, chunks, hyper, nullptr, guard, n_tensors, n_groups, zero_grad);
 }
 
-__global__ __launch_bounds__(SGD_TPB) void lars_sgd_step_kernel(const long* __restrict__ table,
+__global__ __launch_bounds__(CHUNK_TPB) void lars_sgd_step_kernel(const long* __restrict__ table,
                                                                 const long* __restrict__ chunks,
                                                                 const float* __restrict__ hyper,
                                                                 const float* __restrict__ ratios,
                                                                 const float* __restrict__ guard, int n_tensors,
                                                                 int n_groups, int zero_grad) {
   sgd_step_body<true>(table, chunks, hyper, ratios, guard, n_tensors, n_groups, zero_grad);
-}
-
-// the chunks tile the tensors exactly, in table order: (0, 0), (0, C), ..., (1, 0), ... (numel: column `col` of a row)
-bool chunks_tile(const long* tab, int row, int col, int n_tensors, const long* chunks, int n_chunks) {
-  long t = 0, s = 0;
-  for (int i = 0; i < n_chunks; ++i) {
-    if (t >= n_tensors || chunks[2 * i] != t || chunks[2 * i + 1] != s) return false;
-    s += SGD_CHUNK;
-    if (s >= tab[t * row + col]) {
-      ++t;
-      s = 0;
-    }
-  }
-  return t == n_tensors && s == 0;
 }
 
 bool sgd_tables_ok(const long* tab, int n_tensors, const long* chunks, int n_chunks, const float* hyper, int n_groups) {
@@ -475,10 +453,10 @@ constexpr int ADAM_TAB_ROW = 7;  // parameter, gradient, exp_avg, exp_avg_sq, st
 constexpr int ADAM_HYP_ROW = 5;  // lr, beta1, beta2, eps, weight_decay — fp64, what torch's Python floats are
 
 // the step counts first, in a launch of their own: the update's chunks of one tensor all read the new value
-__global__ __launch_bounds__(SGD_TPB) void adam_tick_kernel(const long* __restrict__ table,
+__global__ __launch_bounds__(CHUNK_TPB) void adam_tick_kernel(const long* __restrict__ table,
                                                             const float* __restrict__ guard, int n_tensors) {
   if (guard != nullptr && guard[0] != 0.f) return;
-  for (int t = threadIdx.x; t < n_tensors; t += SGD_TPB) {
+  for (int t = threadIdx.x; t < n_tensors; t += CHUNK_TPB) {
     const long a = table[(long)t * ADAM_TAB_ROW + 4];
     if (a == 0) continue;
     float* s = as_global(a);
@@ -514,13 +492,12 @@ __device__ __forceinline__ void adam_step_body(const long* __restrict__ table, c
                                                int n_tensors, int n_groups, int zero_grad) {
   __shared__ AdamScalars s_a;
   if (guard != nullptr && guard[0] != 0.f) return;  // as in sgd_step_kernel: nothing moves
-  const long* c = chunks + (long)blockIdx.x * 2;
-  const long ti = c[0], start = c[1];
-  if (ti < 0 || ti >= n_tensors) return;
-  const long* row = table + ti * ADAM_TAB_ROW;
-  const long numel = row[5], grp = row[6];
+  Chunk c;
+  if (!chunk_resolve(table, chunks, n_tensors, ADAM_TAB_ROW, 5, &c)) return;
+  const long* row = c.row;
+  const long start = c.start, grp = row[6];
   if (row[0] == 0 || row[1] == 0 || row[2] == 0 || row[3] == 0 || row[4] == 0) return;
-  if (start < 0 || start >= numel || grp < 0 || grp >= n_groups) return;
+  if (grp < 0 || grp >= n_groups) return;
   if (threadIdx.x == 0) {  // the bias corrections once per workgroup, in fp64 as torch's Python floats
     const double* hy = hyper + grp * ADAM_HYP_ROW;
     const double lr = hy[0], b1 = hy[1], b2 = hy[2];
@@ -544,11 +521,11 @@ __device__ __forceinline__ void adam_step_body(const long* __restrict__ table, c
   float* g = as_global(row[1]) + start;
   float* m = as_global(row[2]) + start;
   float* v = as_global(row[3]) + start;
-  const int len = (int)(numel - start < SGD_CHUNK ? numel - start : SGD_CHUNK);
+  const int len = c.len;
   const unsigned long bits = (unsigned long)p | (unsigned long)g | (unsigned long)m | (unsigned long)v;
   if ((bits & 15) == 0) {
     const int n4 = len >> 2;
-    for (int i = threadIdx.x; i < n4; i += SGD_TPB) {
+    for (int i = threadIdx.x; i < n4; i += CHUNK_TPB) {
       f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
       const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
       f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
@@ -574,7 +551,7 @@ __device__ __forceinline__ void adam_step_body(const long* __restrict__ table, c
       if (zero_grad) g[i] = 0.f;
     }
   } else {
-    for (int i = threadIdx.x; i < len; i += SGD_TPB) {
+    for (int i = threadIdx.x; i < len; i += CHUNK_TPB) {
       float me = m[i], ve = v[i];
       p[i] = adam1<DECOUPLED>(p[i], g[i], &me, &ve, a);
       m[i] = me;
@@ -584,7 +561,7 @@ __device__ __forceinline__ void adam_step_body(const long* __restrict__ table, c
   }
 }
 
-__global__ __launch_bounds__(SGD_TPB) void adam_step_kernel(const long* __restrict__ table,
+__global__ __launch_bounds__(CHUNK_TPB) void adam_step_kernel(const long* __restrict__ table,
                                                             const long* __restrict__ chunks,
                                                             const double* __restrict__ hyper,
                                                             const float* __restrict__ guard, int n_tensors,
@@ -592,7 +569,7 @@ __global__ __launch_bounds__(SGD_TPB) void adam_step_kernel(const long* __restri
   adam_step_body<false>(table, chunks, hyper, guard, n_tensors, n_groups, zero_grad);
 }
 
-__global__ __launch_bounds__(SGD_TPB) void adamw_step_kernel(const long* __restrict__ table,
+__global__ __launch_bounds__(CHUNK_TPB) void adamw_step_kernel(const long* __restrict__ table,
                                                              const long* __restrict__ chunks,
                                                              const double* __restrict__ hyper,
                                                              const float* __restrict__ guard, int n_tensors,
@@ -616,12 +593,59 @@ bool adam_tables_ok(const long* tab, int n_tensors, const long* chunks, int n_ch
   }
   return chunks_tile(tab, ADAM_TAB_ROW, 5, n_tensors, chunks, n_chunks);
 }
+
+// ---------------------------------------------------------------------------------------------- the entries' checks
+bool ce_args_ok(const float* logits, int ld, const long* labels, int N, int K, int k_hi, float* dlogits, float* ring,
+                int* counter, int cap, float* loss_out) {
+  if (!logits || !labels || !dlogits || !ring || !counter || !loss_out) return false;
+  return N > 0 && K > 0 && ld >= K && cap > 0 && k_hi >= 1 && k_hi <= K;
+}
+
+bool bce_args_ok(const float* x, int ldx, const float* y, int ldy, int N, int K, int from_logits, float* dx,
+                 float* ring, int* counter, int cap, float* loss_out) {
+  if (!x || !y || !dx || !ring || !counter || !loss_out) return false;
+  return N > 0 && K > 0 && ldx >= K && ldy >= K && cap > 0 && (from_logits == 0 || from_logits == 1);
+}
+
+// sf_sgd_step and, with the ratios, sf_lars_sgd_step
+template <bool LARS>
+int sgd_entry(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
+              int n_chunks, const float* hyper_host, const float* hyper, int n_groups, const float* ratios,
+              const float* guard, int zero_grad, void* stream) {
+  if (!tables_args_ok(table_host, table, n_tensors, chunks_host, chunks, n_chunks)) return SF_EINVAL;
+  if (!hyper_host || !hyper || (LARS && !ratios)) return SF_EINVAL;
+  if (n_groups <= 0 || (zero_grad != 0 && zero_grad != 1)) return SF_EINVAL;
+  if (!sgd_tables_ok(table_host, n_tensors, chunks_host, n_chunks, hyper_host, n_groups)) return SF_EINVAL;
+  if (LARS)
+    hipLaunchKernelGGL(lars_sgd_step_kernel, dim3(n_chunks), dim3(CHUNK_TPB), 0, (hipStream_t)stream, table, chunks,
+                       hyper, ratios, guard, n_tensors, n_groups, zero_grad);
+  else
+    hipLaunchKernelGGL(sgd_step_kernel, dim3(n_chunks), dim3(CHUNK_TPB), 0, (hipStream_t)stream, table, chunks, hyper,
+                       guard, n_tensors, n_groups, zero_grad);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
+
+// sf_adam_step and sf_adamw_step: the tick launch, then the step launch
+template <bool DECOUPLED>
+int adam_entry(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
+               int n_chunks, const double* hyper_host, const double* hyper, int n_groups, const float* guard,
+               int zero_grad, void* stream) {
+  if (!tables_args_ok(table_host, table, n_tensors, chunks_host, chunks, n_chunks)) return SF_EINVAL;
+  if (!hyper_host || !hyper || n_groups <= 0 || (zero_grad != 0 && zero_grad != 1)) return SF_EINVAL;
+  if (!adam_tables_ok(table_host, n_tensors, chunks_host, n_chunks, hyper_host, n_groups)) return SF_EINVAL;
+  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(CHUNK_TPB), 0, (hipStream_t)stream, table, guard, n_tensors);
+  SF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(DECOUPLED ? adamw_step_kernel : adam_step_kernel, dim3(n_chunks), dim3(CHUNK_TPB), 0,
+                     (hipStream_t)stream, table, chunks, hyper, guard, n_tensors, n_groups, zero_grad);
+  SF_CHECK_LAUNCH();
+  return SF_OK;
+}
 }  // namespace
 
 extern "C" int sf_ce_topk(const float* logits, int ld, const long* labels, int N, int K, int k_hi, float* dlogits,
                           float* ring, int* counter, int cap, float* loss_out, void* stream) {
-  if (!logits || !labels || !dlogits || !ring || !counter || !loss_out) return SF_EINVAL;
-  if (N <= 0 || K <= 0 || ld < K || cap <= 0 || k_hi < 1 || k_hi > K) return SF_EINVAL;
+  if (!ce_args_ok(logits, ld, labels, N, K, k_hi, dlogits, ring, counter, cap, loss_out)) return SF_EINVAL;
   hipLaunchKernelGGL(ce_topk_kernel, dim3(1), dim3(CE_TPB), 0, (hipStream_t)stream, logits, ld, labels, N, K, k_hi,
                      dlogits, ring, counter, cap, loss_out);
   SF_CHECK_LAUNCH();
@@ -630,8 +654,7 @@ extern "C" int sf_ce_topk(const float* logits, int ld, const long* labels, int N
 
 extern "C" int sf_ce_topk_w(const float* logits, int ld, const long* labels, const float* weight, int N, int K, int k_hi,
                             float* dlogits, float* ring, int* counter, int cap, float* loss_out, void* stream) {
-  if (!logits || !labels || !weight || !dlogits || !ring || !counter || !loss_out) return SF_EINVAL;
-  if (N <= 0 || K <= 0 || ld < K || cap <= 0 || k_hi < 1 || k_hi > K) return SF_EINVAL;
+  if (!weight || !ce_args_ok(logits, ld, labels, N, K, k_hi, dlogits, ring, counter, cap, loss_out)) return SF_EINVAL;
   hipLaunchKernelGGL(ce_topk_w_kernel, dim3(1), dim3(CE_TPB), 0, (hipStream_t)stream, logits, ld, labels, weight, N, K,
                      k_hi, dlogits, ring, counter, cap, loss_out);
   SF_CHECK_LAUNCH();
@@ -641,8 +664,7 @@ extern "C" int sf_ce_topk_w(const float* logits, int ld, const long* labels, con
 extern "C" int sf_ce_mix(const float* logits, int ld, const long* labels, const long* mix_host, const long* mix, int N,
                          int K, int k_hi, float smoothing, float* dlogits, float* ring, int* counter, int cap,
                          float* loss_out, void* stream) {
-  if (!logits || !labels || !dlogits || !ring || !counter || !loss_out) return SF_EINVAL;
-  if (N <= 0 || K <= 0 || ld < K || cap <= 0 || k_hi < 1 || k_hi > K) return SF_EINVAL;
+  if (!ce_args_ok(logits, ld, labels, N, K, k_hi, dlogits, ring, counter, cap, loss_out)) return SF_EINVAL;
   if (!(smoothing >= 0.f && smoothing < 1.f)) return SF_EINVAL;  // (a NaN fails both)
   if ((mix == nullptr) != (mix_host == nullptr)) return SF_EINVAL;
   if (mix_host != nullptr)
@@ -654,36 +676,25 @@ extern "C" int sf_ce_mix(const float* logits, int ld, const long* labels, const 
   return SF_OK;
 }
 
-extern "C" int sf_sgd_chunk_elems(void) { return SGD_CHUNK; }
+extern "C" int sf_sgd_chunk_elems(void) { return CHUNK_ELEMS; }
 
 extern "C" int sf_sgd_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host,
                            const long* chunks, int n_chunks, const float* hyper_host, const float* hyper, int n_groups,
                            const float* guard, int zero_grad, void* stream) {
-  if (!table_host || !table || !chunks_host || !chunks || !hyper_host || !hyper) return SF_EINVAL;
-  if (n_tensors <= 0 || n_chunks <= 0 || n_groups <= 0 || (zero_grad != 0 && zero_grad != 1)) return SF_EINVAL;
-  if (!sgd_tables_ok(table_host, n_tensors, chunks_host, n_chunks, hyper_host, n_groups)) return SF_EINVAL;
-  hipLaunchKernelGGL(sgd_step_kernel, dim3(n_chunks), dim3(SGD_TPB), 0, (hipStream_t)stream, table, chunks, hyper, guard,
-                     n_tensors, n_groups, zero_grad);
-  SF_CHECK_LAUNCH();
-  return SF_OK;
+  return sgd_entry<false>(table_host, table, n_tensors, chunks_host, chunks, n_chunks, hyper_host, hyper, n_groups,
+                          nullptr, guard, zero_grad, stream);
 }
 
 extern "C" int sf_lars_sgd_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host,
                                 const long* chunks, int n_chunks, const float* hyper_host, const float* hyper,
                                 int n_groups, const float* ratios, const float* guard, int zero_grad, void* stream) {
-  if (!table_host || !table || !chunks_host || !chunks || !hyper_host || !hyper || !ratios) return SF_EINVAL;
-  if (n_tensors <= 0 || n_chunks <= 0 || n_groups <= 0 || (zero_grad != 0 && zero_grad != 1)) return SF_EINVAL;
-  if (!sgd_tables_ok(table_host, n_tensors, chunks_host, n_chunks, hyper_host, n_groups)) return SF_EINVAL;
-  hipLaunchKernelGGL(lars_sgd_step_kernel, dim3(n_chunks), dim3(SGD_TPB), 0, (hipStream_t)stream, table, chunks, hyper,
-                     ratios, guard, n_tensors, n_groups, zero_grad);
-  SF_CHECK_LAUNCH();
-  return SF_OK;
+  return sgd_entry<true>(table_host, table, n_tensors, chunks_host, chunks, n_chunks, hyper_host, hyper, n_groups,
+                         ratios, guard, zero_grad, stream);
 }
 
 extern "C" int sf_bce(const float* x, int ldx, const float* y, int ldy, int N, int K, int from_logits, float* dx,
                       float* ring, int* counter, int cap, float* loss_out, void* stream) {
-  if (!x || !y || !dx || !ring || !counter || !loss_out) return SF_EINVAL;
-  if (N <= 0 || K <= 0 || ldx < K || ldy < K || cap <= 0 || (from_logits != 0 && from_logits != 1)) return SF_EINVAL;
+  if (!bce_args_ok(x, ldx, y, ldy, N, K, from_logits, dx, ring, counter, cap, loss_out)) return SF_EINVAL;
   hipLaunchKernelGGL(bce_kernel, dim3(1), dim3(CE_TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, N, K, from_logits, dx,
                      ring, counter, cap, loss_out);
   SF_CHECK_LAUNCH();
@@ -693,8 +704,7 @@ extern "C" int sf_bce(const float* x, int ldx, const float* y, int ldy, int N, i
 extern "C" int sf_bce_w(const float* x, int ldx, const float* y, int ldy, const float* weight, const float* pos_weight,
                         int N, int K, int from_logits, float* dx, float* ring, int* counter, int cap, float* loss_out,
                         void* stream) {
-  if (!x || !y || !dx || !ring || !counter || !loss_out) return SF_EINVAL;
-  if (N <= 0 || K <= 0 || ldx < K || ldy < K || cap <= 0 || (from_logits != 0 && from_logits != 1)) return SF_EINVAL;
+  if (!bce_args_ok(x, ldx, y, ldy, N, K, from_logits, dx, ring, counter, cap, loss_out)) return SF_EINVAL;
   if (pos_weight && !from_logits) return SF_EINVAL;  // torch's BCELoss has no pos_weight
   hipLaunchKernelGGL(bce_w_kernel, dim3(1), dim3(CE_TPB), 0, (hipStream_t)stream, x, ldx, y, ldy, weight, pos_weight, N,
                      K, from_logits, dx, ring, counter, cap, loss_out);
@@ -705,27 +715,13 @@ extern "C" int sf_bce_w(const float* x, int ldx, const float* y, int ldy, const 
 extern "C" int sf_adam_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host,
                             const long* chunks, int n_chunks, const double* hyper_host, const double* hyper,
                             int n_groups, const float* guard, int zero_grad, void* stream) {
-  if (!table_host || !table || !chunks_host || !chunks || !hyper_host || !hyper) return SF_EINVAL;
-  if (n_tensors <= 0 || n_chunks <= 0 || n_groups <= 0 || (zero_grad != 0 && zero_grad != 1)) return SF_EINVAL;
-  if (!adam_tables_ok(table_host, n_tensors, chunks_host, n_chunks, hyper_host, n_groups)) return SF_EINVAL;
-  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(SGD_TPB), 0, (hipStream_t)stream, table, guard, n_tensors);
-  SF_CHECK_LAUNCH();
-  hipLaunchKernelGGL(adam_step_kernel, dim3(n_chunks), dim3(SGD_TPB), 0, (hipStream_t)stream, table, chunks, hyper,
-                     guard, n_tensors, n_groups, zero_grad);
-  SF_CHECK_LAUNCH();
-  return SF_OK;
+  return adam_entry<false>(table_host, table, n_tensors, chunks_host, chunks, n_chunks, hyper_host, hyper, n_groups,
+                           guard, zero_grad, stream);
 }
 
 extern "C" int sf_adamw_step(const long* table_host, const long* table, int n_tensors, const long* chunks_host,
                              const long* chunks, int n_chunks, const double* hyper_host, const double* hyper,
                              int n_groups, const float* guard, int zero_grad, void* stream) {
-  if (!table_host || !table || !chunks_host || !chunks || !hyper_host || !hyper) return SF_EINVAL;
-  if (n_tensors <= 0 || n_chunks <= 0 || n_groups <= 0 || (zero_grad != 0 && zero_grad != 1)) return SF_EINVAL;
-  if (!adam_tables_ok(table_host, n_tensors, chunks_host, n_chunks, hyper_host, n_groups)) return SF_EINVAL;
-  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(SGD_TPB), 0, (hipStream_t)stream, table, guard, n_tensors);
-  SF_CHECK_LAUNCH();
-  hipLaunchKernelGGL(adamw_step_kernel, dim3(n_chunks), dim3(SGD_TPB), 0, (hipStream_t)stream, table, chunks, hyper,
-                     guard, n_tensors, n_groups, zero_grad);
-  SF_CHECK_LAUNCH();
-  return SF_OK;
+  return adam_entry<true>(table_host, table, n_tensors, chunks_host, chunks, n_chunks, hyper_host, hyper, n_groups,
+                          guard, zero_grad, stream);
 }

@@ -70,23 +70,65 @@ def _rows_view(t, N, K):
     return t, (t.stride(0) if N > 1 else K)
 
 
+def _ce_args(who, preds, labels, host_args=None):
+    """The checks of the [N, K] predictions + [N] labels family, in one order: the shapes, then `host_args(N, K)` (the
+    caller's arguments that can be refused before anything needs the GPU), then the GPU, then the labels.  Returns the
+    row view of preds, its leading dimension, the contiguous labels, N and K."""
+    if preds.dim() != 2 or labels.dim() != 1 or labels.shape[0] != preds.shape[0]:
+        raise ValueError("%s: preds [N, K] and labels [N], got %s and %s" % (who, tuple(preds.shape),
+                                                                             tuple(labels.shape)))
+    N, K = preds.shape
+    if host_args is not None:
+        host_args(N, K)
+    sfhip._require_gpu(preds, who)
+    if labels.dtype != torch.int64 or not labels.is_cuda:
+        raise ValueError("%s: labels must be int64 on the GPU, got %s on %s" % (who, labels.dtype, labels.device))
+    preds, ld = _rows_view(preds, N, K)
+    return preds, int(ld), labels.contiguous(), N, K
+
+
+def _bce_args(who, preds, targets, host_args=None):
+    """The checks of the [N, K] predictions + [N, K] targets family, ordered as `_ce_args`; targets of any real dtype
+    are converted to float32.  Returns both row views with their leading dimensions, N and K."""
+    if preds.dim() != 2 or tuple(targets.shape) != tuple(preds.shape):
+        raise ValueError("%s: preds [N, K] and targets [N, K], got %s and %s" % (who, tuple(preds.shape),
+                                                                                 tuple(targets.shape)))
+    N, K = preds.shape
+    if host_args is not None:
+        host_args(N, K)
+    sfhip._require_gpu(preds, who)
+    if not targets.is_cuda:
+        raise sfhip.SfhipError("%s: targets are on %s — the loss kernel runs on the GPU only" % (who, targets.device))
+    if targets.dtype != torch.float32:
+        targets = targets.float()
+    sfhip._require_gpu(targets, who)
+    preds, ldx = _rows_view(preds, N, K)
+    targets, ldy = _rows_view(targets, N, K)
+    return preds, int(ldx), targets, int(ldy), N, K
+
+
+def _grad_out(N, K, given, out):
+    """The gradient tensor of a loss launch: `given`, or a new fp32 [N, K] beside `out` (fp32 [2]: loss, flag)."""
+    if given is None:
+        given = torch.empty((N, K), dtype=torch.float32, device=out.device)
+    assert given.is_contiguous() and tuple(given.shape) == (N, K) and out.numel() >= 2
+    return given
+
+
+def _ring_args(ring):
+    """(rows pointer, counter pointer, capacity) of a StatsRing as the kernels take them; no ring: (None, None, 0)."""
+    if ring is None:
+        return None, None, 0
+    return _vp(ring.rows), ctypes.cast(ctypes.c_void_p(ring.counter.data_ptr()), sfhip._pi), ring.cap
+
+
 def ce_topk(preds, labels, k_hi, ring, out, dlogits=None):
     """One `sf_ce_topk` launch.  preds fp32 [N, K] (unit column stride, row stride >= K), labels int64 [N], out fp32 [2]
     (loss, non-finite flag).  Returns dlogits [N, K]."""
-    sfhip._require_gpu(preds, "ce_topk")
-    if preds.dim() != 2 or labels.dim() != 1 or labels.shape[0] != preds.shape[0]:
-        raise ValueError("ce_topk: preds [N, K] and labels [N], got %s and %s" % (tuple(preds.shape), tuple(labels.shape)))
-    if labels.dtype != torch.int64 or not labels.is_cuda:
-        raise ValueError("ce_topk: labels must be int64 on the GPU, got %s on %s" % (labels.dtype, labels.device))
-    N, K = preds.shape
-    preds, ld = _rows_view(preds, N, K)
-    labels = labels.contiguous()
-    if dlogits is None:
-        dlogits = torch.empty((N, K), dtype=torch.float32, device=preds.device)
-    assert dlogits.is_contiguous() and tuple(dlogits.shape) == (N, K) and out.numel() >= 2
-    cnt = ctypes.cast(ctypes.c_void_p(ring.counter.data_ptr()), sfhip._pi)
-    sfhip._call("sf_ce_topk", _vp(preds), int(ld), _vp(labels), N, K, int(k_hi), _vp(dlogits), _vp(ring.rows), cnt,
-                ring.cap, _vp(out), tag="ce_topk")
+    preds, ld, labels, N, K = _ce_args("ce_topk", preds, labels)
+    dlogits = _grad_out(N, K, dlogits, out)
+    sfhip._call("sf_ce_topk", _vp(preds), ld, _vp(labels), N, K, int(k_hi), _vp(dlogits), *_ring_args(ring), _vp(out),
+                tag="ce_topk")
     return dlogits
 
 
@@ -94,24 +136,10 @@ def bce(preds, targets, from_logits, ring, out, dgrad=None):
     """One `sf_bce` launch.  preds fp32 [N, K] (probabilities, or logits with from_logits), targets [N, K] of any
     real dtype (the reference's label tensors are float64 or integer: converted to float32), both as row views (unit
     column stride, row stride >= K); out fp32 [2] (loss, non-finite flag).  Returns d loss / d preds [N, K]."""
-    sfhip._require_gpu(preds, "bce")
-    if preds.dim() != 2 or tuple(targets.shape) != tuple(preds.shape):
-        raise ValueError("bce: preds [N, K] and targets [N, K], got %s and %s" % (tuple(preds.shape),
-                                                                                 tuple(targets.shape)))
-    if not targets.is_cuda:
-        raise sfhip.SfhipError("bce: targets are on %s — the loss kernel runs on the GPU only" % targets.device)
-    if targets.dtype != torch.float32:
-        targets = targets.float()
-    sfhip._require_gpu(targets, "bce")
-    N, K = preds.shape
-    preds, ldx = _rows_view(preds, N, K)
-    targets, ldy = _rows_view(targets, N, K)
-    if dgrad is None:
-        dgrad = torch.empty((N, K), dtype=torch.float32, device=preds.device)
-    assert dgrad.is_contiguous() and tuple(dgrad.shape) == (N, K) and out.numel() >= 2
-    cnt = ctypes.cast(ctypes.c_void_p(ring.counter.data_ptr()), sfhip._pi)
-    sfhip._call("sf_bce", _vp(preds), int(ldx), _vp(targets), int(ldy), N, K, 1 if from_logits else 0, _vp(dgrad),
-                _vp(ring.rows), cnt, ring.cap, _vp(out), tag="bce")
+    preds, ldx, targets, ldy, N, K = _bce_args("bce", preds, targets)
+    dgrad = _grad_out(N, K, dgrad, out)
+    sfhip._call("sf_bce", _vp(preds), ldx, _vp(targets), ldy, N, K, 1 if from_logits else 0, _vp(dgrad),
+                *_ring_args(ring), _vp(out), tag="bce")
     return dgrad
 
 
@@ -130,22 +158,11 @@ def _weight_vector(t, K, device, who, name):
 def ce_topk_w(preds, labels, weight, k_hi, ring, out, dlogits=None):
     """One `sf_ce_topk_w` launch: `ce_topk` with class weights, F.cross_entropy(weight=) — the divisor is the sum of
     the rows' weights.  weight fp32 [K], contiguous, on the predictions' GPU."""
-    if preds.dim() != 2 or labels.dim() != 1 or labels.shape[0] != preds.shape[0]:
-        raise ValueError("ce_topk_w: preds [N, K] and labels [N], got %s and %s" % (tuple(preds.shape),
-                                                                                    tuple(labels.shape)))
-    N, K = preds.shape
-    weight = _weight_vector(weight, K, preds.device, "ce_topk_w", "weight")  # refused before anything needs the GPU
-    sfhip._require_gpu(preds, "ce_topk_w")
-    if labels.dtype != torch.int64 or not labels.is_cuda:
-        raise ValueError("ce_topk_w: labels must be int64 on the GPU, got %s on %s" % (labels.dtype, labels.device))
-    preds, ld = _rows_view(preds, N, K)
-    labels = labels.contiguous()
-    if dlogits is None:
-        dlogits = torch.empty((N, K), dtype=torch.float32, device=preds.device)
-    assert dlogits.is_contiguous() and tuple(dlogits.shape) == (N, K) and out.numel() >= 2
-    cnt = ctypes.cast(ctypes.c_void_p(ring.counter.data_ptr()), sfhip._pi)
-    sfhip._call("sf_ce_topk_w", _vp(preds), int(ld), _vp(labels), _vp(weight), N, K, int(k_hi), _vp(dlogits),
-                _vp(ring.rows), cnt, ring.cap, _vp(out), tag="ce_topk_w")
+    preds, ld, labels, N, K = _ce_args(
+        "ce_topk_w", preds, labels, lambda N, K: _weight_vector(weight, K, preds.device, "ce_topk_w", "weight"))
+    dlogits = _grad_out(N, K, dlogits, out)
+    sfhip._call("sf_ce_topk_w", _vp(preds), ld, _vp(labels), _vp(weight), N, K, int(k_hi), _vp(dlogits),
+                *_ring_args(ring), _vp(out), tag="ce_topk_w")
     return dlogits
 
 
@@ -183,72 +200,42 @@ def ce_mix(preds, labels, k_hi, ring, out, mix_host=None, mix=None, smoothing=0.
     CutMix — F.cross_entropy(preds, t) with t = (1 - eps) (lam onehot(a) + (1 - lam) onehot(b)) + eps / K, a the row's
     label, b its partner's.  mix: the device rows int64 [N, 7] `gpu_train_batch_mix` returns (partner, mode, lam as
     float32 bits, box), mix_host their host copy; both None: no mixing."""
-    if preds.dim() != 2 or labels.dim() != 1 or labels.shape[0] != preds.shape[0]:
-        raise ValueError("ce_mix: preds [N, K] and labels [N], got %s and %s" % (tuple(preds.shape), tuple(labels.shape)))
-    N, K = preds.shape
-    eps = _smoothing(smoothing, "ce_mix")  # refused before anything needs the GPU
-    mix_host, mix = _mix_pair(mix_host, mix, N, "ce_mix")
-    sfhip._require_gpu(preds, "ce_mix")
-    if labels.dtype != torch.int64 or not labels.is_cuda:
-        raise ValueError("ce_mix: labels must be int64 on the GPU, got %s on %s" % (labels.dtype, labels.device))
+    def host_args(N, K):
+        _smoothing(smoothing, "ce_mix")
+        _mix_pair(mix_host, mix, N, "ce_mix")
+
+    preds, ld, labels, N, K = _ce_args("ce_mix", preds, labels, host_args)
     if mix is not None and not mix.is_cuda:
         raise sfhip.SfhipError("ce_mix: the mix rows are on %s — the loss kernel runs on the GPU only" % mix.device)
-    preds, ld = _rows_view(preds, N, K)
-    labels = labels.contiguous()
-    if dlogits is None:
-        dlogits = torch.empty((N, K), dtype=torch.float32, device=preds.device)
-    assert dlogits.is_contiguous() and tuple(dlogits.shape) == (N, K) and out.numel() >= 2
-    cnt = ctypes.cast(ctypes.c_void_p(ring.counter.data_ptr()), sfhip._pi)
-    sfhip._call("sf_ce_mix", _vp(preds), int(ld), _vp(labels), _vp(mix_host), _vp(mix), N, K, int(k_hi), eps,
-                _vp(dlogits), _vp(ring.rows), cnt, ring.cap, _vp(out), tag="ce_mix")
+    dlogits = _grad_out(N, K, dlogits, out)
+    sfhip._call("sf_ce_mix", _vp(preds), ld, _vp(labels), _vp(mix_host), _vp(mix), N, K, int(k_hi), float(smoothing),
+                _vp(dlogits), *_ring_args(ring), _vp(out), tag="ce_mix")
     return dlogits
 
 
 def bce_w(preds, targets, from_logits, ring, out, weight=None, pos_weight=None, dgrad=None):
     """One `sf_bce_w` launch: `bce` with nn.BCELoss(weight=) / nn.BCEWithLogitsLoss(weight=, pos_weight=).  weight and
     pos_weight fp32 [K], contiguous, on the predictions' GPU, or None (all ones); pos_weight needs from_logits."""
-    if preds.dim() != 2 or tuple(targets.shape) != tuple(preds.shape):
-        raise ValueError("bce_w: preds [N, K] and targets [N, K], got %s and %s" % (tuple(preds.shape),
-                                                                                   tuple(targets.shape)))
-    if pos_weight is not None and not from_logits:
-        raise ValueError("bce_w: pos_weight belongs to the loss on logits (nn.BCEWithLogitsLoss); nn.BCELoss has none")
-    N, K = preds.shape
-    if weight is not None:  # refused before anything needs the GPU
-        weight = _weight_vector(weight, K, preds.device, "bce_w", "weight")
-    if pos_weight is not None:
-        pos_weight = _weight_vector(pos_weight, K, preds.device, "bce_w", "pos_weight")
-    sfhip._require_gpu(preds, "bce_w")
-    if not targets.is_cuda:
-        raise sfhip.SfhipError("bce_w: targets are on %s — the loss kernel runs on the GPU only" % targets.device)
-    if targets.dtype != torch.float32:
-        targets = targets.float()
-    sfhip._require_gpu(targets, "bce_w")
-    preds, ldx = _rows_view(preds, N, K)
-    targets, ldy = _rows_view(targets, N, K)
-    if dgrad is None:
-        dgrad = torch.empty((N, K), dtype=torch.float32, device=preds.device)
-    assert dgrad.is_contiguous() and tuple(dgrad.shape) == (N, K) and out.numel() >= 2
-    cnt = ctypes.cast(ctypes.c_void_p(ring.counter.data_ptr()), sfhip._pi)
-    sfhip._call("sf_bce_w", _vp(preds), int(ldx), _vp(targets), int(ldy), _vp(weight), _vp(pos_weight), N, K,
-                1 if from_logits else 0, _vp(dgrad), _vp(ring.rows), cnt, ring.cap, _vp(out), tag="bce_w")
+    def host_args(N, K):
+        if pos_weight is not None and not from_logits:
+            raise ValueError("bce_w: pos_weight belongs to the loss on logits (nn.BCEWithLogitsLoss); nn.BCELoss has "
+                             "none")
+        for name, w in (("weight", weight), ("pos_weight", pos_weight)):
+            if w is not None:
+                _weight_vector(w, K, preds.device, "bce_w", name)
+
+    preds, ldx, targets, ldy, N, K = _bce_args("bce_w", preds, targets, host_args)
+    dgrad = _grad_out(N, K, dgrad, out)
+    sfhip._call("sf_bce_w", _vp(preds), ldx, _vp(targets), ldy, _vp(weight), _vp(pos_weight), N, K,
+                1 if from_logits else 0, _vp(dgrad), *_ring_args(ring), _vp(out), tag="bce_w")
     return dgrad
 
 
 def topk_errors(preds, labels, k_hi, ring):
     """One `sf_topk_errors` launch: the top-1 / top-k_hi errors of an evaluation batch (train_net.py:227-232) as a ring
     row of kind KIND_EVAL.  preds fp32 [N, K] (unit column stride, row stride >= K), labels int64 [N]."""
-    sfhip._require_gpu(preds, "topk_errors")
-    if preds.dim() != 2 or labels.dim() != 1 or labels.shape[0] != preds.shape[0]:
-        raise ValueError("topk_errors: preds [N, K] and labels [N], got %s and %s" % (tuple(preds.shape),
-                                                                                      tuple(labels.shape)))
-    if labels.dtype != torch.int64 or not labels.is_cuda:
-        raise ValueError("topk_errors: labels must be int64 on the GPU, got %s on %s" % (labels.dtype, labels.device))
-    N, K = preds.shape
-    preds, ld = _rows_view(preds, N, K)
-    labels = labels.contiguous()
-    cnt = ctypes.cast(ctypes.c_void_p(ring.counter.data_ptr()), sfhip._pi)
-    sfhip._call("sf_topk_errors", _vp(preds), int(ld), _vp(labels), N, K, int(k_hi), _vp(ring.rows), cnt, ring.cap,
-                tag="topk_errors")
+    preds, ld, labels, N, K = _ce_args("topk_errors", preds, labels)
+    sfhip._call("sf_topk_errors", _vp(preds), ld, _vp(labels), N, K, int(k_hi), *_ring_args(ring), tag="topk_errors")
 
 
 class _LossFunction(torch.autograd.Function):
@@ -523,17 +510,24 @@ def build_adam_tables(entries, chunk):
     return _build_tables(entries, chunk, ADAM_TAB_ROW, 5)
 
 
-def _table_step(symbol, dtype, table_host, table, chunks_host, chunks, hyper_host, hyper, guard, zero_grad):
+def _tables_args(tag, table_host, table, chunks_host, chunks):
+    """The six table and count arguments of every table entry; the host tensors are what the device ones were uploaded
+    from."""
     for h, d in ((table_host, table), (chunks_host, chunks)):
-        assert h.dtype == d.dtype == torch.int64 and h.is_contiguous() and d.is_contiguous() and not h.is_cuda
-        assert h.shape == d.shape
+        assert h.dtype == d.dtype == torch.int64 and h.is_contiguous() and d.is_contiguous() and not h.is_cuda, tag
+        assert h.shape == d.shape, tag
+    return (_vp(table_host), _vp(table), table_host.shape[0], _vp(chunks_host), _vp(chunks), chunks_host.shape[0])
+
+
+def _table_step(symbol, dtype, table_host, table, chunks_host, chunks, hyper_host, hyper, guard, zero_grad):
+    tag = symbol[3:]
+    args = _tables_args(tag, table_host, table, chunks_host, chunks)
     assert hyper_host.dtype == hyper.dtype == dtype and hyper_host.shape == hyper.shape and hyper.is_contiguous()
     tag = symbol[3:]
     if not (table.is_cuda and chunks.is_cuda and hyper.is_cuda):
         raise sfhip.SfhipError("%s: table, chunks and hyper live on the GPU — there is no CPU fallback" % tag)
-    sfhip._call(symbol, _vp(table_host), _vp(table), table_host.shape[0], _vp(chunks_host), _vp(chunks),
-                chunks_host.shape[0], _vp(hyper_host), _vp(hyper), hyper_host.shape[0], _vp(guard),
-                1 if zero_grad else 0, tag=tag)
+    sfhip._call(symbol, *args, _vp(hyper_host), _vp(hyper), hyper_host.shape[0], _vp(guard), 1 if zero_grad else 0,
+                tag=tag)
 
 
 def sgd_step(table_host, table, chunks_host, chunks, hyper_host, hyper, guard=None, zero_grad=False):
@@ -563,9 +557,7 @@ def lars_ratios(table_host, table, chunks_host, chunks, hyper_host, hyper, parti
     the guard into state (fp32 [8]: [4] non-finite flag, [5] guard_out).  hyper fp32 [n_groups + 1, 3] = lr,
     weight_decay, apply per group, then trust_coefficient, eps, clip; partials fp64 [n_chunks, 2]; guard the loss's
     (or the clipper's) guard or None."""
-    for h, d in ((table_host, table), (chunks_host, chunks)):
-        assert h.dtype == d.dtype == torch.int64 and h.is_contiguous() and d.is_contiguous() and not h.is_cuda
-        assert h.shape == d.shape
+    args = _tables_args("lars_ratios", table_host, table, chunks_host, chunks)
     assert hyper_host.dtype == hyper.dtype == torch.float32 and hyper_host.shape == hyper.shape
     assert hyper.is_contiguous() and hyper_host.is_contiguous() and hyper_host.shape[0] >= 2
     if not (table.is_cuda and chunks.is_cuda and hyper.is_cuda and partials.is_cuda and ratios.is_cuda and state.is_cuda):
@@ -574,24 +566,20 @@ def lars_ratios(table_host, table, chunks_host, chunks, hyper_host, hyper, parti
     assert partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= 2 * chunks_host.shape[0]
     assert ratios.dtype == torch.float32 and ratios.is_contiguous() and ratios.numel() >= 2 * table_host.shape[0]
     assert state.dtype == torch.float32 and state.is_contiguous() and state.numel() >= CLIP_STATE
-    sfhip._call("sf_lars_ratios", _vp(table_host), _vp(table), table_host.shape[0], _vp(chunks_host), _vp(chunks),
-                chunks_host.shape[0], _vp(hyper_host), _vp(hyper), hyper_host.shape[0] - 1, _vp(guard), _vp(partials),
-                _vp(ratios), _vp(state), tag="lars_ratios")
+    sfhip._call("sf_lars_ratios", *args, _vp(hyper_host), _vp(hyper), hyper_host.shape[0] - 1, _vp(guard),
+                _vp(partials), _vp(ratios), _vp(state), tag="lars_ratios")
 
 
 def lars_sgd_step(table_host, table, chunks_host, chunks, hyper_host, hyper, ratios, guard=None, zero_grad=False):
     """One `sf_lars_sgd_step` launch: `sgd_step` with {r, wd_t} per tensor from `ratios` (fp32 [n, 2] on the GPU)."""
-    for h, d in ((table_host, table), (chunks_host, chunks)):
-        assert h.dtype == d.dtype == torch.int64 and h.is_contiguous() and d.is_contiguous() and not h.is_cuda
-        assert h.shape == d.shape
+    args = _tables_args("lars_sgd_step", table_host, table, chunks_host, chunks)
     assert hyper_host.dtype == hyper.dtype == torch.float32 and hyper_host.shape == hyper.shape
     assert hyper.is_contiguous() and hyper_host.is_contiguous()
     if not (table.is_cuda and chunks.is_cuda and hyper.is_cuda and ratios.is_cuda):
         raise sfhip.SfhipError("lars_sgd_step: table, chunks, hyper and ratios live on the GPU — there is no CPU "
                                "fallback")
     assert ratios.dtype == torch.float32 and ratios.is_contiguous() and ratios.numel() >= 2 * table_host.shape[0]
-    sfhip._call("sf_lars_sgd_step", _vp(table_host), _vp(table), table_host.shape[0], _vp(chunks_host), _vp(chunks),
-                chunks_host.shape[0], _vp(hyper_host), _vp(hyper), hyper_host.shape[0], _vp(ratios), _vp(guard),
+    sfhip._call("sf_lars_sgd_step", *args, _vp(hyper_host), _vp(hyper), hyper_host.shape[0], _vp(ratios), _vp(guard),
                 1 if zero_grad else 0, tag="lars_sgd_step")
 
 
@@ -599,6 +587,30 @@ def adamw_step(table_host, table, chunks_host, chunks, hyper_host, hyper, guard=
     """One `sf_adamw_step` call (two launches); tables and hyper as `adam_step` takes them."""
     _table_step("sf_adamw_step", torch.float64, table_host, table, chunks_host, chunks, hyper_host, hyper, guard,
                 zero_grad)
+
+
+class _HyperStage(object):
+    """The pinned staging ring of the hyper-parameter uploads.  The copy reads the staging row when the stream gets
+    there, not now: every upload takes the next of STAGE_SLOTS pinned rows and leaves an event behind it, and a row is
+    written again only after its event has passed (the host would have to run STAGE_SLOTS learning rates ahead of the
+    device to wait here)."""
+
+    def __init__(self):
+        self._stage = None
+
+    def upload(self, rows, dev_tensor):
+        """One `non_blocking` copy of the host tensor `rows` into `dev_tensor` on the current stream."""
+        if self._stage is None or self._stage.shape[1:] != rows.shape:
+            self._stage = torch.empty((STAGE_SLOTS,) + tuple(rows.shape), dtype=rows.dtype).pin_memory()
+            self._stage_events, self._stage_next = [None] * STAGE_SLOTS, 0
+        i = self._stage_next
+        self._stage_next = (i + 1) % STAGE_SLOTS
+        if self._stage_events[i] is not None:
+            self._stage_events[i].synchronize()
+        self._stage[i].copy_(rows)
+        dev_tensor.copy_(self._stage[i], non_blocking=True)
+        self._stage_events[i] = torch.cuda.Event()
+        self._stage_events[i].record()
 
 
 class _TableOptimizer(object):
@@ -615,7 +627,7 @@ class _TableOptimizer(object):
         self._key = None
         self._table = self._chunks = self._table_dev = self._chunks_dev = None
         self._hyper = self._hyper_dev = self._hyper_vals = None
-        self._stage = None        # pinned staging rows of the hyper-parameter uploads
+        self._stage = _HyperStage()
         self._sig = self._plist = None  # what the table was built from; the flat parameter list
         self._check_params()
 
@@ -667,20 +679,7 @@ class _TableOptimizer(object):
         dev = self.param_groups[0]["params"][0].device
         if self._hyper_dev is None or self._hyper_dev.shape != rows.shape:
             self._hyper_dev = torch.empty(rows.shape, dtype=self._HYP_DTYPE, device=dev)
-        # the copy reads the staging row when the stream gets there, not now: every upload takes the next of STAGE_SLOTS
-        # pinned rows and leaves an event behind it, and a row is written again only after its event has passed (the
-        # host would have to run STAGE_SLOTS learning rates ahead of the device to wait here)
-        if self._stage is None or self._stage.shape[1:] != rows.shape:
-            self._stage = torch.empty((STAGE_SLOTS,) + tuple(rows.shape), dtype=self._HYP_DTYPE).pin_memory()
-            self._stage_events, self._stage_next = [None] * STAGE_SLOTS, 0
-        i = self._stage_next
-        self._stage_next = (i + 1) % STAGE_SLOTS
-        if self._stage_events[i] is not None:
-            self._stage_events[i].synchronize()
-        self._stage[i].copy_(rows)
-        self._hyper_dev.copy_(self._stage[i], non_blocking=True)
-        self._stage_events[i] = torch.cuda.Event()
-        self._stage_events[i].record()
+        self._stage.upload(rows, self._hyper_dev)
         self._hyper, self._hyper_vals = rows, vals
         return True
 
@@ -1061,12 +1060,10 @@ def build_clip_tables(entries, chunk):
 
 
 def _clip_tables_args(tag, table_host, table, chunks_host, chunks):
-    for h, d in ((table_host, table), (chunks_host, chunks)):
-        assert h.dtype == d.dtype == torch.int64 and h.is_contiguous() and d.is_contiguous() and not h.is_cuda
-        assert h.shape == d.shape
+    args = _tables_args(tag, table_host, table, chunks_host, chunks)
     if not (table.is_cuda and chunks.is_cuda):
         raise sfhip.SfhipError("%s: table and chunks live on the GPU — there is no CPU fallback" % tag)
-    return (_vp(table_host), _vp(table), table_host.shape[0], _vp(chunks_host), _vp(chunks), chunks_host.shape[0])
+    return args
 
 
 def grad_norm(table_host, table, chunks_host, chunks, norm_type, partials, state, max_norm=None, guard=None, ring=None):
@@ -1078,9 +1075,8 @@ def grad_norm(table_host, table, chunks_host, chunks, norm_type, partials, state
         raise sfhip.SfhipError("grad_norm: partials and state live on the GPU — there is no CPU fallback")
     assert partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= chunks_host.shape[0]
     assert state.dtype == torch.float32 and state.is_contiguous() and state.numel() >= CLIP_STATE
-    cnt = ctypes.cast(ctypes.c_void_p(ring.counter.data_ptr()), sfhip._pi) if ring is not None else None
     sfhip._call("sf_grad_norm", *args, int(norm_type), _vp(max_norm), _vp(guard), _vp(partials), _vp(state),
-                _vp(ring.rows) if ring is not None else None, cnt, ring.cap if ring is not None else 0, tag="grad_norm")
+                *_ring_args(ring), tag="grad_norm")
 
 
 def grad_scale(table_host, table, chunks_host, chunks, state):
@@ -1161,7 +1157,8 @@ class HipGradClip(object):
         self._params = params
         self._sig = None
         self._table = self._chunks = self._table_dev = self._chunks_dev = self._partials = None
-        self._state = self._hyper_dev = self._hyper_vals = self._stage = None
+        self._state = self._hyper_dev = self._hyper_vals = None
+        self._stage = _HyperStage()
 
     # ---- device memory this object owns
     def _device(self):
@@ -1208,16 +1205,7 @@ class HipGradClip(object):
         row = torch.tensor([v if v is not None else 0.0 for v in vals], dtype=torch.float32)
         if self._hyper_dev is None:
             self._hyper_dev = torch.empty((2,), dtype=torch.float32, device=self._device())
-            self._stage = torch.empty((STAGE_SLOTS, 2), dtype=torch.float32).pin_memory()
-            self._stage_events, self._stage_next = [None] * STAGE_SLOTS, 0
-        i = self._stage_next
-        self._stage_next = (i + 1) % STAGE_SLOTS
-        if self._stage_events[i] is not None:
-            self._stage_events[i].synchronize()
-        self._stage[i].copy_(row)
-        self._hyper_dev.copy_(self._stage[i], non_blocking=True)
-        self._stage_events[i] = torch.cuda.Event()
-        self._stage_events[i].record()
+        self._stage.upload(row, self._hyper_dev)
         self._hyper_vals = vals
         return True
 
