@@ -220,6 +220,9 @@ _SIGNATURES = {
     "sf_adamw_step": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _ci, _vp]),
     "sf_lars_sgd_step": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp]),
     "sf_lars_ratios": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp]),
+    # averaged weights: one-launch EMA / SWA / running-mean update with a device-side count, swap / copy of the pairs
+    "sf_avg_update": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp]),
+    "sf_avg_exchange": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _ci, _vp]),
     # evaluation: top-k errors of a batch, the epoch's row store, mean average precision
     "sf_topk_errors": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _pi, _ci, _vp]),
     "sf_rows_append": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp]),

@@ -613,6 +613,17 @@ class _HyperStage(object):
         self._stage_events[i].record()
 
 
+def carve_views(numels, device):
+    """One zero-filled float32 allocation holding a flat view of each of `numels` elements, every view on 16 bytes ->
+    (the allocation, the views).  Shared by the optimizers' state slots and the averaged weights (models/weight_avg.py)."""
+    offs, n = [], 0
+    for k in numels:
+        offs.append(n)
+        n += (k + 3) // 4 * 4
+    block = torch.zeros((n,), dtype=torch.float32, device=device)
+    return block, [block[o:o + k] for o, k in zip(offs, numels)]
+
+
 class _TableOptimizer(object):
     """What HipSGD and HipAdam share, mixed in in front of torch's optimizer: the parameter checks, 16-byte aligned
     state slots carved from allocations the optimizer owns, the address table cached by a cheap signature, the pinned
@@ -646,14 +657,10 @@ class _TableOptimizer(object):
                     raise ValueError("%s: parameters must be contiguous" % self._NAME)
 
     def _carve(self, numels, device):
-        """One zero-filled allocation holding a flat view of each of `numels` elements, every view on 16 bytes."""
-        offs, n = [], 0
-        for k in numels:
-            offs.append(n)
-            n += (k + 3) // 4 * 4
-        block = torch.zeros((n,), dtype=torch.float32, device=device)
+        """`carve_views` from an allocation this optimizer keeps."""
+        block, views = carve_views(numels, device)
         self._blocks.append(block)
-        return [block[o:o + k] for o, k in zip(offs, numels)]
+        return views
 
     def _invalidate(self):
         self._key = self._sig = self._plist = None

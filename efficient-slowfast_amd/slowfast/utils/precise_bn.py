@@ -19,24 +19,37 @@ def get_bn_modules(model):
 
 @torch.no_grad()
 def update_bn_stats(model, data_loader, num_iters=200):
-    """model: in training mode for the layers that need precise statistics; data_loader: iterable of model inputs."""
+    """model: in training mode for the layers that need precise statistics; data_loader: iterable of model inputs.
+
+    The averaging is ONE native call per iteration (`sf_avg_update`, mode 2) over a table of {accumulator view,
+    running_mean / running_var} pairs of all layers — the accumulators are views of one allocation, the iteration
+    count a word in device memory — instead of six small torch operations per layer.  Per element it is what those
+    operations computed on the GPU, bit for bit: mean += (running - mean) / (k + 1), where torch's division by the host
+    number k + 1 is a multiply by its float32 reciprocal.  At the end one `sf_avg_exchange` launch writes the
+    accumulators into the running statistics (in place: the buffers keep their addresses)."""
+    from slowfast.models import engine, weight_avg
+    from slowfast.models.step_tail import carve_views
     layers = get_bn_modules(model)
     if not layers:
         return
     saved = [bn.momentum for bn in layers]
     for bn in layers:
         bn.momentum = 1.0
-    mean = [torch.zeros_like(bn.running_mean) for bn in layers]
-    var = [torch.zeros_like(bn.running_var) for bn in layers]
+    stats = [t for bn in layers for t in (bn.running_mean, bn.running_var)]
+    for t in stats:
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("precise-BN pass: running statistics must be contiguous float32 tensors, got %s" % t.dtype)
+    _, acc = carve_views([t.numel() for t in stats], stats[0].device)
+    pairs = [(a, t, weight_avg.KIND_AVG) for a, t in zip(acc, stats)]
+    table = weight_avg._PairTable("precise-BN pass")
+    count = torch.zeros((), dtype=torch.int64, device=stats[0].device)
     ind = -1
     for ind, inputs in enumerate(itertools.islice(data_loader, num_iters)):
         model(inputs)
-        for i, bn in enumerate(layers):
-            mean[i] += (bn.running_mean - mean[i]) / (ind + 1)
-            var[i] += (bn.running_var - var[i]) / (ind + 1)
+        weight_avg.avg_update(*table.args(pairs), weight_avg.MODE_RUNNING, count)
     if ind != num_iters - 1:
         raise AssertionError("precise-BN pass: the loader ran dry after %d of the %d batches asked for" % (ind + 1, num_iters))
+    weight_avg.avg_exchange(*table.args(pairs), weight_avg.OP_TO_SOURCE)
+    engine.parameters_changed()  # the running statistics moved behind torch's version counters
     for i, bn in enumerate(layers):
-        bn.running_mean = mean[i]
-        bn.running_var = var[i]
         bn.momentum = saved[i]

@@ -1169,6 +1169,44 @@ int sf_lars_ratios(const long* table_host, const long* table, int n_tensors, con
                    int n_chunks, const float* hyper_host, const float* hyper, int n_groups, const float* guard_in,
                    double* partials, float* ratios, float* state, void* stream);
 
+/* ---- averaged weights (csrc/weight_avg.hip): the EMA / SWA copy of parameters and BN buffers that large-batch recipes
+ * evaluate and checkpoint (torch.optim.swa_utils.AveragedModel), and the running mean of the precise-BN pass, without
+ * the host.  Nothing synchronises or reads back.
+ * table: int64 [n_tensors][4] = average address, source address, numel, kind:
+ *     0  float32, averaged;
+ *     1  float32, copied source -> average (a buffer when buffers are not averaged: torch's use_buffers = False);
+ *     2  int64 words, copied (num_batches_tracked); numel counts 8-byte words.
+ *   chunks: int64 [n_chunks][2] as sf_sgd_step's, tiled at sf_sgd_chunk_elems() in table order.  The *_host arguments are
+ *   the host arrays the device ones were uploaded from: checked before anything is launched, and every workgroup
+ *   re-checks the device row it reads, its numel against the chunk list included (a row that fails touches nothing; a
+ *   numel that moved inside its last chunk's slack cannot be told).  Accesses are 16 bytes wide where both addresses of
+ *   a span allow, else 4; every element has one owner and one formula, so both widths give the same bits.
+ * sf_avg_update: ONE launch over the table, then a one-thread launch.  count: ONE int64 in DEVICE memory, the number of
+ *   updates so far (torch's n_averaged); hyper: ONE fp32 in DEVICE memory (mode 0 only; may be NULL otherwise), hyper_host
+ *   the host value it was uploaded from.  Every kind-0 element a with its source s:
+ *     *count == 0 (any mode):  a = s — the first update is a copy, as in torch;
+ *     mode 0 (EMA):            a = lerp(a, s, w),  w = hyper[0] = 1 - decay;
+ *     mode 1 (equal mean):     a = lerp(a, s, 1.f / (float)(*count + 1));
+ *     mode 2 (running mean):   a = a + (s - a) * (1.f / (float)(*count + 1)) — three fp32 operations rounded one by
+ *                              one, what torch's GPU kernels compute for  m += (s - m) / (k + 1)  with a host k (their
+ *                              division by a host scalar multiplies by the fp32 reciprocal);
+ *     lerp(a, s, w) = w < 0.5 ? fma(w, s - a, a) : fma(-(s - a), 1 - w, s) — torch's lerp, its bits.
+ *   Kinds 1 and 2 are copied at every update.  The second launch stores *count + 1: every workgroup of the first has
+ *   read the old value, no atomics.  guard: NULL, or the loss's / clipper's / LARS's guard — non-zero or NaN switches
+ *   the whole call off, the count included.  A negative count moves nothing.
+ *   SF_EINVAL, nothing enqueued: a null table / chunks / count, non-positive counts, a mode outside 0..2, in mode 0 a
+ *   null hyper / hyper_host or hyper_host[0] outside [0, 1] or NaN, a zero address, numel <= 0, a kind outside 0..2,
+ *   chunks that do not tile the tensors exactly.  SF_EALIGN: a float address not on 4 bytes, a word address or count
+ *   not on 8.
+ * sf_avg_exchange: ONE launch over the same table, all three kinds.  op 0: swap average and source element by element
+ *   (twice restores every bit); op 1: average -> source; op 2: source -> average.  16 bytes per swapped element.
+ *   SF_EINVAL: an op outside 0..2 and the table refusals above; SF_EALIGN as above. */
+int sf_avg_update(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
+                  int n_chunks, int mode, const float* hyper_host, const float* hyper, long* count, const float* guard,
+                  void* stream);
+int sf_avg_exchange(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
+                    int n_chunks, int op, void* stream);
+
 /* ---- evaluation (csrc/eval_metrics.hip): tools/train_net.py:166-251 eval_epoch and utils/meters.py:557-714 (ValMeter,
  * get_map) without the host.  No entry point synchronises or reads anything back.
  * sf_topk_errors: metrics.topks_correct for k = 1 and k = k_hi and the two error percentages (train_net.py:227-232) of
