@@ -1,6 +1,6 @@
 // chunk_table.h — what the kernels addressed through an int64 tensor table and a chunk list share (step_tail.hip: the
-// optimizers; grad_clip.hip; lars.hip).  A table row describes one tensor (addresses, numel, ...; the row width and the
-// numel column differ per table), a chunk is (tensor index, first element) and covers at most CHUNK_ELEMS elements of one
+// optimizers; grad_clip.hip; lars.hip; weight_avg.hip; tensor_stats.hip).  A table row describes one tensor (addresses,
+// numel, ...; the row width and the numel column differ per table), a chunk is (tensor index, first element) and covers at most CHUNK_ELEMS elements of one
 // tensor, one workgroup of CHUNK_TPB threads per chunk.  Here, once each: the sizes, the address cast, the rule that turns
 // a workgroup's chunk into a span or into "do nothing", the host check that the chunks tile the tensors, the fixed-order
 // read-only walk over a span, the fixed-order block fold, and the state block sf_grad_norm / sf_lars_ratios leave.
@@ -94,8 +94,9 @@ struct Sum {  // block_fold
 };
 
 // N thread-sequential values -> xor butterfly -> wavefronts in order through LDS, one array and one barrier for all N;
-// thread 0 holds the results.  No kernel calls this twice: a second call reuses s_part and would need a barrier between
-// the first call's reads and its own writes.
+// thread 0 holds the results.  No kernel calls ONE instantiation twice: a second call reuses s_part and would need a
+// barrier between the first call's reads and its own writes (tensor_stats.hip's second launch calls two: <2, Sum> and
+// <2, Max>, each with an array of its own).
 template <int N, typename F>
 __device__ __forceinline__ void block_fold(double (&v)[N], F comb) {
   __shared__ double s_part[CHUNK_WAVES][N];

@@ -223,6 +223,9 @@ _SIGNATURES = {
     # averaged weights: one-launch EMA / SWA / running-mean update with a device-side count, swap / copy of the pairs
     "sf_avg_update": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp]),
     "sf_avg_exchange": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _ci, _vp]),
+    # training telemetry: per-tensor statistics and sign-and-exponent histograms into a device-side ring (two launches)
+    "sf_tensor_stats_ws_bytes": (_cl, [_ci]),
+    "sf_tensor_stats": (_ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp, _cl, _vp, _ci, _ci, _pi, _vp]),
     # evaluation: top-k errors of a batch, the epoch's row store, mean average precision
     "sf_topk_errors": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _pi, _ci, _vp]),
     "sf_rows_append": (_ci, [_vp, _ci, _vp, _ci, _ci, _ci, _vp, _vp, _pi, _ci, _vp]),
@@ -2246,3 +2249,24 @@ def stripe_pool_bwd(dx, stripes, dz=None, dmean=None, dmax=None, arg=None, accum
     _call("sf_stripe_pool_bwd", *gz, *gm, *gx, _ptr(arg) if dmax is not None else None, dx.N, dx.T, dx.H, dx.W, dx.C,
           stripes, dx.ptr(), dx.cs, dx.coff, 1 if accumulate else 0, tag="stripe_pool_bwd")
     return dx
+
+
+SF_TSTATS_BINS, SF_TSTATS_ROW = 24, 58  # include/sfhip.h: exponent bins per sign; 8-byte slots of a tensor's row
+
+
+def tensor_stats(table_host, table, chunks_host, chunks, ws, ring, cursor):
+    """One `sf_tensor_stats` call (two launches): the statistics row of every tensor of the (address, numel) table into
+    slot cursor[0] of `ring` (int64 [slots, n_tensors, SF_TSTATS_ROW] on the GPU; fp32 / fp64 fields are views of the
+    same slots), cursor (int32 [2] on the GPU: next slot, calls made) advanced by the call itself.  ws: a contiguous GPU
+    tensor of at least sf_tensor_stats_ws_bytes(n_chunks) bytes.  The host tensors are what the device ones were uploaded
+    from; an address of 0 is an absent tensor (a zero row).  No host read: capturable."""
+    for h, d in ((table_host, table), (chunks_host, chunks)):
+        assert h.dtype == d.dtype == torch.int64 and h.is_contiguous() and d.is_contiguous() and not h.is_cuda
+        assert h.shape == d.shape
+    if not (table.is_cuda and chunks.is_cuda and ws.is_cuda and ring.is_cuda and cursor.is_cuda):
+        raise SfhipError("tensor_stats: table, chunks, ws, ring and cursor live on the GPU — there is no CPU fallback")
+    assert ring.dtype == torch.int64 and ring.is_contiguous() and ring.dim() == 3 and ring.shape[1] == table_host.shape[0]
+    assert cursor.dtype == torch.int32 and cursor.is_contiguous() and cursor.numel() == 2 and ws.is_contiguous()
+    _call("sf_tensor_stats", _ptr(table_host), _ptr(table), table_host.shape[0], _ptr(chunks_host), _ptr(chunks),
+          chunks_host.shape[0], _ptr(ws), ws.numel() * ws.element_size(), _ptr(ring), ring.shape[2], ring.shape[0],
+          ctypes.cast(ctypes.c_void_p(cursor.data_ptr()), _pi), tag="tensor_stats")

@@ -1207,6 +1207,52 @@ int sf_avg_update(const long* table_host, const long* table, int n_tensors, cons
 int sf_avg_exchange(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
                     int n_chunks, int op, void* stream);
 
+/* ---- training telemetry (csrc/tensor_stats.hip): what the reference's TensorboardWriter (TENSORBOARD.MODEL_VIS) is
+ * there to watch — per-tensor statistics and a histogram of EVERY parameter or gradient — in one call of TWO launches
+ * that reads every element once, without the host.  Nothing synchronises or reads back.
+ * sf_tensor_stats: table: int64 [n_tensors][2] = address, numel, as sf_grad_norm's; an address of 0 is a tensor that is
+ *   ABSENT (a parameter whose .grad is still None) and not an error: its numel still tiles the chunk list, nothing of it
+ *   is read, and its row is all zeros (present = 0).  chunks: int64 [n_chunks][2] as sf_sgd_step's, tiled at
+ *   sf_sgd_chunk_elems() in table order.  The *_host arguments are the host arrays the two were uploaded from: checked
+ *   before anything is launched, and every kernel re-checks the device row it reads (a row that fails is treated as
+ *   absent, never a wild access).
+ *   The row of a tensor is SF_TSTATS_ROW = 58 slots of 8 bytes:
+ *     [0] present (0 / 1)   [1] numel   [2] n_nan   [3] n_inf (+Inf and -Inf)   [4] n_zero (+0.0 and -0.0)      int64
+ *     [5] min (low 4 bytes), max (high 4 bytes)   [6] absmax (low), 0.f (high)     fp32, over the FINITE elements; none:
+ *                                                                                  min = +inf, max = -inf, absmax = 0
+ *     [7] sum   [8] sumsq       fp64, over the finite elements, each widened to fp64 before it is squared or added
+ *     [9 .. 57] hist[2 B + 1]   int64, B = SF_TSTATS_BINS = 24 exponent bins per sign and one centre bin
+ *   The bin of a finite x, with e = floor(log2 |x|) taken from the exponent field by integer arithmetic:
+ *     |x| < 2^-20 (zeros and denormals included):  the centre bin, hist[B];
+ *     otherwise k = min(max(e + 20, 0), B - 1):    hist[B + 1 + k] for x > 0, hist[B - 1 - k] for x < 0 — everything at
+ *                                                  or above 2^3 lands in the last bin of its side.
+ *   The 2 B + 2 bin boundaries increase: -2^4, -2^3, ..., -2^-20, +2^-20, ..., +2^4 (the outermost two are nominal: the
+ *   outer bins are open).  Every finite element is in exactly one bin and a NaN or an Inf in none:
+ *   sum(hist) + n_nan + n_inf == numel.
+ *   Launch 1, one workgroup per chunk: thread t takes the elements of the groups of four t, t + 256, ... in order
+ *   (sf_grad_norm's walk: 16-byte accesses where the address allows, else 4-byte ones, the same elements in the same order,
+ *   so the bits do not depend on the alignment), the fp64 sums go through the xor butterfly and the four wavefronts in
+ *   order through LDS, the counts through integer LDS adds and min / max through integer LDS min / max (on keys of the
+ *   floats' order) on 32 copies laid out one per bank — integers: order-free; ONE row per chunk goes
+ *   to ws (caller-owned, sf_tensor_stats_ws_bytes(n_chunks) bytes, 8-byte aligned, no need to clear it).
+ *   Launch 2, one workgroup per tensor: thread i folds the tensor's chunk rows i, i + 256, ... in chunk order, then the
+ *   same two steps, and writes the row.  No float atomics, no "last workgroup" finish, no memset: every byte of every
+ *   row is written by one writer and equal inputs give equal bits.
+ *   ring: int64-sized slots [slots][n_tensors][SF_TSTATS_ROW] in DEVICE memory; cursor: int32 [2] in DEVICE memory =
+ *   {the slot this call writes, the calls made so far (saturating)}.  Launch 1 reads the slot (a value outside
+ *   [0, slots) counts as 0), launch 2 writes slot's rows and stores cursor[0] = (slot + 1) % slots, cursor[1] + 1: a caller
+ *   records every step, also inside a captured graph, and reads the ring once per logging period.  row: the row width
+ *   the caller allocated the ring with.
+ *   SF_EINVAL, nothing enqueued: a null table / chunks / ws / ring / cursor, non-positive counts, row != SF_TSTATS_ROW,
+ *   slots <= 0, ws_bytes below sf_tensor_stats_ws_bytes(n_chunks), an address off 4 bytes, numel <= 0, chunks that do
+ *   not tile the tensors exactly.  SF_EALIGN: ws or ring not on 8 bytes, cursor not on 4.
+ * sf_tensor_stats_ws_bytes: host only; 0 for n_chunks <= 0. */
+#define SF_TSTATS_BINS 24
+#define SF_TSTATS_ROW 58
+long sf_tensor_stats_ws_bytes(int n_chunks);
+int sf_tensor_stats(const long* table_host, const long* table, int n_tensors, const long* chunks_host, const long* chunks,
+                    int n_chunks, void* ws, long ws_bytes, long* ring, int row, int slots, int* cursor, void* stream);
+
 /* ---- evaluation (csrc/eval_metrics.hip): tools/train_net.py:166-251 eval_epoch and utils/meters.py:557-714 (ValMeter,
  * get_map) without the host.  No entry point synchronises or reads anything back.
  * sf_topk_errors: metrics.topks_correct for k = 1 and k = k_hi and the two error percentages (train_net.py:227-232) of

@@ -41,7 +41,7 @@ HOT = ("conv_rows_kernel", "conv_bx_kernel", "conv_pw_bx_kernel", "conv_bx_wgrad
        "grad_norm_finish_kernel", "grad_scale_kernel", "grad_clamp_kernel", "ce_mix_kernel",
        "clip_batch_mix_kernel", "clip_batch_mix_gray_kernel", "frame_grey_means_kernel", "clip_batch_jitter_kernel",
        "adamw_step_kernel", "lars_sgd_step_kernel", "lars_partial_kernel", "lars_ratio_kernel",
-       "avg_update_kernel", "avg_exchange_kernel")
+       "avg_update_kernel", "avg_exchange_kernel", "tstats_partial_kernel", "tstats_finish_kernel")
 # kernels that are allowed scratch: the f32-MFMA forms, which run only for views the bf16-piece forms reject
 # (C % 4 != 0, unaligned strides or pointers, sf_attn_fwd without a workspace, the public two-kernel sf_attn_bwd)
 EXEMPT = ("attn_bwd_fused_kernelILi64",    # fused f32 sweep for 32 < d <= 64
