@@ -74,6 +74,10 @@ _SIGNATURES = {
     "sf_clip_batch_mix_gray": (_ci, [_vp, _vp] + [_ci] * 4 + [_cf, _cf, _vp, _vp, _ci, _ci, _ci, _vp]),
     "sf_frame_grey_means": (_ci, [_vp, _vp, _ci, _ci, _ci, _pi, _vp]),
     "sf_clip_batch_jitter": (_ci, [_vp, _vp] + [_ci] * 5 + [_vp, _vp, _pi, _vp, _vp, _ci, _ci, _ci, _vp]),
+    # streaming demo: device frame ring, window pack, label select
+    "sf_stream_push": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _vp]),
+    "sf_stream_window": (_ci, [_vp, _ci, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _ci, _ci, _vp]),
+    "sf_label_select": (_ci, [_vp, _ci, _ci, _cf, _pi, _vp]),
     "sf_ensemble_update": (_ci, [_vp] * 4 + [_pi] * 3 + [_ci] * 4 + [_vp]),
     "sf_ensemble_update_ml": (_ci, [_vp] * 3 + [_ci, _vp, _vp, _pi, _pi] + [_ci] * 4 + [_vp]),
     "sf_ncthw1_pack": (_ci, [_vp, _vp] + [_ci] * 7 + [_vp]),
@@ -602,6 +606,58 @@ def clip_batch_det(table_host, table, n_slow, win_hw, mean, std, fast, slow=None
 
 def _iptr(t):  # a device int32 array where the header says `int*`
     return ctypes.cast(ctypes.c_void_p(t.data_ptr()), _pi)
+
+
+def stream_push(frame_u8, ring, slot, new_hw, mean, std, ph=0, pw=0):
+    """One camera frame (uint8 [H, W, 3], device, BGR) -> slot `slot` of ring [S, new_h+2ph, Wp, 4]: BGR -> RGB, bilinear
+    scale to new_hw, normalise, the whole padded plane written (the PackedClip layout).  mean / std: three values in RGB
+    order."""
+    _require_gpu(ring, "stream_push")
+    if not frame_u8.is_cuda:
+        raise SfhipError("stream_push: the uint8 frame is on %s — copy it to the GPU first" % frame_u8.device)
+    assert frame_u8.dtype == torch.uint8 and frame_u8.dim() == 3 and frame_u8.shape[2] == 3 and frame_u8.is_contiguous()
+    new_h, new_w = int(new_hw[0]), int(new_hw[1])
+    assert ring.is_contiguous() and ring.dim() == 4 and ring.shape[3] == 4 and ring.shape[1] == new_h + 2 * ph
+    assert len(mean) == 3 and len(std) == 3, "the streaming demo is three-channel"
+    m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
+    _call("sf_stream_push", _ptr(frame_u8), frame_u8.shape[0], frame_u8.shape[1], new_h, new_w, ctypes.cast(m3, _vp),
+          ctypes.cast(s3, _vp), _ptr(ring), ring.shape[0], int(slot), ph, pw, ring.shape[2])
+    return ring
+
+
+def stream_window(ring, head, fast_idx, slow_idx, fast, slow=None):
+    """Both pathways of the window whose oldest frame is in ring slot `head`, in one launch: fast [n_fast, Hp, Wp, 4]
+    frame j = ring slot (head + fast_idx[j]) % S, slow [n_slow, Hp, Wp, 4] frame j = Fast frame slow_idx[j] (slow None and
+    slow_idx None or empty: single pathway).  fast_idx / slow_idx: int32 device tensors."""
+    _require_gpu(ring, "stream_window")
+    _require_gpu(fast, "stream_window")
+    assert ring.is_contiguous() and ring.dim() == 4 and ring.shape[3] == 4
+    assert fast.is_contiguous() and fast.dim() == 4 and tuple(fast.shape[1:]) == tuple(ring.shape[1:])
+    assert fast_idx.is_cuda and fast_idx.dtype == torch.int32 and fast_idx.is_contiguous()
+    n_fast, n_slow = fast.shape[0], 0
+    assert fast_idx.numel() == n_fast
+    if slow is not None:
+        _require_gpu(slow, "stream_window")
+        n_slow = slow.shape[0]
+        assert slow.is_contiguous() and tuple(slow.shape[1:]) == tuple(ring.shape[1:])
+        assert slow_idx.is_cuda and slow_idx.dtype == torch.int32 and slow_idx.is_contiguous()
+        assert slow_idx.numel() == n_slow
+    _call("sf_stream_window", _ptr(ring), ring.shape[0], int(head), _ptr(fast_idx), n_fast,
+          _ptr(slow_idx) if n_slow else None, n_slow, _ptr(fast), _ptr(slow), ring.shape[1], ring.shape[2])
+    return fast, slow
+
+
+def label_select(preds, thr, out):
+    """preds [R, C] fp32 -> out int32 [R, 2 + C]: per row count, argmax (first maximal index, -1 for a row of NaNs), then
+    the `count` class indices with preds > thr in ascending order (torch.nonzero's); entries past them are left as they
+    were.  No allocation, no synchronisation."""
+    _require_gpu(preds, "label_select")
+    assert preds.dim() == 2 and preds.is_contiguous()
+    R, C = preds.shape
+    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and tuple(out.shape) == (R, 2 + C)
+    _call("sf_label_select", _ptr(preds), R, C, float(thr), _iptr(out))
+    return out
 
 
 def ensemble_update(preds, video_idx, labels, video_preds, video_labels, clip_count, bad_count, mode):

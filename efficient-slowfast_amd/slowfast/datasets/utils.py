@@ -664,15 +664,15 @@ def gpu_detection_batch(videos, samples, boxes_list, mean, std, alpha, reverse_i
     return out, table[head.numel():].view(torch.float32)[:5 * K].view(K, 5)
 
 
-def stem_input_geometry(model, crop):
+def stem_input_geometry(model, crop, width=None):
     """(ph, pw, Wp) shared by the model's pathway stems (their first convolutions have the same H/W kernel,
-    stride and padding) for crop x crop frames."""
+    stride and padding) for crop x crop frames (crop x width with `width`: a rectangular window)."""
     from slowfast.models import engine
     geos = set()
     stem = next(model.children())  # s1 (s0 for GhostNet): one `pathway{p}_stem` per pathway
     for m in stem.modules():
         if isinstance(m, torch.nn.Conv3d) and m.in_channels <= 4 and m.groups == 1:
-            geos.add(engine.stem_geometry(m, crop, crop))
+            geos.add(engine.stem_geometry(m, crop, crop if width is None else width))
     if len(geos) != 1:
         raise ValueError("pathway stems disagree on the input geometry: %s" % sorted(geos))
     return geos.pop()

@@ -756,6 +756,42 @@ int sf_clip_batch_det(const long* table_host, const long* table, int B, int n_fa
                       int reverse, const float* mean3, const float* std3, float* fast, float* slow, int ph, int pw,
                       int Wp, void* stream);
 
+/* ---- streaming demo (csrc/stream.hip): tools/demo_net.py:160-305 with the frame buffer on the device.  The reference
+ * keeps a Python list of the last S = DATA.NUM_FRAMES * DATA.SAMPLING_RATE scaled frames and rebuilds, normalises,
+ * permutes, index_selects and uploads all of them for every incoming frame.  Here they live in a ring
+ * [S][new_h + 2 ph][Wp][4] of fp32 in the layout sf_clip_prologue writes (channels padded to 4, zero borders, row pitch
+ * Wp); no entry allocates or synchronises.
+ * sf_stream_push (demo_net.py:166-169 cv2.cvtColor + cv2_transform.scale, :193-198 tensor_normalize + permute, for ONE
+ *   frame): frame is uint8 [H,W,3] on the device in the camera's BGR order.  It is scaled bilinearly to (new_h, new_w)
+ *   (== (H, W): no resampling) and normalised as (u/255 - mean)/std with sf_clip_prologue's arithmetic (one device
+ *   function: the slot holds the bits sf_clip_prologue gives for the channel-swapped frame with its window on the whole
+ *   scaled frame), B and R swapped on the read, and written to slot `slot` of the ring — the whole padded plane, zeros
+ *   included, one 16-byte store per pixel.  mean3 / std3: HOST, three floats each, in RGB order (DATA.MEAN / DATA.STD).
+ *   SF_EINVAL, nothing launched: null pointers, non-positive sizes or S, slot outside [0, S), negative ph / pw,
+ *   Wp < new_w + 2 pw, a plane of more than 2^29 pixels, ring not 16-byte aligned.
+ * sf_stream_window (demo_net.py:204-221 the two linspace index_selects, :232-238 the upload): both pathways of the
+ *   window whose oldest frame is in slot `head`, in one launch.  fast_idx: n_fast window positions in [0, S), slow_idx:
+ *   n_slow positions among the Fast frames, both int32 in DEVICE memory.  fast [n_fast][Hp][Wp][4] frame j is ring slot
+ *   (head + fast_idx[j]) % S; slow [n_slow][Hp][Wp][4] frame j is Fast frame slow_idx[j].  Hp = new_h + 2 ph.  A pure
+ *   copy: one 16-byte load per pixel of a Fast frame, stored to fast and — when slow_idx names the frame — to slow.
+ *   The tables are read on the device only: a fast_idx entry outside [0, S) or a slow_idx entry outside [0, n_fast)
+ *   makes that frame zeros, never a wild read, and every element of both buffers still has exactly one owner.
+ *   slow == NULL with n_slow == 0: a single-pathway model.
+ *   SF_EINVAL, nothing launched: null ring / fast_idx / fast, S <= 0, head outside [0, S), n_fast <= 0 or above 65535,
+ *   n_slow < 0 or > n_fast, slow given without n_slow (or the reverse), n_slow > 0 without slow_idx, non-positive Hp /
+ *   Wp, a plane of more than 2^29 pixels, a buffer not 16-byte aligned.
+ * sf_label_select (demo_net.py:264-268 and :292-298 torch.nonzero(preds > 0.1) + .cpu(), :289 argmax): preds [R][C]
+ *   fp32 (R = 1 for classification, the number of boxes for detection) -> out int32 [R][2 + C]: per row count, argmax,
+ *   then the `count` class indices with preds > thr in ascending order; entries past 2 + count are not written.  argmax
+ *   is the first maximal index (torch.argmax).  A NaN is never selected and never wins: a row of NaNs gives count 0,
+ *   argmax -1.  One wavefront per row, any C; order from ballot + popcount, no atomics, no LDS.
+ *   SF_EINVAL, nothing launched: null pointers, R <= 0, C <= 0, a NaN threshold, a pointer off 4 bytes. */
+int sf_stream_push(const unsigned char* frame, int H, int W, int new_h, int new_w, const float* mean3, const float* std3,
+                   float* ring, int S, int slot, int ph, int pw, int Wp, void* stream);
+int sf_stream_window(const float* ring, int S, int head, const int* fast_idx, int n_fast, const int* slow_idx, int n_slow,
+                     float* fast, float* slow, int Hp, int Wp, void* stream);
+int sf_label_select(const float* preds, int R, int C, float thr, int* out, void* stream);
+
 /* sf_ensemble_update (csrc/ensemble.hip): TestMeter.update_stats (utils/meters.py:283-317) on the device.  preds [B,K],
  *   video_idx int32 [B] (clip id / clips per video), labels int32 [B] or NULL; video_preds [Nv,K], video_labels int32
  *   [Nv], clip_count int32 [Nv] are the meter's accumulators.  mode 0: video_preds[video_idx[b]] += preds[b]; mode 1:
